@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — candidate guides scored per second on the BASELINE.json workloads.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c3|c1|c4|c5] [--weak]
+    python bench.py [--gpus N --steps K --warmup W] [--config c3|c1|c4|c5] [--weak] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the device hot path over inputs that are already resident in HBM:
 
@@ -21,10 +21,20 @@ There is no data-path collective: barriers and the timing / count reductions run
 and the single exchange of the job - the RCCL gather of the guide tables over xGMI (hawk_table_gather) - is measured
 once after the timed loop and reported as `gather` next to `value`.
 
-One JSON line on stdout (rank 0): the driver's contract fields plus `roofline` (dominant kernel, algorithmic bytes over
-its HIP-event duration, against the 8 TB/s HBM peak), `cpu_baseline` (the C oracle on one host thread, bounded sample),
+One JSON line on stdout (rank 0): the driver's contract fields (`value` and `ms_per_step` over exactly K timed steps after
+W warm-up steps) and what the timed steps report about themselves (per-kernel times, the cluster dictionary).  A plain run
+does nothing else: set-up, warm-up, the K steps, `--dump-outputs`, the line.
+
+`--full` adds everything that needs work of its own after the timed loop: `roofline` (dominant kernel, algorithmic bytes
+over its HIP-event duration, against the 8 TB/s HBM peak), the dictionary-resident rate, the K2 scan kernel alone, the
+search over materialised planes and per dirty word, `cpu_baseline` (the C oracle on one host thread, bounded sample),
 `cpu_baseline_all_cores`, `end_to_end` (in-memory records -> expand -> search+CFDon -> collapse -> D2H of the report
-groups, wall clock) and per-kernel times.
+groups, wall clock), `shares_on_one_gpu` and, at N > 1, the one exchange (`gather`).  The `--no-*` options thin it out.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's part at N > 1) as DIR/<name>.npy, float64, at
+most 64 MB in all: c3 / c1 the guide table (counts per haplotype row over the whole table + every column of a fixed,
+seeded sample of haplotype rows), c4 the per-tile counts, c5 the off-target hits (a fixed, seeded sample when large).
+The inputs are synthesised from fixed seeds, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -146,6 +156,78 @@ def timed_steps(R: Ranks, step, steps: int, warmup: int):
     outs = [step() for _ in range(steps)]
     R.barrier()
     return R.max_float(time.perf_counter() - t0), outs
+
+
+# ---------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, as float64 .npy files
+# ---------------------------------------------------------------------------------------------------
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SEED = 4242          # fixed: the same sample in every run with the same arguments
+DUMP_SAMPLE_HAPS = 32     # c3: ~5.6e3 guide rows per haplotype row -> ~1.8e5 rows, ~25 MB
+DUMP_MAX_ROWS = 400_000   # rows of any sampled array (at most 10 columns of 8 B: 32 MB)
+
+
+def write_outputs(d, arrays):
+    """Every array as d/<name>.npy in float64 (the integer columns written here are below 2^53: exact); all finite."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: not finite: {bad}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_BYTES_MAX}")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log(f"outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB -> {d}")
+
+
+def _u64_halves(a):
+    """uint64 -> (low, high) 32-bit halves: exact in float64"""
+    a = np.asarray(a, dtype=np.uint64)
+    return a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)
+
+
+def table_outputs(tab):
+    """The guide table of a search as its caller reads it (GuideTable.download: one row per guide), in a form two builds can
+    be compared by: the table's counts, and rows, NA scores and summed CFDon per haplotype row (every row of the table), then
+    every column of the rows of a fixed, seeded sample of haplotype rows, sorted on their content (the order the device writes
+    rows in is not part of the result).  The window bit planes go out as two 32-bit halves; an NA score (NaN in the table) goes
+    out as 0 with `cfdon_na` = 1, so that every array is finite."""
+    tab.download()
+    n_hap = int(tab._hs.n_hap)
+    cf = tab.cfdon
+    na = np.isnan(cf)
+    out = {"counts": [tab.n_rows, tab.n_candidates, tab.n_hits],
+           "rows_per_haplotype": np.bincount(tab.hap, minlength=n_hap),
+           "cfdon_na_per_haplotype": np.bincount(tab.hap, weights=na, minlength=n_hap),
+           "cfdon_sum_per_haplotype": np.bincount(tab.hap, weights=np.where(na, 0.0, cf), minlength=n_hap)}
+    picked = np.zeros(n_hap, bool)
+    picked[np.random.default_rng(DUMP_SEED).choice(n_hap, min(n_hap, DUMP_SAMPLE_HAPS), replace=False)] = True
+    sel = np.flatnonzero(picked[tab.hap])
+    lo, hi = _u64_halves(tab.win[:, sel])
+    cols = {"hap": tab.hap[sel], "strand": tab.strand[sel], "pos": tab.pos[sel], "start": tab.start[sel], "stop": tab.stop[sel],
+            "flags": tab.flags[sel], "cfdon_na": na[sel], "cfdon": np.where(na[sel], 0.0, cf[sel])}  # NA (NaN) as 0 + its flag: finite
+    order = np.lexsort(tuple(reversed(list(cols.values()) + list(lo) + list(hi))))[:DUMP_MAX_ROWS]  # hap first, then strand, ...
+    out.update({"sample_" + k: v[order] for k, v in cols.items()})
+    out["sample_win_lo"], out["sample_win_hi"] = lo[:, order].T, hi[:, order].T
+    return out
+
+
+def hits_outputs(hits, n_guides):
+    """Off-target hits ({guide, row, q, strand, mm, code, nmask} arrays): hits per guide over all of them, then the hits
+    sorted on their content - a fixed, seeded sample of DUMP_MAX_ROWS of them when there are more.  `code` goes out as two
+    32-bit halves."""
+    lo, hi = _u64_halves(hits["code"])
+    cols = {k: hits[k] for k in ("guide", "row", "q", "strand", "mm", "nmask")}
+    cols["code_lo"], cols["code_hi"] = lo, hi
+    n = len(lo)
+    order = np.lexsort(tuple(reversed(list(cols.values()))))
+    if n > DUMP_MAX_ROWS:
+        order = order[np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ROWS, replace=False))]
+    out = {"counts": [n], "hits_per_guide": np.bincount(hits["guide"], minlength=n_guides)}
+    out.update({"sample_" + k: v[order] for k, v in cols.items()})
+    return out
 
 
 def pam_need_planes(pam) -> int:
@@ -431,9 +513,18 @@ def run_region(args, R: Ranks):
             tab.close()
         return tab
 
-    elapsed, tabs = timed_steps(R, step, args.steps, args.warmup)
+    dump = args.dump_outputs is not None and R.rank == 0
+    calls = [0]
+
+    def timed_step():  # --dump-outputs: the last timed step keeps its table (closing it is host bookkeeping only)
+        calls[0] += 1
+        return step(keep=dump and calls[0] == args.warmup + args.steps)
+
+    elapsed, tabs = timed_steps(R, timed_step, args.steps, args.warmup)
+    if dump:
+        write_outputs(args.dump_outputs, table_outputs(tabs[-1]))
     elapsed_resident = None
-    if with_dict:
+    if args.full and with_dict:
         for t in tabs:
             t.close()
         elapsed_resident, tabs = timed_steps(R, lambda keep=False: step(keep, rebuild=False), args.steps, 1)
@@ -472,43 +563,48 @@ def run_region(args, R: Ranks):
         out["config"]["step"] = ("encode + search + CFDon from the expansion plan (REF planes + variant records + their cluster dictionary resident; "
                                  "no haplotype plane written)" if fused else "hawk_search over haplotype planes resident in HBM")
         by_cluster = fused and int(tm[-1]["v_path"]) == 2
+        if with_dict:
+            out["config"]["step"] = ("cluster dictionary of the plan + encode + search + CFDon (REF planes + variant records resident; no haplotype plane "
+                                     "written)")
         if elapsed_resident is not None:
             out["value_dictionary_resident"] = cand_all * args.steps / elapsed_resident
             out["ms_per_step_dictionary_resident"] = elapsed_resident / args.steps * 1e3
-            out["config"]["step"] = ("cluster dictionary of the plan + encode + search + CFDon (REF planes + variant records resident; no haplotype plane "
-                                     "written); value_dictionary_resident: the same without the dictionary build (a second PAM on the same plan)")
+            out["config"]["step"] += "; value_dictionary_resident: the same without the dictionary build (a second PAM on the same plan)"
         if by_cluster:
             cl = plan.cluster_stats()
-            ref_rows = tab_ref_rows(reg, pam, args, mm, pt, R.device) // (R.world if by_region else 1)  # (a stretch holds its share of REF's rows)
-            out["roofline"] = csearch_roofline(rows, ref_rows, positions, tab.n_hits, args.guidelen + len(pam), score, cl, avg("v_templates_ms"),
-                                               avg("v_count_ms") - avg("v_templates_ms"), avg("v_emit_rows_ms"), tkey)
             out["cluster_dictionary"] = dict(cl, share=cl["instances"] / max(cl["distinct"], 1),
                                              what="built once per plan (hawk_csearch.hip): the rows' carried variants cut into clusters (alleles "
                                              "within 64 nt), identical clusters of different rows numbered once; `share` = instances per distinct "
                                              "cluster (below 3 the per-word search of hawk_vsearch.hip takes the plan); inside every timed step and every "
                                              "end_to_end pass")
-        elif fused:
-            out["roofline"] = vsearch_roofline(rows, int(plan_carried(ds)), positions, tab.n_hits, args.guidelen + len(pam), score,
-                                               avg("v_count_ms"), avg("v_emit_ms"), tkey)
-        else:
-            out["roofline"] = search_roofline(pam, positions, rows, avg("count_ms"), avg("emit_list_ms"), avg("emit_ms"), tkey)
-        sl = out["roofline"]["step_level"]
-        sl["ms"] = avg("total_ms")
-        # a view's step is priced by the bytes it moves: the survey's per-position figures describe work the step no longer does
-        # (a fraction of peak over them would exceed 1) and are given as an equivalent rate only
-        sl_bytes = sl["moved_bytes"] if fused else sl["algorithmic_bytes"]
-        sl["frac"] = sl_bytes / (sl["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if sl["ms"] else None
-        if fused:
-            sl["survey_equivalent_GBps"] = sl["algorithmic_bytes"] / (sl["ms"] * 1e-3) / 1e9 if sl["ms"] else None
+        if args.full:  # the cluster path's pricing needs a REF-only search of its own
+            if by_cluster:
+                ref_rows = tab_ref_rows(reg, pam, args, mm, pt, R.device) // (R.world if by_region else 1)  # (a stretch holds its share of REF's rows)
+                out["roofline"] = csearch_roofline(rows, ref_rows, positions, tab.n_hits, args.guidelen + len(pam), score, cl, avg("v_templates_ms"),
+                                                   avg("v_count_ms") - avg("v_templates_ms"), avg("v_emit_rows_ms"), tkey)
+            elif fused:
+                out["roofline"] = vsearch_roofline(rows, int(plan_carried(ds)), positions, tab.n_hits, args.guidelen + len(pam), score,
+                                                   avg("v_count_ms"), avg("v_emit_ms"), tkey)
+            else:
+                out["roofline"] = search_roofline(pam, positions, rows, avg("count_ms"), avg("emit_list_ms"), avg("emit_ms"), tkey)
+            sl = out["roofline"]["step_level"]
+            sl["ms"] = avg("total_ms")
+            # a view's step is priced by the bytes it moves: the survey's per-position figures describe work the step no longer does
+            # (a fraction of peak over them would exceed 1) and are given as an equivalent rate only
+            sl_bytes = sl["moved_bytes"] if fused else sl["algorithmic_bytes"]
+            sl["frac"] = sl_bytes / (sl["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if sl["ms"] else None
+            if fused:
+                sl["survey_equivalent_GBps"] = sl["algorithmic_bytes"] / (sl["ms"] * 1e-3) / 1e9 if sl["ms"] else None
         out["kernels_ms"] = {"count": avg("count_ms"), "offsets": avg("offsets_ms"), "emit": avg("emit_ms"), "emit_list": avg("emit_list_ms"),
                              "vsearch_count": avg("v_count_ms"), "vsearch_emit": avg("v_emit_ms"), "view_templates": avg("v_templates_ms"),
                              "view_path": {0: "planes", 1: "per dirty word (hawk_vsearch.hip)", 2: "per distinct cluster (hawk_csearch.hip)"}[int(tm[-1]["v_path"])],
                              "device_total": avg("total_ms")}
-        out["pam_scan_kernel"] = pam_scan_kernel(ds, pam)
+        if args.full:
+            out["pam_scan_kernel"] = pam_scan_kernel(ds, pam)
         out["haplotype_expansion"] = {"kernels_ms": expand_ms, "rows": ds.n_hap,
                                       "where": "device (hawk_xplan_run); not part of the fused step, which writes no planes" if fused
                                       else "device (hawk_xplan_run), outside the timed steps"}
-        if fused:  # the materialised alternative, for scale: planes written (hawk_xplan_run) and then searched (round 2's kernels)
+        if args.full and fused:  # the materialised alternative, for scale: planes written (hawk_xplan_run) and then searched (round 2's kernels)
             k = max(3, min(10, args.steps))
             R._lib.check(R._lib.lib().hawk_sync(R.ctx), "hawk_sync")
             t_a = time.perf_counter()
@@ -544,7 +640,7 @@ def run_region(args, R: Ranks):
         t.close()
 
     # ---- the one exchange of the job (N > 1): guide tables to rank 0 over RCCL ----------------------
-    if R.world > 1 and not args.no_gather:
+    if R.world > 1 and args.full and not args.no_gather:
         # RCCL with peers cannot be rehearsed on the one-GPU boxes this was built on: if the exchange hangs rather than
         # fails, the measured line must still come out - a watchdog prints it (gather: timeout) and ends the rank
         import threading
@@ -561,7 +657,7 @@ def run_region(args, R: Ranks):
         wd.cancel()
         if R.rank == 0:
             out["gather"] = g
-    if R.rank == 0 and R.world == 1:
+    if R.rank == 0 and R.world == 1 and args.full:
         if not args.no_end_to_end:
             out["end_to_end"] = end_to_end(args, R, reg, pam, mm, pt, info, kept, c1)
             out["value_end_to_end"] = out["end_to_end"].get("candidates_per_s")  # records + genotypes in host memory -> report groups on the host
@@ -577,7 +673,7 @@ def run_region(args, R: Ranks):
                                            "measured": "build container, 8 vCPU, single thread (profiles/r02_reference_python_timing.json); not on this host"}
             if not c1 and not args.no_cpu_all_cores:
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args)
-    if R.rank == 0 and R.world == 1 and not c1 and not args.no_shares and fused and out.get("ms_per_step_dictionary_resident"):
+    if R.rank == 0 and R.world == 1 and args.full and not c1 and not args.no_shares and fused and out.get("ms_per_step_dictionary_resident"):
         out["shares_on_one_gpu"] = shares_projection(args, R, reg, pam, mm, pt, out["ms_per_step"], out["ms_per_step_dictionary_resident"])
     if trs is not None:
         trs.close()
@@ -972,6 +1068,8 @@ def run_c4(args, R: Ranks):
 
     elapsed, outs = timed_steps(R, step, args.steps, args.warmup)
     st = outs[-1]
+    if args.dump_outputs is not None and R.rank == 0:  # what the step returns: per tile counts (its report groups stay in HBM)
+        write_outputs(args.dump_outputs, {"tile_" + k: [s[k] for s in st] for k in ("n_hap", "candidates", "hits", "rows", "groups")})
     cand = sum(s["candidates"] for s in st)
     rows = sum(s["rows"] for s in st)
     positions = sum(s["scanned_positions"] for s in st)
@@ -1029,7 +1127,7 @@ def run_c4(args, R: Ranks):
                                                   "once + what the passes read per cluster instance / record"},
                            "survey_priced": {"bytes": 0.75 * positions + ROW_BYTES * rows,
                                              "effective_GBps": (0.75 * positions + ROW_BYTES * rows) / (search_ms * 1e-3) / 1e9 if search_ms else None}}
-        if R.world == 1 and not args.no_cpu_baseline:
+        if R.world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_c4(seq, panel, n_block, pam, args, *(cfd if cfd else (None, None)))
         out["kernels_ms"] = {"search_all_tiles": search_ms, "collapse_all_tiles": collapse_ms,
                              "wall_per_step": elapsed / args.steps * 1e3}
@@ -1074,6 +1172,8 @@ def run_c5(args, R: Ranks):
 
     elapsed, outs = timed_steps(R, step, args.steps, args.warmup)
     hits, tm = outs[-1]
+    if args.dump_outputs is not None and R.rank == 0:
+        write_outputs(args.dump_outputs, hits_outputs(hits, len(guides)))
     tms = [o[1] for o in outs]
     avg = lambda k: float(np.mean([t[k] for t in tms]))
     tot = R.sum_ints([tm["n_sites"], tm["scanned_positions"], len(hits["guide"])])
@@ -1121,7 +1221,7 @@ def run_c5(args, R: Ranks):
         out["roofline"] = roof
         out["kernels_ms"] = {k: avg(k) for k in ("scan_ms", "sites_ms", "match_ms", "total_ms")}
         out["index_build_s"] = t_idx
-    if R.world > 1:
+    if R.world > 1 and args.full:
         from crisprhawk_hip import parallel
         t0 = time.perf_counter()
         comm = R.ctl
@@ -1134,7 +1234,7 @@ def run_c5(args, R: Ranks):
         if R.rank == 0:
             out["gather"] = {"hits": int(sum(len(p) for p in parts["guide"])), "wall_ms": (time.perf_counter() - t0) * 1e3,
                              "via": type(comm).__name__}
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+    if R.rank == 0 and R.world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_offtargets(args, pam_s, guidelen, right, guides)
     return out
 
@@ -1161,8 +1261,13 @@ def cpu_baseline_offtargets(args, pam_s, guidelen, right, guides):
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default per config: c3 20, c1 200, c4 2, c5 3)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default per config: c3 3, c1 20, c4 1, c5 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the bench measures: roofline, other paths, CPU baselines, end to end, "
+                         "shares, the N > 1 exchange (the --no-* options thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--config", choices=["c1", "c3", "c4", "c5"], default="c3")
     ap.add_argument("--weak", action="store_true", help="every rank its own panel (weak scaling) instead of one block-partitioned panel")
     ap.add_argument("--samples", type=int, default=2504)
@@ -1199,7 +1304,10 @@ def build_parser():
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # our own launcher: N fresh processes, started before this one has made any GPU call
         sys.exit(launch(args.gpus, sys.argv[1:]))

@@ -6,7 +6,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out/kt_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-shares "$@" > /dev/null 2> $out/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python3 $root/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-shares "$@" > /dev/null 2> $out/log.txt
 cd $root
 find $out -name "*kernel_trace.csv" -delete
 python3 - $out > gpurun_out/kstats_$tag.txt <<'PY'

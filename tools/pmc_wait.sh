@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVES" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAVES" "SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_ANY SQ_WAVES" "SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_INST_CYCLES_SALU SQ_WAVES"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --output-format csv -d $out/s$i -o p -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > /dev/null 2> $out/s$i.log
+  rocprofv3 --pmc $set --output-format csv -d $out/s$i -o p -- python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > /dev/null 2> $out/s$i.log
 done
 cd $root
 python3 - <<'PY'
