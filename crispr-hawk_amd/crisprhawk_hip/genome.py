@@ -6,6 +6,7 @@ the "index" is the genome itself as one-hot bit-planes.  Contigs are split into 
 whole by exactly one piece (the piece that owns its start)."""
 import ctypes as C
 from dataclasses import dataclass
+from math import comb
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -116,6 +117,37 @@ def _derived_guides(guides: Sequence[str], G: int, b: int, dna: bool):
     return derived, owner, gaps
 
 
+def derived_per_guide(G: int, b: int, dna: bool) -> int:
+    """How many derived guides _derived_guides makes of one guide of G bases at most (exactly, for DNA bulges)."""
+    return comb(G - 2 + b, b) * 4 ** b if dna else comb(G - 2, b)
+
+
+def min_spacer(guidelen: int) -> int:
+    """The shortest spacer an index of `guidelen` is asked about: the site of an RNA bulge of 2 (scan_bulges)."""
+    return max(1, guidelen - 2)
+
+
+def row_geometry(lengths: Dict[str, int], guidelen: int, pamlen: int, piece: int, max_bulge: int, spacer: int) -> List[Tuple[str, int, int, int]]:
+    """The rows of a genome index and the window starts each owns, without a device: (contig, offset, end, own) per row, in
+    contig order.  A row holds contig bases [offset, end): `piece` bases plus an overlap of the longest window (guidelen +
+    max_bulge + pamlen) less one, clipped to the contig.  Rows exist wherever the SHORTEST window (min_spacer + pamlen) fits,
+    so a tail too short for the full window still has a row for the windows of RNA-bulged sites.  For windows of `spacer` +
+    pamlen bases the row owns starts [offset, offset + own): those of its piece whose window lies inside the row.  Every
+    start s with s + window <= contig length is then owned by exactly one row, for every spacer of min_spacer ..
+    guidelen + max_bulge (tests/test_host_logic.py sweeps the edges)."""
+    Lmin = min_spacer(guidelen) + pamlen
+    overlap = guidelen + pamlen + max_bulge - 1
+    Lw = spacer + pamlen
+    out = []
+    for name, n in lengths.items():
+        for off in range(0, max(n, 1), piece):
+            end = min(n, off + piece + overlap)
+            if end - off < Lmin:
+                continue
+            out.append((name, off, end, max(0, min(piece, end - off - Lw + 1))))
+    return out
+
+
 class GenomeIndex:
     """`shard = (rank, world)`: the genome's rows (pieces) are block-partitioned over the ranks of a multi-GPU job
     ("shard the genome by contig/offset across ranks, guides replicated, rows gathered"); every rank keeps the
@@ -124,26 +156,19 @@ class GenomeIndex:
     def __init__(self, contigs: Dict[str, object], guidelen: int, pamlen: int, piece: int = 1 << 22, device: Optional[int] = None,
                  shard: Optional[Tuple[int, int]] = None, max_bulge: int = 0):
         """`max_bulge`: the largest DNA bulge the index will be asked about - neighbouring rows then overlap by that many bases
-        more, so that the longer windows of bulged sites (guidelen + bulge + pamlen) still lie inside one row."""
+        more, so that the longer windows of bulged sites (guidelen + bulge + pamlen) still lie inside one row.  Rows and the
+        window starts they own: row_geometry."""
         self.L = guidelen + pamlen
         self.guidelen, self.pamlen, self.max_bulge = guidelen, pamlen, int(max_bulge)
-        overlap = self.L + self.max_bulge - 1
-        self.rows: List[Tuple[str, int, int]] = []  # (contig, offset, owned window starts), all ranks' rows
-        spans = []
-        self.total = 0
-        for name, seq in contigs.items():
-            n = len(seq)
-            self.total += n
-            for off in range(0, max(n, 1), piece):
-                end = min(n, off + piece + overlap)
-                if end - off < self.L:
-                    continue
-                own = min(piece, n - off)  # window starts [0, own) belong to this row ...
-                own = min(own, end - off - self.L + 1)  # ... as far as the window fits
-                spans.append((name, off, end))
-                self.rows.append((name, off, own))
+        if self.max_bulge < 0 or self.L + self.max_bulge > 32:
+            raise ValueError(f"windows of {guidelen} + {self.max_bulge} (DNA bulge) + {pamlen} bases: the device encodes windows of up to 32 bases")
+        self._lens = {name: len(seq) for name, seq in contigs.items()}
+        geo = row_geometry(self._lens, guidelen, pamlen, piece, self.max_bulge, guidelen)
+        self.rows: List[Tuple[str, int, int]] = [(name, off, own) for name, off, _end, own in geo]  # (contig, offset, owned window starts), all ranks' rows
+        spans = [(name, off, end) for name, off, end, _own in geo]
+        self.total = sum(self._lens.values())
         if not self.rows:
-            raise ValueError("genome shorter than one guide+PAM window")
+            raise ValueError(f"genome shorter than the shortest window the index is asked about ({min_spacer(guidelen)} + {pamlen} bases)")
         self.n_rows_total = len(self.rows)
         self.row_lo, self.row_hi = 0, self.n_rows_total
         if shard is not None and shard[1] > 1:
@@ -155,8 +180,7 @@ class GenomeIndex:
             arr = np.frombuffer(seq.encode("ascii"), dtype=np.uint8) if isinstance(seq, str) else np.frombuffer(seq, dtype=np.uint8)
             haps.append(HostHaplotype(arr[off:end], PosSegments.identity(off, end - off), True, (0, own)))
         self.ds = None
-        self._spans = spans[self.row_lo:self.row_hi]  # (contig, offset, end) of this rank's rows
-        self._piece, self._lens = piece, {name: len(seq) for name, seq in contigs.items()}
+        self._piece = piece
         self._meta_guidelen = guidelen
         if haps:  # a rank may own no row of a tiny genome
             self.ds = DeviceHapSet(haps, device)
@@ -168,14 +192,11 @@ class GenomeIndex:
         spacer length - the sites of bulged alignments - get their own scan ranges (hawk_hapset_set_meta; planes untouched)."""
         if guidelen == self._meta_guidelen or self.ds is None:
             return
-        if not (1 <= guidelen <= self.guidelen + self.max_bulge):
-            raise ValueError(f"window of {guidelen} + {self.pamlen} bases: the index was built for spacers of up to {self.guidelen + self.max_bulge}")
-        L = guidelen + self.pamlen
-        haps = []
-        for name, off, end in self._spans:
-            own = max(0, min(self._piece, self._lens[name] - off, end - off - L + 1))
-            haps.append(HostHaplotype(b"", PosSegments.identity(off, end - off), True, (0, own)))
-        self.ds.set_meta(haps)
+        if not (min_spacer(self.guidelen) <= guidelen <= self.guidelen + self.max_bulge):
+            raise ValueError(f"window of {guidelen} + {self.pamlen} bases: the index was built for spacers of "
+                             f"{min_spacer(self.guidelen)} to {self.guidelen + self.max_bulge}")
+        geo = row_geometry(self._lens, self.guidelen, self.pamlen, self._piece, self.max_bulge, guidelen)[self.row_lo:self.row_hi]
+        self.ds.set_meta([HostHaplotype(b"", PosSegments.identity(off, end - off), True, (0, own)) for _name, off, end, own in geo])
         self._meta_guidelen = guidelen
 
     def scan_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20, guidelen: Optional[int] = None):
@@ -210,14 +231,17 @@ class GenomeIndex:
         return hits, self.last_timing
 
     # ---- bulged sites (the -bDNA / -bRNA arguments of the reference's CRISPRitz call, offtargets.py:264-268) -------------
-    def scan_bulges(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int, brna: int, cap: int = 1 << 20) -> List["BulgeHit"]:
+    def scan_bulges(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int, brna: int, cap: int = 1 << 20,
+                    max_derived: int = 1 << 20) -> List["BulgeHit"]:
         """Sites that pair with a guide once `b` bases are bulged out - of the DNA (the site's spacer is b bases longer, b <= bdna)
         or of the RNA (b bases shorter, b <= brna) - with at most `max_mm` mismatches among the paired bases.  A bulged alignment
         is a mismatch-only alignment of a DERIVED guide: the guide with b interior bases deleted (RNA bulge), or with b bases
         inserted between its bases, every base tried (DNA bulge); each family of derived guides goes through hawk_offtarget_scan
         with its own spacer length, and the host keeps, per (guide, site, type, size), the placement with the fewest mismatches
         (ties: the lexicographically smallest bulge positions) - the definitions of oracle/hawk_oracle.c: ora_offtargets_bulges.
-        Bulges of up to 2 bases are enumerated (CRISPRitz's own limit)."""
+        Bulges of up to 2 bases are enumerated (CRISPRitz's own limit).  A family is derived and scanned for consecutive slices
+        of the guides, at most `max_derived` derived guides per scan (a DNA bulge of 2 turns a 20-mer into 3040 of them); rows
+        never depend on other guides, so the slicing does not change them."""
         if not (0 <= bdna <= 2 and 0 <= brna <= 2):
             raise ValueError("bulges of 0..2 bases are enumerated")
         if bdna > self.max_bulge:
@@ -227,12 +251,14 @@ class GenomeIndex:
         out: List[BulgeHit] = []
         for dna, bmax in ((True, bdna), (False, brna)):
             for b in range(1, bmax + 1):
-                derived, owner, gaps = _derived_guides(guides, G, b, dna)
-                if not derived:
-                    continue
+                step = max(1, int(max_derived) // max(1, derived_per_guide(G, b, dna)))
                 Gs = G + b if dna else G - b
-                h, _tm = self.scan_arrays(derived, pam, right, max_mm, cap, guidelen=Gs)
-                out += self._bulge_rows(h, guides, np.asarray(owner), np.asarray(gaps, dtype=np.uint64), Gs, b, dna, right, max_mm)
+                for g0 in range(0, len(guides), step):
+                    derived, owner, gaps = _derived_guides(guides[g0:g0 + step], G, b, dna)
+                    if not derived:
+                        continue
+                    h, _tm = self.scan_arrays(derived, pam, right, max_mm, cap, guidelen=Gs)
+                    out += self._bulge_rows(h, guides, np.asarray(owner) + g0, np.asarray(gaps, dtype=np.uint64), Gs, b, dna, right, max_mm)
         self._set_window(self.guidelen)
         out.sort(key=lambda r: (r.guide, r.bulge_type, r.bulge_size, self._contig_rank(r.contig), r.position, r.strand == "-"))
         return out

@@ -283,21 +283,37 @@ def test_bulged_offtargets_match_bruteforce(pam_s, guidelen, right, max_mm, bdna
     assert len(want) > 30 and {t[1] for t in want} == ({"DNA"} if not brna else {"RNA"} if not bdna else {"DNA", "RNA"})
     assert [(h.guide, h.bulge_type, h.bulge_size, h.contig, h.position, h.strand, h.mm, h.gaps) for h in got] == want
     # the strings of a row: the guide and the site re-derived from the genome, '-' at the bulges, mismatches in lower case
-    for h in got[:300]:
-        Gs = guidelen + h.bulge_size if h.bulge_type == "DNA" else guidelen - h.bulge_size
-        w = contigs[h.contig][h.position:h.position + Gs + len(pam_s)].upper()
-        w = ora.revcomp(w) if h.strand == "-" else w
-        w = "".join(c if c in "ACGT" else "N" for c in w)
-        site = w[len(pam_s):] if right else w[:Gs]
-        assert h.crrna.replace("-", "") == guides[h.guide] and h.dna.replace("-", "").upper() == site
-        assert len(h.crrna) == len(h.dna) and h.crrna.count("-") == (h.bulge_size if h.bulge_type == "DNA" else 0)
-        assert h.dna.count("-") == (h.bulge_size if h.bulge_type == "RNA" else 0)
-        assert sum(1 for a, b in zip(h.crrna, h.dna) if a != "-" and b != "-" and a != b.upper() or b.islower() and a == "-") >= 0
-        assert sum(1 for a, b in zip(h.crrna, h.dna) if b.islower()) == h.mm
+    _verify_bulge_rows_on_host(contigs, got[:300], guides, pam_s, guidelen, right, max_mm)
     # un-bulged scans before and after see the same rows: the window metadata is put back
     assert [(x.guide, x.contig, x.position, x.strand, x.mm) for x in idx.scan(guides, pam, right, max_mm)] == \
         sorted(((int(r["guide"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"])) for name, seq in contigs.items()
                 for r in ora.offtargets(seq, guides, pam_s, right, max_mm)), key=lambda t: (t[0], ci[t[1]], t[2], t[3] == "-"))
+
+
+def _verify_bulge_rows_on_host(contigs, rows, guides, pam_s, guidelen, right, max_mm):
+    """Every BulgeHit re-derived from the genome bytes: the crRNA is the guide and the DNA is the site's spacer, with '-' at the
+    bulges (as the gaps bitmask says) and mismatches in lower case; the mismatch count as reported and <= max_mm; the site's PAM
+    inside the PAM's IUPAC sets."""
+    from crisprhawk_hip.pam import IUPAC_BITS
+    nib = {"A": 1, "C": 2, "G": 4, "T": 8, "N": 0}
+    P = len(pam_s)
+    for h in rows:
+        Gs = guidelen + h.bulge_size if h.bulge_type == "DNA" else guidelen - h.bulge_size
+        w = contigs[h.contig][h.position:h.position + Gs + P].upper()
+        assert len(w) == Gs + P
+        w = ora.revcomp(w) if h.strand == "-" else w
+        w = "".join(c if c in "ACGT" else "N" for c in w)
+        site, pm = (w[P:], w[:P]) if right else (w[:Gs], w[Gs:])
+        assert h.pam == pm and all(IUPAC_BITS[q] == 15 or nib[c] & IUPAC_BITS[q] for c, q in zip(pm, pam_s))
+        assert h.crrna.replace("-", "") == guides[h.guide] and h.dna.replace("-", "").upper() == site
+        assert len(h.crrna) == len(h.dna) and h.crrna.count("-") == (h.bulge_size if h.bulge_type == "DNA" else 0)
+        assert h.dna.count("-") == (h.bulge_size if h.bulge_type == "RNA" else 0)
+        dashes = [i for i, (a, b) in enumerate(zip(h.crrna, h.dna)) if a == "-" or b == "-"]
+        assert h.gaps == sum(1 << i for i in dashes)  # DNA: site positions, RNA: guide positions (one column per base of each)
+        assert 0 not in dashes and len(h.crrna) - 1 not in dashes  # interior bulges only
+        assert sum(1 for a, b in zip(h.crrna, h.dna) if b.islower()) == h.mm <= max_mm
+        assert all(b.upper() != a or b.upper() == "N" for a, b in zip(h.crrna, h.dna) if b.islower())
+        assert all(b == a for a, b in zip(h.crrna, h.dna) if a != "-" and b != "-" and not b.islower())
 
 
 def test_offtarget_stage_with_bulges_writes_their_rows(tmp_path):
@@ -326,3 +342,293 @@ def test_offtarget_stage_with_bulges_writes_their_rows(tmp_path):
             assert "-" in r[3] and int(r[7]) == 1
         if r[8] == "RNA":
             assert "-" in r[4] and int(r[7]) == 1
+
+
+# ---- the row geometry at its edges, every match kernel, against the brute force -------------------------------------------------
+_CONCRETE = {"NGG": "TGG", "TTTV": "TTTA"}
+_KINDS = (("X", 0), ("DNA", 1), ("DNA", 2), ("RNA", 1), ("RNA", 2))
+
+
+def _mutate(rng, guide: str, kind: str, b: int, n_mm: int, ins: str = "") -> str:
+    """the site spacer of a planted site: the guide with n_mm substitutions, then b interior bases inserted (DNA bulge; `ins`
+    names them, else random) or deleted (RNA bulge)"""
+    sp = list(guide)
+    for p in rng.choice(len(sp), n_mm, replace=False).tolist():
+        sp[p] = "ACGT"["ACGT".index(sp[p]) ^ int(rng.integers(1, 4))]
+    for k in range(b):
+        if kind == "DNA":
+            sp.insert(int(rng.integers(1, len(sp))), ins[k] if ins else "ACGT"[int(rng.integers(0, 4))])
+        elif kind == "RNA":
+            del sp[int(rng.integers(1, len(sp) - 1))]
+    return "".join(sp)
+
+
+def _place(g: list, start: int, spacer: str, pam: str, right: bool, minus: bool):
+    w = (pam + spacer) if right else (spacer + pam)
+    w = ora.revcomp(w) if minus else w
+    g[start:start + len(w)] = list(w)
+    return len(w)
+
+
+def _edge_genome(pam_s: str, G: int, right: bool, piece: int, seed: int = 4242):
+    """Contigs at the edges of the row geometry - lengths L-2, L-1, L, piece+L-2, piece+L-1, k*piece, k*piece+1 - with sites of
+    every kind (mismatch-only, DNA / RNA bulges of 1 and 2) planted at start 0, at the contig's last start n - Lw, and at every
+    start from seam - Lw through the seam of many row seams (one per seam), on both strands; N / IUPAC bases as first and last
+    bases, in a PAM and as a DNA-bulged base.  Returns (contigs, guides: 70 guides in seed-sharing families, planted: the sites
+    as (guide, contig, start, strand, kind, bulge))."""
+    rng = np.random.default_rng(seed + piece + G)
+    P, pam = len(pam_s), _CONCRETE[pam_s]
+    L = G + P
+    guides = [synth.random_sequence(rng, G) for _ in range(70)]
+    for k in range(6, 70, 5):  # families: pairs that share seed blocks
+        g = list(guides[k % 6])
+        g[int(rng.integers(0, G))] = "ACGT"[int(rng.integers(0, 4))]
+        guides[k] = "".join(g)
+    contigs, planted = {}, []
+
+    def plant(g, name, start, gi, kind, b, minus, n_mm=None, ins=""):
+        sp = _mutate(rng, guides[gi], kind, b, int(rng.integers(0, 3)) if n_mm is None else n_mm, ins)
+        _place(g, start, sp, pam, right, minus)
+        planted.append((gi, name, start, "-" if minus else "+", kind, b))
+
+    # whole contigs that are one window each: L-2 (an RNA bulge of 2), L-1 (of 1), L (mismatch-only)
+    for n, (kind, b) in ((L - 2, ("RNA", 2)), (L - 1, ("RNA", 1)), (L, ("X", 0))):
+        for minus in (False, True):
+            g = list(synth.random_sequence(rng, n))
+            plant(g, f"w{n}{'m' if minus else 'p'}", 0, 0, kind, b, minus, n_mm=0)
+            contigs[f"w{n}{'m' if minus else 'p'}"] = "".join(g)
+    # contigs that end at or just past a seam: sites at start 0 and at the last start
+    for ci, n in enumerate((piece + L - 2, piece + L - 1, piece, piece + 1, 2 * piece, 2 * piece + 1, 3 * piece + L - 1)):
+        for minus in (False, True):
+            name = f"e{n}{'m' if minus else 'p'}"
+            g = list(synth.random_sequence(rng, n))
+            for ki, where in ((ci % 5, 0), ((ci + 2) % 5, None)):  # one kind at start 0, another at its last start
+                kind, b = _KINDS[ki]
+                Lw = L + (b if kind == "DNA" else -b)
+                plant(g, name, n - Lw if where is None else 0, (ki + 1) % 6, kind, b, minus)
+            contigs[name] = "".join(g)
+    # seams: every kind at every start seam - Lw .. seam, strands alternating, one site per seam of 16-piece contigs
+    todo = [(kind, b, d, (d + ki) % 2 == 1) for ki, (kind, b) in enumerate(_KINDS) for d in range(0, L + (b if kind == "DNA" else -b) + 1)]
+    per = 15
+    for c0 in range(0, len(todo), per):
+        name = f"s{c0 // per}"
+        g = list(synth.random_sequence(rng, 16 * piece + L - 1))
+        for j, (kind, b, d, minus) in enumerate(todo[c0:c0 + per]):
+            plant(g, name, (j + 1) * piece - d, j % 4, kind, b, minus)
+        contigs[name] = "".join(g)
+    # N / IUPAC: first and last bases, a PAM base, a DNA-bulged base
+    name = "amb"
+    g = list(synth.random_sequence(rng, 3 * piece))
+    plant(g, name, 0, 1, "X", 0, False, n_mm=0)
+    plant(g, name, len(g) - L, 2, "X", 0, True, n_mm=0)
+    g[0], g[-1] = "N", "R"
+    ppos = 0 if right else G  # the PAM's first base (+ strand)
+    plant(g, name, piece - 7, 3, "X", 0, False, n_mm=0)
+    g[piece - 7 + ppos + P - 1] = "N"
+    plant(g, name, 2 * piece - 9, 4, "X", 0, False, n_mm=0)
+    g[2 * piece - 9 + ppos + P - 1] = "S"
+    plant(g, name, piece + 100, 0, "DNA", 1, False, n_mm=0, ins="N")
+    plant(g, name, piece + 300, 1, "DNA", 2, True, n_mm=0, ins="YA")
+    contigs[name] = "".join(g)
+    return contigs, guides, planted
+
+
+_EDGE_CACHE = {}
+
+
+def _edge_case(pam_s: str, G: int, right: bool, piece: int, max_mm: int = 2):
+    """(contigs, guides, planted, want mismatch-only rows, want bulge rows) of an edge genome - the brute force once per case"""
+    key = (pam_s, G, right, piece, max_mm)
+    if key not in _EDGE_CACHE:
+        contigs, guides, planted = _edge_genome(pam_s, G, right, piece)
+        ci = {n: i for i, n in enumerate(contigs)}
+        want_mm, want_b = [], []
+        for name, seq in contigs.items():
+            want_mm += [(int(r["guide"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"]))
+                        for r in ora.offtargets(seq, guides, pam_s, right, max_mm)]
+            want_b += [(int(r["guide"]), "DNA" if r["btype"] == 1 else "RNA", int(r["bsize"]), name, int(r["pos"]), "-" if r["strand"] else "+",
+                        int(r["mm"]), int(r["gaps"])) for r in ora.offtargets_bulges(seq, guides[:6], pam_s, right, max_mm, 2, 2)]
+        want_mm.sort(key=lambda t: (t[0], ci[t[1]], t[2], t[3] == "-"))
+        want_b.sort(key=lambda t: (t[0], t[1], t[2], ci[t[3]], t[4], t[5] == "-"))
+        _EDGE_CACHE[key] = (contigs, guides, planted, want_mm, want_b)
+    return _EDGE_CACHE[key]
+
+
+def _edge_scan(pam_s: str, G: int, right: bool, piece: int, max_mm: int = 2, max_derived: int = 1 << 20):
+    """the device's rows of an edge genome: mismatch-only for all 70 guides, DNA / RNA bulges of up to 2 for the first 6"""
+    contigs, guides, _planted = _edge_genome(pam_s, G, right, piece)
+    pam = PAM(pam_s, right, True)
+    pam.encode(0)
+    idx = GenomeIndex(contigs, G, len(pam_s), piece=piece, max_bulge=2)
+    got_mm = [(h.guide, h.contig, h.position, h.strand, h.mm) for h in idx.scan(guides, pam, right, max_mm)]
+    got_b = [(h.guide, h.bulge_type, h.bulge_size, h.contig, h.position, h.strand, h.mm, h.gaps)
+             for h in idx.scan_bulges(guides[:6], pam, right, max_mm, 2, 2, max_derived=max_derived)]
+    return got_mm, got_b
+
+
+def _child_scan(env: dict, args: tuple):
+    """_edge_scan in a fresh process: HAWK_OT_SEED_GLOBAL / HAWK_OT_ALLPAIRS are read once per process.  One run, bounded; its
+    failure ends the test."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (f"import sys, json\nsys.path[:0] = {[os.path.join(root, 'crispr-hawk_amd'), root, os.path.join(root, 'tests')]!r}\n"
+            f"import test_gpu_offtargets as t\nprint('RESULT', json.dumps(t._edge_scan(*{args!r})))\n")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got_mm, got_b = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][0][7:])
+    return [tuple(t) for t in got_mm], [tuple(t) for t in got_b]
+
+
+@pytest.mark.parametrize("kernel", ["pair_seeds", "seeded_lds", "seeded_global", "all_pairs"])
+@pytest.mark.parametrize("pam_s,G,right,piece", [("NGG", 20, False, 512), ("TTTV", 23, True, 1000)])
+def test_offtarget_edges_match_bruteforce(pam_s, G, right, piece, kernel, monkeypatch):
+    """Sites at the edges of the row geometry (a contig's first and last window start, every start around a row seam, contigs
+    no longer than one window, N / IUPAC bases at the ends, in a PAM and in a bulge), mismatch-only and with DNA / RNA bulges of
+    1 and 2, on both strands, through each of the four match kernels: exactly the brute force's rows."""
+    contigs, guides, planted, want_mm, want_b = _edge_case(pam_s, G, right, piece)
+    if kernel in ("pair_seeds", "seeded_lds"):
+        if kernel == "seeded_lds":
+            monkeypatch.setenv("HAWK_OT_PAIRS", "0")
+        got_mm, got_b = _edge_scan(pam_s, G, right, piece)
+    else:
+        got_mm, got_b = _child_scan({"HAWK_OT_SEED_GLOBAL": "1"} if kernel == "seeded_global" else {"HAWK_OT_ALLPAIRS": "1"},
+                                    (pam_s, G, right, piece))
+    # the brute force sees what was planted (the ambiguous-base plants excepted): the sweep reaches every edge it claims to
+    sites_mm = {(t[0], t[1], t[2], t[3]) for t in want_mm}
+    sites_b = {(t[0], t[1], t[2], t[3], t[4], t[5]) for t in want_b}
+    for gi, name, start, strand, kind, b in planted:
+        if name == "amb":
+            continue
+        assert ((gi, name, start, strand) in sites_mm) if kind == "X" else ((gi, kind, b, name, start, strand) in sites_b), (gi, name, start, kind, b)
+    assert got_mm == want_mm
+    assert got_b == want_b
+
+
+def test_bulged_site_in_a_contig_tail_is_reported():
+    """Regression: an RNA-bulged site whose window starts at `piece` of a contig of piece + L - 1 bases, and one that is a whole
+    contig of L - 1 bases, lie in no row of full windows; both must be reported."""
+    rng = np.random.default_rng(31)
+    G, P, piece = 20, 3, 4096
+    L = G + P
+    guide = synth.random_sequence(rng, G)
+    site = guide[:9] + guide[10:]  # an RNA bulge of 1 at guide position 9
+    tail = synth.random_sequence(rng, piece + L - 1 - (L - 1)) + site + "AGG"
+    short = site + "TGG"
+    contigs = {"tail": tail, "short": short}
+    pam = PAM("NGG", False, True)
+    pam.encode(0)
+    idx = GenomeIndex(contigs, G, P, piece=piece)
+    got = [(h.guide, h.bulge_type, h.bulge_size, h.contig, h.position, h.strand, h.mm, h.gaps) for h in idx.scan_bulges([guide], pam, False, 0, 0, 2)]
+    assert {(t[3], t[4]) for t in got if t[1:3] == ("RNA", 1) and t[5:7] == ("+", 0)} >= {("tail", piece), ("short", 0)}
+    want = sorted(((0, "RNA", int(r["bsize"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"]), int(r["gaps"]))
+                   for name, seq in contigs.items() for r in ora.offtargets_bulges(seq, [guide], "NGG", False, 0, 0, 2)),
+                  key=lambda t: (t[0], t[1], t[2], ["tail", "short"].index(t[3]), t[4], t[5] == "-"))
+    assert got == want
+
+
+@pytest.mark.parametrize("n_guides", [63, 64, 1024, 1025])
+@pytest.mark.parametrize("pairs", [True, False])
+@pytest.mark.parametrize("pam_s,G,right,max_mm", [("NGG", 20, False, 3), ("TTTV", 23, True, 4)])
+def test_offtarget_guide_count_boundaries(pam_s, G, right, max_mm, n_guides, pairs, monkeypatch):
+    """Mismatch-only scans at the guide counts where the match kernel changes: 63 / 64 (all pairs below 64 guides, seeds from 64)
+    and 1024 / 1025 (one LDS chunk of the single-block seeds, or two), pair seeds and LDS seeds, guides in families that share
+    seed blocks: exactly the brute force's rows."""
+    if not pairs:
+        monkeypatch.setenv("HAWK_OT_PAIRS", "0")
+    rng = np.random.default_rng(n_guides + G)
+    guides = [synth.random_sequence(rng, G) for _ in range(n_guides)]
+    for k in range(6, n_guides, 7):
+        g = list(guides[k % 6])
+        for p in rng.choice(G, int(rng.integers(1, max_mm + 2)), replace=False).tolist():
+            g[p] = "ACGT"[int(rng.integers(0, 4))]
+        guides[k] = "".join(g)
+    contigs = {}
+    for name, n in (("c1", 20_000), ("c2", 4096 + G + len(pam_s) - 1)):
+        g = list(synth.random_sequence(rng, n, iupac_frac=0.001))
+        for gd in guides[:6] + guides[-3:]:
+            _plant(rng, g, gd, _CONCRETE[pam_s], right, 4, max_mm)
+        contigs[name] = "".join(g)
+    pam = PAM(pam_s, right, True)
+    pam.encode(0)
+    got = GenomeIndex(contigs, G, len(pam_s), piece=4096).scan(guides, pam, right, max_mm)
+    ci = {n: i for i, n in enumerate(contigs)}
+    want = sorted(((int(r["guide"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"])) for name, seq in contigs.items()
+                   for r in ora.offtargets(seq, guides, pam_s, right, max_mm)), key=lambda t: (t[0], ci[t[1]], t[2], t[3] == "-"))
+    assert len(want) > 40 and any(t[0] == n_guides - 1 for t in want)  # the last guide (the one past a chunk edge) has rows
+    assert [(h.guide, h.contig, h.position, h.strand, h.mm) for h in got] == want
+
+
+@pytest.mark.parametrize("pam_s,G,right,bdna,brna", [("NGG", 29, False, 0, 0), ("TTTV", 28, True, 0, 0), ("NGG", 27, False, 2, 2)])
+def test_offtarget_32_base_windows(pam_s, G, right, bdna, brna):
+    """Windows at the 32-base limit of the window code (29 + NGG, 28 + TTTV; 27 + NGG with a DNA bulge of 2): exactly the brute
+    force's rows.  One base more is refused before any device work."""
+    rng = np.random.default_rng(G + bdna)
+    max_mm = 3 if not bdna else 2
+    guides = [synth.random_sequence(rng, G) for _ in range(70 if not bdna else 3)]
+    contigs = {}
+    for name, n in (("c1", 12_000), ("c2", 1024 + G + len(pam_s) + bdna - 1)):
+        g = list(synth.random_sequence(rng, n, iupac_frac=0.001))
+        for gi in range(3):
+            for _ in range(6):
+                kind, b = _KINDS[int(rng.integers(0, 5 if bdna else 1))]
+                sp = _mutate(rng, guides[gi], kind, b, int(rng.integers(0, max_mm + 1)))
+                _place(g, int(rng.integers(0, n - len(sp) - len(pam_s))), sp, _CONCRETE[pam_s], right, bool(rng.random() < 0.5))
+        contigs[name] = "".join(g)
+    pam = PAM(pam_s, right, True)
+    pam.encode(0)
+    idx = GenomeIndex(contigs, G, len(pam_s), piece=1024, max_bulge=bdna)
+    ci = {n: i for i, n in enumerate(contigs)}
+    got = [(h.guide, h.contig, h.position, h.strand, h.mm) for h in idx.scan(guides, pam, right, max_mm)]
+    want = sorted(((int(r["guide"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"])) for name, seq in contigs.items()
+                   for r in ora.offtargets(seq, guides, pam_s, right, max_mm)), key=lambda t: (t[0], ci[t[1]], t[2], t[3] == "-"))
+    assert len(want) >= 3 and got == want
+    assert all(len(h.window) == G + len(pam_s) for h in idx.scan(guides[:3], pam, right, max_mm))
+    if bdna or brna:
+        rows = idx.scan_bulges(guides, pam, right, max_mm, bdna, brna)
+        got_b = [(h.guide, h.bulge_type, h.bulge_size, h.contig, h.position, h.strand, h.mm, h.gaps) for h in rows]
+        want_b = sorted(((int(r["guide"]), "DNA" if r["btype"] == 1 else "RNA", int(r["bsize"]), name, int(r["pos"]), "-" if r["strand"] else "+",
+                          int(r["mm"]), int(r["gaps"])) for name, seq in contigs.items()
+                         for r in ora.offtargets_bulges(seq, guides, pam_s, right, max_mm, bdna, brna)),
+                        key=lambda t: (t[0], t[1], t[2], ci[t[3]], t[4], t[5] == "-"))
+        assert ("DNA", 2) in {(t[1], t[2]) for t in want_b} and got_b == want_b
+        _verify_bulge_rows_on_host(contigs, rows, guides, pam_s, G, right, max_mm)
+    with pytest.raises(ValueError, match="32 bases"):
+        GenomeIndex(contigs, G + 1, len(pam_s), max_bulge=bdna)
+
+
+def test_bulged_offtargets_at_scale():
+    """1 500 guides with DNA and RNA bulges of up to 2 on 120 kb (4.6 million derived guides for the DNA bulges of 2): the rows of
+    a random sample of guides equal the brute force's on those guides alone (rows never depend on other guides); the whole row
+    list is the same with the derived guides scanned 4 096 at a time and at the default cap; every row re-derives on the host."""
+    import random
+    rng = np.random.default_rng(2024)
+    G, P, max_mm = 20, 3, 2
+    guides = [synth.random_sequence(rng, G) for _ in range(1500)]
+    contigs = {}
+    for name, n in (("c1", 70_000), ("c2", 50_000 + G + P - 1)):
+        g = list(synth.random_sequence(rng, n, iupac_frac=0.0005))
+        for gi in rng.choice(len(guides), 150, replace=False).tolist():
+            kind, b = _KINDS[int(rng.integers(0, 5))]
+            sp = _mutate(rng, guides[gi], kind, b, int(rng.integers(0, max_mm + 1)))
+            _place(g, int(rng.integers(0, n - len(sp) - P)), sp, "AGG", False, bool(rng.random() < 0.5))
+        contigs[name] = "".join(g)
+    pam = PAM("NGG", False, True)
+    pam.encode(0)
+    idx = GenomeIndex(contigs, G, P, piece=1 << 15, max_bulge=2)
+    key = lambda h: (h.guide, h.bulge_type, h.bulge_size, h.contig, h.position, h.strand, h.mm, h.gaps, h.crrna, h.dna, h.pam)
+    full = [key(h) for h in idx.scan_bulges(guides, pam, False, max_mm, 2, 2)]
+    small = idx.scan_bulges(guides, pam, False, max_mm, 2, 2, max_derived=4096)
+    assert [key(h) for h in small] == full
+    assert len(full) > 300 and {(t[1], t[2]) for t in full} == {("DNA", 1), ("DNA", 2), ("RNA", 1), ("RNA", 2)}
+    _verify_bulge_rows_on_host(contigs, small, guides, "NGG", G, False, max_mm)
+    # a sample of guides (some with planted sites, some without) against the brute force on those guides alone
+    with_rows = sorted({t[0] for t in full})
+    sample = sorted(random.Random(7).sample(with_rows, 12) + random.Random(8).sample(range(len(guides)), 8))
+    sample = list(dict.fromkeys(sample))
+    ci = {n: i for i, n in enumerate(contigs)}
+    want = sorted(((sample[int(r["guide"])], "DNA" if r["btype"] == 1 else "RNA", int(r["bsize"]), name, int(r["pos"]),
+                    "-" if r["strand"] else "+", int(r["mm"]), int(r["gaps"])) for name, seq in contigs.items()
+                   for r in ora.offtargets_bulges(seq, [guides[i] for i in sample], "NGG", False, max_mm, 2, 2)),
+                  key=lambda t: (t[0], t[1], t[2], ci[t[3]], t[4], t[5] == "-"))
+    chosen = set(sample)
+    assert [t[:8] for t in full if t[0] in chosen] == want and len(want) >= 12

@@ -121,3 +121,77 @@ def test_posmap_rev_helper_matches_numpy():
     for g in (startp, startp + 100, startp + 9_999, deleted, startp + 25_000, startp - 1):
         assert np.array_equal(m._rev_all(g), m._rev_all_numpy(g)), g
     assert (m._rev_all(deleted) == -1).any()
+
+
+def _old_row_own(n, off, end, piece, L):
+    """the owned starts of a row as the index computed them for mismatch-only windows before the tail rows existed"""
+    return min(piece, n - off, end - off - L + 1) if end - off >= L else None
+
+
+@pytest.mark.parametrize("guidelen,pamlen", [(20, 3), (23, 4), (29, 3)])
+@pytest.mark.parametrize("piece", [64, 512, 1000, 4096])
+def test_genome_row_geometry_owns_every_window_once(guidelen, pamlen, piece):
+    """GenomeIndex's rows (genome.row_geometry) at the edges of the piece geometry: every window start of every window length
+    the index can be asked about - RNA-bulged sites (spacer guidelen - 1, - 2: no extra overlap needed) up to DNA-bulged ones
+    (guidelen + max_bulge) - is owned by exactly one row, and its window lies inside that row.  Mismatch-only windows keep the
+    rows they had."""
+    for max_bulge in range(0, min(2, 32 - guidelen - pamlen) + 1):  # windows of up to the 32 bases the device encodes
+        _check_row_geometry(guidelen, pamlen, piece, max_bulge)
+
+
+def _check_row_geometry(guidelen, pamlen, piece, max_bulge):
+    from crisprhawk_hip.genome import min_spacer, row_geometry
+    L = guidelen + pamlen
+    overlap = L + max_bulge - 1
+    lens = sorted({0, 1, *range(L - 3, L + 4), *range(piece - 1, piece + 2), *range(piece + L - 4, piece + L + 3),
+                   2 * piece + overlap - 1, 2 * piece + overlap, 2 * piece + overlap + 1, 3 * piece, 3 * piece + 1})
+    lengths = {f"c{n}": n for n in lens}
+    spans = None
+    for spacer in range(min_spacer(guidelen), guidelen + max_bulge + 1):
+        Lw = spacer + pamlen
+        geo = row_geometry(lengths, guidelen, pamlen, piece, max_bulge, spacer)
+        if spans is None:
+            spans = [r[:3] for r in geo]
+        assert [r[:3] for r in geo] == spans  # the rows themselves do not depend on the window
+        owned = {name: np.zeros(n + 1, dtype=np.int64) for name, n in lengths.items()}
+        for name, off, end, own in geo:
+            n = lengths[name]
+            assert 0 <= off < end <= n and own >= 0
+            if own:
+                assert off + own - 1 + Lw <= end  # the last owned window lies inside the row
+            owned[name][off:off + own] += 1
+        for name, n in lengths.items():
+            m = max(0, n - Lw + 1)  # starts s with s + Lw <= n
+            bad = np.flatnonzero(owned[name][:m] != 1)
+            assert len(bad) == 0, f"{name}, window {Lw}: starts {bad[:8].tolist()} owned {owned[name][bad[:8]].tolist()} times"
+            assert not owned[name][m:].any(), f"{name}, window {Lw}: a start past the last window is owned"
+        assert [r[0] for r in geo] == sorted((r[0] for r in geo), key=list(lengths).index)  # contig order
+    # mismatch-only windows: the rows that existed before own what they owned; the tail rows added for shorter windows own nothing
+    for name, off, end, own in row_geometry(lengths, guidelen, pamlen, piece, max_bulge, guidelen):
+        old = _old_row_own(lengths[name], off, end, piece, L)
+        assert own == (0 if old is None else old)
+
+
+def test_genome_index_refuses_before_device_work():
+    """Windows the device cannot encode (more than 32 bases with the largest DNA bulge) and genomes without a single window are
+    refused at construction, before any device is touched; the message names the shortest window."""
+    from crisprhawk_hip.genome import GenomeIndex
+    with pytest.raises(ValueError, match="32 bases"):
+        GenomeIndex({"c": "ACGT" * 100}, 28, 3, max_bulge=2)
+    with pytest.raises(ValueError, match="32 bases"):
+        GenomeIndex({"c": "ACGT" * 100}, 30, 3)
+    with pytest.raises(ValueError, match=r"18 \+ 3 bases"):
+        GenomeIndex({"a": "ACGTACGTACGTACGTACGT", "b": ""}, 20, 3)
+
+
+@pytest.mark.parametrize("G", [17, 20, 23])
+def test_derived_guide_count_bounds_a_chunk(G):
+    """scan_bulges sizes its guide slices by derived_per_guide: exact for DNA bulges, an upper bound for RNA bulges (identical
+    deletions are kept once)."""
+    from crisprhawk_hip.genome import _derived_guides, derived_per_guide
+    rng = np.random.default_rng(G)
+    for g in ("".join("ACGT"[i] for i in rng.integers(0, 4, G)), "A" * G, "AC" * (G // 2) + "A" * (G % 2)):
+        for b in (1, 2):
+            assert len(_derived_guides([g], G, b, True)[0]) == derived_per_guide(G, b, True)
+            assert 0 < len(_derived_guides([g], G, b, False)[0]) <= derived_per_guide(G, b, False)
+    assert derived_per_guide(20, 2, True) == 3040
