@@ -21,9 +21,8 @@ static int collapse_by_templates(hawk_table* t, uint32_t flank_up, uint32_t flan
 int hawk_table_collapse_ex(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
   if (!t || !n_groups || !t->hs || hawk_table_stale(t)) return HAWK_E_INVALID;
   if (flank_up > HAWK_PAD || flank_down > HAWK_PAD) return HAWK_E_UNSUPPORTED;
-  // A table the cluster search wrote is grouped on its template rows (HAWK_COLLAPSE_TEMPLATES=0: on its own rows, as any table)
-  const char* et = getenv("HAWK_COLLAPSE_TEMPLATES");
-  if (t->by_cluster && t->n_rows && !(et && et[0] == '0')) return collapse_by_templates(t, flank_up, flank_down, n_groups, kernel_ms);
+  // A table the cluster search wrote is grouped on its template rows
+  if (t->by_cluster && t->n_rows) return collapse_by_templates(t, flank_up, flank_down, n_groups, kernel_ms);
   return collapse_rows(t, flank_up, flank_down, n_groups, kernel_ms);
 }
 static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {

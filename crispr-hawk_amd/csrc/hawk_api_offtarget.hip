@@ -14,6 +14,51 @@
 
 #include "hawk_host.h"
 
+// The spacer cut into nb blocks of G / nb bases (the first G % nb one longer); a block's key is its first <= kmax bases.
+static void ot_blocks(int G, int nb, int kmax, int32_t* start, int32_t* klen, uint64_t* pmask2) {
+  int startb = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int len = G / nb + (b < G % nb ? 1 : 0), kl = std::min(len, kmax);
+    start[b] = startb; klen[b] = kl;
+    for (int t = 0; t < kl; ++t) pmask2[b] |= 1ull << (2 * (startb + t));
+    startb += len;
+  }
+}
+
+// The bucketed guide tables of the seeded match kernels, one counting sort per table t: its bucket offsets (4^key_bases(t) + 1)
+// back to back in otoff from off_base[t], the guides' codes and ids in bucket order in row t of otcode / otid ([n_tables][n_guides]).
+// A bucket keeps its guides in input order.
+template <class KeyBases, class KeyOf>
+static int ot_seed_tables(hawk_hapset* hs, const uint64_t* guides2, uint32_t n_guides, int n_tables, uint32_t* off_base,
+                          KeyBases key_bases, KeyOf key_of) {
+  std::vector<uint32_t> goff, keys(n_guides);
+  std::vector<uint64_t> gcode((size_t)n_tables * n_guides, 0);
+  std::vector<uint32_t> gid((size_t)n_tables * n_guides, 0);
+  for (int t = 0; t < n_tables; ++t) {
+    const uint32_t nkeys = 1u << (2 * key_bases(t));
+    off_base[t] = (uint32_t)goff.size();
+    std::vector<uint32_t> cnt(nkeys + 1, 0);
+    for (uint32_t g = 0; g < n_guides; ++g) ++cnt[(keys[g] = key_of(t, guides2[g])) + 1];
+    for (uint32_t v = 0; v < nkeys; ++v) cnt[v + 1] += cnt[v];
+    goff.insert(goff.end(), cnt.begin(), cnt.end());
+    std::vector<uint32_t> cur(cnt.begin(), cnt.end() - 1);
+    for (uint32_t g = 0; g < n_guides; ++g) {
+      const uint32_t slot = cur[keys[g]]++;
+      gcode[(size_t)t * n_guides + slot] = guides2[g];
+      gid[(size_t)t * n_guides + slot] = g;
+    }
+  }
+  int rc;
+  if ((rc = hs->otoff.reserve(goff.size() * 4)) || (rc = hs->otcode.reserve(gcode.size() * 8)) || (rc = hs->otid.reserve(gid.size() * 4)))
+    return rc;
+  hipStream_t st = hs->ctx->stream;
+  HIPCHK(hipMemcpyAsync(hs->otoff.p, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(hs->otcode.p, gcode.data(), gcode.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(hs->otid.p, gid.data(), gid.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));  // the host vectors go out of scope
+  return HAWK_OK;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------- K7 off-targets
@@ -49,105 +94,38 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
       (rc = hs->partial.reserve((ncnt / 1024 + 2) * 8)) || (rc = hs->misc.reserve(512 * 8 + 64)) ||
       (rc = hs->guides.reserve(std::max<size_t>((size_t)n_guides * 8, 16))))
     return rc;
-  // Pigeonhole seeds when they pay: enough guides to bucket, and blocks of at least two bases.  HAWK_OT_ALLPAIRS=1
-  // keeps the all-pairs kernel (A/B measurements, and the parity test runs both).
-  static const bool force_allpairs = [] { const char* e = getenv("HAWK_OT_ALLPAIRS"); return e && e[0] == '1'; }();
+  // The match kernel is a function of (n_guides, max_mm, G) alone.  Pigeonhole seeds pay with enough guides to bucket and blocks
+  // of at least two bases: pair seeds (max_mm + 2 blocks, k_ot_match_pairs) where they fit, else single-block seeds (max_mm + 1
+  // blocks, k_ot_match_seeded).  All pairs otherwise; HAWK_OT_ALLPAIRS=1 (read per call) forces them, the reference the parity
+  // tests compare the seeded kernels against.
+  const char* e_all = getenv("HAWK_OT_ALLPAIRS");
   const int G = (int)p->guidelen, nb = (int)p->max_mm + 1;
-  const bool seeded = !force_allpairs && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
+  const bool seeded = !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
+  const bool pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
   OtSeeds sd;
-  memset(&sd, 0, sizeof(sd));
-  // LDS variant: guides in chunks of OT_LDS_CHUNK, 4 key bases per block (nb * 8.5 KB of LDS must leave room for a few
-  // workgroups per CU); HAWK_OT_SEED_GLOBAL=1 keeps the single-table global-gather kernel
-  static const bool seed_global = [] { const char* e = getenv("HAWK_OT_SEED_GLOBAL"); return e && e[0] == '1'; }();
-  // Pair seeds (max_mm + 2 blocks, buckets per pair of blocks: hawk_offtarget.hip k_ot_match_pairs) are the default where they
-  // apply: HAWK_OT_PAIRS=0 keeps the single-block seeds (the parity tests run every kernel against the brute force)
-  const char* e_pairs = getenv("HAWK_OT_PAIRS");
-  const int nb2 = (int)p->max_mm + 2;
-  const bool pairs = seeded && !seed_global && !(e_pairs && e_pairs[0] == '0') && nb2 <= OT_MAX_BLOCKS && nb2 <= G;
-  const bool seed_lds = seeded && !pairs && !seed_global && nb <= 6;
-  const uint32_t chunk = seed_lds ? OT_LDS_CHUNK : n_guides;
-  const uint32_t n_chunks = seeded ? (n_guides + chunk - 1) / chunk : 0;
   OtPairSeeds ps;
+  memset(&sd, 0, sizeof(sd));
   memset(&ps, 0, sizeof(ps));
   if (pairs) {
-    ps.nb = nb2;
-    int startb = 0;
-    for (int b = 0; b < nb2; ++b) {  // blocks of G / nb2 bases (the first G % nb2 one longer); key = a block's first <= 4 bases
-      const int len = G / nb2 + (b < G % nb2 ? 1 : 0), kl = std::min(len, 4);
-      ps.start[b] = startb; ps.klen[b] = kl;
-      for (int t = 0; t < kl; ++t) ps.pmask2[b] |= 1ull << (2 * (startb + t));
-      startb += len;
-    }
-    for (int bi = 0; bi < nb2; ++bi)
-      for (int bj = bi + 1; bj < nb2; ++bj) { ps.pi[ps.n_pairs] = (uint8_t)bi; ps.pj[ps.n_pairs] = (uint8_t)bj; ++ps.n_pairs; }
-    std::vector<uint32_t> goff;
-    std::vector<uint64_t> gcode((size_t)ps.n_pairs * n_guides, 0);
-    std::vector<uint32_t> gid((size_t)ps.n_pairs * n_guides, 0);
-    std::vector<uint32_t> keys(n_guides);
-    for (int q = 0; q < ps.n_pairs; ++q) {
-      const int bi = ps.pi[q], bj = ps.pj[q];
-      const uint32_t mi = (1u << (2 * ps.klen[bi])) - 1u, mj = (1u << (2 * ps.klen[bj])) - 1u;
-      const uint32_t nkeys = 1u << (2 * (ps.klen[bi] + ps.klen[bj]));
-      ps.off_base[q] = (uint32_t)goff.size();
-      std::vector<uint32_t> cnt(nkeys + 1, 0);
-      for (uint32_t g = 0; g < n_guides; ++g) {
-        keys[g] = ((uint32_t)(guides2[g] >> (2 * ps.start[bi])) & mi) | (((uint32_t)(guides2[g] >> (2 * ps.start[bj])) & mj) << (2 * ps.klen[bi]));
-        ++cnt[keys[g] + 1];
-      }
-      for (uint32_t v = 0; v < nkeys; ++v) cnt[v + 1] += cnt[v];
-      goff.insert(goff.end(), cnt.begin(), cnt.end());
-      std::vector<uint32_t> cur(cnt.begin(), cnt.end() - 1);
-      for (uint32_t g = 0; g < n_guides; ++g) {  // counting sort: guides of one bucket stay in input order
-        const uint32_t slot = cur[keys[g]]++;
-        gcode[(size_t)q * n_guides + slot] = guides2[g];
-        gid[(size_t)q * n_guides + slot] = g;
-      }
-    }
-    if ((rc = hs->otoff.reserve(goff.size() * 4)) || (rc = hs->otcode.reserve(gcode.size() * 8)) || (rc = hs->otid.reserve(gid.size() * 4)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(hs->otoff.p, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hs->otcode.p, gcode.data(), gcode.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hs->otid.p, gid.data(), gid.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
+    ps.nb = nb + 1;
+    ot_blocks(G, ps.nb, 4, ps.start, ps.klen, ps.pmask2);
+    for (int bi = 0; bi < ps.nb; ++bi)
+      for (int bj = bi + 1; bj < ps.nb; ++bj) { ps.pi[ps.n_pairs] = (uint8_t)bi; ps.pj[ps.n_pairs] = (uint8_t)bj; ++ps.n_pairs; }
+    // pair q's key: the key bases of block pi[q], then those of block pj[q]
+    rc = ot_seed_tables(hs, guides2, n_guides, ps.n_pairs, ps.off_base, [&](int q) { return ps.klen[ps.pi[q]] + ps.klen[ps.pj[q]]; },
+                        [&](int q, uint64_t c) {
+                          const int bi = ps.pi[q], bj = ps.pj[q];
+                          const uint32_t ki = (uint32_t)(c >> (2 * ps.start[bi])) & ((1u << (2 * ps.klen[bi])) - 1u);
+                          const uint32_t kj = (uint32_t)(c >> (2 * ps.start[bj])) & ((1u << (2 * ps.klen[bj])) - 1u);
+                          return ki | (kj << (2 * ps.klen[bi]));
+                        });
   } else if (seeded) {
     sd.nb = nb;
-    const int kmax = seed_lds ? 4 : 6;
-    int startb = 0;
-    for (int b = 0; b < nb; ++b) {
-      const int len = G / nb + (b < G % nb ? 1 : 0), kl = std::min(len, kmax);
-      sd.start[b] = startb; sd.klen[b] = kl;
-      for (int t = 0; t < kl; ++t) sd.pmask2[b] |= 1ull << (2 * (startb + t));
-      startb += len;
-    }
-    // tables per (chunk, block): bucket offsets (inside the chunk), codes and guide ids in bucket order
-    std::vector<uint32_t> goff;
-    std::vector<uint64_t> gcode((size_t)n_chunks * nb * chunk, 0);
-    std::vector<uint32_t> gid((size_t)n_chunks * nb * chunk, 0);
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-      const uint32_t g0 = c * chunk, ng = std::min<uint32_t>(chunk, n_guides - g0);
-      for (int b = 0; b < nb; ++b) {
-        const uint32_t nkeys = seed_lds ? OT_LDS_KEYS : (1u << (2 * sd.klen[b])), kmask = (1u << (2 * sd.klen[b])) - 1u;
-        if (c == 0) sd.off_base[b] = (uint32_t)goff.size();  // global variant: one chunk, per-block table sizes differ
-        std::vector<uint32_t> cnt(nkeys + 1, 0);
-        for (uint32_t g = 0; g < ng; ++g) ++cnt[((uint32_t)(guides2[g0 + g] >> (2 * sd.start[b])) & kmask) + 1];
-        for (uint32_t v = 0; v < nkeys; ++v) cnt[v + 1] += cnt[v];
-        goff.insert(goff.end(), cnt.begin(), cnt.end());
-        std::vector<uint32_t> cur(cnt.begin(), cnt.end() - 1);
-        const size_t base = ((size_t)c * nb + b) * chunk;
-        for (uint32_t g = 0; g < ng; ++g) {  // counting sort: guides of one bucket stay in input order
-          const uint32_t slot = cur[(uint32_t)(guides2[g0 + g] >> (2 * sd.start[b])) & kmask]++;
-          gcode[base + slot] = guides2[g0 + g];
-          gid[base + slot] = g0 + g;
-        }
-      }
-    }
-    if ((rc = hs->otoff.reserve(goff.size() * 4)) || (rc = hs->otcode.reserve(gcode.size() * 8)) || (rc = hs->otid.reserve(gid.size() * 4)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(hs->otoff.p, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hs->otcode.p, gcode.data(), gcode.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hs->otid.p, gid.data(), gid.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
+    ot_blocks(G, nb, 6, sd.start, sd.klen, sd.pmask2);
+    rc = ot_seed_tables(hs, guides2, n_guides, nb, sd.off_base, [&](int b) { return sd.klen[b]; },
+                        [&](int b, uint64_t c) { return (uint32_t)(c >> (2 * sd.start[b])) & ((1u << (2 * sd.klen[b])) - 1u); });
   }
+  if (rc) return rc;
   hipEvent_t* ev = ctx->ev;
   if (n_guides) HIPCHK(hipMemcpyAsync(hs->guides.p, guides2, (size_t)n_guides * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(hs->misc.p, 0, 64, ctx->stream));
@@ -173,14 +151,9 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
     hawk_launch_ot_match_pairs(ctx->stream, hs->sites.as<OtSite>(), nsites, ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
                                hs->otid.as<uint32_t>(), n_guides, G, p->right ? (int)p->pamlen : 0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
   } else if (seeded) {
-    if (seed_lds)
-      hawk_launch_ot_match_seeded_lds(ctx->stream, hs->sites.as<OtSite>(), nsites, sd, hs->otoff.as<uint32_t>(),
-                                      hs->otcode.as<uint64_t>(), hs->otid.as<uint32_t>(), n_guides, n_chunks, G,
-                                      p->right ? (int)p->pamlen : 0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
-    else
-      hawk_launch_ot_match_seeded(ctx->stream, hs->sites.as<OtSite>(), nsites, sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                                  hs->otid.as<uint32_t>(), n_guides, G, p->right ? (int)p->pamlen : 0, (int)p->max_mm,
-                                  hs->hits.as<OtHit>(), cap, d_nhits);
+    hawk_launch_ot_match_seeded(ctx->stream, hs->sites.as<OtSite>(), nsites, sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
+                                hs->otid.as<uint32_t>(), n_guides, G, p->right ? (int)p->pamlen : 0, (int)p->max_mm,
+                                hs->hits.as<OtHit>(), cap, d_nhits);
   } else {
     hawk_launch_ot_match(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, (int)p->guidelen,
                          p->right ? (int)p->pamlen : 0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);

@@ -57,24 +57,17 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
       (rc = hs->misc.reserve(512 * 8 + 64)) ||
       (rc = hs->cfd.reserve(336 * 8)) || (rc = hs->partial.reserve((nscan / 1024 + 2) * 8)))
     return rc;
-  // hand-over lists (2 KB per tile): the count pass leaves each small tile's valid survivors for the emit pass.
-  // HAWK_LIST_EMIT=0 keeps the recompute-everything emit pass (A/B measurements).
-  static const bool list_emit_env = [] { const char* e = getenv("HAWK_LIST_EMIT"); return !(e && e[0] == '0'); }();
   // A view of an expansion plan (hawk_xplan_view) holds no planes: its REF row runs through the plane kernels below on the
-  // plan's REF planes (without hand-over lists: a handful of tiles), every other row through hawk_vsearch.hip.
+  // plan's REF planes (hand-over lists included), every other row through hawk_vsearch.hip or hawk_csearch.hip.
   const hawk_xplan* vx = hs->vplan;
-  const bool list_emit = list_emit_env;
   const uint32_t plane_tiles = vx ? sp.bph * (hs->ref_index == 0 ? 1u : 0u) : (uint32_t)ntile;  // tiles the plane kernels take
   if (vx && (hs->ref_index != 0 || hs->n_ref_rows != 1)) return HAWK_E_INVALID;                 // a plan's rows: REF first, once
-  uint32_t* d_lists = nullptr;
-  unsigned long long* d_big = nullptr;
-  if (list_emit) {
-    // a REF tile takes one work-list entry per 512 survivors (<= 128 per tile), any other big tile one
-    const uint64_t n_ref_tiles = (uint64_t)sp.bph * hs->n_ref_rows;
-    if ((rc = hs->lists.reserve((size_t)plane_tiles * HAWK_LIST_CAP * 4 + 16)) || (rc = hs->big.reserve(((size_t)plane_tiles + 128 * n_ref_tiles) * 8 + 16))) return rc;
-    d_lists = hs->lists.as<uint32_t>();
-    d_big = hs->big.as<unsigned long long>();
-  }
+  // hand-over lists (2 KB per tile): the count pass leaves each small tile's valid survivors for the emit pass.
+  // A REF tile takes one work-list entry per 512 survivors (<= 128 per tile), any other big tile one.
+  const uint64_t n_ref_tiles = (uint64_t)sp.bph * hs->n_ref_rows;
+  if ((rc = hs->lists.reserve((size_t)plane_tiles * HAWK_LIST_CAP * 4 + 16)) || (rc = hs->big.reserve(((size_t)plane_tiles + 128 * n_ref_tiles) * 8 + 16))) return rc;
+  uint32_t* const d_lists = hs->lists.as<uint32_t>();
+  unsigned long long* const d_big = hs->big.as<unsigned long long>();
   if (p->score_cfdon) {  // the tables go up once; later searches with the same tables find them in HBM
     if (hs->cfd_host.size() != 336 || memcmp(hs->cfd_host.data(), p->cfd_mm, 320 * 8) != 0 ||
         memcmp(hs->cfd_host.data() + 320, p->cfd_pam, 16 * 8) != 0) {
@@ -229,8 +222,19 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
   int status = 0;
   uint64_t nrows = 0;
   bool emitted = false;
-  auto template_overflow = [&](uint64_t tc_used) {  // the rerun reserves what this search asked for (+ 1/8), at most the plan's bound
-    hs->cs_tcap = std::min<uint64_t>(vx->cl.slots, tc_used + tc_used / 8 + 64);
+  // the status block after the count side (and a speculative emit): totals, status, and the template rows a cluster search
+  // used.  If those outgrew their reservation the rerun reserves what this search asked for (+ 1/8), at most the plan's bound
+  auto read_block = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(h_block, d_block, 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    memcpy(&tot, h_block + 32, sizeof(tot));
+    memcpy(&status, h_block, 4);
+    if (!by_cluster) return HAWK_OK;
+    uint64_t tcu;
+    memcpy(&tcu, h_block + 8, 8);
+    if (tcu > tcap) { hs->cs_tcap = std::min<uint64_t>(vx->cl.slots, tcu + tcu / 8 + 64); return HAWK_RETRY_TEMPLATES; }
+    t_rows_used = tcu;
+    return HAWK_OK;
   };
   if (table_cap) {
     // The table of an earlier search on this set is still reserved: launch the emit pass straight behind the offset
@@ -241,11 +245,7 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
     emit_all(ca, tc);
     HIPCHK(hipEventRecord(ev[4], ctx->stream));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_block, d_block, 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    memcpy(&tot, h_block + 32, sizeof(tot));
-    memcpy(&status, h_block, 4);
-    if (by_cluster) { uint64_t tcu; memcpy(&tcu, h_block + 8, 8); if (tcu > tcap) { template_overflow(tcu); return HAWK_RETRY_TEMPLATES; } t_rows_used = tcu; }
+    if ((rc = read_block())) return rc;
     nrows = tot.n_keep;
     emitted = nrows <= table_cap;
     if (!emitted) {
@@ -256,11 +256,7 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
       HIPCHK(hipMemsetAsync(d_status, 0, 4, ctx->stream));
     }
   } else {
-    HIPCHK(hipMemcpyAsync(h_block, d_block, 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    memcpy(&tot, h_block + 32, sizeof(tot));
-    memcpy(&status, h_block, 4);
-    if (by_cluster) { uint64_t tcu; memcpy(&tcu, h_block + 8, 8); if (tcu > tcap) { template_overflow(tcu); return HAWK_RETRY_TEMPLATES; } t_rows_used = tcu; }
+    if ((rc = read_block())) return rc;
     if (status) return status;
     nrows = tot.n_keep;
   }
@@ -280,7 +276,7 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
     (void)hipEventElapsedTime(&timing->count_ms, ev[0], ev[1]);
     (void)hipEventElapsedTime(&timing->offsets_ms, ev[1], ev[2]);
     (void)hipEventElapsedTime(&timing->emit_ms, ev[3], ev[4]);
-    if (nrows && d_lists) (void)hipEventElapsedTime(&timing->emit_list_ms, ev[3], ev[5]);
+    if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, ev[3], ev[5]);
     (void)hipEventElapsedTime(&timing->total_ms, ev[0], ev[4]);
     if (vx) {
       (void)hipEventElapsedTime(&timing->v_count_ms, ev[6], ev[1]);

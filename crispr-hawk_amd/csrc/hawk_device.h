@@ -154,7 +154,6 @@ struct ClDict {
   const uint32_t* u_seg;     // a position-map segment of that row in force in front of every position a search of the cluster maps
 };
 size_t hawk_cs_row_bytes();
-void hawk_launch_scan_u32(hipStream_t st, const uint32_t* cnt, uint32_t n, uint32_t* off);  // exclusive scan into n + 1 offsets, one workgroup
 void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b);  // two arrays, one launch
 void hawk_launch_hx_heads(hipStream_t st, const void* recs, const uint32_t* hv_idx, uint64_t n, void* heads);  // {o, rs, alt_len, variant} per record
 // (the hawk_launch_cl_* passes take the HEADS as `recs`)
@@ -243,11 +242,6 @@ void hawk_launch_ot_match(hipStream_t st, const OtSite* sites, uint64_t n_sites,
 void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
                                  const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
                                  OtHit* hits, uint64_t cap, unsigned long long* n_hits);
-#define OT_LDS_CHUNK 1024  // guides per LDS-resident chunk of the seeded match
-#define OT_LDS_KEYS 256    // buckets per block in the LDS variant (4 key bases)
-void hawk_launch_ot_match_seeded_lds(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
-                                     const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, uint32_t n_chunks, int guidelen,
-                                     int sp0, int max_mm, OtHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const OtHit* hits, uint64_t n_hits, OtSite* out);
 void hawk_launch_pack(hipStream_t st, const uint8_t* ascii, const uint64_t* seq_off, uint32_t hap0, uint32_t n_hap_batch,
                       uint64_t batch_base, const uint32_t* hap_len, uint32_t S, uint32_t* const* plane,

@@ -56,10 +56,9 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
   __shared__ uint32_t s_acc[4];
   const ScanParams& p = p_in;
   const uint32_t tid = threadIdx.x;
-  // list mode: the count pass hands the valid survivors of small tiles to k_emit_list; this kernel's emit
-  // pass then only serves the tiles whose list did not fit (REF tiles, very dense tiles)
-  const bool list_mode = PASS == 0 && lists != nullptr;
-  if (PASS == 1 && lists != nullptr && counts[tile] <= LIST_CAP) return;
+  // the count pass hands the valid survivors of small tiles to k_emit_list; the emit pass here only serves the tiles
+  // whose list did not fit (REF tiles, very dense tiles)
+  if (PASS == 1 && counts[tile] <= LIST_CAP) return;
   // The tile's row and index within the row are arithmetic (tmeta is laid out [row][tile]), so the plane loads below do
   // not wait for the TileMeta record: both go out together and one level of memory latency leaves the wave's lifetime.
   const uint32_t h = tile / p.bph, blk = tile - h * p.bph;
@@ -71,7 +70,6 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
   const int ss = tm.scan_start, se = tm.scan_stop;
   const bool isref = tm.is_ref != 0;
   const bool dedup = ri.index >= 0 && !isref;  // rows of this tile can be redundant with REF
-  const bool stage = PASS == 1 || dedup || list_mode;  // phase C runs if the tile has survivors
   const bool lds_planes = PASS == 1;            // PASS 0 classifies its few survivors straight from L2/HBM
   const uint32_t w0 = blk * TILE_WORDS;         // first plane word of the tile
   const uint32_t tile_q0 = w0 * 32u;
@@ -95,29 +93,27 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
   uint32_t halo = 0, seg_r = 0xffffffffu;
   int64_t seg_g = 0;
   bool seg_in = false, ovf = false;
-  if (stage) {
-    if (lds_planes && tid < 3 * HAWK_PLANES) {
-      const uint32_t pl = tid / 3, j = tid % 3;  // j: 0 -> word -1, 1 -> word TILE_WORDS, 2 -> TILE_WORDS+1
-      const long long w = j == 0 ? (long long)w0 - 1 : (long long)w0 + TILE_WORDS + (j - 1);
-      if (w >= 0 && w < (long long)hs.S) halo = hs.plane[pl][rowbase + (size_t)w];
-    }
-    if (tid < NSEG) {  // the tile's slice of the position map
-      const uint32_t k = k0 + tid;
-      if (k < kend) {
-        seg_r = hs.seg_rel[k];
-        seg_g = hs.seg_gen[k];
-        seg_in = tid == 0 || seg_r < tile_end;
-      }
-    }
-    ovf = k0 + NSEG < kend && hs.seg_rel[k0 + NSEG] < tile_end;  // rare: > NSEG segments in a tile
-    if (PASS == 1 && gp.score_cfdon) for (uint32_t i = tid; i < 336; i += HAWK_BLOCK) s_cfd[i] = gp.cfd_mm[i];  // mm[320] then pam[16]
+  if (lds_planes && tid < 3 * HAWK_PLANES) {
+    const uint32_t pl = tid / 3, j = tid % 3;  // j: 0 -> word -1, 1 -> word TILE_WORDS, 2 -> TILE_WORDS+1
+    const long long w = j == 0 ? (long long)w0 - 1 : (long long)w0 + TILE_WORDS + (j - 1);
+    if (w >= 0 && w < (long long)hs.S) halo = hs.plane[pl][rowbase + (size_t)w];
   }
+  if (tid < NSEG) {  // the tile's slice of the position map
+    const uint32_t k = k0 + tid;
+    if (k < kend) {
+      seg_r = hs.seg_rel[k];
+      seg_g = hs.seg_gen[k];
+      seg_in = tid == 0 || seg_r < tile_end;
+    }
+  }
+  ovf = k0 + NSEG < kend && hs.seg_rel[k0 + NSEG] < tile_end;  // rare: > NSEG segments in a tile
+  if (PASS == 1 && gp.score_cfdon) for (uint32_t i = tid; i < 336; i += HAWK_BLOCK) s_cfd[i] = gp.cfd_mm[i];  // mm[320] then pam[16]
 
   // ---- phase A: scan + filters on registers; stage the slices phase C reads --------------
   load6_finish(la, A); load6_finish(lc, C); load6_finish(lg, G); load6_finish(lt, Tp);
   uint32_t V[4] = {lv.v.x, lv.v.y, lv.v.z, lv.v.w};
   if (!isref) load6_finish(lv, E);
-  if (stage && lds_planes) {
+  if (lds_planes) {
     *reinterpret_cast<uint4*>(&s_pl[0][LDS_OFF + 4 * tid]) = make_uint4(A[0], A[1], A[2], A[3]);
     *reinterpret_cast<uint4*>(&s_pl[1][LDS_OFF + 4 * tid]) = make_uint4(C[0], C[1], C[2], C[3]);
     *reinterpret_cast<uint4*>(&s_pl[2][LDS_OFF + 4 * tid]) = make_uint4(G[0], G[1], G[2], G[3]);
@@ -128,14 +124,12 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
       s_pl[pl][j == 0 ? LDS_OFF - 1 : LDS_OFF + TILE_WORDS + (j - 1)] = halo;
     }
   }
-  if (stage) {
-    if (tid < NSEG) {  // NSEG == WAVE: wave 0 holds the whole slice
-      s_segrel[tid] = seg_in ? seg_r : 0xffffffffu;
-      s_seggen[tid] = seg_g;
-      if (PASS == 1) {  // the count pass searches the sentinel-padded slice with a fixed step count and needs no length
-        const unsigned long long bm = __ballot(seg_in);
-        if (tid == 0) s_acc[3] = (uint32_t)__popcll(bm);
-      }
+  if (tid < NSEG) {  // NSEG == WAVE: wave 0 holds the whole slice
+    s_segrel[tid] = seg_in ? seg_r : 0xffffffffu;
+    s_seggen[tid] = seg_g;
+    if (PASS == 1) {  // the count pass searches the sentinel-padded slice with a fixed step count and needs no length
+      const unsigned long long bm = __ballot(seg_in);
+      if (tid == 0) s_acc[3] = (uint32_t)__popcll(bm);
     }
   }
   uint32_t kF[4], kR[4];
@@ -186,10 +180,10 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
   const uint32_t TF = TT & 0xffffu, TR = TT >> 16, exF = exFR & 0xffffu, exR = exFR >> 16;
   const uint32_t T = TF + TR;
 
-  uint32_t nvalid = 0;  // this thread's share (PASS 0)
-  uint32_t lrun = 0;  // valid survivors listed so far (list mode)
-  if (!stage || (PASS == 0 && !dedup && (!list_mode || T > LIST_CAP))) {
-    if (tid == 0) nvalid = T;  // nothing can be redundant here and no list is wanted: the count is the survivor count
+  uint32_t nvalid = 0;  // the tile's count, held by thread 0 (PASS 0)
+  uint32_t lrun = 0;    // valid survivors listed so far (PASS 0)
+  if (PASS == 0 && !dedup && T > LIST_CAP) {
+    if (tid == 0) nvalid = T;  // nothing can be redundant here and the list cannot hold the rows: the count is the survivor count
   } else if (T) {  // workgroup-uniform
     const int nloc = (int)s_acc[3];
     const size_t refbase = ri.index >= 0 ? (size_t)ri.index * hs.S : 0;
@@ -391,16 +385,12 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
           }
           }
         }
-        if (PASS == 0) {
-          if (list_mode) {  // compact the valid survivors into the tile's hand-over list
-            uint32_t tot;
-            const uint32_t ex = block_rank<HAWK_BLOCK / WAVE>(valid != 0, s_w, &tot);
-            if (valid && lrun + ex < LIST_CAP) lists[(size_t)tile * LIST_CAP + lrun + ex] = ql | (s << 15) | ((uint32_t)has_ref << 16);
-            lrun += tot;
-            if (tid == 0) nvalid += tot;
-          } else {
-            nvalid += valid;
-          }
+        if (PASS == 0) {  // compact the valid survivors into the tile's hand-over list
+          uint32_t tot;
+          const uint32_t ex = block_rank<HAWK_BLOCK / WAVE>(valid != 0, s_w, &tot);
+          if (valid && lrun + ex < LIST_CAP) lists[(size_t)tile * LIST_CAP + lrun + ex] = ql | (s << 15) | ((uint32_t)has_ref << 16);
+          lrun += tot;
+          if (tid == 0) nvalid += tot;
         } else {
           uint32_t tot;
           const uint32_t ex = block_excl_scan<HAWK_BLOCK / WAVE>(valid, s_w, &tot);
@@ -437,11 +427,8 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
   }
   if (PASS == 0) {
     const uint32_t w1s = wave_sum(cand | (hits << 16));  // per-wave sums < 2^16
-    // in list mode (and whenever phase C did not run) thread 0 alone holds the tile's count
-    const bool spread = stage && !list_mode && T != 0 && !(PASS == 0 && !dedup);
-    const uint32_t w0s = spread ? wave_sum(nvalid) : nvalid;  // workgroup-uniform choice
     __syncthreads();  // s_w is free again (the last scan's second barrier lies behind every reader)
-    if ((tid & (WAVE - 1)) == 0) { s_w[tid / WAVE] = w0s; s_kw[0][tid / WAVE] = w1s; }
+    if ((tid & (WAVE - 1)) == 0) { s_w[tid / WAVE] = nvalid; s_kw[0][tid / WAVE] = w1s; }
     __syncthreads();
     if (tid == 0) {
       uint32_t a0 = 0, a1 = 0, a2 = 0;
@@ -452,7 +439,7 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
       // then runs over them alone instead of launching one workgroup per tile to find out
       // (a REF tile - thousands of rows, none ever dropped - is named once per round of CAP survivors, so that its rounds
       // spread over workgroups: 31 REF tiles of ~4000 rows were a 50 us critical path of their own)
-      if (list_mode && a0 > LIST_CAP) {
+      if (a0 > LIST_CAP) {
         const uint32_t nr = isref ? (T + CAP - 1) / CAP : 1u;
         const uint32_t at = atomicAdd(big_count, nr);
         for (uint32_t r = 0; r < nr; ++r)
@@ -478,10 +465,6 @@ __global__ __launch_bounds__(HAWK_BLOCK)
 void k_search_emit(HapSetDev hs, ScanParams p, GuideParams gp, RefInfo ri, const TileMeta* __restrict__ tmeta,
                    uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets, GuideCols out, int* status,
                    uint32_t* __restrict__ lists, const uint32_t* __restrict__ big_count, const unsigned long long* __restrict__ big_list) {
-  if (lists == nullptr) {  // no hand-over lists: every tile recomputes and emits here
-    search_tile<1>(hs, p, gp, ri, tmeta, counts, nullptr, offsets, out, status, lists, blockIdx.x, nullptr, nullptr, -1);
-    return;
-  }
   const uint32_t n_big = *big_count;
 #pragma unroll 1
   for (uint32_t i = blockIdx.x; i < n_big; i += gridDim.x) {  // workgroup-uniform
@@ -676,11 +659,11 @@ void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const Sca
   if (pass == 0) {
     hipLaunchKernelGGL(k_search_count, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, shards, status, lists, big_count, big_list);
   } else {
-    // lists != nullptr: small tiles are assembled from their hand-over lists, the named big ones recompute
-    if (lists) hipLaunchKernelGGL(k_emit_list, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, lists, out, status);
+    // small tiles are assembled from their hand-over lists, the named big ones recompute
+    hipLaunchKernelGGL(k_emit_list, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, lists, out, status);
     if (mid) (void)hipEventRecord(mid, st);  // timing: k_emit_list ends here
-    // list mode: a walk over the work list (<= 128 entries per REF tile, usually ~8; one per other big tile)
-    const dim3 egrid(lists ? (ntile * 8u < 2048u ? ntile * 8u : 2048u) : ntile);
+    // a walk over the work list (<= 128 entries per REF tile, usually ~8; one per other big tile)
+    const dim3 egrid(ntile * 8u < 2048u ? ntile * 8u : 2048u);
     hipLaunchKernelGGL(k_search_emit, egrid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, out, status, lists, big_count, big_list);
   }
 }

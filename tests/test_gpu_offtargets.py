@@ -26,15 +26,14 @@ def _plant(rng, genome: list, guide: str, pam_seq: str, right: bool, n: int, max
 
 
 @pytest.mark.parametrize("n_guides", [6, 200, 2300, -2300])  # 6: all pairs; 200 / 2300: pair seeds (max_mm + 2 blocks, candidates dealt
-#   evenly over a wave); -2300: the single-block seeds of rounds 1-3 (HAWK_OT_PAIRS=0: guides in three LDS chunks)
+#   evenly over a wave); -2300: 2300 guides at max_mm = 7, the single-block seeds (pair seeds would need 9 blocks)
 @pytest.mark.parametrize("pam_s,guidelen,right,max_mm,piece", [("NGG", 20, False, 4, 1 << 22), ("TTTV", 23, True, 3, 4096),
                                                               ("TTTV", 23, True, 4, 1 << 22),  # C5 as BASELINE.json states it
                                                               ("NNGRRT", 21, False, 2, 10000), ("NGG", 20, False, 0, 1 << 22),
                                                               ("NGG", 17, False, 6, 1 << 22)])
-def test_offtarget_scan_matches_bruteforce(pam_s, guidelen, right, max_mm, piece, n_guides, monkeypatch):
+def test_offtarget_scan_matches_bruteforce(pam_s, guidelen, right, max_mm, piece, n_guides):
     if n_guides < 0:
-        monkeypatch.setenv("HAWK_OT_PAIRS", "0")
-        n_guides = -n_guides
+        n_guides, max_mm = -n_guides, 7
     rng = np.random.default_rng(77)
     contigs = {}
     guides = [synth.random_sequence(rng, guidelen) for _ in range(n_guides)]
@@ -141,11 +140,11 @@ def _verify_hits_on_host(contig_arrays, idx, hits, guides, pam_s, guidelen, righ
 C5_CONTIG_NT, C5_GUIDES = 129_166_667, 10_000  # 24 contigs: 3.1 x 10^9 nt
 
 
-def test_c5_full_size_properties(monkeypatch):
+def test_c5_full_size_properties():
     """C5 at BASELINE.json's full size - a 3.1 x 10^9-nt genome in 24 contigs, 10^4 guides, TTTV / 23, <= 4 mismatches - which no
-    brute force reaches: the four match
-    kernels (pair seeds; single-block pigeonhole seeds from L2 and from LDS; all pairs) must report the same hit set, every guide
-    must find its planted on-target, and every hit must re-verify against the genome bytes on the host."""
+    brute force reaches: the pair-seed
+    match kernel must report the hit set of the all-pairs kernel, every guide must find its planted on-target, and every hit must
+    re-verify against the genome bytes on the host."""
     import subprocess, sys, os, json
     code = r"""
 import json, sys, hashlib
@@ -176,14 +175,13 @@ print("RESULT", json.dumps({"n": int(len(order)), "digest": h.hexdigest(), "n_si
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = code % (C5_CONTIG_NT, C5_GUIDES, os.path.join(root, "crispr-hawk_amd"), root)
     res = {}
-    for label, env in (("pair_seeds", {}), ("seeded_lds", {"HAWK_OT_PAIRS": "0"}), ("seeded_global", {"HAWK_OT_SEED_GLOBAL": "1"}),
-                       ("all_pairs", {"HAWK_OT_ALLPAIRS": "1"})):
+    for label, env in (("pair_seeds", {}), ("all_pairs", {"HAWK_OT_ALLPAIRS": "1"})):
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=1100)
         assert r.returncode == 0, r.stderr[-2000:]
         res[label] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT")][0][7:])
-    assert res["pair_seeds"]["digest"] == res["seeded_lds"]["digest"] == res["seeded_global"]["digest"] == res["all_pairs"]["digest"]
+    assert res["pair_seeds"]["digest"] == res["all_pairs"]["digest"]
     print("match_ms", {k: round(v["match_ms"], 2) for k, v in res.items()})
-    assert res["seeded_lds"]["n"] >= 100  # ~1 guide in 85 sits behind a TTTV and is its own on-target; the rest are chance near-matches
+    assert res["pair_seeds"]["n"] >= 100  # ~1 guide in 85 sits behind a TTTV and is its own on-target; the rest are chance near-matches
     # in-process: host re-verification of the default kernel's hits
     rng = np.random.default_rng(1006)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -201,7 +199,7 @@ print("RESULT", json.dumps({"n": int(len(order)), "digest": h.hexdigest(), "n_si
     pam.encode(0)
     idx = GenomeIndex(contigs, 23, 4)
     hits, _tm = idx.scan_arrays(guides, pam, True, 4)
-    assert len(hits["guide"]) == res["seeded_lds"]["n"]
+    assert len(hits["guide"]) == res["pair_seeds"]["n"]
     _verify_hits_on_host(contigs, idx, hits, guides, "TTTV", 23, True, 4)
     # a guide cut out right behind a TTTV is its own 0-mismatch on-target at PAM start = origin - 4
     found = {(int(g), idx.rows[int(r)][0], idx.rows[int(r)][1] + int(q)) for g, r, q, s, m in
@@ -466,33 +464,18 @@ def _edge_scan(pam_s: str, G: int, right: bool, piece: int, max_mm: int = 2, max
     return got_mm, got_b
 
 
-def _child_scan(env: dict, args: tuple):
-    """_edge_scan in a fresh process: HAWK_OT_SEED_GLOBAL / HAWK_OT_ALLPAIRS are read once per process.  One run, bounded; its
-    failure ends the test."""
-    import json, os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = (f"import sys, json\nsys.path[:0] = {[os.path.join(root, 'crispr-hawk_amd'), root, os.path.join(root, 'tests')]!r}\n"
-            f"import test_gpu_offtargets as t\nprint('RESULT', json.dumps(t._edge_scan(*{args!r})))\n")
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    got_mm, got_b = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][0][7:])
-    return [tuple(t) for t in got_mm], [tuple(t) for t in got_b]
-
-
-@pytest.mark.parametrize("kernel", ["pair_seeds", "seeded_lds", "seeded_global", "all_pairs"])
+@pytest.mark.parametrize("kernel", ["pair_seeds", "single_block", "all_pairs"])
 @pytest.mark.parametrize("pam_s,G,right,piece", [("NGG", 20, False, 512), ("TTTV", 23, True, 1000)])
 def test_offtarget_edges_match_bruteforce(pam_s, G, right, piece, kernel, monkeypatch):
     """Sites at the edges of the row geometry (a contig's first and last window start, every start around a row seam, contigs
     no longer than one window, N / IUPAC bases at the ends, in a PAM and in a bulge), mismatch-only and with DNA / RNA bulges of
-    1 and 2, on both strands, through each of the four match kernels: exactly the brute force's rows."""
-    contigs, guides, planted, want_mm, want_b = _edge_case(pam_s, G, right, piece)
-    if kernel in ("pair_seeds", "seeded_lds"):
-        if kernel == "seeded_lds":
-            monkeypatch.setenv("HAWK_OT_PAIRS", "0")
-        got_mm, got_b = _edge_scan(pam_s, G, right, piece)
-    else:
-        got_mm, got_b = _child_scan({"HAWK_OT_SEED_GLOBAL": "1"} if kernel == "seeded_global" else {"HAWK_OT_ALLPAIRS": "1"},
-                                    (pam_s, G, right, piece))
+    1 and 2, on both strands, through each of the three match kernels (single-block seeds: max_mm = 7): exactly the brute force's
+    rows."""
+    max_mm = 7 if kernel == "single_block" else 2
+    if kernel == "all_pairs":
+        monkeypatch.setenv("HAWK_OT_ALLPAIRS", "1")
+    contigs, guides, planted, want_mm, want_b = _edge_case(pam_s, G, right, piece, max_mm)
+    got_mm, got_b = _edge_scan(pam_s, G, right, piece, max_mm)
     # the brute force sees what was planted (the ambiguous-base plants excepted): the sweep reaches every edge it claims to
     sites_mm = {(t[0], t[1], t[2], t[3]) for t in want_mm}
     sites_b = {(t[0], t[1], t[2], t[3], t[4], t[5]) for t in want_b}
@@ -529,12 +512,12 @@ def test_bulged_site_in_a_contig_tail_is_reported():
 @pytest.mark.parametrize("n_guides", [63, 64, 1024, 1025])
 @pytest.mark.parametrize("pairs", [True, False])
 @pytest.mark.parametrize("pam_s,G,right,max_mm", [("NGG", 20, False, 3), ("TTTV", 23, True, 4)])
-def test_offtarget_guide_count_boundaries(pam_s, G, right, max_mm, n_guides, pairs, monkeypatch):
-    """Mismatch-only scans at the guide counts where the match kernel changes: 63 / 64 (all pairs below 64 guides, seeds from 64)
-    and 1024 / 1025 (one LDS chunk of the single-block seeds, or two), pair seeds and LDS seeds, guides in families that share
-    seed blocks: exactly the brute force's rows."""
+def test_offtarget_guide_count_boundaries(pam_s, G, right, max_mm, n_guides, pairs):
+    """Mismatch-only scans at the guide count where the match kernel changes, 63 / 64 (all pairs below 64 guides, seeds from 64),
+    and at 1024 / 1025, with pair seeds and with single-block seeds (max_mm = 7), guides in families that share seed blocks:
+    exactly the brute force's rows."""
     if not pairs:
-        monkeypatch.setenv("HAWK_OT_PAIRS", "0")
+        max_mm = 7
     rng = np.random.default_rng(n_guides + G)
     guides = [synth.random_sequence(rng, G) for _ in range(n_guides)]
     for k in range(6, n_guides, 7):
@@ -554,7 +537,7 @@ def test_offtarget_guide_count_boundaries(pam_s, G, right, max_mm, n_guides, pai
     ci = {n: i for i, n in enumerate(contigs)}
     want = sorted(((int(r["guide"]), name, int(r["pos"]), "-" if r["strand"] else "+", int(r["mm"])) for name, seq in contigs.items()
                    for r in ora.offtargets(seq, guides, pam_s, right, max_mm)), key=lambda t: (t[0], ci[t[1]], t[2], t[3] == "-"))
-    assert len(want) > 40 and any(t[0] == n_guides - 1 for t in want)  # the last guide (the one past a chunk edge) has rows
+    assert len(want) > 40 and any(t[0] == n_guides - 1 for t in want)  # the last guide has rows
     assert [(h.guide, h.contig, h.position, h.strand, h.mm) for h in got] == want
 
 
