@@ -94,7 +94,7 @@ class HostHaplotype:
 class DeviceHapSet:
     @classmethod
     def from_handle(cls, handle, hap_len: np.ndarray, device: Optional[int] = None) -> "DeviceHapSet":
-        """Wrap planes that already exist in HBM (hawk_hapset_expand); set_meta() must follow."""
+        """Wrap a set the library already holds (hawk_xplan_run, hawk_xplan_view); its metadata comes from the plan."""
         self = cls.__new__(cls)
         self._L = _lib.lib()
         self._ctx = _lib.context(device)
@@ -137,7 +137,7 @@ class DeviceHapSet:
         self.set_meta(haps)
 
     def set_meta(self, haps: Sequence[HostHaplotype]) -> None:
-        is_ref, ss, se, seg_off, seg_rel, seg_gen, self.ref_index = haps.meta_arrays() if hasattr(haps, "meta_arrays") else _meta_arrays(haps)
+        is_ref, ss, se, seg_off, seg_rel, seg_gen, self.ref_index = _meta_arrays(haps)
         self.is_ref = is_ref
         _lib.check(self._L.hawk_hapset_set_meta(self._h, _p(is_ref), _p(ss), _p(se), _p(seg_off), _p(seg_rel), _p(seg_gen),
                                                 self.ref_index), "hawk_hapset_set_meta")
@@ -225,12 +225,6 @@ class ExpansionPlan:
         self.device = device
         self.ref_index = -1
         self.is_ref = None
-
-    def set_meta(self, haps: Sequence["HostHaplotype"]) -> None:
-        is_ref, ss, se, seg_off, seg_rel, seg_gen, ref_index = haps.meta_arrays() if hasattr(haps, "meta_arrays") else _meta_arrays(haps)
-        _lib.check(self._L.hawk_xplan_set_meta(self._x, _p(is_ref), _p(ss), _p(se), _p(seg_off), _p(seg_rel), _p(seg_gen), ref_index),
-                   "hawk_xplan_set_meta")
-        self.ref_index, self.is_ref = ref_index, is_ref
 
     def run(self, want_hash: bool = False, timed: bool = False):
         """-> (DeviceHapSet, hashes[n_hap, 2] or None, kernel ms or None)"""

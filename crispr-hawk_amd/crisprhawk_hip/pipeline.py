@@ -2,7 +2,7 @@
 inputs, with every stage on the device path of this package.
 
     FASTA + BED (+ VCF)  --readers-->  region string, VCF record text
-                         --hawk_gt_parse / hawk_gt_lists / hawk_hapset_expand-->  haplotype planes in HBM
+                         --hawk_gt_parse / hawk_gt_lists / hawk_xplan_create_gt-->  expansion plan in HBM
                          --hawk_search (+ CFDon)-->  guide table in HBM
                          --hawk_table_collapse-->  report groups
                          --reports.report_frame-->  crisprhawk_guides__*.tsv

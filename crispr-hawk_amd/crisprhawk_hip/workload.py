@@ -243,17 +243,15 @@ def _scan_for(seg: PosSegments, startp: int, stopp: int, pamlen: int, own: Optio
 
 
 class RowMeta:
-    """Position maps and scan ranges of the rows of an expanded set, as flat arrays (CSR segments) - what
-    hawk_hapset_set_meta takes - with list-like access to per-row `HostHaplotype` views for the few callers that want one
-    (labels keep `host_meta[r].seg`).  Replaces 5009 Python objects and as many numpy calls per expansion."""
+    """Position maps and scan ranges of the rows of a device-built plan, with list-like access to per-row `HostHaplotype`
+    views for the few callers that want one (labels keep `host_meta[r].seg`).  Replaces 5009 Python objects and as many
+    numpy calls per expansion."""
 
-    def __init__(self, seg_start, seg_rel, seg_gen, hap_len: np.ndarray, alias: np.ndarray, startp: int, fetch=None, rev=None):
-        """`fetch`: a callable returning (seg_start, seg_rel, seg_gen) - the segments of a device-built plan are downloaded
-        only when something on the host reads them; `rev`: {genomic position: posmap_rev of every row}, computed on the
-        device beside the segments."""
-        self._segs = None if fetch is not None else (seg_start, seg_rel, seg_gen)
-        self._fetch, self._rev = fetch, dict(rev or {})
-        self.hap_len, self.alias, self.startp = np.asarray(hap_len, dtype=np.int64), alias, startp
+    def __init__(self, fetch, hap_len: np.ndarray, alias: np.ndarray):
+        """`fetch`: a callable returning (seg_start, seg_rel, seg_gen) - the plan's segments are downloaded only when
+        something on the host reads them."""
+        self._segs, self._fetch = None, fetch
+        self.hap_len, self.alias = np.asarray(hap_len, dtype=np.int64), alias
         self.n = len(hap_len)
         self.scan_lo = np.zeros(self.n, dtype=np.int64)
         self.scan_hi = np.zeros(self.n, dtype=np.int64)
@@ -280,43 +278,13 @@ class RowMeta:
     def __iter__(self):
         return (self[r] for r in range(self.n))
 
-    def _rev_all(self, g: int) -> np.ndarray:
-        """posmap_rev[g] of every row at once: the last relative position whose genomic position is g, -1 where g is
-        deleted (the reference rebuilds the reverse dict by overwrite, haplotype.py:159).  One pass over the segments in
-        the library's host helper; `_rev_all_numpy` is the same in numpy (cross-check of tests/test_host_logic.py)."""
-        import ctypes as C
-        from . import _lib
-        from .hapset import _p
-        from .reports import _host_lib
-        if int(g) in self._rev:
-            return self._rev[int(g)]
-        ss = np.ascontiguousarray(self.seg_start, dtype=np.uint64)
-        sr = np.ascontiguousarray(self.seg_rel, dtype=np.uint32)
-        sg = np.ascontiguousarray(self.seg_gen, dtype=np.int64)
-        hl = np.ascontiguousarray(self.hap_len, dtype=np.uint32)
-        out = np.empty(self.n, dtype=np.int64)
-        _lib.check(_host_lib().hawk_host_posmap_rev(_p(ss), _p(sr), _p(sg), _p(hl), C.c_uint32(self.n), C.c_int64(int(g)), _p(out)),
-                   "hawk_host_posmap_rev")
-        return out
-
-    def _rev_all_numpy(self, g: int) -> np.ndarray:
-        ends = np.empty(len(self.seg_rel), dtype=np.int64)
-        ends[:-1] = self.seg_rel[1:]
-        ends[self.seg_start[1:] - 1] = self.hap_len          # a row's last segment runs to the row's end
-        last_gen = self.seg_gen + (ends - self.seg_rel.astype(np.int64)) - 1
-        hit = (self.seg_gen <= g) & (g <= last_gen)
-        k = np.where(hit, np.arange(len(hit)), -1)
-        lastk = np.maximum.reduceat(k, self.seg_start[:-1])
-        rel = self.seg_rel[np.maximum(lastk, 0)].astype(np.int64) + (g - self.seg_gen[np.maximum(lastk, 0)])
-        return np.where(lastk >= 0, rel, -1)
-
-    def compute_scans(self, startp: int, stopp: int, pamlen: int, own: Optional["ScanOwnership"]) -> None:
-        """compute_scan_start_stop (search_guides.py:49-84), or a tile's ownership range, for every live row; rows whose
-        boundary position is deleted (rare) take the per-row walk of `_scan_for`."""
+    def compute_scans(self, lo: np.ndarray, hi: np.ndarray, startp: int, stopp: int, pamlen: int,
+                      own: Optional["ScanOwnership"]) -> None:
+        """compute_scan_start_stop (search_guides.py:49-84), or a tile's ownership range, for every live row.  `lo` / `hi`:
+        posmap_rev of every row at the two genomic positions the bounds start from (the last relative position with that
+        genomic position, -1 where it is deleted; computed on the device beside the segments).  Rows whose boundary
+        position is deleted (rare) take the per-row walk of `_scan_for`."""
         live = self.alias == np.arange(self.n)
-        lo_g = startp + 100 if (own is None or own.own_lo is None) else own.own_lo
-        hi_g = stopp - 100 if (own is None or own.own_hi is None) else own.own_hi
-        lo, hi = self._rev_all(lo_g), self._rev_all(hi_g)
         if own is None or own.own_hi is None:
             hi = np.where(hi >= 0, hi - pamlen + 1, hi)
         slow = live & ((lo < 0) | (hi < 0))
@@ -329,74 +297,6 @@ class RowMeta:
         for r in np.flatnonzero(slow).tolist():
             a, b = _scan_for(self.seg(r), startp, stopp, pamlen, own)
             self.scan_lo[r], self.scan_hi[r] = a, b
-
-    def meta_arrays(self):
-        is_ref = np.zeros(self.n, dtype=np.uint8)
-        is_ref[0] = 1
-        return (is_ref, self.scan_lo.astype(np.int32), self.scan_hi.astype(np.int32), self.seg_start.astype(np.uint32),
-                np.ascontiguousarray(self.seg_rel, dtype=np.uint32), np.ascontiguousarray(self.seg_gen, dtype=np.int64), 0)
-
-
-def build_segments(ind, hv_idx, hv_o, hv_off, r0, chain, startp: int, hap_len, alias):
-    """Position-map segments of all rows of an expansion as CSR arrays (seg_start[n + 1], seg_rel u32, seg_gen i64) from the
-    carried indels `ind` (entry indices into hv_idx / hv_o, ascending): the library's host helper
-    (hawk_host_build_segments; one pass over the ~10 % of list entries that are indels).  `build_segments_numpy` is the
-    same in numpy - what ran before, kept as the cross-check of tests/test_host_logic.py."""
-    import ctypes as C
-    from . import _lib
-    from .hapset import _p
-    from .reports import _host_lib
-    L = _host_lib()  # libhawk_hip.so, or the sanitizer build of the host helpers (HAWK_HOSTUTIL_LIB)
-    n = len(hap_len)
-    ind = np.ascontiguousarray(ind, dtype=np.uint32)
-    hv_idx = np.ascontiguousarray(hv_idx, dtype=np.uint32)
-    hv_o = np.ascontiguousarray(hv_o, dtype=np.int32)
-    hv_off = np.ascontiguousarray(hv_off, dtype=np.uint64)
-    r0_, ch_ = np.ascontiguousarray(r0, dtype=np.int64), np.ascontiguousarray(chain, dtype=np.int64)
-    hl, al = np.ascontiguousarray(hap_len, dtype=np.uint32), np.ascontiguousarray(alias, dtype=np.int64)
-    seg_start = np.zeros(n + 1, dtype=np.uint64)
-    args = (_p(ind), C.c_uint64(len(ind)), _p(hv_idx), _p(hv_o), _p(hv_off), C.c_uint32(n), _p(r0_), _p(ch_), C.c_int64(int(startp)), _p(hl), _p(al),
-            _p(seg_start))
-    _lib.check(L.hawk_host_build_segments(*args, None, None, C.c_uint64(0)), "hawk_host_build_segments")
-    tot = int(seg_start[-1])
-    seg_rel = np.zeros(tot, dtype=np.uint32)
-    seg_gen = np.zeros(tot, dtype=np.int64)
-    _lib.check(L.hawk_host_build_segments(*args, _p(seg_rel), _p(seg_gen), C.c_uint64(tot)), "hawk_host_build_segments")
-    return seg_start.astype(np.int64), seg_rel, seg_gen
-
-
-def build_segments_numpy(ind, hv_idx, hv_o, hv_off, r0, chain, startp: int, hap_len, alias):
-    """build_segments in numpy (all rows at once): every carried deletion opens one segment behind it, every carried
-    insertion of n bases opens n + 1 (the inserted bases all map to the anchor position, haplotype.py:106-159)."""
-    n_hap = len(hap_len)
-    ind = np.asarray(ind, dtype=np.int64)
-    o_i = hv_o[ind].astype(np.int64)
-    pos_i = r0[hv_idx[ind]] + startp
-    ch_i = chain[hv_idx[ind]]
-    row_i = np.searchsorted(np.asarray(hv_off[1:], dtype=np.int64), ind, side="right")  # row of the entry (row 0 is REF)
-    nseg_i = np.where(ch_i < 0, 1, ch_i + 1)
-    first_of = np.cumsum(nseg_i) - nseg_i
-    k_in = np.arange(int(nseg_i.sum())) - np.repeat(first_of, nseg_i)  # 0..n within an insertion's run, 0 for a deletion
-    base_i = np.where(ch_i < 0, pos_i + 1 - ch_i, pos_i)
-    bump_at = np.where(ch_i < 0, np.iinfo(np.int64).max, ch_i)
-    seg_rel_all = np.repeat(o_i + 1, nseg_i) + k_in
-    seg_gen_all = np.repeat(base_i, nseg_i) + (k_in >= np.repeat(bump_at, nseg_i))
-    seg_row_all = np.repeat(row_i, nseg_i)
-    keep = seg_rel_all < np.asarray(hap_len)[seg_row_all].astype(np.int64)
-    seg_rel_all, seg_gen_all, seg_row_all = seg_rel_all[keep], seg_gen_all[keep], seg_row_all[keep]
-    # rows collapsed onto another keep the identity map only; every row starts with the identity segment (rel 0 ->
-    # startp).  The rows' own segments come out in (row, rel) order already - list entries are ordered by row, then by
-    # variant, and output positions grow with the variant - so the identity segments are slotted in, not sorted in.
-    live_seg = np.asarray(alias)[seg_row_all] == seg_row_all
-    seg_rel_all, seg_gen_all, seg_row_all = seg_rel_all[live_seg], seg_gen_all[live_seg], seg_row_all[live_seg]
-    own_cnt = np.bincount(seg_row_all, minlength=n_hap)
-    seg_start = np.concatenate(([0], np.cumsum(own_cnt + 1)))
-    dst = np.arange(len(seg_rel_all)) + seg_row_all + 1    # own segment i of row r lands behind r + 1 identity segments
-    rel_m = np.zeros(int(seg_start[-1]), dtype=np.int64)
-    gen_m = np.full(int(seg_start[-1]), startp, dtype=np.int64)
-    rel_m[dst] = seg_rel_all
-    gen_m[dst] = seg_gen_all
-    return seg_start, rel_m.astype(np.uint32), gen_m
 
 
 class _RowInfos:
@@ -527,82 +427,15 @@ def _collapse_rows(hashes: np.ndarray, samples: List[str], live: np.ndarray, n_h
     return alias, _RowInfos(n_hap, samples, e_s, e_g, e_r, e_owner, rows_of)
 
 
-def _expand_rows(ref_set, seq: str, startp: int, stopp: int, pamlen: int, samples: List[str], tab, live: np.ndarray,
-                 counts_live: np.ndarray, hv_idx: np.ndarray, hv_o: np.ndarray, tot_live: np.ndarray, device,
-                 own: Optional[ScanOwnership] = None, keep_plan: bool = False, indel_entries: Optional[np.ndarray] = None):
-    """Common tail of the device expansions: rows = REF + every chromosome copy (column) with a non-empty carried
-    list, in column order.  Builds the expansion plan (hawk_xplan_create), runs it, then labels / homozygous merge /
-    collapse on the 16-byte content hashes (haplotypes.py:232-368) and the position-map segments + scan bounds of every
-    kept row.  With `keep_plan` the plan (inputs + metadata resident in HBM) stays attached as `ds.plan`, so the set can
-    be re-expanded with device work only."""
-    import ctypes as C
-    from . import _lib
-    from .expand import HaplotypeBuildError
-    from .hapset import DeviceHapSet, ExpansionPlan, _p
-    r0, span, chain, altlen, alt_off, alt_codes = tab
-    n_ref, nv = len(seq), len(r0)
-    n_hap = 1 + len(live)
-    hv_off = np.zeros(n_hap + 1, dtype=np.uint64)
-    hv_off[2:] = np.cumsum(counts_live)
-    hv_idx = np.ascontiguousarray(hv_idx, dtype=np.uint32)
-    hv_o = np.ascontiguousarray(hv_o, dtype=np.int32)
-    hap_len = np.concatenate(([n_ref], n_ref + np.asarray(tot_live, dtype=np.int64))).astype(np.uint32)
-    # the carried indels: listed by the device inversion (hawk_gt_lists_indels), else one byte-table gather over the lists
-    ind = indel_entries if indel_entries is not None else np.flatnonzero((chain != 0).astype(np.uint8)[hv_idx])
-    if len(ind) and own is None:
-        # the reference's clamp (haplotype.py:199-201) would fire.  It compares with the REGION's original length, which a
-        # tile of a larger region cannot know (the shift accumulated before the tile): tiled searches do not reproduce
-        # that end-of-region error (DESIGN.md, divergences).  Only INDELS can trip it: the reference applies a copy's SNVs
-        # first (haplotype.py:494-512), while the position map is still the identity.
-        if np.any(hv_o[ind].astype(np.int64) + span[hv_idx[ind]] > n_ref):
-            raise HaplotypeBuildError("variant beyond the original region length (haplotype.py:199-201 clamp)")
-    L = _lib.lib()
-    xh = C.c_void_p()
-    u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
-    arrs = [u32(r0), u32(span), u32(alt_off), u32(altlen), np.ascontiguousarray(alt_codes)]
-    rc = L.hawk_xplan_create(ref_set._h, nv, _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]), len(alt_codes),
-                             n_hap, _p(hv_off), _p(hv_idx), _p(hv_o), _p(hap_len), C.byref(xh))
-    if rc == _lib.HAWK_E_INVALID and len(hv_idx) > 1:
-        # the library validates every list it is given (ascending, non-overlapping, prefix sums consistent); say which
-        # rule of the reference a refused input broke (haplotype.py:214-252 raises on overlapping variants of one copy)
-        row_of = np.repeat(np.arange(len(live)), counts_live)
-        same_row = row_of[1:] == row_of[:-1]
-        if np.any(same_row & (r0[hv_idx[1:]] < r0[hv_idx[:-1]] + span[hv_idx[:-1]])):
-            raise HaplotypeBuildError("a chromosome copy carries overlapping variants")
-    _lib.check(rc, "hawk_xplan_create")
-    plan = ExpansionPlan(xh, hap_len, device)
-    plan.n_records = int(len(hv_idx))
-    ds, hashes, ms_val = plan.run(want_hash=True)
-    ms = C.c_float(ms_val)
-    hv_off_i = hv_off.astype(np.int64)
-    alias, info = _collapse_rows(hashes, samples, live, n_hap, lambda o: hv_idx[hv_off_i[o]:hv_off_i[o + 1]], ds)
-    # ---- position-map segments + scan bounds per row ------------------------------------------
-    seg_start, seg_rel_all, seg_gen_all = build_segments(ind, hv_idx, hv_o, hv_off, r0, chain, startp, hap_len, alias)
-    haps = RowMeta(seg_start, seg_rel_all.astype(np.uint32), seg_gen_all, hap_len, alias, startp)
-    haps.compute_scans(startp, stopp, pamlen, own)
-    ds.set_meta(haps)
-    if own is not None and own.partner is not None:
-        _lib.check(L.hawk_hapset_set_ref_partner_range(ds._h, int(own.partner[0]), int(own.partner[1])), "hawk_hapset_set_ref_partner_range")
-    ds.alias = alias
-    ds.host_meta = haps
-    if keep_plan:
-        plan.set_meta(haps)
-        if own is not None and own.partner is not None:
-            _lib.check(L.hawk_xplan_set_ref_partner_range(plan._x, int(own.partner[0]), int(own.partner[1])), "hawk_xplan_set_ref_partner_range")
-        plan.alias, plan.host_meta = alias, haps
-        ds.plan = plan
-    else:
-        plan.close()
-    kept = np.flatnonzero(alias == np.arange(n_hap)).tolist()
-    return ds, _KeptInfos(info, kept), float(ms.value), kept
-
-
 def _expand_rows_gt(ref_set, seq, startp: int, stopp: int, pamlen: int, samples: List[str], tab, g, col_off: np.ndarray, device,
                     keep_plan: bool = False, own: Optional[ScanOwnership] = None):
-    """_expand_rows for lists that are still on the device (`g`: a hawk_gt after hawk_gt_lists): the plan is created from
-    them in place (hawk_xplan_create_gt) - checks, position-map segments and the scan bounds' reverse look-ups are kernels
-    over the lists; the host sees a few words per ROW (lengths, content hashes, two look-ups) and decides which rows
-    collapse.  Labels read the lists / segments lazily (CarriedLists, RowMeta's fetch).  Takes ownership of `g`."""
+    """Common tail of the device expansions: rows = REF + every chromosome copy (column) with a non-empty carried list, in
+    column order.  `g` is a hawk_gt after hawk_gt_lists whose lists are still on the device: the expansion plan is created
+    from them in place (hawk_xplan_create_gt) - checks, position-map segments and the scan bounds' reverse look-ups are
+    kernels over the lists; the host sees a few words per ROW (lengths, content hashes, two look-ups) and does the labels /
+    homozygous merge / collapse on the 16-byte content hashes (haplotypes.py:232-368).  Labels read the lists / segments
+    lazily (CarriedLists, RowMeta's fetch).  With `keep_plan` the plan stays attached as `ds.plan`, so the set can be
+    re-expanded with device work only.  Takes ownership of `g`."""
     import ctypes as C
     from . import _lib
     from .expand import HaplotypeBuildError
@@ -644,8 +477,8 @@ def _expand_rows_gt(ref_set, seq, startp: int, stopp: int, pamlen: int, samples:
         sr, sg = np.zeros(nseg.value, dtype=np.uint32), np.zeros(nseg.value, dtype=np.int64)
         _lib.check(L.hawk_xplan_segments(plan._x, _p(so), _p(sr), _p(sg), C.c_uint64(nseg.value), None), "hawk_xplan_segments")
         return so.astype(np.int64), sr, sg
-    haps = RowMeta(None, None, None, hap_len, alias, startp, fetch=fetch, rev={lo_g: rev0, hi_g: rev1})
-    haps.compute_scans(startp, stopp, pamlen, own)
+    haps = RowMeta(fetch, hap_len, alias)
+    haps.compute_scans(rev0, rev1, startp, stopp, pamlen, own)
     _lib.check(L.hawk_xplan_finish_meta(plan._x, _p(haps.scan_lo.astype(np.int32)), _p(haps.scan_hi.astype(np.int32))), "hawk_xplan_finish_meta")
     if own is not None and own.partner is not None:
         _lib.check(L.hawk_xplan_set_ref_partner_range(plan._x, int(own.partner[0]), int(own.partner[1])), "hawk_xplan_set_ref_partner_range")
@@ -704,50 +537,10 @@ def invert_on_device(ctx, G: np.ndarray, r0: np.ndarray, chain: np.ndarray):
     return g, col_off
 
 
-def carried_lists_on_device(ctx, G: np.ndarray, r0: np.ndarray, chain: np.ndarray, want_indels: bool = False):
-    """A 0/1 genotype matrix G[variant, chromosome copy] -> per-copy carried-variant lists, on the device: the matrix goes
-    up as allele codes (hawk_gt_from_codes) and is inverted by the kernels of the VCF path (hawk_gt_lists).
-    -> (col_off[n_cols + 1], col_delta[n_cols], hv_idx, hv_o[, entry indices of the carried indels])"""
-    import ctypes as C
-    from . import _lib
-    from .hapset import _p
-    G = np.ascontiguousarray(G, dtype=np.uint8)
-    nv, n_cols = G.shape
-    if n_cols % 2:
-        raise ValueError("genotype matrix needs two columns per sample")
-    L = _lib.lib()
-    g = C.c_void_p()
-    _lib.check(L.hawk_gt_from_codes(ctx, _p(G), C.c_uint64(nv), n_cols // 2, C.byref(g)), "hawk_gt_from_codes")
-    try:
-        col_off = np.zeros(n_cols + 1, dtype=np.uint64)
-        col_delta = np.zeros(n_cols, dtype=np.int64)
-        ms_l = C.c_float(0)
-        _lib.check(L.hawk_gt_lists(g, _p(np.arange(nv, dtype=np.uint32)), _p(np.ones(nv, dtype=np.uint8)),
-                                   _p(np.ascontiguousarray(r0, dtype=np.int32)), _p(np.ascontiguousarray(chain, dtype=np.int32)), nv,
-                                   _p(col_off), _p(col_delta), C.byref(ms_l)), "hawk_gt_lists")
-        ne = int(col_off[-1])
-        hv_idx = np.zeros(max(ne, 1), dtype=np.uint32)
-        hv_o = np.zeros(max(ne, 1), dtype=np.int32)
-        _lib.check(L.hawk_gt_lists_download(g, _p(hv_idx), _p(hv_o)), "hawk_gt_lists_download")
-        indel = None
-        if want_indels:
-            ni = C.c_uint64(0)
-            _lib.check(L.hawk_gt_lists_indels(g, None, C.c_uint64(0), C.byref(ni)), "hawk_gt_lists_indels")
-            indel = np.zeros(max(ni.value, 1), dtype=np.uint32)
-            _lib.check(L.hawk_gt_lists_indels(g, _p(indel), C.c_uint64(ni.value), C.byref(ni)), "hawk_gt_lists_indels")
-            indel = indel[:ni.value]
-    finally:
-        L.hawk_gt_destroy(g)
-    if want_indels:
-        return col_off, col_delta, hv_idx[:ne], hv_o[:ne], indel
-    return col_off, col_delta, hv_idx[:ne], hv_o[:ne]
-
-
 def expand_on_device(reg: SynthRegion, pamlen: int, device: Optional[int] = None, sample_range: Optional[Tuple[int, int]] = None,
                      keep_plan: bool = False):
-    """build_phased_haplotypes() with the sequence work done by hawk_hapset_expand: the host only
-    prepares index arrays (which variants each chromosome copy carries, prefix sums of their length
-    changes), labels and position-map segments; no haplotype string is ever formed.
+    """build_phased_haplotypes() with the sequence work done on the device (hawk_gt_lists, hawk_xplan_create_gt,
+    hawk_xplan_run): the host only prepares the variant table and labels; no haplotype string is ever formed.
     Returns (DeviceHapSet, [HapInfo] of the kept rows, kernel ms, kept row indices).  Rows that collapse onto an earlier row
     (haplotypes.py:274-294; homozygous copies, 326-333) stay in HBM with an empty scan range."""
     seq, startp, stopp = reg.sequence, reg.startp, reg.stopp

@@ -17,8 +17,8 @@
 extern "C" {
 
 // ---------------------------------------------------------------------------- f1 haplotype expansion
-// An expansion plan keeps everything hawk_hapset_expand needs in HBM - the variant table, the carried-variant lists, the
-// per-workgroup variant ranges and (after hawk_xplan_set_meta) the metadata of the rows it produces - so that running
+// An expansion plan keeps everything an expansion needs in HBM - the variant table, the carried-variant lists, the
+// per-workgroup variant ranges and (after hawk_xplan_finish_meta) the metadata of the rows it produces - so that running
 // it is device work only: the per-tile loop of a whole-contig search re-expands its tiles without touching the host.
 void hawk_xplan_destroy(hawk_xplan* x) {
   if (!x) return;
@@ -35,12 +35,10 @@ void hawk_xplan_destroy(hawk_xplan* x) {
 }
 
 // The device half of plan creation: copies of REF's planes, the variant table, one record per carried variant, the tile
-// index.  The carried-variant lists come from the host (hv_idx / hv_o, uploaded into temporaries) or are already in HBM
-// (d_idx / d_o: the genotype inversion left them there, hawk_xplan_create_gt).
+// index.  The carried-variant lists d_idx / d_o are already in HBM: the genotype inversion left them there.
 static int xplan_build(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span, const uint32_t* v_alt_off,
                        const uint32_t* v_alt_len, const uint8_t* alt_codes, uint32_t alt_codes_len, uint32_t n_hap, const uint64_t* hv_off,
-                       const uint32_t* hv_idx, const int32_t* hv_o, const uint32_t* d_idx, const int32_t* d_o, const uint32_t* hap_len,
-                       uint32_t maxlen, hawk_xplan** out) {
+                       const uint32_t* d_idx, const int32_t* d_o, const uint32_t* hap_len, uint32_t maxlen, hawk_xplan** out) {
   hawk_ctx* ctx = ref_set->ctx;
   const uint32_t ref_len = ref_set->hap_len[0];
   const uint64_t ncar = hv_off[n_hap];
@@ -59,15 +57,13 @@ static int xplan_build(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r
   int rc = HAWK_OK;
   for (int p = 0; p < 4 && !rc; ++p) rc = hawk_pool_alloc((void**)&x->ref_plane[p], (size_t)x->ref_S * 4);
   // the per-variant and per-carried-variant tables only feed the record / tile kernels: temporaries of this call
-  DevBuf t_r0, t_span, t_ao, t_al, t_am, t_idx, t_o;
-  DevBuf* temps[] = {&t_r0, &t_span, &t_ao, &t_al, &t_am, &t_idx, &t_o};
+  DevBuf t_r0, t_span, t_ao, t_al, t_am;
+  DevBuf* temps[] = {&t_r0, &t_span, &t_ao, &t_al, &t_am};
   if (!rc) rc = t_r0.reserve(nv * 4);
   if (!rc) rc = t_span.reserve(nv * 4);
   if (!rc) rc = t_ao.reserve(nv * 4);
   if (!rc) rc = t_al.reserve(nv * 4);
   if (!rc) rc = t_am.reserve(nv * 16);
-  if (!rc && !d_idx) rc = t_idx.reserve(nc * 4);
-  if (!rc && !d_idx) rc = t_o.reserve(nc * 4);
   if (!rc) rc = x->recs.reserve(nc * hawk_hx_record_bytes());
   if (!rc) rc = x->heads.reserve(nc * 16);
   if (!rc) rc = x->tiles.reserve(nwg * hawk_hx_tile_bytes());
@@ -103,95 +99,21 @@ static int xplan_build(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r
     if (e == hipSuccess) e = hipMemcpyAsync(t_am.p, am.data(), (size_t)n_var * 16, hipMemcpyHostToDevice, st);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(x->off.p, hv_off, (size_t)(n_hap + 1) * 8, hipMemcpyHostToDevice, st);
-  if (ncar && e == hipSuccess && !d_idx) {
-    e = hipMemcpyAsync(t_idx.p, hv_idx, ncar * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(t_o.p, hv_o, ncar * 4, hipMemcpyHostToDevice, st);
-  }
   if (e == hipSuccess) e = hipMemcpyAsync(x->hlen.p, hap_len, (size_t)n_hap * 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    hawk_launch_hx_prepare(st, x->off.as<uint64_t>(), d_idx ? d_idx : t_idx.as<uint32_t>(), d_o ? d_o : t_o.as<int32_t>(), ncar, t_r0.as<uint32_t>(),
-                           t_span.as<uint32_t>(), t_ao.as<uint32_t>(), t_al.as<uint32_t>(), t_am.p, x->hlen.as<uint32_t>(), n_hap, x->S,
-                           x->recs.p, x->tiles.p);
-    hawk_launch_hx_heads(st, x->recs.p, d_idx ? d_idx : t_idx.as<uint32_t>(), ncar, x->heads.p);
+    hawk_launch_hx_prepare(st, x->off.as<uint64_t>(), d_idx, d_o, ncar, t_r0.as<uint32_t>(), t_span.as<uint32_t>(), t_ao.as<uint32_t>(),
+                           t_al.as<uint32_t>(), t_am.p, x->hlen.as<uint32_t>(), n_hap, x->S, x->recs.p, x->tiles.p);
+    hawk_launch_hx_heads(st, x->recs.p, d_idx, ncar, x->heads.p);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (auto* b : temps) b->release();
   if (e != hipSuccess) {
-    snprintf(hawk_hip_err_buf(), 256, "hawk_xplan_create: %s", hipGetErrorString(e));
+    snprintf(hawk_hip_err_buf(), 256, "hawk_xplan_create_gt: %s", hipGetErrorString(e));
     hawk_xplan_destroy(x);
     return HAWK_E_HIP;
   }
   *out = x;
-  return HAWK_OK;
-}
-
-int hawk_xplan_create(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
-                      const uint32_t* v_alt_off, const uint32_t* v_alt_len, const uint8_t* alt_codes, uint32_t alt_codes_len,
-                      uint32_t n_hap, const uint64_t* hv_off, const uint32_t* hv_idx, const int32_t* hv_o,
-                      const uint32_t* hap_len, hawk_xplan** out) {
-  if (!ref_set || !out || !n_hap || !hv_off || !hap_len || (n_var && (!v_r0 || !v_span || !v_alt_off || !v_alt_len || !alt_codes)))
-    return HAWK_E_INVALID;
-  const uint32_t ref_len = ref_set->hap_len[0];
-  const uint64_t ncar = hv_off[n_hap];
-  if (ncar && (!hv_idx || !hv_o)) return HAWK_E_INVALID;
-  // validate everything the kernel will index with, on the host
-  for (uint32_t i = 0; i < n_var; ++i) {
-    if ((uint64_t)v_r0[i] + v_span[i] > ref_len || v_span[i] == 0 || v_alt_len[i] == 0) return HAWK_E_INVALID;
-    if ((uint64_t)v_alt_off[i] + v_alt_len[i] > alt_codes_len) return HAWK_E_INVALID;
-    if (i && v_r0[i] < v_r0[i - 1]) return HAWK_E_INVALID;  // sorted by position (alleles of one site may share it)
-  }
-  uint32_t maxlen = 0;
-  for (uint32_t h = 0; h < n_hap; ++h) {
-    if (hv_off[h + 1] < hv_off[h]) return HAWK_E_INVALID;
-    int64_t off = 0;
-    uint32_t prev = 0;
-    for (uint64_t k = hv_off[h]; k < hv_off[h + 1]; ++k) {
-      const uint32_t vi = hv_idx[k];
-      if (vi >= n_var || (k > hv_off[h] && (vi <= prev || v_r0[vi] < v_r0[prev] + v_span[prev]))) return HAWK_E_INVALID;  // ascending, non-overlapping within a row
-      if ((int64_t)hv_o[k] != (int64_t)v_r0[vi] + off) return HAWK_E_INVALID;  // exclusive prefix of the length changes
-      off += (int64_t)v_alt_len[vi] - (int64_t)v_span[vi];
-      prev = vi;
-    }
-    if ((int64_t)hap_len[h] != (int64_t)ref_len + off) return HAWK_E_INVALID;
-    if (hap_len[h] >= (1u << 31) - 256) return HAWK_E_UNSUPPORTED;
-    maxlen = std::max(maxlen, hap_len[h]);
-  }
-  return xplan_build(ref_set, n_var, v_r0, v_span, v_alt_off, v_alt_len, alt_codes, alt_codes_len, n_hap, hv_off, hv_idx, hv_o, nullptr, nullptr,
-                     hap_len, maxlen, out);
-}
-
-int hawk_xplan_set_meta(hawk_xplan* x, const uint8_t* is_ref, const int32_t* scan_start, const int32_t* scan_stop,
-                        const uint32_t* seg_off, const uint32_t* seg_rel, const int64_t* seg_gen, int32_t ref_index) {
-  if (!x) return HAWK_E_INVALID;
-  hawk_ctx* ctx = x->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint32_t n = x->n_hap;
-  std::vector<TileMeta> t0;
-  int64_t mn, mx;
-  int rc = meta_build(n, x->hap_len, x->bph, is_ref, scan_start, scan_stop, seg_off, seg_rel, seg_gen, ref_index, &t0, &mn, &mx);
-  if (rc) return rc;
-  const uint32_t nseg = seg_off[n];
-  if ((rc = x->m_is_ref.reserve(n)) || (rc = x->m_ss.reserve((size_t)n * 4)) || (rc = x->m_se.reserve((size_t)n * 4)) ||
-      (rc = x->m_seg_off.reserve((size_t)(n + 1) * 4)) || (rc = x->m_seg_rel.reserve((size_t)nseg * 4)) ||
-      (rc = x->m_seg_gen.reserve((size_t)nseg * 8)) || (rc = x->m_tile.reserve(t0.size() * sizeof(TileMeta))))
-    return rc;
-  hipStream_t st = ctx->stream;
-  HIPCHK(hipMemcpyAsync(x->m_is_ref.p, is_ref, n, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_ss.p, scan_start, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_se.p, scan_stop, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_seg_off.p, seg_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_seg_rel.p, seg_rel, (size_t)nseg * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_seg_gen.p, seg_gen, (size_t)nseg * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(x->m_tile.p, t0.data(), t0.size() * sizeof(TileMeta), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  x->nseg = nseg; x->ref_index = ref_index; x->ref_startp = ref_index >= 0 ? seg_gen[seg_off[ref_index]] : 0;
-  x->min_gen = mn; x->max_gen = mx;
-  x->scan_start.assign(scan_start, scan_start + n);
-  x->scan_stop.assign(scan_stop, scan_stop + n);
-  x->n_ref_rows = 0;
-  for (uint32_t h = 0; h < n; ++h) x->n_ref_rows += is_ref[h] ? 1u : 0u;
-  x->has_meta = true; x->cl.built = false; x->cl.usable = false;
   return HAWK_OK;
 }
 
@@ -450,7 +372,7 @@ int hawk_xplan_create_gt(hawk_hapset* ref_set, hawk_gt* g, uint32_t n_var, const
   hawk_ctx* ctx = ref_set->ctx;
   if (g->ctx != ctx) return HAWK_E_INVALID;
   const uint32_t ref_len = ref_set->hap_len[0];
-  for (uint32_t i = 0; i < n_var; ++i) {  // the variant table: everything the kernels index with (as hawk_xplan_create)
+  for (uint32_t i = 0; i < n_var; ++i) {  // the variant table: everything the kernels index with
     if ((uint64_t)v_r0[i] + v_span[i] > ref_len || v_span[i] == 0 || v_alt_len[i] == 0) return HAWK_E_INVALID;
     if ((uint64_t)v_alt_off[i] + v_alt_len[i] > alt_codes_len) return HAWK_E_INVALID;
     if (i && v_r0[i] < v_r0[i - 1]) return HAWK_E_INVALID;
@@ -474,8 +396,8 @@ int hawk_xplan_create_gt(hawk_hapset* ref_set, hawk_gt* g, uint32_t n_var, const
   const uint32_t n_hap = (uint32_t)hap_len.size();
   *n_hap_out = n_hap;
   hawk_xplan* x = nullptr;
-  int rc = xplan_build(ref_set, n_var, v_r0, v_span, v_alt_off, v_alt_len, alt_codes, alt_codes_len, n_hap, hv_off.data(), nullptr, nullptr,
-                       g->d_idx, g->d_o, hap_len.data(), maxlen, &x);
+  int rc = xplan_build(ref_set, n_var, v_r0, v_span, v_alt_off, v_alt_len, alt_codes, alt_codes_len, n_hap, hv_off.data(), g->d_idx, g->d_o,
+                       hap_len.data(), maxlen, &x);
   if (rc) return rc;
   // ---- checks over every list entry, position-map segments, the two reverse look-ups: device work over the lists in place
   hipStream_t st = ctx->stream;
@@ -577,21 +499,6 @@ int hawk_xplan_segments(hawk_xplan* x, uint32_t* seg_off, uint32_t* seg_rel, int
   if (seg_gen) HIPCHK(hipMemcpyAsync(seg_gen, x->m_seg_gen.p, (size_t)x->nseg * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return HAWK_OK;
-}
-
-int hawk_hapset_expand(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
-                       const uint32_t* v_alt_off, const uint32_t* v_alt_len, const uint8_t* alt_codes, uint32_t alt_codes_len,
-                       uint32_t n_hap, const uint64_t* hv_off, const uint32_t* hv_idx, const int32_t* hv_o,
-                       const uint32_t* hap_len, hawk_hapset** out, uint64_t* hash_out, float* kernel_ms) {
-  hawk_xplan* x = nullptr;
-  int rc = hawk_xplan_create(ref_set, n_var, v_r0, v_span, v_alt_off, v_alt_len, alt_codes, alt_codes_len, n_hap, hv_off, hv_idx, hv_o,
-                             hap_len, &x);
-  if (rc) return rc;
-  std::vector<uint64_t> tmp;
-  if (!hash_out) { tmp.resize((size_t)n_hap * 2); hash_out = tmp.data(); }  // run synchronously either way
-  rc = hawk_xplan_run(x, out, hash_out, kernel_ms);
-  hawk_xplan_destroy(x);
-  return rc;
 }
 
 // ---------------------------------------------------------------------------- f3: VCF genotypes

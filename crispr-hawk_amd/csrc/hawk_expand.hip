@@ -9,7 +9,7 @@
 // planes (funnel shift), alt alleles are written from their IUPAC codes with the V bit set
 // (the reference lower-cases every alt base, haplotype.py:120: a deletion's anchor is marked
 // even though it equals REF).
-//   once per plan (hawk_xplan_create):
+//   once per plan (hawk_xplan_create_gt):
 //   k_hx_records one 32-byte record per carried variant of every row: where it starts in the row, where REF resumes
 //               behind it, its first 32 alt bases as plane bits
 //   k_hx_index  per (row, tile of 32768 output positions): the row's records the tile needs, the REF words it reads

@@ -126,8 +126,8 @@ struct hawk_hapset {
   DevBuf crep[8];  // hawk_table_collapse_export: one representative row per group
 };
 
-// An expansion plan keeps everything hawk_hapset_expand needs in HBM - the variant table, the carried-variant lists, the
-// per-workgroup variant ranges and (after hawk_xplan_set_meta) the metadata of the rows it produces - so that running
+// An expansion plan keeps everything an expansion needs in HBM - the variant table, the carried-variant lists, the
+// per-workgroup variant ranges and (after hawk_xplan_finish_meta) the metadata of the rows it produces - so that running
 // it is device work only: the per-tile loop of a whole-contig search re-expands its tiles without touching the host.
 struct hawk_xplan {
   hawk_ctx* ctx;
@@ -139,7 +139,7 @@ struct hawk_xplan {
   DevBuf ref5[HAWK_PLANES];  // the same planes (+ an all-zero V plane) at the ROWS' stride S: row 0 of a view (hawk_xplan_view)
   DevBuf recs, tiles, codes, off, hlen, hash;  // 32 B per carried variant, 16 B per (row, tile): hawk_expand.hip
   DevBuf heads;                               // the records' first 16 bytes {o, rs, alt_len, alt_off} once more: what the dictionary passes stream
-  // metadata of the produced rows (hawk_xplan_set_meta)
+  // metadata of the produced rows: segments from hawk_xplan_create_gt, scan ranges and tile records from hawk_xplan_finish_meta
   bool has_meta;
   std::vector<int32_t> scan_start, scan_stop;
   DevBuf m_is_ref, m_ss, m_se, m_seg_off, m_seg_rel, m_seg_gen, m_tile;

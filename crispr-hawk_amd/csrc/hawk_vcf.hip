@@ -11,8 +11,8 @@
 //   k_gt_count / k_gt_fill   one wave per chromosome copy (column): variants are tested 64 at a time
 //                (codes[line(j)][col] == allele(j)), the ballots kept; the fill pass turns them into the
 //                ascending carried-variant list of the column plus, per entry, its offset in the
-//                haplotype being built (r0 + running sum of the length changes): exactly the hv_idx / hv_o
-//                inputs of hawk_hapset_expand.
+//                haplotype being built (r0 + running sum of the length changes): exactly the lists
+//                hawk_xplan_create_gt expands in place.
 #include "hawk_bits.h"
 
 #define GT_CHUNK 16

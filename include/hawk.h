@@ -109,37 +109,41 @@ int hawk_hapset_rows_equal(hawk_hapset* hs, uint32_t n_pairs, const uint32_t* ro
 int hawk_hapset_upload_planes(hawk_hapset* hs, const uint32_t* planes);
 
 /* ---- haplotype expansion on the device, replacing Haplotype.add_variants_phased
- * (haplotype.py:214-252) per chromosome copy.  ref_set: a one-row hapset holding the REF region.
- * Variant table (position-sorted, non-overlapping): v_r0 = position in the region, v_span = REF bases
- * replaced (SNV 1, deletion len(ref), insertion 1), alt allele = v_alt_len IUPAC codes (encoder.py
- * nibbles, one per byte) at alt_codes + v_alt_off.  Row h of the new set carries variants
- * hv_idx[hv_off[h] .. hv_off[h+1]) (ascending) whose output start positions hv_o are the exclusive
- * prefix sums r0 + sum of earlier (alt_len - span); hap_len[h] = region length + its total change
- * (all verified on the host before launch).  Alt bases are written with the V plane set, exactly as
- * the reference lower-cases them.  hash_out (optional, 2 words per row): content hash for
- * collapse_haplotypes (haplotypes.py:274-294).  The caller finishes with hawk_hapset_set_meta. */
-int hawk_hapset_expand(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
-                       const uint32_t* v_alt_off, const uint32_t* v_alt_len, const uint8_t* alt_codes, uint32_t alt_codes_len,
-                       uint32_t n_hap, const uint64_t* hv_off, const uint32_t* hv_idx, const int32_t* hv_o,
-                       const uint32_t* hap_len, hawk_hapset** out, uint64_t* hash_out, float* kernel_ms);
-
-/* The same expansion as a reusable plan: hawk_xplan_create validates the inputs once and keeps them in HBM (it copies
- * the REF planes, so ref_set may be destroyed), hawk_xplan_run writes a fresh haplotype set from them with device work
- * only, hawk_xplan_set_meta stores the metadata (arguments as hawk_hapset_set_meta) every later run installs into the
- * set it returns.  This is what the region-tiling loop of a whole-contig search (search_guides.py:510-548 over one
- * 50 Mb region; here one tile at a time inside a fixed HBM budget) runs per tile.  hash_out / kernel_ms may be NULL
- * (then the run is asynchronous on the context's stream). */
+ * (haplotype.py:214-252) per chromosome copy, as a reusable plan whose inputs stay in HBM.  ref_set: a one-row hapset
+ * holding the REF region (the plan copies its planes, so ref_set may be destroyed).  Variant table (sorted by position):
+ * v_r0 = position in the region, v_span = REF bases replaced (SNV 1, deletion len(ref), insertion 1), alt allele =
+ * v_alt_len IUPAC codes (encoder.py nibbles, one per byte) at alt_codes + v_alt_off, v_chain[i] = alt_len - span.  Alt
+ * bases are written with the V plane set, exactly as the reference lower-cases them.
+ * Plan creation straight from the genotype inversion: `g` is a hawk_gt after hawk_gt_lists, whose carried-variant lists
+ * are still in HBM - they are used in place (rows = REF + every chromosome copy with a non-empty list, in column order),
+ * nothing is downloaded, and what the host used to do over every list entry runs as kernels: the ascending /
+ * non-overlapping check (HAWK_E_OVERLAP), the reference's end-of-region clamp for indels when check_clamp != 0
+ * (HAWK_E_CLAMP), the position-map segments of every row (haplotype.py:90-159) and posmap_rev at the two genomic positions
+ * rev_g0 / rev_g1 the scan bounds start from (search_guides.py:49-84).  hawk_xplan_rows returns the rows' lengths and
+ * the two look-ups (-1: the position is deleted from that row); the caller turns them into scan ranges (rows collapsed
+ * onto another get an empty one) and hawk_xplan_finish_meta builds the per-tile records.
+ * hawk_xplan_segments downloads the segments (for labels / reports); hawk_xplan_install_meta gives a set hawk_xplan_run
+ * wrote BEFORE the metadata existed (the run whose hashes decide which rows collapse) the finished metadata.
+ * hawk_xplan_set_ref_partner_range: hawk_hapset_set_ref_partner_range for every set the plan installs its metadata into.
+ * hawk_xplan_run writes a fresh haplotype set from the plan with device work only: what the region-tiling loop of a
+ * whole-contig search (search_guides.py:510-548 over one 50 Mb region; here one tile at a time inside a fixed HBM
+ * budget) runs per tile.  hash_out (optional, 2 words per row): content hash for collapse_haplotypes
+ * (haplotypes.py:274-294).  hash_out / kernel_ms may be NULL (then the run is asynchronous on the context's stream). */
 typedef struct hawk_xplan hawk_xplan;
-int hawk_xplan_create(hawk_hapset* ref_set, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
-                      const uint32_t* v_alt_off, const uint32_t* v_alt_len, const uint8_t* alt_codes, uint32_t alt_codes_len,
-                      uint32_t n_hap, const uint64_t* hv_off, const uint32_t* hv_idx, const int32_t* hv_o,
-                      const uint32_t* hap_len, hawk_xplan** out);
-int hawk_xplan_set_meta(hawk_xplan* x, const uint8_t* is_ref, const int32_t* scan_start, const int32_t* scan_stop,
-                        const uint32_t* seg_off, const uint32_t* seg_rel, const int64_t* seg_gen, int32_t ref_index);
+typedef struct hawk_gt hawk_gt;
+int hawk_xplan_create_gt(hawk_hapset* ref_set, hawk_gt* g, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
+                         const uint32_t* v_alt_off, const uint32_t* v_alt_len, const int32_t* v_chain, const uint8_t* alt_codes,
+                         uint32_t alt_codes_len, int64_t startp, int check_clamp, int64_t rev_g0, int64_t rev_g1, uint32_t* n_hap_out,
+                         hawk_xplan** out);
+int hawk_xplan_rows(hawk_xplan* x, uint32_t* hap_len, int64_t* rev0, int64_t* rev1);
+int hawk_xplan_finish_meta(hawk_xplan* x, const int32_t* scan_start, const int32_t* scan_stop);
+int hawk_xplan_segments(hawk_xplan* x, uint32_t* seg_off, uint32_t* seg_rel, int64_t* seg_gen, uint64_t cap, uint64_t* n_seg);
+int hawk_xplan_install_meta(hawk_xplan* x, hawk_hapset* hs);
 int hawk_xplan_set_ref_partner_range(hawk_xplan* x, int32_t start, int32_t stop);
 int hawk_xplan_run(hawk_xplan* x, hawk_hapset** out, uint64_t* hash_out, float* kernel_ms);
-/* A VIEW of the plan's rows: a haplotype set with the plan's metadata (hawk_xplan_set_meta must have been called, REF = row
- * 0) but WITHOUT planes.  hawk_search on a view computes the same table, totals and row order as on the set hawk_xplan_run
+void hawk_xplan_destroy(hawk_xplan* x);
+/* A VIEW of the plan's rows: a haplotype set with the plan's metadata (hawk_xplan_finish_meta must have been called, REF =
+ * row 0) but WITHOUT planes.  hawk_search on a view computes the same table, totals and row order as on the set hawk_xplan_run
  * writes - encode (encoder.py:48-57 over every haplotype) and search (search_guides.py:510-548) in one step, straight from
  * REF + the rows' variant records: windows without a variant base are dropped by the reference (search_guides.py:468-471),
  * so only the words around a row's variants are assembled (in registers) and matched; the PAM hits of the verbatim REF
@@ -159,26 +163,6 @@ int hawk_xplan_cluster_stats(const hawk_xplan* x, uint32_t* usable, uint32_t* n_
 /* Builds the dictionary again from the plan's records (same result; buffers reused).  What bench.py calls inside its timed
  * step so that `value` carries the dictionary's cost: the product builds one per plan and searches it once (pipeline.search_files). */
 int hawk_xplan_cluster_rebuild(hawk_xplan* x);
-/* Plan creation straight from the genotype inversion: `g` is a hawk_gt after hawk_gt_lists, whose carried-variant lists
- * are still in HBM - they are used in place (rows = REF + every chromosome copy with a non-empty list, in column order),
- * nothing is downloaded, and what the host used to do over every list entry runs as kernels: the ascending /
- * non-overlapping check (HAWK_E_OVERLAP), the reference's end-of-region clamp for indels when check_clamp != 0
- * (HAWK_E_CLAMP), the position-map segments of every row (haplotype.py:90-159) and posmap_rev at the two genomic positions
- * rev_g0 / rev_g1 the scan bounds start from (search_guides.py:49-84).  v_chain[i] = alt_len - span.  hawk_xplan_rows
- * returns the rows' lengths and the two look-ups (-1: the position is deleted from that row); the caller turns them into
- * scan ranges (rows collapsed onto another get an empty one) and hawk_xplan_finish_meta builds the per-tile records.
- * hawk_xplan_segments downloads the segments (for labels / reports); hawk_xplan_install_meta gives a set hawk_xplan_run
- * wrote BEFORE the metadata existed (the run whose hashes decide which rows collapse) the finished metadata. */
-typedef struct hawk_gt hawk_gt;
-int hawk_xplan_create_gt(hawk_hapset* ref_set, hawk_gt* g, uint32_t n_var, const uint32_t* v_r0, const uint32_t* v_span,
-                         const uint32_t* v_alt_off, const uint32_t* v_alt_len, const int32_t* v_chain, const uint8_t* alt_codes,
-                         uint32_t alt_codes_len, int64_t startp, int check_clamp, int64_t rev_g0, int64_t rev_g1, uint32_t* n_hap_out,
-                         hawk_xplan** out);
-int hawk_xplan_rows(hawk_xplan* x, uint32_t* hap_len, int64_t* rev0, int64_t* rev1);
-int hawk_xplan_finish_meta(hawk_xplan* x, const int32_t* scan_start, const int32_t* scan_stop);
-int hawk_xplan_segments(hawk_xplan* x, uint32_t* seg_off, uint32_t* seg_rel, int64_t* seg_gen, uint64_t cap, uint64_t* n_seg);
-int hawk_xplan_install_meta(hawk_xplan* x, hawk_hapset* hs);
-void hawk_xplan_destroy(hawk_xplan* x);
 
 /* ---- K2: pam_search() (search_guides.py:102-131) ---------------------------------------
  * Raw PAM hits of every haplotype inside its [scan_start, scan_stop): ascending relative
@@ -375,17 +359,6 @@ int hawk_host_group_samples(const uint64_t* member_off, const uint32_t* member_h
                             const uint16_t* ent_a2, const uint8_t* ent_ok, uint64_t n_entries, const uint8_t* name_pool,
                             const uint64_t* name_off, uint64_t n_samples, const uint8_t* ent_pool, const uint64_t* ent_pool_off,
                             uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint8_t* group_flags);
-/* Position-map segments (haplotype.py:90-159 as unit-slope segments) of all rows of an expansion from its carried
- * indels (hawk_gt_lists_indels): CSR seg_start[n_rows + 1] (always written: call with cap = 0 for the size), seg_rel,
- * seg_gen.  Rows aliasing another row keep the identity segment only. */
-int hawk_host_build_segments(const uint32_t* indel_entry, uint64_t n_indel, const uint32_t* hv_idx, const int32_t* hv_o,
-                             const uint64_t* hv_off, uint32_t n_rows, const int64_t* var_r0, const int64_t* var_chain, int64_t startp,
-                             const uint32_t* hap_len, const int64_t* alias, uint64_t* seg_start, uint32_t* seg_rel, int64_t* seg_gen,
-                             uint64_t cap);
-/* posmap_rev[g] (haplotype.py:159: the last relative position whose genomic position is g; -1 where g is deleted) of every
- * row of such a segment table at once: what compute_scan_start_stop (search_guides.py:49-84) looks up per haplotype. */
-int hawk_host_posmap_rev(const uint64_t* seg_start, const uint32_t* seg_rel, const int64_t* seg_gen, const uint32_t* hap_len,
-                         uint32_t n_rows, int64_t g, int64_t* out);
 
 /* ---- the one exchange of a multi-GPU job.  One process per GPU, haplotypes block-partitioned with REF
  * on every rank (search_guides.py:111-131, 530-547 loop over independent haplotypes), no collective on the search
@@ -428,8 +401,8 @@ int hawk_host_gather_plan(int world, int rank, int dst, const uint64_t* dir4, ui
  *   (column c = 2*sample + copy) the ascending list of carried variants is built on the device; col_off[2*n_samples+1]
  *   (host) receives the CSR offsets, col_delta (host, may be NULL) the summed length change per column.
  *   hawk_gt_lists_download copies hv_idx and hv_o = var_r0 + exclusive running sum of var_chain within the
- *   column (host or device destinations) - the inputs of hawk_hapset_expand for the rows "columns with a
- *   non-empty list, in column order". */
+ *   column (host or device destinations): the lists hawk_xplan_create_gt expands in place, for the rows "columns
+ *   with a non-empty list, in column order". */
 int hawk_gt_parse(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, const uint64_t* gt_off,
                   uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms);
 /* The same object from an allele-code matrix the caller already holds (codes[n_lines][2*n_samples], host): genotypes that

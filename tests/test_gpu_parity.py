@@ -166,7 +166,7 @@ def test_tile_boundary_lengths(region_len):
 
 @pytest.mark.parametrize("case", ["phased4", "phased16", "cpf1", "indel_dense", "tiny"])
 def test_device_haplotype_expansion_vs_reference_vectors(case):
-    """planes written by hawk_hapset_expand == planes packed from the haplotype
+    """planes written by hawk_xplan_run == planes packed from the haplotype
     strings the reference built; labels, position maps and scan bounds too; then the search."""
     from crisprhawk_hip.workload import expand_on_device
     from util import synth_region_from_fixture, posmap_from_breaks
