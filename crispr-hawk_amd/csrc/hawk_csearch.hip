@@ -131,6 +131,10 @@ size_t hawk_cl_listed_bytes() { return sizeof(ClListed); }
 // the records of lanes + 1, + 2 (a cluster's second and third record are the records of the lanes above - nine clusters in ten are
 // one record, ninety-nine in a hundred at most three: no dependent load until a cluster is longer or crosses the wave's end).
 struct ClCut { int32_t o_first, o_end, pa, rb; uint32_t n, cls; unsigned long long key; bool run_inside, too_long; };
+#ifdef HAWK_TEST_HOOKS  // libhawk_hip_hooks.so only (tests/hooks_cluster_check.py): HAWK_CLUSTER_WEAK_HASH=1 keys a cluster by its FIRST
+// record alone, so that clusters which share it collide in the table and k_cl_uid's record-by-record compare has something to catch
+__device__ uint32_t cl_weak_hash;
+#endif
 __device__ __forceinline__ ClCut cl_cut(const HxHead* __restrict__ recs, uint64_t lo, uint64_t hi, uint64_t j, const uint4& r0, const uint4& rp,
                                          const uint4& nx1, const uint4& nx2, uint32_t lane, int32_t ss, int32_t se, int32_t hl, uint32_t row) {
   ClCut c;
@@ -142,6 +146,9 @@ __device__ __forceinline__ ClCut cl_cut(const HxHead* __restrict__ recs, uint64_
   uint64_t e = j + 1, h = cl_mix(0x243F6A8885A308D3ull, (uint64_t)(uint32_t)(c.o_first + c.rb));
   h = cl_mix(h, (uint64_t)r0.w | ((uint64_t)r0.z << 32));
   h = cl_mix(h, (uint64_t)r0.y);
+#ifdef HAWK_TEST_HOOKS
+  const uint64_t h_first = h;
+#endif
   c.n = 1;
   c.o_end = (int32_t)r0.x + (int32_t)r0.z;  // end of the cluster's last allele so far
   bool open = e < hi;                        // the record at e may still belong to the cluster
@@ -159,6 +166,9 @@ __device__ __forceinline__ ClCut cl_cut(const HxHead* __restrict__ recs, uint64_
     ++c.n; ++e;
     open = e < hi;
   }
+#ifdef HAWK_TEST_HOOKS
+  if (cl_weak_hash) h = h_first;
+#endif
   // window starts the cluster can touch: [o_first - (L - 1), o_end), L <= 44; the ranges they are tested against
   // (search_guides.py:49-84, 395-420) are [ss - po, se - po) and [PAD, len - L - PAD], po in {0, guidelen}
   const bool outside = c.o_end <= ss - 44 || c.o_first - 43 >= se;
@@ -561,6 +571,13 @@ void hawk_launch_cl_fill(hipStream_t st, const void* recs, const uint64_t* hv_of
                          const uint32_t* list_base, int32_t* o, uint32_t* row, int32_t* pa, int32_t* rb, uint32_t* inst_uid, void* var_desc,
                          uint32_t* claim_bits, uint32_t n_var, void* cx_list, uint32_t* status) {
   ClInst ci{o, row, pa, rb, inst_uid};
+#ifdef HAWK_TEST_HOOKS
+  {
+    const char* wk = getenv("HAWK_CLUSTER_WEAK_HASH");
+    const uint32_t weak = wk && wk[0] == '1' ? 1u : 0u;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(cl_weak_hash), &weak, sizeof(weak));
+  }
+#endif
   // (a small job - a stretch of a region on one of several GPUs - has no crowd to keep away from one address, and two launches
   // of pure latency to save: everything in the second launch, where every instance whose variant nobody described writes it)
   const uint32_t n_head = ch_bound < 16 * CL_HEAD_CHUNKS ? 0u : CL_HEAD_CHUNKS;
