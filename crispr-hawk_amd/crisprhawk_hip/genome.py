@@ -343,6 +343,47 @@ class GenomeIndex:
                                     decode_window(int(h["code"][i]), int(h["nmask"][i]), self.L)))
         return out
 
+    def summary(self, guides: Sequence[str], pam, right: bool, max_mm: int, cfd_tables=None, comm=None) -> dict:
+        """The scan's per-guide aggregates without its hits (hawk_offtarget_summary; mismatch-only): dict(hist = uint32
+        [n_guides, max_mm + 1] hits per guide and mismatch count - the on-target site included -, cfd_e4 = int64[n_guides]
+        the sum of round(CFD(guide, site), 4) over the guide's hits in units of 1e-4 (None without `cfd_tables` = (mm[20,4,4],
+        pam[16])), n_hits, n_unscorable = hits with a non-ACGT base under a CFD lookup, which count in hist and add nothing
+        to cfd_e4).  Every hit is consumed inside the match kernel: no capacity, no retry, nothing sized by the hits.
+        Duplicate guides get equal rows; an index without rows on this rank returns zeros.  The arrays are integers, so
+        shards add up exactly: with a communicator every rank's arrays are gathered to rank 0, which returns their sum
+        (other ranks return their own shard's)."""
+        n, stride = len(guides), int(max_mm) + 1
+        g2 = encode_guides(guides)
+        hist = np.zeros((n, stride), dtype=np.uint32)
+        cfd = np.zeros(n, dtype=np.int64) if cfd_tables is not None else None
+        nh, nu = C.c_uint64(0), C.c_uint64(0)
+        self._set_window(self.guidelen)
+        timing = dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+        if self.ds is not None:
+            mm = pt = None
+            if cfd_tables is not None:
+                mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
+                pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
+            par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), self.guidelen, int(bool(right)), int(max_mm))
+            tm = _lib.OtTiming()
+            rc = self.ds._L.hawk_offtarget_summary(self.ds._h, C.byref(par), _p(g2), n, None if mm is None else _p(mm),
+                                                   None if pt is None else _p(pt), _p(hist), None if cfd is None else _p(cfd),
+                                                   C.byref(nh), C.byref(nu), C.byref(tm))
+            _lib.check(rc, "hawk_offtarget_summary")
+            timing = {k: getattr(tm, k) for k, _ in tm._fields_}
+        self.last_timing = timing
+        out = dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value))
+        if comm is not None and comm.world > 1:
+            tail = np.array([out["n_hits"], out["n_unscorable"]], dtype=np.int64)
+            flat = np.concatenate([hist.reshape(-1).astype(np.int64), cfd if cfd is not None else np.zeros(0, np.int64), tail])
+            parts = comm.gatherv_bytes(flat, 0)
+            if comm.rank == 0:
+                tot = np.sum(np.stack(parts), axis=0, dtype=np.int64)
+                out = dict(hist=tot[:n * stride].astype(np.uint32).reshape(n, stride),
+                           cfd_e4=tot[n * stride:n * stride + n].copy() if cfd is not None else None,
+                           n_hits=int(tot[-2]), n_unscorable=int(tot[-1]))
+        return out
+
     def scan(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20, comm=None) -> List[OffTargetHit]:
         """All windows within ``max_mm`` mismatches of any guide, both strands, sorted by
         (guide, contig order, position, strand).  With a communicator (parallel.RcclComm / TcpComm) the hits of every

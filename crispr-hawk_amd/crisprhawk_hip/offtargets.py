@@ -3,9 +3,14 @@
 (offtargets.py:328-363) computed in one GPU batch.  The scan's hits are rendered as
 CRISPRitz-format report lines so that ``Offtarget`` parsing, the per-guide counts and the global
 CFD ``100 / (100 + sum(cfd))`` (offtargets.py:561-627) keep the reference's semantics.
+When only the guide report's two columns are wanted (``pipeline.search_files(offtargets_table=False)``),
+``specificity_by_spacer`` takes them from ``GenomeIndex.summary``: the match kernels sum, per guide, the hits
+and their CFD rounded to 4 decimals as integers, and no site is listed, rendered, parsed or scored on the host.
 BED annotation of the off-target table and Elevation are out of scope."""
 import os
 from typing import Dict, List, Set
+
+import numpy as np
 
 from .crisprhawk_error import CrisprHawkOffTargetsError
 from .exception_handlers import exception_handler
@@ -167,6 +172,33 @@ def offtargets_by_spacer(offtargets: List[Offtarget], spacers) -> Dict[str, tupl
     for ot in offtargets:
         rows[ot.grna_.upper().replace("-", "")].append(ot)
     return {sp: (len(r), str(round_score(_calculate_global_cfd(r)))) for sp, r in rows.items()}
+
+
+def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen: int, right: bool, debug: bool) -> Dict[str, tuple]:
+    """{SPACER: (count, global CFD text)} - offtargets_by_spacer's result without the per-site route: one
+    GenomeIndex.summary over the unique spacers (mismatch-only).  `count` is the guide's hits at 0..mm mismatches, the
+    on-target site included (the reference's len(rows)); the global CFD is 100 / (100 + sum of the sites' CFD rounded to 4
+    decimals), the sum kept as an integer number of 1e-4 units on the device.  PAMs outside SpCas9 / xCas9 get no CFD
+    ("1.0", what the table route's NA -> 0 gives).  The CFD tables are scoring.set_cfd_tables'; a hit with a non-ACGT base
+    under a lookup raises CrisprHawkCfdScoreError as compute_cfd_batch does."""
+    from .crisprhawk_error import CrisprHawkCfdScoreError
+    from .utils import round_score
+    uniq = sorted({sp.upper() for sp in spacers})
+    if not uniq:
+        return {}
+    tables = None
+    if pam.cas_system in (SPCAS9, XCAS9):
+        from .scoring import _tables
+        tables = _tables(debug)
+    try:
+        res = _genome_index(crispritz_index, guidelen, len(pam)).summary(uniq, pam, right, mm, cfd_tables=tables)
+    except ValueError as e:
+        exception_handler(CrisprHawkOffTargetsError, f"Off-targets search failed: {e}", os.EX_DATAERR, debug, e)
+    if res["n_unscorable"] > 0:
+        exception_handler(CrisprHawkCfdScoreError, "CFDon score calculation failed", os.EX_DATAERR, debug)
+    counts = res["hist"].sum(axis=1, dtype=np.int64).tolist()
+    sums = res["cfd_e4"].tolist() if res["cfd_e4"] is not None else [0] * len(uniq)
+    return {sp: (int(c), str(round_score(100 / (100 + e4 / 1e4)))) for sp, c, e4 in zip(uniq, counts, sums)}
 
 
 def estimate_offtargets_spacers(spacers, pam: PAM, crispritz_index, region, mm: int, bdna: int, brna: int, guidelen: int, right: bool,

@@ -42,7 +42,9 @@ def _labels(ds, info: List[HapInfo], kept: List[int], vt) -> List[Optional[RowLa
 
 def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir: str, debug: bool):
     """--estimate-offtargets for one region: {SPACER: (count, global CFD)} + offtargets_{contig}_{start}_{stop}.tsv."""
-    from .offtargets import estimate_offtargets_spacers
+    from .offtargets import estimate_offtargets_spacers, specificity_by_spacer
+    if not ot.get("table", True):  # the report's two columns alone: summed per guide on the device, no site listed
+        return specificity_by_spacer(spacers, pam, ot["genome"], ot["mm"], guidelen, right, debug)
     return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug)
 
 
@@ -96,7 +98,7 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, device: Optional[int] = None,
                  debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
-                 timings: Optional[Dict[str, float]] = None) -> Dict[str, str]:
+                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True) -> Dict[str, str]:
     """One report per BED interval; returns {str(coordinate): path}.  `cfd_tables = (mm[20,4,4], pam[16])` adds the
     CFDon column for SpCas9-class PAMs (scoring.py:352-387); `azimuth_model` (a fitted sklearn GBR or the flattened
     dict of scoring.azimuth_model_from_sklearn) and `deepcpf1_weights` (scoring.set_deepcpf1_weights layout) switch
@@ -104,7 +106,9 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     reference's --estimate-offtargets with its --crispritz-index: a genome.GenomeIndex, a {contig: sequence} dict or a
     FASTA path) runs the off-target stage per region: the `offtargets` / `cfd` columns of the guide report
     (reports.py:292-333, 612-660) and offtargets_{contig}_{start}_{stop}.tsv next to it (offtargets.py:486-558); `mm`,
-    `bdna`, `brna` as on the reference's command line (bulges of up to 2 bases).  The per-site CFD needs `cfd_tables`."""
+    `bdna`, `brna` as on the reference's command line (bulges of up to 2 bases).  The per-site CFD needs `cfd_tables`.
+    `offtargets_table=False` fills the two columns from the device's per-guide summary (offtargets.specificity_by_spacer)
+    and writes no offtargets_*.tsv; it is mismatch-only, so asking for it with `bdna` or `brna` is a ValueError."""
     import time as _time
     _t = [_time.perf_counter()]
 
@@ -113,6 +117,8 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
             now = _time.perf_counter()
             timings[stage] = timings.get(stage, 0.0) + now - _t[0]
             _t[0] = now
+    if not offtargets_table and (bdna or brna):
+        raise ValueError("offtargets_table=False is the mismatch-only summary: bulged sites (bdna / brna) need the off-targets table")
     ot = None
     if estimate_offtargets is not None:
         from .genome import GenomeIndex, read_fasta
@@ -121,7 +127,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
             genome = read_fasta(str(genome))
         if isinstance(genome, dict):
             genome = GenomeIndex(genome, guidelen, len(pam_seq), device=device, max_bulge=bdna)  # once for all regions
-        ot = dict(genome=genome, mm=mm, bdna=bdna, brna=brna)
+        ot = dict(genome=genome, mm=mm, bdna=bdna, brna=brna, table=bool(offtargets_table))
         if cfd_tables is not None:
             scoring.set_cfd_tables(*cfd_tables)
     if azimuth_model is not None:

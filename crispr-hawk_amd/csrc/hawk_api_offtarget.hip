@@ -1,4 +1,4 @@
-// hawk_api_offtarget.hip - C ABI: the off-target scan (K7)
+// hawk_api_offtarget.hip - C ABI: the off-target scan (K7) and its per-guide summary
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,25 +59,21 @@ static int ot_seed_tables(hawk_hapset* hs, const uint64_t* guides2, uint32_t n_g
   return HAWK_OK;
 }
 
-extern "C" {
-
-// ---------------------------------------------------------------------------- K7 off-targets
-int hawk_genome_finalize(hawk_hapset* rows) {
-  if (!rows || rows->vplan) return HAWK_E_INVALID;
-  HIPCHK(hipSetDevice(rows->ctx->device));
-  hawk_launch_ot_onehot(rows->ctx->stream, rows->plane, (uint64_t)rows->n_hap * rows->S);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(rows->ctx->stream));
-  return HAWK_OK;
-}
-
-int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
-                        uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm,
-                        uint64_t* out_code, uint32_t* out_nmask, uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing) {
-  if (!hs || !p || !hs->has_meta || !n_out || (n_guides && !guides2)) return HAWK_E_INVALID;
+// The front half hawk_offtarget_scan and hawk_offtarget_summary share: argument checks, the choice of the match kernel and its
+// bucketed guide tables, PAM scan -> site records (events 0..3 recorded), guides uploaded, the first 64 bytes of `misc` zeroed.
+struct OtFront {
+  hawk_ctx* ctx;
+  uint64_t nsites;
+  int G, sp0;
+  bool seeded, pairs;
+  OtSeeds sd;
+  OtPairSeeds ps;
+};
+static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, OtFront* f) {
+  if (!hs || !p || !hs->has_meta || (n_guides && !guides2)) return HAWK_E_INVALID;
   if (hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
   if (p->guidelen + p->pamlen > 32 || p->guidelen == 0) return HAWK_E_UNSUPPORTED;  // window code = 2 bits x 32
-  hawk_ctx* ctx = hs->ctx;
+  hawk_ctx* ctx = f->ctx = hs->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   ScanParams sp;
   int rc = make_scan_params(hs, p->pam_fwd, p->pam_rev, p->pamlen, p->guidelen, p->right, false, &sp);
@@ -99,11 +95,12 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
   // blocks, k_ot_match_seeded).  All pairs otherwise; HAWK_OT_ALLPAIRS=1 (read per call) forces them, the reference the parity
   // tests compare the seeded kernels against.
   const char* e_all = getenv("HAWK_OT_ALLPAIRS");
-  const int G = (int)p->guidelen, nb = (int)p->max_mm + 1;
-  const bool seeded = !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
-  const bool pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
-  OtSeeds sd;
-  OtPairSeeds ps;
+  const int G = f->G = (int)p->guidelen, nb = (int)p->max_mm + 1;
+  f->sp0 = p->right ? (int)p->pamlen : 0;
+  const bool seeded = f->seeded = !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
+  const bool pairs = f->pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
+  OtSeeds& sd = f->sd;
+  OtPairSeeds& ps = f->ps;
   memset(&sd, 0, sizeof(sd));
   memset(&ps, 0, sizeof(ps));
   if (pairs) {
@@ -138,25 +135,62 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
   ScanTotals tot;
   HIPCHK(hipMemcpyAsync(&tot, hs->totals.p, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint64_t nsites = tot.n_keep;
-  if ((rc = hs->sites.reserve(std::max<uint64_t>(nsites, 1) * sizeof(OtSite))) ||
-      (rc = hs->hits.reserve(std::max<uint64_t>(cap, 1) * sizeof(OtHit))))
-    return rc;
-  unsigned long long* d_nhits = hs->misc.as<unsigned long long>();
+  const uint64_t nsites = f->nsites = tot.n_keep;
+  if ((rc = hs->sites.reserve(std::max<uint64_t>(nsites, 1) * sizeof(OtSite)))) return rc;
   HIPCHK(hipEventRecord(ev[2], ctx->stream));
   if (nsites) hawk_launch_ot_sites(ctx->stream, d, sp, hs->keepF.as<uint32_t>(), hs->keepR.as<uint32_t>(),
                                    hs->offsets.as<uint64_t>(), hs->sites.as<OtSite>());
   HIPCHK(hipEventRecord(ev[3], ctx->stream));
-  if (pairs) {
-    hawk_launch_ot_match_pairs(ctx->stream, hs->sites.as<OtSite>(), nsites, ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                               hs->otid.as<uint32_t>(), n_guides, G, p->right ? (int)p->pamlen : 0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
-  } else if (seeded) {
-    hawk_launch_ot_match_seeded(ctx->stream, hs->sites.as<OtSite>(), nsites, sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                                hs->otid.as<uint32_t>(), n_guides, G, p->right ? (int)p->pamlen : 0, (int)p->max_mm,
-                                hs->hits.as<OtHit>(), cap, d_nhits);
+  return HAWK_OK;
+}
+// events 0..4 -> hawk_ot_timing; the match kernel ran between events m0 and 4
+static void ot_timing(hawk_hapset* hs, uint64_t nsites, hawk_ot_timing* timing, int m0 = 3) {
+  if (!timing) return;
+  hipEvent_t* ev = hs->ctx->ev;
+  memset(timing, 0, sizeof(*timing));
+  (void)hipEventElapsedTime(&timing->scan_ms, ev[0], ev[1]);
+  (void)hipEventElapsedTime(&timing->sites_ms, ev[2], ev[3]);
+  (void)hipEventElapsedTime(&timing->match_ms, ev[m0], ev[4]);
+  (void)hipEventElapsedTime(&timing->total_ms, ev[0], ev[4]);
+  timing->n_sites = nsites;
+  uint64_t pos = 0;
+  for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
+  timing->scanned_positions = pos;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------- K7 off-targets
+int hawk_genome_finalize(hawk_hapset* rows) {
+  if (!rows || rows->vplan) return HAWK_E_INVALID;
+  HIPCHK(hipSetDevice(rows->ctx->device));
+  hawk_launch_ot_onehot(rows->ctx->stream, rows->plane, (uint64_t)rows->n_hap * rows->S);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(rows->ctx->stream));
+  return HAWK_OK;
+}
+
+int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
+                        uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm,
+                        uint64_t* out_code, uint32_t* out_nmask, uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing) {
+  if (!n_out) return HAWK_E_INVALID;
+  OtFront f;
+  int rc = ot_front(hs, p, guides2, n_guides, &f);
+  if (rc) return rc;
+  hawk_ctx* ctx = f.ctx;
+  hipEvent_t* ev = ctx->ev;
+  const uint64_t nsites = f.nsites;
+  if ((rc = hs->hits.reserve(std::max<uint64_t>(cap, 1) * sizeof(OtHit)))) return rc;
+  unsigned long long* d_nhits = hs->misc.as<unsigned long long>();
+  if (f.pairs) {
+    hawk_launch_ot_match_pairs(ctx->stream, hs->sites.as<OtSite>(), nsites, f.ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
+                               hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
+  } else if (f.seeded) {
+    hawk_launch_ot_match_seeded(ctx->stream, hs->sites.as<OtSite>(), nsites, f.sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
+                                hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
   } else {
-    hawk_launch_ot_match(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, (int)p->guidelen,
-                         p->right ? (int)p->pamlen : 0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
+    hawk_launch_ot_match(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, f.G, f.sp0,
+                         (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
   }
   HIPCHK(hipEventRecord(ev[4], ctx->stream));
   HIPCHK(hipGetLastError());
@@ -164,17 +198,7 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
   HIPCHK(hipMemcpyAsync(&nh, d_nhits, 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *n_out = nh;
-  if (timing) {
-    memset(timing, 0, sizeof(*timing));
-    (void)hipEventElapsedTime(&timing->scan_ms, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&timing->sites_ms, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&timing->match_ms, ev[3], ev[4]);
-    (void)hipEventElapsedTime(&timing->total_ms, ev[0], ev[4]);
-    timing->n_sites = nsites;
-    uint64_t pos = 0;
-    for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
-    timing->scanned_positions = pos;
-  }
+  ot_timing(hs, nsites, timing);
   if (nh > cap) return HAWK_E_CAPACITY;
   if (!nh) return HAWK_OK;
   std::vector<OtHit> hh(nh);
@@ -195,6 +219,66 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
     if (out_code) out_code[i] = ss[i].code;
     if (out_nmask) out_nmask[i] = ss[i].nmask;
   }
+  return HAWK_OK;
+}
+
+int hawk_offtarget_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, const double* cfd_mm,
+                           const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable,
+                           hawk_ot_timing* timing) {
+  if (!n_hits || !n_unscorable || (n_guides && !out_hist) || !cfd_mm != !cfd_pam || (cfd_mm && n_guides && !out_cfd_e4)) return HAWK_E_INVALID;
+  if (p && ((cfd_mm && p->pamlen < 2) || p->max_mm > 32)) return HAWK_E_UNSUPPORTED;  // the PAM table is keyed by PAM[-2:]; a window has <= 32 bases
+  OtFront f;
+  int rc = ot_front(hs, p, guides2, n_guides, &f);
+  if (rc) return rc;
+  hawk_ctx* ctx = f.ctx;
+  // One block, sized by the guides alone: counters[2] | cfd_e4[n_guides] | CFD tables[336] | hist[n_guides][max_mm + 1].
+  // No hits / othit buffer is reserved on this path: a hit ends in these sums inside the match kernel.
+  const uint32_t stride = p->max_mm + 1;
+  const size_t off_tab = 16 + (size_t)n_guides * 8, off_hist = off_tab + 336 * 8;
+  const size_t bytes = off_hist + (size_t)n_guides * stride * 4;
+  if ((rc = hs->otsum.reserve(bytes))) return rc;
+  char* base = hs->otsum.as<char>();
+  HIPCHK(hipMemsetAsync(base, 0, bytes, ctx->stream));
+  if (cfd_mm) {
+    HIPCHK(hipMemcpyAsync(base + off_tab, cfd_mm, 320 * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(base + off_tab + 320 * 8, cfd_pam, 16 * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  OtSummary sm;
+  sm.sites = hs->sites.as<OtSite>();
+  sm.tab = cfd_mm ? reinterpret_cast<const double*>(base + off_tab) : nullptr;
+  sm.hist = reinterpret_cast<uint32_t*>(base + off_hist);
+  sm.cfd_e4 = reinterpret_cast<unsigned long long*>(base + 16);
+  sm.counters = reinterpret_cast<unsigned long long*>(base);
+  sm.stride = stride;
+  sm.sp0 = f.sp0;
+  sm.pam2 = (p->right ? 0 : f.G) + (int)p->pamlen - 2;
+  sm.ncmp = std::min(f.G, 20);
+  HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));  // the zeroing and the table upload are not the match kernel's time
+  if (f.pairs) {
+    hawk_launch_ot_match_pairs_sum(ctx->stream, sm.sites, f.nsites, f.ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
+                                   hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
+  } else if (f.seeded) {
+    hawk_launch_ot_match_seeded_sum(ctx->stream, sm.sites, f.nsites, f.sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
+                                    hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
+  } else {
+    hawk_launch_ot_match_sum(ctx->stream, sm.sites, f.nsites, hs->guides.as<uint64_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
+  }
+  HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
+  HIPCHK(hipGetLastError());
+  // one download: everything but the tables would do, the block is small either way
+  std::vector<char> host(bytes);
+  HIPCHK(hipMemcpyAsync(host.data(), base, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  uint64_t cnt[2];
+  memcpy(cnt, host.data(), 16);
+  *n_hits = cnt[0];
+  *n_unscorable = cnt[1];
+  if (n_guides) {
+    memcpy(out_hist, host.data() + off_hist, (size_t)n_guides * stride * 4);
+    if (out_cfd_e4 && cfd_mm) memcpy(out_cfd_e4, host.data() + 16, (size_t)n_guides * 8);
+    else if (out_cfd_e4) memset(out_cfd_e4, 0, (size_t)n_guides * 8);
+  }
+  ot_timing(hs, f.nsites, timing, 5);
   return HAWK_OK;
 }
 

@@ -243,6 +243,24 @@ void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n
                                  const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
                                  OtHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const OtHit* hits, uint64_t n_hits, OtSite* out);
+// The match kernels with the summary's hit sink (hawk_offtarget.hip: OtSumSink): where a hit goes instead of hits[].
+struct OtSummary {
+  const OtSite* sites;
+  const double* tab;             // CFD tables mm[20][4][4] + pam[16]; nullptr: counts only
+  uint32_t* hist;                // [n_guides][stride], zeroed
+  unsigned long long* cfd_e4;    // [n_guides], zeroed: per-guide sum of round(CFD, 4) in units of 1e-4 (two's complement)
+  unsigned long long* counters;  // [0] hits, [1] hits with an ambiguous base under a CFD lookup; zeroed
+  uint32_t stride;               // max_mm + 1
+  int32_t sp0, pam2, ncmp;       // window positions of spacer base 0 and of PAM[-2]; min(guidelen, 20)
+};
+void hawk_launch_ot_match_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
+                              int guidelen, int sp0, int max_mm, const OtSummary& sm);
+void hawk_launch_ot_match_seeded_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
+                                     const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
+                                     const OtSummary& sm);
+void hawk_launch_ot_match_pairs_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
+                                    const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
+                                    const OtSummary& sm);
 void hawk_launch_pack(hipStream_t st, const uint8_t* ascii, const uint64_t* seq_off, uint32_t hap0, uint32_t n_hap_batch,
                       uint64_t batch_base, const uint32_t* hap_len, uint32_t S, uint32_t* const* plane,
                       unsigned long long* bad_index);

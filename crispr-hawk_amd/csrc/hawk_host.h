@@ -108,6 +108,7 @@ struct hawk_hapset {
   uint64_t last_groups = 0;   // groups of the last collapse on this set (sizes the table of the next one)
   std::shared_ptr<uint64_t> plan_groups;  // ... shared with the expansion plan the set came from: the next run of the plan starts from it
   DevBuf otoff, otcode, otid, othit;  // hawk_offtarget_scan: bucketed guides, gathered hit sites
+  DevBuf otsum;                       // hawk_offtarget_summary: counters, per-guide sums, CFD tables - sized by the guides, not the hits
   DevBuf big;                 // tiles whose rows exceed the hand-over list (k_search_emit's work list)
   DevBuf refbits;             // REF's candidate-window bitmaps, one per strand (k_ref_bits)
   bool refbits_valid = false;

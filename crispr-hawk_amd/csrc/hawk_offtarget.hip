@@ -21,6 +21,9 @@
 //                 ~ (max_mm + 1) / 4^blocklen of the all-pairs work (max_mm = 7, where pair seeds do not fit)
 //   k_ot_match_pairs   the same with max_mm + 2 blocks and the guides bucketed per PAIR of blocks (max_mm <= 6)
 //   k_ot_gather   hit sites -> compact array for one download
+// What a match kernel does with a hit is its Sink (a template parameter): OtListSink appends it to hits[] for
+// hawk_offtarget_scan; OtSumSink consumes it where it is found - per-guide mismatch histogram and the sum of the sites' CFD in
+// units of 1e-4 - for hawk_offtarget_summary, which therefore holds nothing that grows with the number of hits.
 #include "hawk_bits.h"
 
 // reverse the low L (<= 32) bits
@@ -104,14 +107,70 @@ void hawk_launch_ot_sites(hipStream_t st, const HapSetDev& hs, const ScanParams&
   hipLaunchKernelGGL(k_ot_sites, dim3(hs.n_hap * p.bph), dim3(HAWK_BLOCK), 0, st, hs, p, keepF, keepR, offsets, sites);
 }
 
+// ---- hit sinks.  operator()(site index, guide index, the guide's 2-bit code, mismatches); the guide index is taken by reference
+// so that a sink which may drop the hit (OtListSink past cap) does not load it first.
+struct OtListSink {
+  OtHit* __restrict__ hits;
+  uint64_t cap;
+  unsigned long long* __restrict__ n_hits;
+  __device__ __forceinline__ void operator()(uint64_t site, const uint32_t& guide, uint64_t, int mm) const {
+    const unsigned long long o = atomicAdd(n_hits, 1ull);  // the compiler aggregates this per wave
+    if (o < cap) { OtHit hh; hh.site = site; hh.guide = guide; hh.mm = (uint32_t)mm; hits[o] = hh; }
+  }
+};
+
+// round(x, 4) of Python as an integer number of 1e-4 units: the nearest integer to the EXACT product x * 1e4, exact ties to
+// even (float_round -> dtoa mode 3 is correctly rounded on the binary value).  With k = floor(fl(x * 1e4)) the answer is k or
+// k + 1, decided by the sign of x * 1e4 - (k + 0.5), which one fma gives exactly in sign (the difference of two doubles below
+// 2^53 is far above the underflow range, so a non-zero exact residual never rounds to zero); zero is a true tie.
+__device__ __forceinline__ long long ot_round_e4(double x) {
+  const double k = floor(x * 1e4);
+  const double r = fma(x, 1e4, -(k + 0.5));
+  const long long ki = (long long)k;
+  if (r > 0.0) return ki + 1;
+  if (r < 0.0) return ki;
+  return ki + (ki & 1);
+}
+
+// The summary's sink.  Per hit: hist[guide][mm] += 1 and, with tables, cfd_e4[guide] += round(CFD(guide, site), 4) * 1e4 with the CFD
+// formed as compute_cfd forms it (cfdscore.py:53-95; the string form is k_cfd, hawk_kernels.hip): a left-to-right fp64 product
+// over the positions i < min(G, 20) where guide and site differ, times the entry of the site's PAM[-2:].  tab = mm[20][4][4]
+// ([position][guide base][site base], the r<wt>:d<revcomp(sg)> key already folded into the layout) + pam[16].  A site with an
+// ambiguous base under a lookup - among the first min(G, 20) spacer bases, where it always differs from the guide, or in PAM[-2:]
+// - is the reference's KeyError: counted in counters[1], still in hist, nothing added to cfd_e4.  Integer sums: the result does
+// not depend on the order of the atomics nor on how a genome is sharded.  The site record is read back per hit (hits are rare
+// next to candidates; the record is in L2 from the kernel's own first read).
+struct OtSumSink : OtSummary {  // hawk_device.h: sites, tab, hist, cfd_e4, counters, stride, sp0, pam2, ncmp
+  __device__ __forceinline__ void operator()(uint64_t site, const uint32_t& guide, uint64_t gcode, int mm) const {
+    const uint32_t g = guide;
+    atomicAdd(counters, 1ull);  // one address: aggregated per wave by the compiler
+    atomicAdd(hist + (size_t)g * stride + (uint32_t)mm, 1u);
+    if (!tab) return;
+    const OtSite st = sites[site];
+    if (((st.nmask >> sp0) & ((1u << ncmp) - 1u)) | ((st.nmask >> pam2) & 3u)) { atomicAdd(counters + 1, 1ull); return; }
+    const uint64_t sc = st.code >> (2 * sp0);
+    const uint64_t x = sc ^ gcode;
+    uint64_t d = (x | (x >> 1)) & 0x5555555555555555ull & ((1ull << (2 * ncmp)) - 1ull);
+    double s = 1.0;
+    while (d) {  // ascending position
+      const int b = __builtin_ctzll(d);
+      d &= d - 1;
+      s *= tab[((b >> 1) * 4 + (int)((gcode >> b) & 3u)) * 4 + (int)((sc >> b) & 3u)];
+    }
+    const uint32_t pp = (uint32_t)(st.code >> (2 * pam2)) & 15u;
+    s *= tab[320 + 4 * (pp & 3u) + (pp >> 2)];
+    atomicAdd(cfd_e4 + g, (unsigned long long)ot_round_e4(s));
+  }
+};
+
 // All pairs.  Each thread owns one site; the guides stream through LDS in chunks and are read
 // by every lane at the same address (LDS broadcast, conflict-free).  Per pair: XOR the 2-bit
 // codes, fold each base's two bits into one, add the ambiguity bits, popcount.
 #define OT_GCHUNK 1024
+template <class Sink>
 __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match(const OtSite* __restrict__ sites, uint64_t n_sites,
                                                           const uint64_t* __restrict__ guides, uint32_t n_guides, int guidelen,
-                                                          int sp0, int max_mm, OtHit* __restrict__ hits, uint64_t cap,
-                                                          unsigned long long* __restrict__ n_hits) {
+                                                          int sp0, int max_mm, Sink sink) {
   __shared__ uint64_t s_g[OT_GCHUNK];
   const uint64_t i = (uint64_t)blockIdx.x * HAWK_BLOCK + threadIdx.x;
   const bool have = i < n_sites;
@@ -136,28 +195,25 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match(const OtSite* __restric
       const uint64_t x = code ^ s_g[t];
       const uint64_t m = ((x | (x >> 1)) & 0x5555555555555555ull) | nm2;
       const int mm = __popcll(m);
-      if (mm <= max_mm) {
-        const unsigned long long o = atomicAdd(n_hits, 1ull);  // the compiler aggregates this per wave
-        if (o < cap) { OtHit hh; hh.site = i; hh.guide = g0 + t; hh.mm = (uint32_t)mm; hits[o] = hh; }
-      }
+      if (mm <= max_mm) sink(i, g0 + t, s_g[t], mm);
     }
   }
 }
 void hawk_launch_ot_match(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
                           int guidelen, int sp0, int max_mm, OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
   if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites, n_sites,
-                     guides, n_guides, guidelen, sp0, max_mm, hits, cap, n_hits);
+  hipLaunchKernelGGL(k_ot_match<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
+                     n_sites, guides, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
 }
 
 // Seeded match.  Each thread owns one site and visits, per block, the bucket of guides whose key bases equal the
 // site's (a gather from the L2-resident bucketed guide table).  A pair that agrees in the key bases of several
 // blocks is met several times; it is reported at the first of them.
+template <class Sink>
 __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_seeded(const OtSite* __restrict__ sites, uint64_t n_sites, OtSeeds sd,
                                                                  const uint32_t* __restrict__ goff, const uint64_t* __restrict__ gcode,
                                                                  const uint32_t* __restrict__ gid, uint32_t n_guides, int guidelen,
-                                                                 int sp0, int max_mm, OtHit* __restrict__ hits, uint64_t cap,
-                                                                 unsigned long long* __restrict__ n_hits) {
+                                                                 int sp0, int max_mm, Sink sink) {
   const uint64_t i = (uint64_t)blockIdx.x * HAWK_BLOCK + threadIdx.x;
   if (i >= n_sites) return;
   const OtSite st = sites[i];
@@ -181,8 +237,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_seeded(const OtSite* __
       bool earlier = false;
       for (int j = 0; j < b; ++j) earlier = earlier || (m & sd.pmask2[j]) == 0;
       if (earlier) continue;
-      const unsigned long long o = atomicAdd(n_hits, 1ull);
-      if (o < cap) { OtHit hh; hh.site = i; hh.guide = gi[t]; hh.mm = (uint32_t)mm; hits[o] = hh; }
+      sink(i, gi[t], gc[t], mm);
     }
   }
 }
@@ -190,8 +245,8 @@ void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n
                                  const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
                                  OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
   if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_seeded, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
-                     n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, hits, cap, n_hits);
+  hipLaunchKernelGGL(k_ot_match_seeded<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st,
+                     sites, n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
 }
 
 // Pair seeds, candidates dealt evenly.  A wave takes 64 sites.  Per pair of blocks every lane looks its site's bucket up (two
@@ -200,11 +255,11 @@ void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n
 // consecutive candidates are consecutive words of the bucketed table.  No lane idles because its own bucket is shorter than a
 // neighbour's (the per-lane bucket walks of the single-block seeded kernels ran at a third of their lanes: profiles/r03_c5_pmc.json).
 // A pair that agrees in more than two blocks is met in several tables and reported in the first (lowest two agreeing blocks).
+template <class Sink>
 __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_pairs(const OtSite* __restrict__ sites, uint64_t n_sites, OtPairSeeds sd,
                                                                 const uint32_t* __restrict__ goff, const uint64_t* __restrict__ gcode,
                                                                 const uint32_t* __restrict__ gid, uint32_t n_guides, int guidelen,
-                                                                int sp0, int max_mm, OtHit* __restrict__ hits, uint64_t cap,
-                                                                unsigned long long* __restrict__ n_hits) {
+                                                                int sp0, int max_mm, Sink sink) {
   __shared__ uint64_t s_code[HAWK_BLOCK / WAVE][WAVE], s_nm2[HAWK_BLOCK / WAVE][WAVE];
   __shared__ uint32_t s_ex[HAWK_BLOCK / WAVE][WAVE + 1], s_lo[HAWK_BLOCK / WAVE][WAVE];
   const uint32_t wv = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
@@ -257,7 +312,8 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_pairs(const OtSite* __r
 #pragma unroll
         for (uint32_t step = WAVE / 2; step; step >>= 1) l += (s_ex[wv][l + step] <= c) ? step : 0u;  // the last lane whose candidates start at or before c
         const uint32_t t = s_lo[wv][l] + (c - s_ex[wv][l]);
-        const uint64_t x = s_code[wv][l] ^ gc[t];
+        const uint64_t gct = gc[t];
+        const uint64_t x = s_code[wv][l] ^ gct;
         const uint64_t m = ((x | (x >> 1)) & 0x5555555555555555ull) | s_nm2[wv][l];
         const int mm = __popcll(m);
         if (mm <= max_mm) {
@@ -265,10 +321,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_pairs(const OtSite* __r
           int first = -1, second = -1;
           for (int b = 0; b < sd.nb; ++b)
             if ((m & sd.pmask2[b]) == 0) { if (first < 0) first = b; else if (second < 0) second = b; }
-          if (first == bi && second == bj) {
-            const unsigned long long o = atomicAdd(n_hits, 1ull);
-            if (o < cap) { OtHit hh; hh.site = i0 + l; hh.guide = gi[t]; hh.mm = (uint32_t)mm; hits[o] = hh; }
-          }
+          if (first == bi && second == bj) sink(i0 + l, gi[t], gct, mm);
         }
       }
     }
@@ -281,8 +334,30 @@ void hawk_launch_ot_match_pairs(hipStream_t st, const OtSite* sites, uint64_t n_
                                 const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
                                 OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
   if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_pairs, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites, n_sites, sd,
-                     goff, gcode, gid, n_guides, guidelen, sp0, max_mm, hits, cap, n_hits);
+  hipLaunchKernelGGL(k_ot_match_pairs<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
+                     n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
+}
+
+// The same three kernels with the summary's sink (hawk_offtarget_summary).
+void hawk_launch_ot_match_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
+                              int guidelen, int sp0, int max_mm, const OtSummary& sm) {
+  if (!n_sites || !n_guides) return;
+  hipLaunchKernelGGL(k_ot_match<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
+                     n_sites, guides, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
+}
+void hawk_launch_ot_match_seeded_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
+                                     const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
+                                     const OtSummary& sm) {
+  if (!n_sites || !n_guides) return;
+  hipLaunchKernelGGL(k_ot_match_seeded<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st,
+                     sites, n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
+}
+void hawk_launch_ot_match_pairs_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
+                                    const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
+                                    const OtSummary& sm) {
+  if (!n_sites || !n_guides) return;
+  hipLaunchKernelGGL(k_ot_match_pairs<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
+                     n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
 }
 
 __global__ __launch_bounds__(256) void k_ot_gather(const OtSite* __restrict__ sites, const OtHit* __restrict__ hits, uint64_t n_hits,

@@ -436,6 +436,21 @@ int hawk_genome_finalize(hawk_hapset* rows);
 int hawk_offtarget_scan(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
                         uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm,
                         uint64_t* out_code, uint32_t* out_nmask, uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing);
+/* The same scan with every hit consumed inside the match kernel instead of listed: per-guide aggregates, mismatch-only, and no
+ * memory on host or device that grows with the number of hits (no capacity, no retry).
+ *   out_hist[g][m]  (row stride max_mm + 1) hits of guide g with m mismatches - the on-target site included
+ *   out_cfd_e4[g]   sum over guide g's hits of round(CFD(guide, site), 4) in units of 1e-4, with the CFD formed as hawk_cfd forms
+ *                   it (wildtype = the guide, sg = the site's spacer, the site's PAM[-2:]; same tables) and rounded as Python's
+ *                   round(x, 4): correctly rounded on the binary value, exact ties to even.  The reference's global CFD is
+ *                   100 / (100 + out_cfd_e4[g] / 1e4) (offtargets.py:561-627).  Integer sums: independent of the order of the
+ *                   device's atomics and exactly additive over genome shards.
+ * cfd_mm / cfd_pam both NULL: counts only (out_cfd_e4, if given, is zeroed).  A hit whose site has a non-ACGT base under a CFD
+ * lookup (among the first min(guidelen, 20) spacer bases or in PAM[-2:]) - hawk_cfd's HAWK_E_CFD - is counted in *n_unscorable,
+ * still counts in out_hist and adds nothing to out_cfd_e4.  *n_hits = all hits.  Argument checks as hawk_offtarget_scan;
+ * HAWK_E_UNSUPPORTED also for max_mm > 32 and for CFD tables with pamlen < 2.  Duplicate guides get equal rows. */
+int hawk_offtarget_summary(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
+                           const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
+                           uint64_t* n_hits, uint64_t* n_unscorable, hawk_ot_timing* timing);
 
 /* ---- K4 stand-alone: compute_cfd() (scores/cfdscore/cfdscore.py:53-95) on n triples --------
  * wt / sg: n spacers of `len` characters each (host, contiguous, any case, T or U); pam2: n
