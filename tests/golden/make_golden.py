@@ -22,6 +22,8 @@ Fixtures:
   g3_search_*.json.gz   haplotype construction + pam_search + search() + reverse_guides +
                         scorer input k-mers + CFDon (synthetic tables) for several regions
   g5_cfd.json.gz        compute_cfd on random (wt, sg, pam) triples, synthetic tables
+  g5_cfd_edges.json.gz  compute_cfd on rows with '-', U, mixed case, ambiguity codes, lengths 1..25 and each table
+                        entry as the only factor; rows on which it raises hold the exception's class name
   g6_deepcpf1.json.gz   SeqDeepCpf1 forward on random 34-mers, seeded synthetic weights
   g8_vcf_lines.json.gz  VariantRecord.read_vcf_line / split() on multi-allelic, missing-allele and
                         extra-FORMAT records
@@ -506,6 +508,105 @@ def g5_cfd():
     dump("g5_cfd.json.gz", dict(seed=2001, cases=cases))
 
 
+def g5_cfd_edges():
+    """compute_cfd at its edges: bulge placeholders, U, case, lengths around the 20-base limit, ambiguity codes, every
+    table entry as the only factor.  A row on which the reference raises holds the exception's class name."""
+    rng = np.random.default_rng(5055)
+    mm, pt = synth.cfd_tables()
+    mmd, pamd = synth.cfd_tables_as_dicts(mm, pt)
+    rows = []
+
+    def add(wt, sg, pam):
+        try:
+            rows.append([wt, sg, pam, R_cfd.compute_cfd(wt, sg, pam, mmd, pamd, True)])
+        except Exception as e:  # noqa: BLE001 - the class name is the recorded outcome
+            rows.append([wt, sg, pam, {"error": type(e).__name__}])
+
+    def put(s, i, c):
+        return s[:i] + c + s[i + 1:]
+
+    def other(c):
+        return "ACGT"[("ACGT".index(c.upper()) + int(rng.integers(1, 4))) % 4]
+
+    def mutated(s, k):
+        for p in rng.choice(len(s), size=min(k, len(s)), replace=False):
+            s = put(s, int(p), other(s[p]))
+        return s
+
+    # each mismatch entry alone: 20 positions x 4 wildtype x 3 other sgRNA bases, one PAM; each PAM entry alone
+    base = synth.random_sequence(rng, 20)
+    for i in range(20):
+        for a in "ACGT":
+            for b in "ACGT":
+                if a != b:
+                    add(put(base, i, a), put(base, i, b), "GG")
+    for p in (x + y for x in "ACGT" for y in "ACGT"):
+        add(base, base, p)
+        add(base, base, p.lower())
+    # lengths around the limit: matches only, one mismatch at every index, several mismatches
+    for n in (1, 2, 16, 19, 20, 21, 24, 25):
+        for _ in range(8):
+            wt = synth.random_sequence(rng, n)
+            add(wt, wt, synth.random_sequence(rng, 2))
+            for i in range(n):
+                add(wt, put(wt, i, other(wt[i])), synth.random_sequence(rng, 2))
+            for k in (2, 3, 5):
+                add(wt, mutated(wt, k), synth.random_sequence(rng, 2))
+    # index 19 is the last scored base, index 20 the first ignored one; 20 mismatches in one row
+    for _ in range(40):
+        wt = synth.random_sequence(rng, 23)
+        pam = synth.random_sequence(rng, 2)
+        add(wt, put(wt, 19, other(wt[19])), pam)
+        add(wt, put(wt, 20, other(wt[20])), pam)
+        add(wt, put(put(wt, 19, other(wt[19])), 20, other(wt[20])), pam)
+        add(wt[:20], "".join(other(c) for c in wt[:20]), pam)
+        add(wt, "".join(other(c) for c in wt), pam)
+    # bulge placeholders: in the wildtype, in the sgRNA, in both at one position, before and after position 20
+    for n in (20, 21, 22, 24):
+        for _ in range(30):
+            wt = synth.random_sequence(rng, n)
+            sg = mutated(wt, int(rng.integers(0, 4)))
+            pam = synth.random_sequence(rng, 2)
+            for i in sorted({0, 1, int(rng.integers(2, 18)), 18, 19, 20, n - 1} & set(range(n))):
+                add(put(wt, i, "-"), sg, pam)
+                add(wt, put(sg, i, "-"), pam)
+                add(put(wt, i, "-"), put(sg, i, "-"), pam)
+            i, j = (int(v) for v in rng.choice(n, size=2, replace=False))
+            add(put(wt, i, "-"), put(sg, j, "-"), pam)
+            add(put(put(wt, i, "-"), j, "-"), sg, pam)
+    # U and lower case in either string
+    for _ in range(150):
+        n = int(rng.choice([19, 20, 21, 23]))
+        wt = synth.random_sequence(rng, n)
+        sg = mutated(wt, int(rng.integers(0, 5)))
+        pam = synth.random_sequence(rng, 2)
+        add(wt.replace("T", "U"), sg, pam)
+        add(wt, sg.replace("T", "U"), pam)
+        add(wt.replace("T", "u"), sg.replace("T", "U"), pam)
+        add(wt.lower(), sg, pam)
+        add(wt, sg.lower(), pam.lower())
+        add("".join(c.lower() if rng.random() < 0.5 else c for c in wt), "".join(c.lower() if rng.random() < 0.5 else c for c in sg), pam)
+    # ambiguity codes: equal to the partner (no look-up), unequal (KeyError), unequal beyond the limit (ignored), beside a bulge
+    for code in "NRYSWKMBDHVn":
+        for _ in range(4):
+            wt = synth.random_sequence(rng, 23)
+            pam = synth.random_sequence(rng, 2)
+            i = int(rng.integers(0, 20))
+            add(put(wt, i, code), put(wt, i, code), pam)
+            add(put(wt, i, code), put(wt, i, code.swapcase()), pam)
+            add(put(wt, i, code), wt, pam)
+            add(wt, put(wt, i, code), pam)
+            add(put(wt, 19, code), wt, pam)
+            add(put(wt, 20, code), wt, pam)
+            add(wt, put(wt, 22, code), pam)
+            add(put(wt, i, code), put(wt, i, "-"), pam)
+            add(put(wt, i, "-"), put(wt, i, code), pam)
+    # PAMs the table does not hold
+    for pam in ("NG", "GN", "UG", "GU", "-G", "nn", "ug"):
+        add(base, base, pam)
+    dump("g5_cfd_edges.json.gz", dict(seed=2001, rows=rows))
+
+
 # ---------------------------------------------------------------------------- G6
 def g6_deepcpf1():
     import torch
@@ -865,6 +966,8 @@ if __name__ == "__main__":
             g4_unphased(_name)
     if "g5" in which:
         g5_cfd()
+    if "g5" in which or "g5_edges" in which:
+        g5_cfd_edges()
     if "g6" in which:
         g6_deepcpf1()
     if "g7" in which:
