@@ -34,6 +34,7 @@ EXPORTS = [
     "hawk_xplan_finish_meta", "hawk_xplan_segments", "hawk_xplan_install_meta", "hawk_host_alloc", "hawk_host_free", "hawk_hapset_rows_equal",
     "hawk_xplan_destroy", "hawk_hapset_set_ref_partner_range", "hawk_xplan_set_ref_partner_range", "hawk_table_collapse_ex", "hawk_table_collapse_export", "hawk_comm_unique_id", "hawk_comm_init",
     "hawk_comm_destroy", "hawk_comm_last_error", "hawk_comm_allgather_u64", "hawk_comm_gatherv", "hawk_table_gather", "hawk_host_ragged_join", "hawk_host_tsv_write", "hawk_host_vcf_index", "hawk_host_polish_rows", "hawk_host_variant_window", "hawk_host_polish_windows", "hawk_host_group_join", "hawk_host_group_samples", "hawk_gbt_predict", "hawk_gt_from_codes",
+    "hawk_annot_create", "hawk_annot_query", "hawk_annot_download", "hawk_annot_free",
 ]
 
 
@@ -82,6 +83,11 @@ class OtParams(C.Structure):
                 ("right", C.c_uint32), ("max_mm", C.c_uint32)]
 
 
+class AnnotTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("count_ms", C.c_float), ("scan_ms", C.c_float), ("fill_ms", C.c_float),
+                ("reserved", C.c_float), ("total_ms", C.c_float), ("out_bytes", C.c_uint64), ("walk_steps", C.c_uint64)]
+
+
 class OtTiming(C.Structure):
     _fields_ = [("scan_ms", C.c_float), ("sites_ms", C.c_float), ("match_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_sites", C.c_uint64), ("scanned_positions", C.c_uint64)]
@@ -113,6 +119,7 @@ def lib() -> C.CDLL:
         L.hawk_xplan_destroy.restype = None
         L.hawk_comm_destroy.restype = None
         L.hawk_host_free.restype = None
+        L.hawk_annot_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)

@@ -6,7 +6,8 @@ CFD ``100 / (100 + sum(cfd))`` (offtargets.py:561-627) keep the reference's sema
 When only the guide report's two columns are wanted (``pipeline.search_files(offtargets_table=False)``),
 ``specificity_by_spacer`` takes them from ``GenomeIndex.summary``: the match kernels sum, per guide, the hits
 and their CFD rounded to 4 decimals as integers, and no site is listed, rendered, parsed or scored on the host.
-BED annotation of the off-target table and Elevation are out of scope."""
+With `annotations` the off-targets table gets one column per BED file (offtargets.py:407-483), joined on the device
+(bedannot.AnnotTable: one handle per file and contig of the table).  Elevation is out of scope."""
 import os
 from typing import Dict, List, Set
 
@@ -96,26 +97,64 @@ def _tsv_float(x: str) -> str:
     return "NA" if x == "NA" else repr(float(x))
 
 
-def offtargets_table(offtargets: List[Offtarget]) -> str:
+def _annotate_rows(rows: List[List[str]], annotations, anncolnames, debug: bool, device=None):
+    """annotate_offtargets (offtargets.py:447-483) for the sorted table rows: per file one column, row = the 4th BED column of
+    the features overlapping (chrom, position, position + len(spacer)) - `spacer` as the table prints it - or NA.  One device
+    table per (file, contig present in the rows); the rows are sorted by (chrom, position), the order the join likes."""
+    from .bedannot import BedAnnotation
+    names = list(anncolnames) if anncolnames else [f"annotation_{i + 1}" for i in range(len(annotations))]
+    chrom = np.array([f[0] for f in rows], dtype=object)
+    pos = np.array([int(f[1]) for f in rows], dtype=np.int64)
+    stop = pos + np.array([len(f[4]) for f in rows], dtype=np.int64)
+    out = []
+    for fann in annotations:
+        bedann = fann if isinstance(fann, BedAnnotation) else BedAnnotation(fann, 0, debug)
+        col = np.full(len(rows), "NA", dtype=object)
+        try:
+            for c in dict.fromkeys(chrom.tolist()):
+                idx = np.flatnonzero(chrom == c)
+                col[idx] = bedann.table(c, 0, device).query(pos[idx], stop[idx]).strings()
+        finally:
+            if bedann is not fann:
+                bedann.close()
+        out.append(col.tolist())
+    return names, out
+
+
+def offtargets_table(offtargets: List[Offtarget], annotations=None, anncolnames=None, debug: bool = True, device=None) -> str:
     """The text of offtargets_*.tsv: header, rows sorted by (chrom, position) - pandas' two-key sort_values is a stable
     lexsort, ties keep file order -, a trailing newline.  A column without a single number (elevation; cfd for PAMs
-    outside SpCas9 / xCas9) comes back from read_csv as all-NaN and is written NA throughout."""
+    outside SpCas9 / xCas9) comes back from read_csv as all-NaN and is written NA throughout.  `annotations` (paths or opened
+    BedAnnotation objects): one more column per file behind `elevation`, named anncolnames[i] or annotation_{i + 1}."""
     rows = sorted(offtargets, key=lambda o: (o.chrom, o.position))
-    out = ["\t".join(OTREPCNAMES)]
+    fields = []
     for o in rows:
         f = o.report_line().split("\t")
         f[9], f[10] = _tsv_float(f[9]), _tsv_float(f[10])
-        out.append("\t".join(f))
-    return "\n".join(out) + "\n"
+        fields.append(f)
+    header = list(OTREPCNAMES)
+    if annotations:
+        names, cols = _annotate_rows(fields, annotations, anncolnames, debug, device)
+        header += names
+        if any(ch in x for col in cols for x in set(col) for ch in '"\t\n\r') or any(ch in x for x in names for ch in '"\t\n\r'):
+            import io
+            import pandas as pd  # a label csv quoting reacts to: written as the reference's to_csv writes it
+            df = pd.DataFrame({h: [f[k] for f in fields] for k, h in enumerate(OTREPCNAMES)})
+            for nm, col in zip(names, cols):
+                df[nm] = col
+            buf = io.StringIO()
+            df.to_csv(buf, sep="\t", index=False, na_rep="NA")
+            return buf.getvalue()
+        for f, *labels in zip(fields, *cols):
+            f.extend(labels)
+    return "\n".join(["\t".join(header)] + ["\t".join(f) for f in fields]) + "\n"
 
 
 def report_offtargets(crispritz_targets_file, region: Region, pam: PAM, guidelen: int, annotations: List[str], anncolnames: List[str],
-                      compute_elevation: bool, right: bool, outdir: str, verbosity: int, debug: bool) -> List[Offtarget]:
-    """offtargets.py:486-558, same arguments.  CFD for SpCas9 / xCas9 PAMs in one device batch; BED annotation of the
-    table and Elevation are outside the path and refused, not skipped."""
-    if annotations:
-        from .crisprhawk_error import CrisprHawkAnnotationError
-        exception_handler(CrisprHawkAnnotationError, "BED annotation of the off-targets table is not part of the GPU path", os.EX_DATAERR, debug)
+                      compute_elevation: bool, right: bool, outdir: str, verbosity: int, debug: bool, device=None) -> List[Offtarget]:
+    """offtargets.py:486-558, same arguments (+ `device`: whose context holds the annotation tables; default: the process default).  CFD for SpCas9 / xCas9 PAMs in one device batch; `annotations` (BED paths, or
+    bedannot.BedAnnotation objects a caller opened once) add their columns to the table by the device join.  Elevation is
+    outside the path and refused, not skipped."""
     if compute_elevation and guidelen + len(pam) == 23 and not right:
         from .crisprhawk_error import CrisprHawkElevationScoreError
         exception_handler(CrisprHawkElevationScoreError, "Elevation is not part of the GPU scoring path", os.EX_DATAERR, debug)
@@ -125,9 +164,10 @@ def report_offtargets(crispritz_targets_file, region: Region, pam: PAM, guidelen
     print_verbosity("Writing off-targets report", verbosity, VERBOSITYLVL[1])
     if outdir:
         fname = os.path.join(outdir, f"offtargets_{region.contig}_{region.start + PADDING}_{region.stop - PADDING}.tsv")
+        text = offtargets_table(offtargets, annotations, anncolnames, debug, device)
         try:
             with open(fname, "w") as f:
-                f.write(offtargets_table(offtargets))
+                f.write(text)
         except OSError as e:
             exception_handler(CrisprHawkOffTargetsError, f"Failed writing off-targets report for region {region}", os.EX_IOERR, debug, e)
     return offtargets
@@ -202,12 +242,12 @@ def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen:
 
 
 def estimate_offtargets_spacers(spacers, pam: PAM, crispritz_index, region, mm: int, bdna: int, brna: int, guidelen: int, right: bool,
-                                outdir: str, verbosity: int, debug: bool) -> Dict[str, tuple]:
+                                outdir: str, verbosity: int, debug: bool, annotations=None, anncolnames=None, device=None) -> Dict[str, tuple]:
     """estimate_offtargets for the columnar report (pipeline.search_files): the same stage - unique spacers -> device scan
     -> CFD -> offtargets_*.tsv -> per-spacer aggregates - without Guide objects."""
     uniq = sorted({sp.upper() for sp in spacers})
     lines = search(_genome_index(crispritz_index, guidelen, len(pam), bdna), uniq, pam, right, mm, verbosity, debug, bdna, brna) if uniq else []
-    ots = report_offtargets(lines, region, pam, guidelen, [], [], False, right, outdir, verbosity, debug)
+    ots = report_offtargets(lines, region, pam, guidelen, annotations or [], anncolnames or [], False, right, outdir, verbosity, debug, device)
     return offtargets_by_spacer(ots, uniq)
 
 

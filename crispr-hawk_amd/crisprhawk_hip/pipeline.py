@@ -5,11 +5,11 @@ inputs, with every stage on the device path of this package.
                          --hawk_gt_parse / hawk_gt_lists / hawk_xplan_create_gt-->  expansion plan in HBM
                          --hawk_search (+ CFDon)-->  guide table in HBM
                          --hawk_table_collapse-->  report groups
+                         --hawk_annot_query-->  BED / gene annotation columns of the groups (optional)
                          --reports.report_frame-->  crisprhawk_guides__*.tsv
 
 Only what the reference's search sub-command does between reading its inputs and writing the guide report is covered;
-BED/gene annotations, the non-CFDon scorers (model files) and the off-target stage have their own entry points
-(`scoring.py`, `offtargets.py`).
+the non-CFDon scorers (model files) and the off-target stage have their own entry points (`scoring.py`, `offtargets.py`).
 """
 import os
 from typing import Dict, List, Optional
@@ -24,6 +24,7 @@ from .expand import HaplotypeBuildError
 from .workload import HapInfo, RowLabel, expand_from_vcf, hap_labels
 
 PADDING = 100  # region_constructor.py:21
+ANN_STAGE = "BED / gene annotation of the groups (device join)"
 
 
 def _labels(ds, info: List[HapInfo], kept: List[int], vt) -> List[Optional[RowLabel]]:
@@ -40,16 +41,71 @@ def _labels(ds, info: List[HapInfo], kept: List[int], vt) -> List[Optional[RowLa
     return out
 
 
+def check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames) -> None:
+    """The reference's checks of --annotation / --gene-annotation and their column names (crisprhawk_argparse.py:252-330), as
+    ValueError: names without files, counts that differ, files that are missing or empty."""
+    for files, names, what in ((annotations, annotation_colnames, "annotation"), (gene_annotations, gene_annotation_colnames, "gene annotation")):
+        files, names = list(files or []), list(names or [])
+        missing = [f for f in files if not os.path.isfile(f)]
+        if missing:
+            raise ValueError(f"Cannot find the specified {what} BED files {', '.join(missing)}")
+        empty = [f for f in files if os.stat(f).st_size <= 0]
+        if empty:
+            raise ValueError(f"{', '.join(empty)} look empty")
+        if names and not files:
+            raise ValueError(f"{what.capitalize()} column names provided, but no input {what} file")
+        if names and len(names) != len(files):
+            raise ValueError(f"Mismatching number of {what} files and {what} column names")
+
+
+class AnnotationSet:
+    """The annotation files of one search_files call: opened once, one device table per (file, contig) made on first use and
+    reused across BED intervals.  `columns(contig)` is what reports.group_columns / report_frame take as `annotations`."""
+
+    def __init__(self, annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug: bool):
+        from .bedannot import FUNC, GENE, BedAnnotation
+        self.device = device
+        self.func = [BedAnnotation(f, 0, debug) for f in (annotations or [])]
+        self.gene = [BedAnnotation(f, 0, debug) for f in (gene_annotations or [])]
+        for b in self.func:
+            b.require(FUNC)
+        for b in self.gene:
+            b.require(GENE)
+        self.names = reports.annotation_colnames(len(self.func), annotation_colnames, len(self.gene), gene_annotation_colnames)
+        self.func_names = list(annotation_colnames) if annotation_colnames else None  # the off-targets table's own default names
+        self._kinds = [(b, FUNC) for b in self.func] + [(b, GENE) for b in self.gene]
+
+    def __bool__(self) -> bool:
+        return bool(self._kinds)
+
+    def columns(self, contig: str, lap=None):
+        """(starts, stops) -> {column: Ragged}; `lap` (search_files' stage clock) is charged with the join when given"""
+        def join(starts, stops):
+            if lap is not None:
+                lap("host-built route: haplotypes, search, scoring, grouping")
+            cols = {name: bed.table(contig, kind, self.device).query(starts, stops) for name, (bed, kind) in zip(self.names, self._kinds)}
+            if lap is not None:
+                lap(ANN_STAGE)
+            return cols
+        return join
+
+    def close(self) -> None:
+        for b, _ in self._kinds:
+            b.close()
+
+
 def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir: str, debug: bool):
     """--estimate-offtargets for one region: {SPACER: (count, global CFD)} + offtargets_{contig}_{start}_{stop}.tsv."""
     from .offtargets import estimate_offtargets_spacers, specificity_by_spacer
     if not ot.get("table", True):  # the report's two columns alone: summed per guide on the device, no site listed
         return specificity_by_spacer(spacers, pam, ot["genome"], ot["mm"], guidelen, right, debug)
-    return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug)
+    ann = ot.get("ann")
+    return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug,
+                                       ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None)
 
 
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
-                       ot=None) -> str:
+                       ot=None, ann=None, lap=None) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows,
     resolve_guide on the host, search_guides.py:163-257) and the fallback for phased records the device expansion
@@ -88,7 +144,8 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         from .utils import _RC_TRANS
         cores = [g.sequence[10:-10][::-1].translate(_RC_TRANS) if g.strand == 1 else g.sequence[10:-10] for g in guides]
         otmap = _offtargets([c[len(pam):] if right else c[:guidelen] for c in cores], pam, ot, coord, guidelen, right, outdir, debug)
-    df = reports.report_from_guides(guides, haps, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", cfd, otmap)
+    df = reports.report_from_guides(guides, haps, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", cfd, otmap,
+                                    ann.columns(coord.contig, lap) if ann else None)
     path = os.path.join(outdir, reports.report_filename(coord.contig, bed_start, bed_stop, pam, guidelen))
     with open(path, "w") as f:
         f.write(reports.to_tsv(df))
@@ -98,7 +155,9 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, device: Optional[int] = None,
                  debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
-                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True) -> Dict[str, str]:
+                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, annotations: Optional[List[str]] = None,
+                 annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
+                 gene_annotation_colnames: Optional[List[str]] = None) -> Dict[str, str]:
     """One report per BED interval; returns {str(coordinate): path}.  `cfd_tables = (mm[20,4,4], pam[16])` adds the
     CFDon column for SpCas9-class PAMs (scoring.py:352-387); `azimuth_model` (a fitted sklearn GBR or the flattened
     dict of scoring.azimuth_model_from_sklearn) and `deepcpf1_weights` (scoring.set_deepcpf1_weights layout) switch
@@ -108,8 +167,13 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     (reports.py:292-333, 612-660) and offtargets_{contig}_{start}_{stop}.tsv next to it (offtargets.py:486-558); `mm`,
     `bdna`, `brna` as on the reference's command line (bulges of up to 2 bases).  The per-site CFD needs `cfd_tables`.
     `offtargets_table=False` fills the two columns from the device's per-guide summary (offtargets.specificity_by_spacer)
-    and writes no offtargets_*.tsv; it is mismatch-only, so asking for it with `bdna` or `brna` is a ValueError."""
+    and writes no offtargets_*.tsv; it is mismatch-only, so asking for it with `bdna` or `brna` is a ValueError.
+    `annotations` / `gene_annotations` (the reference's --annotation / --gene-annotation BED files, plain, gzip or BGZF, no .tbi
+    needed) add one column per file to every guide report - the 4th BED column, or feature:gene_name, of the features a guide
+    overlaps - named by `annotation_colnames` / `gene_annotation_colnames` or annotation_{i} / gene_annotation_{i}; the
+    `annotations` files also annotate the rows of offtargets_*.tsv.  The join runs on the device (bedannot.AnnotTable)."""
     import time as _time
+    check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
 
     def lap(stage: str) -> None:  # stage seconds into `timings` (bench.py's files_to_tsv line); no-op without it
@@ -147,12 +211,29 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     os.makedirs(outdir, exist_ok=True)
     paths = {}
     lap("open inputs (FASTA index, VCF header + line index)")
-    for coord in Bed(bedfile, PADDING, debug):
+    ann = None
+    if annotations or gene_annotations:
+        ann = AnnotationSet(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug)
+        if ot is not None:
+            ot["ann"] = ann
+        lap("open annotation BED files")
+    try:
+        return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap)
+    finally:
+        if ann is not None:
+            ann.close()
+
+
+def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
+                      deepcpf1_weights, paths, lap) -> Dict[str, str]:
+    """search_files' loop over the BED intervals."""
+    for coord in bed:
         seq = fastas[coord.contig].fetch(coord).sequence
         v = vcf_by_contig.get(coord.contig)
         if v is not None and not v.phased:
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
-                                                   pt if score else None, debug, ot)
+                                                   pt if score else None, debug, ot, ann, lap)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])
@@ -164,7 +245,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
             # records the device expansion does not take (overlapping records on one chromosome copy, deletions with a
             # multi-base alt): the host builder mirrors the reference's own construction, the search stays on the device
             paths[str(coord)] = _search_host_built(coord, seq, v, True, pam, guidelen, right, outdir, mmt if score else None,
-                                                   pt if score else None, debug, ot)
+                                                   pt if score else None, debug, ot, ann, lap)
             continue
         # the search runs from the expansion plan (hawk_xplan_view: once per distinct cluster of neighbouring variants when the
         # panel shares them, per row otherwise; no planes read) - a region without variants has no plan and searches REF's planes
@@ -191,11 +272,15 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                 scores["score_azimuth"] = np.asarray(scoring.azimuth(kmers, debug), dtype=np.float64)
             if deepcpf1_on:
                 scores["score_deepcpf1"] = np.asarray(scoring.deepcpf1(kmers, debug), dtype=np.float64)
+        anncols = None
+        if ann:  # one join per file over the groups' (start, stop), while the table is closed and before the report's own threads start
+            anncols = ann.columns(coord.contig)(np.asarray(groups.start, dtype=np.int64), np.asarray(groups.stop, dtype=np.int64))
+            lap(ANN_STAGE)
         otcb = None if ot is None else (lambda spacers: _offtargets(spacers, pam, ot, coord, guidelen, right, outdir, debug))
         # the report as columns (no Python string per row: the carriers' columns of a 2504-sample panel are 0.6 GB of text), written
         # by the library's TSV writer
         cols, order, plain = reports.group_columns(groups, labels, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", scores, score,
-                                                   is_ref_hap=np.asarray(ds.is_ref, dtype=bool), offtargets=otcb)
+                                                   is_ref_hap=np.asarray(ds.is_ref, dtype=bool), offtargets=otcb, annotations=anncols)
         if plan is not None:
             plan.close()
         ds.close()

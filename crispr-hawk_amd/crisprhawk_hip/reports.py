@@ -118,18 +118,66 @@ def collapse_haplotype_ids(hapids: Sequence[str]) -> str:  # reports.py:845-857
     return "" if not len(hapids) else ",".join(sorted(set(",".join(hapids).split(","))))
 
 
-def select_reportcols(pam: PAM, right: bool, estimate_offtargets: bool = False) -> List[str]:
-    """Final column order (reports.py:612-660) without the optional annotation / Elevation columns.  With
-    --estimate-offtargets: `offtargets` (+ `cfd` for SpCas9 / xCas9 PAMs, reports.py:384-404) between `af` and `target`."""
+def annotation_colnames(n_annotations: int, colnames: Optional[Sequence[str]] = None, n_gene_annotations: int = 0,
+                        gene_colnames: Optional[Sequence[str]] = None) -> List[str]:
+    """Names of the optional annotation columns, functional files first (reports.py:352-381): the caller's names, else
+    annotation_{i + 1} / gene_annotation_{i + 1}."""
+    return [colnames[i] if colnames else f"annotation_{i + 1}" for i in range(n_annotations)] + \
+        [gene_colnames[i] if gene_colnames else f"gene_annotation_{i + 1}" for i in range(n_gene_annotations)]
+
+
+def select_reportcols(pam: PAM, right: bool, estimate_offtargets: bool = False, annotation_cols: Sequence[str] = ()) -> List[str]:
+    """Final column order (reports.py:612-660) without the Elevation column.  `annotation_cols` (annotation_colnames: functional
+    then gene annotations) follow `af`; with --estimate-offtargets `offtargets` (+ `cfd` for SpCas9 / xCas9 PAMs,
+    reports.py:384-404) comes behind them; `target` and `haplotype_id` close the row."""
     cols = (REPORTCOLS[:3] + REPORTCOLS[4:5] + REPORTCOLS[3:4] + REPORTCOLS[5:7]) if right else REPORTCOLS[:7]
     if pam.cas_system in (SPCAS9, XCAS9):
         cols = cols + REPORTCOLS[7:12] + REPORTCOLS[13:14]
     elif pam.cas_system == CPF1:
         cols = cols + REPORTCOLS[12:13]
-    cols = cols + REPORTCOLS[15:20]
+    cols = cols + REPORTCOLS[15:20] + list(annotation_cols)
     if estimate_offtargets:
         cols = cols + REPORTCOLS[22:23] + (REPORTCOLS[23:24] if pam.cas_system in (SPCAS9, XCAS9) else [])
     return cols + REPORTCOLS[20:22]
+
+
+def dedup_labels(col: "Ragged") -> "Ragged":
+    """An annotation column as the guide report holds it: the reference's groupby aggregates every annotation cell with
+    ",".join(set(cell.split(","))) (reports.py:861-874, 941-950), so a label is listed once per row.  The ORDER of that set is
+    Python's hash order, which changes from process to process; here the labels stay in file order (first occurrence).  Rows
+    without a comma - nearly all of a functional annotation - are not touched."""
+    n = len(col)
+    if n == 0 or len(col.blob) == 0:
+        return col
+    cs = np.zeros(len(col.blob) + 1, dtype=np.int64)
+    np.cumsum(col.blob == 44, out=cs[1:])
+    off = col.off.astype(np.int64)
+    rows = np.flatnonzero(cs[off[1:]] != cs[off[:-1]])
+    if len(rows) == 0:
+        return col
+    memo: Dict[str, str] = {}
+    changed = {}
+    for r, s in zip(rows.tolist(), col.take(rows)):
+        d = memo.get(s)
+        if d is None:
+            d = memo[s] = ",".join(dict.fromkeys(s.split(",")))
+        if d != s:
+            changed[r] = d
+    if not changed:
+        return col
+    strings = col.strings()
+    for r, d in changed.items():
+        strings[r] = d
+    return Ragged.from_strings(strings)
+
+
+def _annotation_columns(annotations, start, stop) -> Dict[str, "Ragged"]:
+    """{column name: Ragged, one row per report row} from the caller's `annotations`: that dict itself, or a callable
+    (starts, stops) -> dict (bedannot / pipeline.AnnotationSet.columns: one device join per file)."""
+    if annotations is None:
+        return {}
+    cols = annotations(np.asarray(start, dtype=np.int64), np.asarray(stop, dtype=np.int64)) if callable(annotations) else annotations
+    return {name: dedup_labels(c if isinstance(c, Ragged) else Ragged.from_strings(list(c))) for name, c in cols.items()}
 
 
 def _offtarget_columns(spacers: Sequence[str], offtargets: Dict[str, tuple], with_cfd: bool):
@@ -219,12 +267,18 @@ def scorer_kmers(inp: ReportInput):
 
 
 def report_frame(inp: ReportInput, haplotypes, pam: PAM, contig: str, target: str, scores: Optional[Dict[str, np.ndarray]] = None,
-                 with_cfdon: bool = True, offtargets: Optional[Dict[str, tuple]] = None):
+                 with_cfdon: bool = True, offtargets: Optional[Dict[str, tuple]] = None, annotations=None):
     """The collapsed, sorted report of one region as a pandas DataFrame (what reports.report_guides hands to
     to_csv).  `haplotypes[i]` needs .samples .variants .afs .id and .segments (PosSegments); `scores` may map a
-    score column name to a per-row float array (NaN -> "NA")."""
+    score column name to a per-row float array (NaN -> "NA").  `annotations`: a callable (starts, stops) -> {column: Ragged}
+    over the report's rows (an annotation is a function of (chr, start, stop), so neither grouping nor order depends on it)."""
     import pandas as pd
-    cols = select_reportcols(pam, inp.right, offtargets is not None)
+    ann = {}
+    if annotations is not None:
+        off_ = np.asarray(inp.group_off, dtype=np.int64)
+        reps_ = np.asarray(inp.group_perm, dtype=np.int64)[off_[:-1]]
+        ann = {name: c.strings() for name, c in _annotation_columns(annotations, np.asarray(inp.start)[reps_], np.asarray(inp.stop)[reps_]).items()}
+    cols = select_reportcols(pam, inp.right, offtargets is not None, list(ann))
     L = inp.guidelen + inp.pamlen
     pamclass = compute_pam_class(pam)
     parsed_cache: Dict[int, Dict[int, List]] = {}
@@ -291,6 +345,8 @@ def report_frame(inp: ReportInput, haplotypes, pam: PAM, contig: str, target: st
         rec["haplotype_id"] = agg[1]
         if offtargets is not None:
             rec["offtargets"], rec["cfd"] = str(offtargets[guideseq.upper()][0]), offtargets[guideseq.upper()][1]
+        for name, vals in ann.items():
+            rec[name] = vals[g]
         recs.append(rec)
     if not recs:
         return pd.DataFrame({c: [] for c in cols})
@@ -1052,13 +1108,15 @@ def _report_order(cols: Dict[str, object], gcols: List[str], n: int) -> np.ndarr
 
 
 def group_columns(G, haplotypes, pam: PAM, contig: str, target: str, scores: Optional[Dict[str, np.ndarray]] = None,
-                  with_cfdon: bool = True, is_ref_hap: Optional[np.ndarray] = None, offtargets=None):
+                  with_cfdon: bool = True, is_ref_hap: Optional[np.ndarray] = None, offtargets=None, annotations=None):
     """The guide report of group-level inputs (hapset.GroupTable, tiling.MergedGroups.groups(), ReportGroups) as COLUMNS -
     {name: ConstCol / FixedCol / IntCol / VocabCol / Ragged} in the report's column order - plus the row order and whether every
     field is plain text (no character csv quoting reacts to).  Nothing here is a Python string per row: the two columns that list
-    every carrier of every row (C3: 0.64 GB) stay the byte blobs the library's helpers wrote.  `scores[c]` is per GROUP."""
-    names = select_reportcols(pam, G.right, offtargets is not None)
+    every carrier of every row (C3: 0.64 GB) stay the byte blobs the library's helpers wrote.  `scores[c]` is per GROUP.
+    `annotations`: {column name: Ragged per group} in annotation_colnames' order, or a callable (starts, stops) -> that dict."""
     ng = G.n_groups
+    ann = _annotation_columns(annotations, np.asarray(G.start)[:ng], np.asarray(G.stop)[:ng])
+    names = select_reportcols(pam, G.right, offtargets is not None, list(ann))
     if ng == 0:
         return {c: Ragged(np.zeros(0, np.uint8), np.zeros(1, np.uint64)) for c in names}, np.zeros(0, np.int64), True
     L = G.guidelen + G.pamlen
@@ -1075,8 +1133,14 @@ def group_columns(G, haplotypes, pam: PAM, contig: str, target: str, scores: Opt
     try:
         c_samples = pool.submit(_samples_raw, member_off, member_hap, lab.samples)
         c_hapids = pool.submit(_hapids_raw, member_off, member_hap, lab.ids)
-        return _group_columns(G, lab, pam, contig, target, scores, with_cfdon, is_ref_hap, offtargets, names, member_off, member_hap, rep_hap,
-                              pool, c_samples, c_hapids)
+        cols, order, plain = _group_columns(G, lab, pam, contig, target, scores, with_cfdon, is_ref_hap, offtargets,
+                                            [c for c in names if c not in ann], member_off, member_hap, rep_hap, pool, c_samples, c_hapids)
+        if ann:
+            from .bedannot import plain_labels
+            cols.update(ann)
+            cols = {c: cols[c] for c in names}
+            plain = plain and _plain(list(ann)) and all(plain_labels(c) for c in ann.values())
+        return cols, order, plain
     finally:
         pool.shutdown(wait=True)
 
@@ -1144,11 +1208,11 @@ def _group_columns(G, lab, pam, contig, target, scores, with_cfdon, is_ref_hap, 
 
 
 def report_from_groups(G, haplotypes, pam: PAM, contig: str, target: str, scores: Optional[Dict[str, np.ndarray]] = None,
-                       with_cfdon: bool = True, is_ref_hap: Optional[np.ndarray] = None, offtargets=None):
+                       with_cfdon: bool = True, is_ref_hap: Optional[np.ndarray] = None, offtargets=None, annotations=None):
     """report_frame's result from group-level inputs, assembled column by column (group_columns): same DataFrame, same order,
     same strings."""
     import pandas as pd
-    cols, order, _ = group_columns(G, haplotypes, pam, contig, target, scores, with_cfdon, is_ref_hap, offtargets)
+    cols, order, _ = group_columns(G, haplotypes, pam, contig, target, scores, with_cfdon, is_ref_hap, offtargets, annotations)
     if G.n_groups == 0:
         return pd.DataFrame({c: [] for c in cols})
     return pd.DataFrame({c: _col_array(col)[order] for c, col in cols.items()})
@@ -1202,7 +1266,7 @@ def write_report_tsv(path: str, cols: Dict[str, object], order: np.ndarray, plai
 
 
 def report_from_guides(guides, haplotypes, pam: PAM, contig: str, target: str, cfdon: Optional[Sequence[float]] = None,
-                       offtargets: Optional[Dict[str, tuple]] = None):
+                       offtargets: Optional[Dict[str, tuple]] = None, annotations=None):
     """The report of a Guide list as search() returns it (windows still on the + strand, i.e. BEFORE
     annotation.reverse_guides) - the route of unphased inputs, whose guides are resolved on the host
     (search_guides.resolve_guide) and therefore are not rows of the device table.  Rows the report merges are grouped
@@ -1210,7 +1274,7 @@ def report_from_guides(guides, haplotypes, pam: PAM, contig: str, target: str, c
     if not guides:
         return report_frame(ReportInput(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint8), np.zeros(0, np.int64),
                                         np.zeros(0, np.int64), [], None, np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(0, np.uint8),
-                                        np.zeros(0, np.uint8), 0, len(pam), False), haplotypes, pam, contig, target)
+                                        np.zeros(0, np.uint8), 0, len(pam), False), haplotypes, pam, contig, target, annotations=annotations)
     g0 = guides[0]
     guidelen, pamlen = g0.guidelen, g0.pamlen
     right = bool(g0.right) != bool(g0.strand)  # Guide.right is stored flipped for strand 1 (search_guides.py:538)
@@ -1239,4 +1303,4 @@ def report_from_guides(guides, haplotypes, pam: PAM, contig: str, target: str, c
         den.append(gc + sum(spacer.count(c) for c in "ATWUatwu"))
     inp = ReportInput(start, stop, strand, hap, pos, wins, cfd, np.array(perm, dtype=np.int64), np.array(off, dtype=np.int64),
                       np.array(num), np.array(den), guidelen, pamlen, right)
-    return report_frame(inp, haplotypes, pam, contig, target, with_cfdon=cfd is not None, offtargets=offtargets)
+    return report_frame(inp, haplotypes, pam, contig, target, with_cfdon=cfd is not None, offtargets=offtargets, annotations=annotations)

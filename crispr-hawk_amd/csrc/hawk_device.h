@@ -336,3 +336,21 @@ void hawk_launch_hx_build(hipStream_t st, const uint32_t* const* ref, uint32_t r
                           const uint64_t* hv_off, const uint32_t* hap_len, uint32_t n_hap, uint32_t S, uint32_t* const* plane,
                           const void* tiles);
 void hawk_launch_hx_hash(hipStream_t st, uint32_t* const* plane, uint32_t n_hap, uint32_t S, unsigned long long* hash);
+
+// ---- BED annotation join (hawk_annot.hip): the features of one (file, contig, label kind), sorted by start, resident in HBM
+struct AnnDev {
+  const int64_t *start, *end;  // [n] 0-based half-open
+  const int64_t* rmax;         // [n] max(end[0..i])
+  const int64_t* bmax;         // [ceil(n / 64)] max(end) per block of 64 features
+  const uint64_t* loff;        // [n + 1] label i = blob[loff[i], loff[i + 1])
+  const uint8_t* blob;
+  uint64_t n;
+};
+uint64_t hawk_ann_scan_blocks(uint64_t n);  // entries of the `partial` workspace a scan over n elements needs
+void hawk_launch_ann_index(hipStream_t st, const int64_t* end, uint64_t n, int64_t* partial, int64_t* rmax, int64_t* bmax);
+// off[q] <- bytes of row q; totals[0] += overlaps, totals[1] += walk steps
+void hawk_launch_ann_count(hipStream_t st, const AnnDev& A, const int64_t* qs, const int64_t* qe, uint64_t nq, uint64_t* off,
+                           unsigned long long* totals);
+// off[nq + 1] <- exclusive 64-bit sums of off[0..nq), in place
+void hawk_launch_ann_offsets(hipStream_t st, uint64_t* off, uint64_t nq, uint64_t* partial);
+void hawk_launch_ann_fill(hipStream_t st, const AnnDev& A, const int64_t* qs, const int64_t* qe, uint64_t nq, const uint64_t* off, uint8_t* out);

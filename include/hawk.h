@@ -502,6 +502,36 @@ int hawk_azimuth(hawk_ctx* ctx, const char* seqs30, uint64_t n, const hawk_gbt_m
 int hawk_gbt_predict(hawk_ctx* ctx, const double* feats, uint64_t n, uint32_t n_features, const hawk_gbt_model* model, int cast_f32,
                      double* out);
 
+/* ---- BED annotation join: BedAnnotation.fetch_features + the label join per guide / off-target row (bedfile.py:406-425,
+ * annotation.py:373-462, offtargets.py:407-483) for a whole batch of rows ----------------------------------------------------
+ * One handle per (annotation file, contig, label kind), resident in HBM.  `start` / `end`: the contig's n features in FILE order,
+ * 0-based half-open, sorted by start (what tabix requires of a BED file) with end >= start - HAWK_E_INVALID otherwise; feature
+ * i's label is label_blob[label_off[i], label_off[i + 1]) (label_off[0] = 0).  All arrays are host memory and are copied.
+ * n = 0 is a valid table (a contig the file does not have): every row of every query is "NA".  *index_ms (may be NULL): device
+ * time of the two index kernels (running maximum of end, maximum per block of 64 features).
+ *
+ * hawk_annot_query: feature [fs, fe) and query [qs, qe) overlap iff fs < qe && fe > qs (tabix's half-open rule; parity
+ * unpinned: pysam absent).  Row q of the result is the labels of query q's overlapping features joined by ',' in file order
+ * (an empty label is an empty field: one overlap with an empty label gives the empty row, as the reference's join does), or
+ * the two bytes "NA" when nothing overlaps.  The rows are left in HBM; *n_bytes = bytes of their blob, *n_overlaps (may be
+ * NULL) = (feature, query) pairs found.  Offsets and coordinates are 64 bits.  Queries may come in any order; callers'
+ * queries are sorted by position, which is what makes neighbouring lanes read the same lines.
+ * hawk_annot_download copies the rows of the last query into the caller's buffers - blob[n_bytes], off = uint64[nq + 1], row
+ * q = blob[off[q], off[q + 1]); page-locked buffers (hawk_host_alloc) take the copy at link speed - and returns the batch's
+ * device workspace to the caching allocator.  Once per query; HAWK_E_INVALID without a query before it. */
+typedef struct hawk_annot hawk_annot;
+typedef struct {
+  float upload_ms, count_ms, scan_ms, fill_ms, reserved, total_ms; /* HIP events around the stages of one query call */
+  uint64_t out_bytes;  /* bytes of the blob */
+  uint64_t walk_steps; /* features and skipped blocks the count pass stepped over, all queries */
+} hawk_annot_timing;
+int hawk_annot_create(hawk_ctx* ctx, const int64_t* start, const int64_t* end, const uint8_t* label_blob, const uint64_t* label_off,
+                      uint64_t n, hawk_annot** out, float* index_ms);
+int hawk_annot_query(hawk_annot* annot, const int64_t* qstart, const int64_t* qstop, uint64_t nq, uint64_t* n_bytes,
+                     uint64_t* n_overlaps, hawk_annot_timing* timing);
+int hawk_annot_download(hawk_annot* annot, uint8_t* blob, uint64_t* off, float* download_ms);
+void hawk_annot_free(hawk_annot* annot);
+
 #ifdef __cplusplus
 }
 #endif
