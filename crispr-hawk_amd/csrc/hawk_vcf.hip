@@ -17,8 +17,45 @@
 
 #define GT_CHUNK 16
 
-// flags per record: 1 = a genotype without '|' (unphased separator or haploid), 2 = field count != n_samples,
-// 4 = unexpected character inside a genotype
+// flags per record, OR-ed over its first n_samples fields (g = a field up to its first ':'):
+//   1 = g is not exactly two '|'-separated parts: unphased separator, haploid, three or more parts, empty (what
+//       _parse_genotype_phased, variant.py:514-520, refuses before it looks at an allele);
+//   2 = field count != n_samples;
+//   4 = one of the first two parts of g (split at '|' if g holds one, else at '/') is neither '.' nor all digits; its code
+//       stays 255.  "0|1/2" and "|1" are two '|'-parts of which one is no number: 4 alone, as int() fails there in the reference.
+// Any field that is not a plain "a|b" goes through gt_classify, which states this rule byte by byte (oracle.vcf_genotype_codes
+// is the same statement in Python); returns flags | code0 << 8 | code1 << 16.  Allele numbers clamp at 254.
+__device__ __noinline__ uint32_t gt_classify(const uint8_t* __restrict__ text, uint64_t s, uint64_t hi) {
+  uint64_t e = s;
+  uint32_t nbar = 0, nslash = 0;
+  for (; e < hi && text[e] != '\t' && text[e] != ':'; ++e) {
+    nbar += text[e] == '|';
+    nslash += text[e] == '/';
+  }
+  const bool has_sep = nbar || nslash;
+  const uint8_t sep = nbar ? (uint8_t)'|' : (uint8_t)'/';
+  const uint32_t nparts = (nbar ? nbar : nslash) + 1u;
+  uint32_t fl = nbar == 1u ? 0u : 1u, v[2] = {255u, 255u};
+  uint64_t p = s;
+  for (uint32_t c = 0; c < 2u && c < nparts; ++c) {
+    uint64_t q = p;
+    while (q < e && !(has_sep && text[q] == sep)) ++q;
+    if (!(q - p == 1 && text[p] == '.')) {
+      bool num = q > p;
+      uint32_t x = 0;
+      for (uint64_t t = p; t < q; ++t) {
+        const uint8_t ch = text[t];
+        if (ch < '0' || ch > '9') { num = false; break; }
+        x = x * 10u + (ch - '0');
+        if (x > 254u) x = 254u;
+      }
+      if (num) v[c] = x; else fl |= 4u;
+    }
+    p = q + 1;
+  }
+  return fl | v[0] << 8 | v[1] << 16;
+}
+
 __global__ __launch_bounds__(256) void k_gt_parse(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_off,
                                                   const uint64_t* __restrict__ gt_off, uint32_t n_samples,
                                                   uint8_t* __restrict__ codes, uint8_t* __restrict__ flags) {
@@ -53,26 +90,30 @@ __global__ __launch_bounds__(256) void k_gt_parse(const uint8_t* __restrict__ te
         if (f < n_samples) {
           uint64_t p = a + k;
           uint32_t v[2] = {255u, 255u};
-          int nal = 0;
-          bool bar = false;
-          for (; nal < 2; ++nal) {
+          bool plain = true;  // "a|b" ended by a tab, a ':' or the record: every field of a well-formed phased file
+          for (int nal = 0; nal < 2; ++nal) {
             uint8_t ch = p < hi ? text[p] : (uint8_t)'\t';
             if (ch == '.') { v[nal] = 255u; ++p; }
             else if (ch >= '0' && ch <= '9') {
               uint32_t x = 0;
               while (p < hi && (ch = text[p]) >= '0' && ch <= '9') { x = x * 10u + (ch - '0'); if (x > 254u) x = 254u; ++p; }
               v[nal] = x;
-            } else { myflag |= 4u; break; }
-            ch = p < hi ? text[p] : (uint8_t)'\t';
+            } else { plain = false; break; }
             if (nal == 0) {
-              if (ch == '|') { bar = true; ++p; }
-              else if (ch == '/') { ++p; }
-              else { ++nal; break; }  // haploid
+              if (p < hi && text[p] == '|') ++p;
+              else { plain = false; break; }
             }
           }
-          if (!bar) myflag |= 1u;
-          const uint8_t endc = p < hi ? text[p] : (uint8_t)'\t';
-          if (endc != '\t' && endc != ':') myflag |= (endc == '|' || endc == '/') ? 1u : 4u;  // more than two alleles -> not phased diploid
+          if (plain) {
+            const uint8_t endc = p < hi ? text[p] : (uint8_t)'\t';
+            plain = endc == '\t' || endc == ':';
+          }
+          if (!plain) {
+            const uint32_t r = gt_classify(text, a + k, hi);
+            myflag |= r & 0xffu;
+            v[0] = (r >> 8) & 0xffu;
+            v[1] = (r >> 16) & 0xffu;
+          }
           out[2ull * f] = (uint8_t)v[0];
           out[2ull * f + 1] = (uint8_t)v[1];
         }
@@ -85,6 +126,9 @@ __global__ __launch_bounds__(256) void k_gt_parse(const uint8_t* __restrict__ te
   // fields = tabs + 1 (an empty section has no field at all)
   const uint32_t nfields = hi > lo ? field_base + 1 : 0;
   if (nfields != n_samples) myflag |= 2u;
+  // a tab as the section's last byte: the last field is empty and starts at hi, where no chunk owns it - the empty genotype's
+  // flags (one part, no number) are set here, its codes stay 255
+  if (tid == 0 && hi > lo && text[hi - 1] == '\t' && field_base < n_samples) myflag |= 5u;
   if (myflag) atomicOr(&s_flag, myflag);
   __syncthreads();
   if (tid == 0) flags[rec] = (uint8_t)s_flag;
@@ -116,7 +160,7 @@ __global__ __launch_bounds__(256) void k_gt_count(const uint8_t* __restrict__ co
 #pragma unroll
     for (int jj = 0; jj < 64; ++jj) {
       const uint32_t line = (uint32_t)__builtin_amdgcn_readlane((int)my_line, jj);
-      c[jj] = (live && (uint32_t)jj < nj) ? codes[(size_t)line * n_cols + col] : (uint8_t)254;  // 254: no allele of a variant (they are <= 253)
+      c[jj] = (live && (uint32_t)jj < nj) ? codes[(size_t)line * n_cols + col] : (uint8_t)254;  // a filler only: no ballot bit comes from it (`carried` needs jj < nj, stores and counts need `live`)
     }
 #pragma unroll
     for (int jj = 0; jj < 64; ++jj) {

@@ -394,9 +394,21 @@ int hawk_host_gather_plan(int world, int rank, int dst, const uint64_t* dir4, ui
  * hawk_gt_parse: text = the raw bytes of n_lines VCF records ('\n'-terminated), record i =
  *   text[line_off[i], line_off[i+1]), its first sample column starts at gt_off[i] (host arrays).  The device
  *   keeps codes[n_lines][2*n_samples]: allele carried by copy 0 / copy 1 of each sample (0 REF, k = k-th ALT,
- *   255 missing or absent), and a flag byte per record: 1 = a genotype without '|' (unphased or haploid),
- *   2 = field count != n_samples, 4 = unexpected character.  hawk_gt_codes downloads both (NULL skips).
- * hawk_gt_lists: variants j = (record var_line[j], allele var_allele[j] >= 1), ascending; var_r0[j] = offset of
+ *   255 missing or absent; an allele number >= 254 reads 254), and a flag byte per record, OR-ed over its first
+ *   n_samples sample columns.  With g = a column up to its first ':':
+ *     1 = g is not exactly two '|'-separated parts: unphased separator, haploid, three or more parts, empty column (the
+ *         arity refusal of _parse_genotype_phased, variant.py:514-520, which comes before any look at the alleles);
+ *     2 = the record does not have n_samples columns (columns beyond n_samples are not read, absent ones stay 255);
+ *     4 = one of the first two parts of g - split at '|' if g holds one, else at '/' - is neither '.' nor all ASCII
+ *         digits (no sign, no blank); its code stays 255.  "|1", "0|" , "0|1/2" and "0/1|2" are two '|'-parts of which
+ *         one is no number: 4 alone, where the reference fails in int().  Next to 1 it is additional information.
+ *   A record with any bit set is rejected by the callers (workload.expand_from_vcf: 2, then 1, then 4 decide the
+ *   message).  A section that is empty (gt_off at the record's end or at its line terminator) has no column at all.
+ *   hawk_gt_codes downloads both arrays (NULL skips).
+ * hawk_gt_lists: variants j = (record var_line[j], allele var_allele[j] in 1..254); "ascending" below means ascending
+ *   j - the caller's variant order (by position) - and var_line need not be monotone (multi-allelic records are
+ *   re-positioned allele by allele).  Allele 254 matches code 254, i.e. every allele number the parser clamped.
+ *   var_r0[j] = offset of
  *   the variant in the reference region, var_chain[j] = alt length - replaced length.  Per chromosome copy
  *   (column c = 2*sample + copy) the ascending list of carried variants is built on the device; col_off[2*n_samples+1]
  *   (host) receives the CSR offsets, col_delta (host, may be NULL) the summed length change per column.

@@ -27,6 +27,8 @@ Fixtures:
   g6_deepcpf1.json.gz   SeqDeepCpf1 forward on random 34-mers, seeded synthetic weights
   g8_vcf_lines.json.gz  VariantRecord.read_vcf_line / split() on multi-allelic, missing-allele and
                         extra-FORMAT records
+  g12_vcf_wide.json.gz  the same at panel width: 2504 samples, every record wide enough for three 4096-byte sweeps of the
+                        device parser (multi-digit alleles, ':'-tails of varying length, '.' alleles, three ALT alleles)
   g9_azimuth.json.gz    scores/azimuth: features/featurization.featurize_data + util.concatenate_feature_sets with the
                         learn_options save_final_model_V3(include_position=False) pickles (model_comparison.py:474-497) on
                         random 30-mers -> the 627-column matrix; model_comparison.predict driven with a locally fitted
@@ -677,6 +679,46 @@ def g8_vcf_lines():
     dump("g8_vcf_lines.json.gz", dict(samples=samples, records=out))
 
 
+# ---------------------------------------------------------------------------- G12 (VCF records at panel width)
+def g12_vcf_wide():
+    """g8's schema on records of 2504 samples: read_vcf_line (variant.py:286-311) where one record's sample columns are 10 kB
+    and more.  Genotypes stay a|b with alleles inside the record's ALT count, as the reference demands of a phased file."""
+    rng = np.random.default_rng(12012)
+    samples = [f"P{i:04d}" for i in range(2504)]
+    shapes = [("A", ["G"], "AF=0.25", "GT", 0),
+              ("ACG", ["A"], "AF=0.0125", "GT:DP", 1),
+              ("C", ["A", "G", "T"], "AF=0.1,0.2,0.3", "GT:DP:PL", 2),
+              ("GT", ["G", "GTT", "AT"], "AF=0.01,0.02,0.5;DB", "GT:AD:DP:GQ:PL", 3),
+              ("A", [c * (1 + j % 3) for j, c in enumerate("CGTCGTCGTCGT")], "AF=" + ",".join(f"{0.001 * (j + 1):.3f}" for j in range(12)), "GT:GQ", 2),
+              ("T", ["TGA", "C"], "AF=0.1,0.2", "GT:FT", 3)]
+    recs, pos = [], 5000
+    for ref, alts, info, fmt, tail in shapes:
+        pos += int(rng.integers(1, 40))
+        gts = []
+        for _ in samples:
+            a = [("." if rng.random() < 0.04 else str(int(rng.integers(0, len(alts) + 1)))) for _ in range(2)]
+            g = "|".join(a)
+            if tail == 1:
+                g += f":{int(rng.integers(0, 300))}"
+            elif tail == 2:
+                g += f":{int(rng.integers(1, 99))}:" + ",".join(str(int(x)) for x in rng.integers(0, 255, int(rng.integers(1, 5))))
+            elif tail == 3:
+                g += ":" + "".join(rng.choice(list("0123456789.,|/:"), int(rng.integers(0, 21))))
+            gts.append(g)
+        recs.append(["chrV", str(pos), ".", ref, ",".join(alts), "50", "PASS", info, fmt] + gts)
+    out = []
+    for fields in recs:
+        assert len("\t".join(fields[9:])) > 2 * 4096
+        vr = VariantRecord(True)
+        vr.read_vcf_line(fields, samples, True)
+        out.append(dict(
+            fields=fields, alt=vr.alt, vtype=vr.vtype, afs=[None if a != a else a for a in vr.afs], ids=vr.id, filter=vr.filter,
+            samples=[[sorted(s0), sorted(s1)] for s0, s1 in vr.samples],
+            split=[[v.position, v.ref, v.alt[0], v.id[0], v.vtype[0]] for v in vr.split()],
+        ))
+    dump("g12_vcf_wide.json.gz", dict(samples=samples, records=out))
+
+
 # ---------------------------------------------------------------------------- G9 (Azimuth / Rule Set 2, SURVEY row a19)
 def _tm_nn_restated(seq, **kw):
     """Biopython 1.83 Bio.SeqUtils.MeltingTemp.Tm_NN(seq) with its defaults (nn_table DNA_NN3 = Allawi & SantaLucia
@@ -954,7 +996,7 @@ def g10_offtargets():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g12"]
     if "g1" in which:
         g1_tables()
     if "g2" in which:
@@ -974,6 +1016,8 @@ if __name__ == "__main__":
         g7_all()
     if "g8" in which:
         g8_vcf_lines()
+    if "g12" in which:
+        g12_vcf_wide()
     if "g10" in which:  # before g9: g9 re-registers crisprhawk.scores' sub-packages
         g10_offtargets()
     if "g9" in which:
