@@ -211,10 +211,12 @@ def test_device_expansion_matches_host_expansion_200kb():
 
 
 def test_device_expansion_crowded_tiles_and_long_deletions():
-    # what the expansion kernel stages per tile of 32768 output positions has a capacity: 256 carried variants and the
-    # tile's image in REF plus 2048 net deleted bases.  Here one tile carries a SNV every 25 nt (the variants beyond the
-    # staged ones come from global memory), another loses 4 x 1500 nt to deletions (its REF image does not fit: copies
-    # read global memory), and a 400-nt insertion crosses a word-quad boundary.
+    # what the expansion kernel stages per tile of 32768 output positions has a capacity: HX_MAXV = 96 carried variants and
+    # HX_RW = 1088 REF words, the tile's image in REF plus about 2048 net deleted bases.  Here one tile carries a SNV every
+    # 25 nt (some 900 a tile on the row that carries them all: the variants beyond the 96 staged ones come from global
+    # memory), another loses 4 x 1500 nt to deletions (its REF image does not fit: copies read global memory), and a 400-nt
+    # insertion crosses a word-quad boundary.  tests/test_gpu_expansion.py sits exactly ON these limits (96 against 97
+    # records, 1088 against 1089 words); this case is far beyond both.
     from crisprhawk_hip.workload import build_phased_haplotypes, expand_on_device
     reg = synth.make_region(7351, "chrK", 170_000, 5_000, 165_000)
     rng = np.random.default_rng(7352)
@@ -251,6 +253,19 @@ def test_device_expansion_crowded_tiles_and_long_deletions():
         assert np.array_equal(got[:, r, :n], want[:, j, :n])
         assert not got[:, r, n:].any()
         assert np.array_equal(ds.host_meta[r].seg.rel, haps[j].seg.rel) and np.array_equal(ds.host_meta[r].seg.gen, haps[j].seg.gen)
+    # and against rows the product had no part in: the oracle's strings, packed in numpy
+    from expansion_refs import canonical_segments, planes_from_string
+    fx = dict(region_seq=reg.sequence, startp=reg.startp, samples=reg.samples,
+              variants=[[v.pos, v.ref, v.alt, v.af, ["".join(str(int(x)) for x in row) for row in v.gt]] for v in reg.variants])
+    ohaps = oracle_haplotypes(fx)
+    assert len(ohaps) == len(kept) and max(len(h["seq"]) for h in ohaps) <= 32 * ds.stride
+    for j, r in enumerate(kept):
+        assert int(ds.hap_len[r]) == len(ohaps[j]["seq"]) and sorted(info_d[j].samples) == ohaps[j]["samples"]
+        assert np.array_equal(got[:, r, :], planes_from_string(ohaps[j]["seq"], ds.stride)), (j, r)
+        assert np.array_equal(ds.host_meta[r].seg.full(), ohaps[j]["posmap"])
+        rel, gen = canonical_segments(ds.host_meta[r].seg.rel, ds.host_meta[r].seg.gen)  # without the break behind an insertion
+        want_rel, want_gen = segments_from_posmap(ohaps[j]["posmap"])
+        assert np.array_equal(rel, want_rel) and np.array_equal(gen, want_gen)
 
 
 def test_clamp_error_is_for_indels_only():

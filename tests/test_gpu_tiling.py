@@ -148,8 +148,10 @@ def test_plan_tiles_covers_the_interval_once():
 
 
 def test_dense_carried_variants_overflow_the_staged_range():
-    """More than HX_MAXV = 192 carried variants inside one expansion workgroup's 8192 output positions:
-    the variants beyond the LDS-staged range are read from global memory; planes must still equal the host build."""
+    """More than HX_MAXV = 96 carried variants inside one expansion workgroup's tile of 32768 output positions:
+    the variants beyond the LDS-staged range are read from global memory; planes must still equal the host build and the
+    oracle's strings.  (The density below is still counted per 8192 positions, the tile of an earlier geometry: more than
+    400 there is more than 1600 a tile, far beyond 96; tests/test_gpu_expansion.py holds the 96-against-97 cases.)"""
     from crisprhawk_hip.hapset import DeviceHapSet
     from crisprhawk_hip.workload import build_phased_haplotypes
     reg = synth.make_region(4491, "chrD", 30_000, 1_000, 28_000)
@@ -165,6 +167,15 @@ def test_dense_carried_variants_overflow_the_staged_range():
         n = (int(host.hap_len[i]) + 31) // 32
         assert ds.hap_len[r] == host.hap_len[i]
         assert np.array_equal(pd_[:, r, :n], ph[:, i, :n]), (i, r)
+    # and against rows the product had no part in: the oracle's strings, packed in numpy
+    from expansion_refs import planes_from_string
+    fx = dict(region_seq=reg.sequence, startp=reg.startp, samples=reg.samples,
+              variants=[[v.pos, v.ref, v.alt, v.af, ["".join(str(int(x)) for x in row) for row in v.gt]] for v in reg.variants])
+    ohaps = oracle_haplotypes(fx)
+    assert len(ohaps) == len(kept)
+    for j, r in enumerate(kept):
+        assert int(ds.hap_len[r]) == len(ohaps[j]["seq"]) and sorted(info[j].samples) == ohaps[j]["samples"]
+        assert np.array_equal(pd_[:, r, :], planes_from_string(ohaps[j]["seq"], ds.stride)), (j, r)
 
 
 def test_tiled_equals_one_piece_at_megabase_scale():
