@@ -124,11 +124,15 @@ static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, 
   }
   if (verified_bad) continue;
   unsigned long long cnt[3] = {0, 0, 0};
-  for (int attempt = 0; attempt < 4; ++attempt) {  // a new seed whenever two different rows collide in the hash bits
+  // A new seed whenever two different rows of one (start, strand) collide: in the hash bits of the key (24 to 31) on the usual
+  // path, which needs them apart to keep equal rows contiguous - thousands of different rows under one start (k of them collide
+  // with probability ~ k^2 / 2^(bits + 1) per seed) can use up all four seeds, and the call goes to the exact path; there only in
+  // all 63 hash bits, because its rows are sorted by identity below the key (hawk_launch_collapse).
+  for (int attempt = 0; attempt < 4; ++attempt) {
     HIPCHK(hipMemsetAsync(hs->ccnt.p, 0, 32, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
     if (hawk_launch_collapse(ctx->stream, t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)t->right, (int)flank_up,
-                             (int)flank_down, hs->min_gen, begin_bit, end_bit, 0x9e3779b97f4a7c15ull * (uint64_t)(attempt + 1), hs->ctemp.p,
+                             (int)flank_down, hs->min_gen, exact ? 0u : begin_bit, end_bit, 0x9e3779b97f4a7c15ull * (uint64_t)(attempt + 1), hs->ctemp.p,
                              temp_bytes, hs->ckeys.as<uint64_t>(), hs->cvals.as<uint32_t>(), hs->cflags.as<uint32_t>(),
                              hs->cgidx.as<uint32_t>(), hs->ccnt.as<unsigned long long>(), hs->cgoff.as<uint64_t>(), hs->cgc.as<uint8_t>(),
                              hs->cgc.as<uint8_t>() + n, hs->cgidx.as<uint32_t>(), exact ? hs->cfull.p : nullptr, weak && !exact))

@@ -11,6 +11,8 @@
 //   rocprim::radix_sort_pairs (key, row id) over the bits in use - the low hash bits are dropped (zero in the key) so
 //                     that start + strand + hash fill a whole number of 8-bit passes with >= 24 hash bits (a 4 Mb tile:
 //                     48 bits, 6 passes instead of 7); stable, so equal keys keep table order (haplotype ascending)
+//                     exact path: all 31 hash bits, and a stable sort by id2 in front, so that the rows of one key lie
+//                     ordered by (id2, table order) - any number of different rows may share a (start, strand)
 //   k_collapse_heads  neighbours in sorted order open a group when their keys differ or, with equal keys, their id2
 //                     (two 4-byte gathers); counts heads by key and heads by identity - if they differ, two different
 //                     rows of one (start, strand) collided in the 31 key bits and may interleave: the host layer
@@ -84,6 +86,14 @@ __global__ __launch_bounds__(256) void k_collapse_keys(GuideCols c, const uint8_
   id2[i] = (uint32_t)h & id_mask;  // id_mask / hash_mask = 0: the test that forces hash collisions (HAWK_COLLAPSE_WEAK_HASH)
 }
 
+// exact path: the keys in the order of a stable sort of the rows by identity, so that the stable sort by key that follows leaves
+// the rows of one key ordered by (identity, table order) - equal rows contiguous however many different rows share the key
+__global__ __launch_bounds__(256) void k_collapse_by_id(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ order, uint64_t n,
+                                                        uint64_t* __restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) out[j] = keys[order[j]];
+}
+
 __device__ __forceinline__ bool same4(const ulonglong4& a, const ulonglong4& b) {
   return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
 }
@@ -102,7 +112,12 @@ __global__ __launch_bounds__(256) void k_collapse_heads(const ulonglong4* __rest
       hk = keys[j] != keys[j - 1];
       if (!hk) {
         const uint64_t a = vals[j], b = vals[j - 1];
-        hf = full ? !(same4(full[2 * a], full[2 * b]) && same4(full[2 * a + 1], full[2 * b + 1])) : id2[a] != id2[b];
+        if (full) {  // exact: rows of one key lie sorted by identity (k_collapse_by_id), so the identity counts as key here
+          hk = id2[a] != id2[b];
+          hf = hk || !(same4(full[2 * a], full[2 * b]) && same4(full[2 * a + 1], full[2 * b + 1]));
+        } else {
+          hf = id2[a] != id2[b];
+        }
       } else {
         hf = 1;
       }
@@ -224,11 +239,16 @@ void hawk_launch_rows_equal(hipStream_t st, const HapSetDev& hs, uint32_t n_pair
 size_t hawk_collapse_full_bytes(uint64_t n) { return (size_t)n * 64; }
 
 size_t hawk_collapse_temp_bytes(uint64_t n, unsigned begin_bit, unsigned end_bit) {
-  size_t a = 0, b = 0;
+  size_t a = 0, b = 0, d = 0, e = 0;
   (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, begin_bit,
                                   end_bit, (hipStream_t)0);
   (void)rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(), (hipStream_t)0);
-  return a > b ? a : b;
+  // the exact path: every hash bit in the key, and the sort by identity in front of it
+  (void)rocprim::radix_sort_pairs(nullptr, d, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, end_bit,
+                                  (hipStream_t)0);
+  (void)rocprim::radix_sort_pairs(nullptr, e, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 32,
+                                  (hipStream_t)0);
+  return std::max(std::max(a, b), std::max(d, e));
 }
 
 // keys/vals: [2][n] ping-pong; flags, gidx: [n]; counters: [2], zeroed by the caller; group_off must hold
@@ -242,7 +262,20 @@ int hawk_launch_collapse(hipStream_t st, const GuideCols& c, const uint8_t* is_r
   hipLaunchKernelGGL(k_collapse_keys, grid, block, 0, st, c, is_ref, n, L, flank_up, flank_down, base, seed,
                      weak_hash ? 0u : (~((1u << begin_bit) - 1u) & 0x7fffffffu), weak_hash ? 0u : 0xffffffffu, keys, vals, id2, (ulonglong4*)full);
   size_t tb = temp_bytes;
-  if (rocprim::radix_sort_pairs(temp, tb, keys, keys + n, vals, vals + n, n, begin_bit, end_bit, st) != hipSuccess) return -2;
+  if (full) {
+    // Exact path (begin_bit = 0 here): rows by identity first (`flags` takes the sorted identities, free until the head pass),
+    // then by key.  The head pass then needs no collision-free key: it opens a group where key, identity or full record change,
+    // and counts a changed record under one key + identity (63 equal hash bits, never seen) for the host to answer with a seed.
+    if (rocprim::radix_sort_pairs(temp, tb, id2, flags, vals, vals + n, n, 0, 32, st) != hipSuccess) return -2;
+    hipLaunchKernelGGL(k_collapse_by_id, grid, block, 0, st, keys, vals + n, n, keys + n);
+    tb = temp_bytes;
+    if (rocprim::radix_sort_pairs(temp, tb, keys + n, keys, vals + n, vals, n, begin_bit, end_bit, st) != hipSuccess) return -2;
+    if (hipMemcpyAsync(keys + n, keys, n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(vals + n, vals, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return -2;
+  } else if (rocprim::radix_sort_pairs(temp, tb, keys, keys + n, vals, vals + n, n, begin_bit, end_bit, st) != hipSuccess) {
+    return -2;
+  }
   hipLaunchKernelGGL(k_collapse_heads, grid, block, 0, st, (const ulonglong4*)full, id2, n, keys + n, vals + n, flags, counters);
   tb = temp_bytes;
   if (rocprim::exclusive_scan(temp, tb, flags, gidx, 0u, n, rocprim::plus<uint32_t>(), st) != hipSuccess) return -2;

@@ -258,7 +258,11 @@ int hawk_table_device_columns(hawk_table* t, void** hap, void** pos, void** stra
  *                        gc_num / gc_den (annotation.py:513-541 -> Biopython gc_fraction, ambiguous bases dropped)
  * Rows of one (start, strand) are told apart by 63 bits of a hash of everything compared (a false merge needs a 63-bit
  * collision inside one (start, strand): ~1e-12 over a whole-chromosome run); with HAWK_COLLAPSE_EXACT=1 in the
- * environment (read per call) the full keys are compared instead, at about twice the time. */
+ * environment (read per call) the full keys are compared instead; that path's cost is unmeasured.
+ * Any number of different rows may share one (start, strand): when they collide in the key's hash bits under every seed the
+ * usual path tries (thousands of different rows under one start), the call answers through the exact path, which orders the
+ * rows of one key by identity and needs no collision-free key.  HAWK_E_UNSUPPORTED is left for more than 2^32 - 1 rows, for a
+ * position-map range max - min above 0xffffffff, and for a flank above the 10 stored bases. */
 int hawk_table_collapse(hawk_table* t, uint64_t* n_groups, float* kernel_ms);
 int hawk_table_collapse_download(hawk_table* t, uint32_t* perm, uint64_t* group_off, uint8_t* gc_num, uint8_t* gc_den);
 /* The same grouping with the compared sequence widened by flank_up bases 5' and flank_down bases 3' of the guide (as it
