@@ -7,7 +7,11 @@ reference's chain of helpers: every haplotype is "a region string + one list of 
 `Haplotype.add_variants_*`"; what differs between the modes is only how records are dealt to carriers (`_deal`) and
 which stretch of the region a haplotype covers (`_Stretch`).  Identical cased sequences are then merged (`_merge_equal`,
 collapse_haplotypes in the reference, 274-294).
+
+`haplotypes_table` (818-859) writes the haplotypes of a region as a TSV; the strings of a device-built expansion plan come
+from the plan as text (hawk_xplan_text), a batch of whole rows at a time.
 """
+import os
 import random
 import string
 from typing import Callable, Dict, Iterable, List, Optional, Sequence as Seq, Tuple
@@ -173,3 +177,81 @@ def generate_haplotype_ids(haplotypes: Dict[Region, List[Haplotype]]) -> Dict[Re
         for h, hid in zip(haps, seen):
             h.id = hid
     return haplotypes
+
+
+# ---------------------------------------------------------------------------------------------- haplotypes table
+HAPTABCNAMES = ["id", "haplotype", "variants", "samples"]  # the reference's column names
+TEXT_BATCH_BYTES = 256 << 20  # text fetched from a plan per call, unless HAWK_HAPTEXT_BATCH_BYTES or the caller says otherwise
+
+
+def haplotypes_table_filename(contig: str, start: int, stop: int) -> str:
+    """haplotypes.py:839-841; start / stop are the padded region's coordinates"""
+    return f"haplotypes_table_{contig}_{start}_{stop}.tsv"
+
+
+def text_batch_bytes(batch_bytes: Optional[int] = None) -> int:
+    """the byte budget of one text batch: the argument, else HAWK_HAPTEXT_BATCH_BYTES (read per call), else 256 MiB"""
+    if batch_bytes is not None:
+        return int(batch_bytes)
+    return int(os.environ.get("HAWK_HAPTEXT_BATCH_BYTES", TEXT_BATCH_BYTES))
+
+
+def text_batches(lengths: Seq[int], budget: int) -> List[Tuple[int, int]]:
+    """Rows of the given lengths, in order, cut into batches [a, b) of whole rows whose bytes stay within `budget`; a row that
+    alone exceeds the budget is a batch of its own, so every batch holds at least one row."""
+    out: List[Tuple[int, int]] = []
+    a, used = 0, 0
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if i > a and used + n > budget:
+            out.append((a, i))
+            a, used = i, 0
+        used += n
+    if len(lengths) > a:
+        out.append((a, len(lengths)))
+    return out
+
+
+def _label_bytes(x) -> bytes:
+    return x if isinstance(x, (bytes, bytearray)) else str(x).encode("ascii")
+
+
+def write_haplotypes_table(path: str, ids: Seq, variants: Seq, samples: Seq, chunks: Iterable) -> str:
+    """The table itself: the header, then `id haplotype variants samples` per row.  `chunks` yields (buffer, offsets) for
+    consecutive runs of rows - row j of a chunk is buffer[offsets[j]:offsets[j + 1]], any bytes-like buffer (the page-locked
+    array of ExpansionPlan.text, or an encoded string) - and its bytes go to the file as they are: no str per haplotype."""
+    k = 0
+    with open(path, "wb") as f:
+        f.write(("\t".join(HAPTABCNAMES) + "\n").encode("ascii"))
+        for buf, off in chunks:
+            mv = memoryview(buf)
+            for j in range(len(off) - 1):
+                f.write(_label_bytes(ids[k]) + b"\t")
+                f.write(mv[int(off[j]):int(off[j + 1])])
+                f.write(b"\t" + _label_bytes(variants[k]) + b"\t" + _label_bytes(samples[k]) + b"\n")
+                k += 1
+    if k != len(ids):
+        raise ValueError(f"haplotypes table: {k} sequences for {len(ids)} rows")
+    return path
+
+
+def haplotypes_table(contig: str, start: int, stop: int, outdir: str, ids: Seq, variants: Seq, samples: Seq, plan=None,
+                     rows: Optional[Seq[int]] = None, sequences: Optional[Seq] = None, batch_bytes: Optional[int] = None) -> str:
+    """haplotypes_table (haplotypes.py:818-859) for one region: haplotypes_table_{contig}_{start}_{stop}.tsv in `outdir`, one
+    line per haplotype in the order given (REF first), labels as given - `ids` are what the guide report's haplotype_id
+    column holds, so the two files join (the reference draws random ids, generate_haplotype_ids).  The sequences come either
+    from an expansion plan (`plan` = hapset.ExpansionPlan, `rows` = the plan's kept rows the labels belong to: their text is
+    fetched with hawk_xplan_text in batches of whole rows under text_batch_bytes(batch_bytes), so neither the device nor the
+    host ever holds more than a batch - or one row, if that is longer) or from the host (`sequences`: str / bytes per row).
+    Returns the path."""
+    path = os.path.join(outdir, haplotypes_table_filename(contig, start, stop))
+    if (plan is None) == (sequences is None):
+        raise ValueError("haplotypes_table takes the rows of a plan or host sequences")
+    if plan is not None:
+        import numpy as np
+        rows = np.arange(plan.n_hap, dtype=np.uint32) if rows is None else np.asarray(rows, dtype=np.uint32)
+        budget = text_batch_bytes(batch_bytes)
+        chunks = (plan.text(rows[a:b]) for a, b in text_batches(plan.hap_len[rows].tolist(), budget))
+    else:
+        chunks = ((_label_bytes(s), (0, len(s))) for s in sequences)
+    return write_haplotypes_table(path, ids, variants, samples, chunks)

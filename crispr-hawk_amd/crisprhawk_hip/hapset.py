@@ -254,6 +254,22 @@ class ExpansionPlan:
             self._view = v
         return v
 
+    def text(self, rows=None, timed: bool = False):
+        """hawk_xplan_text: the cased IUPAC strings of the given rows (default: all, in row order; any order, repeats allowed)
+        -> (uint8 array holding them back to back, offsets[len(rows) + 1]); with `timed` the kernel's ms as a third value.  The
+        bytes sit in a page-locked buffer (_lib.pinned_empty) that returns to its cache when the array is collected.  Nothing
+        is written to the plan: a view of it searches the same before and after.  The whole selection exists on the device
+        and on the host at once - haplotypes.haplotypes_table asks in batches (haplotypes.text_batches)."""
+        rows = np.arange(self.n_hap, dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if len(rows) and int(rows.max()) >= self.n_hap:
+            raise IndexError(f"row {int(rows.max())} of a plan of {self.n_hap} rows")
+        off = np.zeros(len(rows) + 1, dtype=np.uint64)
+        np.cumsum(self.hap_len[rows], dtype=np.uint64, out=off[1:])
+        buf = _lib.pinned_empty(int(off[-1]), np.uint8, self.device)
+        ms = C.c_float(0)
+        _lib.check(self._L.hawk_xplan_text(self._x, len(rows), _p(rows), _p(off), _p(buf), C.byref(ms) if timed else None), "hawk_xplan_text")
+        return (buf, off, ms.value) if timed else (buf, off)
+
     def rebuild_dictionary(self) -> None:
         """hawk_xplan_cluster_rebuild: the cluster dictionary built again (bench.py's timed step; the result is the same)"""
         _lib.check(self._L.hawk_xplan_cluster_rebuild(self._x), "hawk_xplan_cluster_rebuild")

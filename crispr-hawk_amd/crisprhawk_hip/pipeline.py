@@ -7,6 +7,7 @@ inputs, with every stage on the device path of this package.
                          --hawk_table_collapse-->  report groups
                          --hawk_annot_query-->  BED / gene annotation columns of the groups (optional)
                          --reports.report_frame-->  crisprhawk_guides__*.tsv
+                         --hawk_xplan_text-->  haplotypes_table_*.tsv (optional: the plan's rows as text)
 
 Only what the reference's search sub-command does between reading its inputs and writing the guide report is covered;
 the non-CFDon scorers (model files) and the off-target stage have their own entry points (`scoring.py`, `offtargets.py`).
@@ -25,6 +26,7 @@ from .workload import HapInfo, RowLabel, expand_from_vcf, hap_labels
 
 PADDING = 100  # region_constructor.py:21
 ANN_STAGE = "BED / gene annotation of the groups (device join)"
+HAPTAB_STAGE = "haplotypes table (rows as text from the plan + write)"
 
 
 def _labels(ds, info: List[HapInfo], kept: List[int], vt) -> List[Optional[RowLabel]]:
@@ -104,8 +106,19 @@ def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir
                                        ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None)
 
 
+def _plan_row_variants(info, vt) -> List[bytes]:
+    """the `variants` label of every kept row of an expansion: the ids of what it carries in the reference's order (SNVs by
+    position, then indels: haplotype.py:234-242), NA for REF"""
+    out = []
+    for inf in info:
+        idx = [int(i) for i in inf.variant_idx]
+        ids = [vt.id[i] for i in idx if len(vt.ref[i]) == len(vt.alt[i])] + [vt.id[i] for i in idx if len(vt.ref[i]) != len(vt.alt[i])]
+        out.append((",".join(ids) if ids else "NA").encode("ascii"))
+    return out
+
+
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
-                       ot=None, ann=None, lap=None) -> str:
+                       ot=None, ann=None, lap=None, tables=None) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows,
     resolve_guide on the host, search_guides.py:163-257) and the fallback for phased records the device expansion
@@ -125,6 +138,10 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         haps = build(haps, region, vcf.samples, records, phased, debug)
     for i, h in enumerate(haps):
         h.id = f"hap_{i:08d}"
+    if tables is not None:  # the strings are on the host already: the same writer, no kernel
+        tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, [h.id for h in haps],
+                                                      [h.variants for h in haps], [h.samples for h in haps],
+                                                      sequences=[h.sequence.sequence for h in haps])
     guides = search(pam, region, haps, None, guidelen, right, bool(records), phased, 0, debug)
     cfd = None
     if mm is not None:
@@ -157,7 +174,8 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                  debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
                  timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
-                 gene_annotation_colnames: Optional[List[str]] = None) -> Dict[str, str]:
+                 gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
+                 tables: Optional[Dict[str, str]] = None) -> Dict[str, str]:
     """One report per BED interval; returns {str(coordinate): path}.  `cfd_tables = (mm[20,4,4], pam[16])` adds the
     CFDon column for SpCas9-class PAMs (scoring.py:352-387); `azimuth_model` (a fitted sklearn GBR or the flattened
     dict of scoring.azimuth_model_from_sklearn) and `deepcpf1_weights` (scoring.set_deepcpf1_weights layout) switch
@@ -171,7 +189,12 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     `annotations` / `gene_annotations` (the reference's --annotation / --gene-annotation BED files, plain, gzip or BGZF, no .tbi
     needed) add one column per file to every guide report - the 4th BED column, or feature:gene_name, of the features a guide
     overlaps - named by `annotation_colnames` / `gene_annotation_colnames` or annotation_{i} / gene_annotation_{i}; the
-    `annotations` files also annotate the rows of offtargets_*.tsv.  The join runs on the device (bedannot.AnnotTable)."""
+    `annotations` files also annotate the rows of offtargets_*.tsv.  The join runs on the device (bedannot.AnnotTable).
+    `haplotype_table=True` (the reference's --haplotype-table, haplotypes.py:818-859) also writes
+    haplotypes_table_{contig}_{start}_{stop}.tsv per BED interval (padded coordinates): id, haplotype, variants, samples of every
+    haplotype searched, REF first, `id` being the guide report's haplotype_id.  The strings of a device-built plan are fetched
+    as text in batches (haplotypes.haplotypes_table; HAWK_HAPTEXT_BATCH_BYTES, default 256 MiB).  The returned dict stays
+    {str(coordinate): report path}; pass a dict as `tables` and it is filled in place with {str(coordinate): table path}."""
     import time as _time
     check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
@@ -210,6 +233,10 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     mmt, pt = cfd_tables if score else (None, None)
     os.makedirs(outdir, exist_ok=True)
     paths = {}
+    if haplotype_table and tables is None:
+        tables = {}
+    if not haplotype_table:
+        tables = None
     lap("open inputs (FASTA index, VCF header + line index)")
     ann = None
     if annotations or gene_annotations:
@@ -219,21 +246,21 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
         lap("open annotation BED files")
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
-                                 ann, azimuth_model, deepcpf1_weights, paths, lap)
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables)
     finally:
         if ann is not None:
             ann.close()
 
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
-                      deepcpf1_weights, paths, lap) -> Dict[str, str]:
+                      deepcpf1_weights, paths, lap, tables=None) -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
     for coord in bed:
         seq = fastas[coord.contig].fetch(coord).sequence
         v = vcf_by_contig.get(coord.contig)
         if v is not None and not v.phased:
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
-                                                   pt if score else None, debug, ot, ann, lap)
+                                                   pt if score else None, debug, ot, ann, lap, tables)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])
@@ -245,7 +272,7 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
             # records the device expansion does not take (overlapping records on one chromosome copy, deletions with a
             # multi-base alt): the host builder mirrors the reference's own construction, the search stays on the device
             paths[str(coord)] = _search_host_built(coord, seq, v, True, pam, guidelen, right, outdir, mmt if score else None,
-                                                   pt if score else None, debug, ot, ann, lap)
+                                                   pt if score else None, debug, ot, ann, lap, tables)
             continue
         # the search runs from the expansion plan (hawk_xplan_view: once per distinct cluster of neighbouring variants when the
         # panel shares them, per row otherwise; no planes read) - a region without variants has no plan and searches REF's planes
@@ -281,6 +308,17 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         # by the library's TSV writer
         cols, order, plain = reports.group_columns(groups, labels, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", scores, score,
                                                    is_ref_hap=np.asarray(ds.is_ref, dtype=bool), offtargets=otcb, annotations=anncols)
+        lap("report assembly")
+        if tables is not None:  # the plan's metadata is finished; its rows as text, batch by batch, straight into the file
+            from . import haplotypes as hap_mod
+            hap_ids, hap_samples = [labels.ids[r] for r in kept], [labels.samples[r] for r in kept]
+            if plan is not None:
+                tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, hap_ids, _plan_row_variants(info, vt),
+                                                              hap_samples, plan=plan, rows=kept)
+            else:  # no variants: REF alone, upper case as the reference's REF haplotype (sequence.py:49)
+                tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, hap_ids, ["NA"], hap_samples,
+                                                              sequences=[seq.upper()])
+            lap(HAPTAB_STAGE)
         if plan is not None:
             plan.close()
         ds.close()

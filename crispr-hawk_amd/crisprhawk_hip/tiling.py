@@ -258,8 +258,14 @@ class TiledRegionSearch:
                 ds.close()      # (a view lives and dies with its plan)
 
     # ---- the whole region ---------------------------------------------------------------------------
-    def run(self, cfd=None, flank_key: Tuple[int, int] = (0, 0), cfd_na_on_ambiguous: bool = True, keep_plans: bool = False):
-        """All tiles; returns a MergedGroups (report groups of the whole region, seam groups merged)."""
+    def run(self, cfd=None, flank_key: Tuple[int, int] = (0, 0), cfd_na_on_ambiguous: bool = True, keep_plans: bool = False,
+            haplotype_table: bool = False):
+        """All tiles; returns a MergedGroups (report groups of the whole region, seam groups merged).  There is no haplotypes
+        table of a tiled region: rows are haplotypes of ONE tile (two samples that share a tile's variants are one row there and
+        two in the next), so the region has no single row set to list - `haplotype_table=True` is a ValueError."""
+        if haplotype_table:
+            raise ValueError("haplotype_table: a tiled region search has no whole-region haplotypes (haplotype identity is per tile); "
+                             "use pipeline.search_files on an interval that fits one plan")
         acc = None
         stats = []
         base = 0

@@ -460,6 +460,43 @@ int hawk_xplan_rows(hawk_xplan* x, uint32_t* hap_len, int64_t* rev0, int64_t* re
   return HAWK_OK;
 }
 
+// The rows' text (hawk_haptext.hip).  Everything is checked before anything is queued; the device image of the call's rows is
+// compact and keeps the destination's phase on the 16-byte grid - row i at out_off[i] - (out_off[0] & ~15) - and reaches the
+// host in one copy.
+int hawk_xplan_text(hawk_xplan* x, uint32_t n_rows, const uint32_t* rows, const uint64_t* out_off, char* out, float* kernel_ms) {
+  if (!x) return HAWK_E_INVALID;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (n_rows == 0) return HAWK_OK;
+  if (!rows || !out_off || !out) return HAWK_E_INVALID;
+  for (uint32_t i = 0; i < n_rows; ++i) {
+    if (rows[i] >= x->n_hap || out_off[i + 1] < out_off[i]) return HAWK_E_INVALID;
+    if (out_off[i + 1] - out_off[i] != (uint64_t)x->hap_len[rows[i]]) return HAWK_E_INVALID;
+  }
+  hawk_ctx* ctx = x->ctx;
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint64_t total = out_off[n_rows] - out_off[0];
+  std::vector<uint64_t> rel(n_rows);
+  const uint64_t phase = out_off[0] & 15u;
+  for (uint32_t i = 0; i < n_rows; ++i) rel[i] = out_off[i] - out_off[0] + phase;
+  PoolScope tmp;
+  uint32_t* d_rows; uint64_t* d_off; uint8_t* d_text;
+  TEMPCHK(tmp, &d_rows, (size_t)n_rows * 4);
+  TEMPCHK(tmp, &d_off, (size_t)n_rows * 8);
+  TEMPCHK(tmp, &d_text, (size_t)(total + phase));
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(d_rows, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_off, rel.data(), (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  hawk_launch_hx_text(st, x->ref_plane, x->ref_S, x->recs.p, x->codes.as<uint8_t>(), x->off.as<uint64_t>(), x->hlen.as<uint32_t>(), x->S,
+                      x->tiles.p, n_rows, d_rows, d_off, d_text);
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out + out_off[0], d_text + phase, (size_t)total, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // `rel` and the temporaries live until here
+  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]);
+  return HAWK_OK;
+}
+
 int hawk_xplan_finish_meta(hawk_xplan* x, const int32_t* scan_start, const int32_t* scan_stop) {
   if (!x || !scan_start || !scan_stop || !x->nseg) return HAWK_E_INVALID;
   hawk_ctx* ctx = x->ctx;

@@ -336,6 +336,10 @@ void hawk_launch_hx_build(hipStream_t st, const uint32_t* const* ref, uint32_t r
                           const uint64_t* hv_off, const uint32_t* hap_len, uint32_t n_hap, uint32_t S, uint32_t* const* plane,
                           const void* tiles);
 void hawk_launch_hx_hash(hipStream_t st, uint32_t* const* plane, uint32_t n_hap, uint32_t S, unsigned long long* hash);
+// hawk_haptext.hip: the listed rows of a plan as cased IUPAC text, row i at out + dst_off[i] (device memory, any alignment)
+void hawk_launch_hx_text(hipStream_t st, const uint32_t* const* ref, uint32_t ref_S, const void* recs, const uint8_t* alt_codes,
+                         const uint64_t* hv_off, const uint32_t* hap_len, uint32_t S, const void* tiles, uint32_t n_rows, const uint32_t* rows,
+                         const uint64_t* dst_off, uint8_t* out);
 
 // ---- BED annotation join (hawk_annot.hip): the features of one (file, contig, label kind), sorted by start, resident in HBM
 struct AnnDev {

@@ -16,6 +16,7 @@
 //   every run (hawk_xplan_run):
 //   k_hx_build  one thread per four consecutive output words; the tile's records and its image in the REF planes
 //               are staged in LDS first (two independent coalesced loads), then no thread waits on global memory
+//   (the staging and the word assembly are hx_tile_quad, hawk_hx.h: k_hx_text of hawk_haptext.hip turns the same words into text)
 //   k_hx_hash   128-bit position-tagged content hash per row (for collapse_haplotypes,
 //               haplotypes.py:274-294, and the homozygous test 326-333, done by the caller)
 #include "hawk_hx.h"
@@ -78,38 +79,6 @@ __global__ __launch_bounds__(256) void k_hx_index(const uint64_t* __restrict__ h
   tiles[i] = HxTile{(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)n | flags, ws};
 }
 
-// Staged REF word i of a plane lives at (i & 3) * HX_RW / 4 + (i >> 2): a thread owns four consecutive output words, so
-// the lanes of a wave read words 4 apart - a 4-way bank conflict in the natural layout, consecutive banks in this one.
-__device__ __forceinline__ uint32_t hx_slot(uint32_t i) { return (i & 3u) * (HX_RW / 4) + (i >> 2); }
-
-struct HxArgs {
-  const uint32_t* ref[4];
-  uint32_t ref_S;
-  const HxVar* recs;
-  const uint8_t* alt_codes;
-};
-
-// The four words of one thread (hx_words_t, hawk_hx.h).  FAST: every record the tile needs and its whole REF image are in
-// LDS (the usual tile); otherwise records beyond the staged ones and / or the REF words come from global memory.
-template <bool FAST>
-__device__ __forceinline__ void hx_words(const HxArgs& g, const HxVar* __restrict__ s_v, const uint32_t (*__restrict__ s_ref)[HX_RW],
-                                         const HxVar* __restrict__ first, int n, int j_end /* records of the row from `first` on */,
-                                         bool head, bool staged, uint32_t ws, int32_t p0, int32_t len,
-                                         uint32_t (&oA)[4], uint32_t (&oC)[4], uint32_t (&oG)[4], uint32_t (&oT)[4], uint32_t (&oV)[4]) {
-  // 32 bits of REF plane pl from bit r.  A read under a mapping that a later variant of the word replaces, or of bits
-  // past the end of the row, may point outside what exists: the word index is clamped, the bits are overwritten / masked.
-  auto ref32 = [&](int pl, uint32_t r) -> uint32_t {
-    if (FAST || staged) {
-      uint32_t w = (r >> 5) - ws;
-      w = w < HX_RW - 2 ? w : HX_RW - 2;
-      return fsh(s_ref[pl][hx_slot(w)], s_ref[pl][hx_slot(w + 1)], r & 31u);
-    }
-    const uint32_t w = (r >> 5) < g.ref_S - 3 ? (r >> 5) : g.ref_S - 3;
-    return ext_glb(g.ref[pl], (w << 5) | (r & 31u)).lo;
-  };
-  hx_words_t<FAST, 4>(g.alt_codes, s_v, first, n, j_end, head, p0, len, ref32, oA, oC, oG, oT, oV);
-}
-
 __global__ __launch_bounds__(HAWK_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hx_build(HxArgs g, const uint64_t* __restrict__ hv_off, const uint32_t* __restrict__ hap_len,
                                                           uint32_t S, uint32_t wpr /*tiles per row*/, const HxTile* __restrict__ tiles,
                                                           uint32_t* pA, uint32_t* pC, uint32_t* pG, uint32_t* pT, uint32_t* pV) {
@@ -117,36 +86,9 @@ __global__ __launch_bounds__(HAWK_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8
   __shared__ uint32_t s_ref[4][HX_RW];
   const uint32_t h = blockIdx.x / wpr, wb = blockIdx.x % wpr;
   const uint32_t w0 = wb * HX_TW + threadIdx.x * 4u;
-  const HxTile t = tiles[blockIdx.x];  // k_hx_index
-  const int32_t len = (int32_t)hap_len[h];
-  const int n = (int)(t.n_flags & 0xffffu);
-  const bool staged = (t.n_flags & HX_FITS) != 0, all = (t.n_flags & HX_ALL) != 0, head = (t.n_flags & HX_HEAD) != 0;
-  const uint32_t ws = t.ws;
-  const HxVar* first = g.recs + (((uint64_t)t.first_hi << 32) | t.first_lo);
-  // both stagings are independent coalesced loads, in flight together
-  if (staged) {  // the REF words the tile's copies read: 16-byte loads, each word to its swizzled slot
-    for (uint32_t i = threadIdx.x; i < HX_RW / 4; i += HAWK_BLOCK) {
-      const uint32_t w = ws + 4 * i + 4 <= g.ref_S ? ws + 4 * i : g.ref_S - 4;  // rows are whole 16-byte quads
-#pragma unroll
-      for (int pl = 0; pl < 4; ++pl) {
-        const uint4 q = *reinterpret_cast<const uint4*>(g.ref[pl] + w);
-        s_ref[pl][i] = q.x; s_ref[pl][HX_RW / 4 + i] = q.y; s_ref[pl][2 * (HX_RW / 4) + i] = q.z; s_ref[pl][3 * (HX_RW / 4) + i] = q.w;
-      }
-    }
-  }
-  if ((int)threadIdx.x < n) s_v[threadIdx.x] = first[threadIdx.x];  // n <= HX_MAXV < workgroup size
-  __syncthreads();
-  if (w0 >= S) return;
   uint32_t oA[4] = {0, 0, 0, 0}, oC[4] = {0, 0, 0, 0}, oG[4] = {0, 0, 0, 0}, oT[4] = {0, 0, 0, 0}, oV[4] = {0, 0, 0, 0};
-  const int32_t p0 = (int32_t)(w0 * 32u);
-  if (p0 < len) {
-    if (staged && all) {
-      hx_words<true>(g, s_v, s_ref, first, n, n, head, true, ws, p0, len, oA, oC, oG, oT, oV);
-    } else {  // more records than LDS holds start inside the tile (one every 200 nt over all of it), or a long REF image
-      const int j_end = (int)(g.recs + hv_off[h + 1] - first);
-      hx_words<false>(g, s_v, s_ref, first, n, j_end, head, staged, ws, p0, len, oA, oC, oG, oT, oV);
-    }
-  }
+  hx_tile_quad(g, hv_off, h, tiles[blockIdx.x] /* k_hx_index */, (int32_t)hap_len[h], w0, s_v, s_ref, oA, oC, oG, oT, oV);
+  if (w0 >= S) return;
   const size_t o = (size_t)h * S + w0;  // S and w0 are multiples of 4: one 16-byte store per plane
   *reinterpret_cast<uint4*>(pA + o) = make_uint4(oA[0], oA[1], oA[2], oA[3]);
   *reinterpret_cast<uint4*>(pC + o) = make_uint4(oC[0], oC[1], oC[2], oC[3]);

@@ -1,5 +1,6 @@
 // hawk_hx.h - records of an expansion plan and the word builder shared by the expansion kernel (hawk_expand.hip) and the
-// search that runs straight from a plan (hawk_vsearch.hip).  See hawk_expand.hip for what the records mean.
+// search that runs straight from a plan (hawk_vsearch.hip), and the (row, tile) workgroup's staging and word assembly shared by the
+// expansion kernel and the text kernel (hawk_haptext.hip).  See hawk_expand.hip for what the records mean.
 #pragma once
 #include "hawk_bits.h"
 
@@ -109,5 +110,71 @@ __device__ __forceinline__ void hx_words_t(const uint8_t* __restrict__ alt_codes
     }
     const uint32_t wm = hx_low(wend - wp0);  // the row ends inside (or before) the word
     oA[wi] = xA & wm; oC[wi] = xC & wm; oG[wi] = xG & wm; oT[wi] = xT & wm; oV[wi] = xV & wm;
+  }
+}
+
+// Staged REF word i of a plane lives at (i & 3) * HX_RW / 4 + (i >> 2): a thread owns four consecutive output words, so
+// the lanes of a wave read words 4 apart - a 4-way bank conflict in the natural layout, consecutive banks in this one.
+__device__ __forceinline__ uint32_t hx_slot(uint32_t i) { return (i & 3u) * (HX_RW / 4) + (i >> 2); }
+
+struct HxArgs {
+  const uint32_t* ref[4];
+  uint32_t ref_S;
+  const HxVar* recs;
+  const uint8_t* alt_codes;
+};
+
+// The four words of one thread (hx_words_t, hawk_hx.h).  FAST: every record the tile needs and its whole REF image are in
+// LDS (the usual tile); otherwise records beyond the staged ones and / or the REF words come from global memory.
+template <bool FAST>
+__device__ __forceinline__ void hx_words(const HxArgs& g, const HxVar* __restrict__ s_v, const uint32_t (*__restrict__ s_ref)[HX_RW],
+                                         const HxVar* __restrict__ first, int n, int j_end /* records of the row from `first` on */,
+                                         bool head, bool staged, uint32_t ws, int32_t p0, int32_t len,
+                                         uint32_t (&oA)[4], uint32_t (&oC)[4], uint32_t (&oG)[4], uint32_t (&oT)[4], uint32_t (&oV)[4]) {
+  // 32 bits of REF plane pl from bit r.  A read under a mapping that a later variant of the word replaces, or of bits
+  // past the end of the row, may point outside what exists: the word index is clamped, the bits are overwritten / masked.
+  auto ref32 = [&](int pl, uint32_t r) -> uint32_t {
+    if (FAST || staged) {
+      uint32_t w = (r >> 5) - ws;
+      w = w < HX_RW - 2 ? w : HX_RW - 2;
+      return fsh(s_ref[pl][hx_slot(w)], s_ref[pl][hx_slot(w + 1)], r & 31u);
+    }
+    const uint32_t w = (r >> 5) < g.ref_S - 3 ? (r >> 5) : g.ref_S - 3;
+    return ext_glb(g.ref[pl], (w << 5) | (r & 31u)).lo;
+  };
+  hx_words_t<FAST, 4>(g.alt_codes, s_v, first, n, j_end, head, p0, len, ref32, oA, oC, oG, oT, oV);
+}
+
+// One thread's part of a (row, tile) workgroup of HAWK_BLOCK threads, shared by k_hx_build (the words go to the planes) and
+// k_hx_text (hawk_haptext.hip: the words become letters): the tile's records and its image in the REF planes are staged in LDS
+// (two independent coalesced loads, in flight together), the workgroup waits once, then the thread builds the four words from
+// w0 - zero where the row has ended.  Every thread of the workgroup must call it (it holds a barrier).
+__device__ __forceinline__ void hx_tile_quad(const HxArgs& g, const uint64_t* __restrict__ hv_off, uint32_t h, const HxTile t, int32_t len, uint32_t w0,
+                                             HxVar* __restrict__ s_v, uint32_t (*__restrict__ s_ref)[HX_RW],
+                                             uint32_t (&oA)[4], uint32_t (&oC)[4], uint32_t (&oG)[4], uint32_t (&oT)[4], uint32_t (&oV)[4]) {
+  const int n = (int)(t.n_flags & 0xffffu);
+  const bool staged = (t.n_flags & HX_FITS) != 0, all = (t.n_flags & HX_ALL) != 0, head = (t.n_flags & HX_HEAD) != 0;
+  const uint32_t ws = t.ws;
+  const HxVar* first = g.recs + (((uint64_t)t.first_hi << 32) | t.first_lo);
+  if (staged) {  // the REF words the tile's copies read: 16-byte loads, each word to its swizzled slot
+    for (uint32_t i = threadIdx.x; i < HX_RW / 4; i += HAWK_BLOCK) {
+      const uint32_t w = ws + 4 * i + 4 <= g.ref_S ? ws + 4 * i : g.ref_S - 4;  // rows are whole 16-byte quads
+#pragma unroll
+      for (int pl = 0; pl < 4; ++pl) {
+        const uint4 q = *reinterpret_cast<const uint4*>(g.ref[pl] + w);
+        s_ref[pl][i] = q.x; s_ref[pl][HX_RW / 4 + i] = q.y; s_ref[pl][2 * (HX_RW / 4) + i] = q.z; s_ref[pl][3 * (HX_RW / 4) + i] = q.w;
+      }
+    }
+  }
+  if ((int)threadIdx.x < n) s_v[threadIdx.x] = first[threadIdx.x];  // n <= HX_MAXV < workgroup size
+  __syncthreads();
+  const int32_t p0 = (int32_t)(w0 * 32u);
+  if (w0 * 32u < (uint32_t)len) {  // (unsigned: the words of a tile may lie behind the stride, past 2^31 positions)
+    if (staged && all) {
+      hx_words<true>(g, s_v, s_ref, first, n, n, head, true, ws, p0, len, oA, oC, oG, oT, oV);
+    } else {  // more records than LDS holds start inside the tile (one every 200 nt over all of it), or a long REF image
+      const int j_end = (int)(g.recs + hv_off[h + 1] - first);
+      hx_words<false>(g, s_v, s_ref, first, n, j_end, head, staged, ws, p0, len, oA, oC, oG, oT, oV);
+    }
   }
 }

@@ -142,6 +142,17 @@ int hawk_xplan_install_meta(hawk_xplan* x, hawk_hapset* hs);
 int hawk_xplan_set_ref_partner_range(hawk_xplan* x, int32_t start, int32_t stop);
 int hawk_xplan_run(hawk_xplan* x, hawk_hapset** out, uint64_t* hash_out, float* kernel_ms);
 void hawk_xplan_destroy(hawk_xplan* x);
+/* The rows of a plan as text: the `haplotype` column of the reference's haplotypes_table (haplotypes.py:818-859, written by
+ * `search --haplotype-table`) - the cased IUPAC string of a haplotype, alt bases in lower case - without planes in HBM and
+ * without a decode on the host (crispr-hawk_amd/csrc/hawk_haptext.hip: the words the expansion would write, turned into
+ * letters).  rows: n_rows row indices of the plan, in any order, repeats allowed.  Row i of the call is written to
+ * out[out_off[i] .. out_off[i + 1]) (host memory; page-locked memory copies fastest; no alignment is asked of the offsets) and
+ * is exactly as long as hawk_xplan_rows reports for it; no other byte of `out` is written.  HAWK_E_INVALID, with nothing
+ * written, when a row index is >= the plan's rows, when out_off[i + 1] - out_off[i] is not that row's length, or when out_off
+ * is not ascending.  n_rows == 0 is HAWK_OK.  The device image of the call's rows (out_off[n_rows] - out_off[0] bytes) comes
+ * from the library's caching allocator: callers with many long rows call in batches of whole rows.  The plan is only read: a
+ * search of its view gives the same table before and after.  kernel_ms may be NULL. */
+int hawk_xplan_text(hawk_xplan* x, uint32_t n_rows, const uint32_t* rows, const uint64_t* out_off, char* out, float* kernel_ms);
 /* A VIEW of the plan's rows: a haplotype set with the plan's metadata (hawk_xplan_finish_meta must have been called, REF =
  * row 0) but WITHOUT planes.  hawk_search on a view computes the same table, totals and row order as on the set hawk_xplan_run
  * writes - encode (encoder.py:48-57 over every haplotype) and search (search_guides.py:510-548) in one step, straight from
