@@ -25,279 +25,312 @@ int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c) {
   c->rows = nullptr; c->startp = 0;
   return HAWK_OK;
 }
-extern "C" {
 
 #define HAWK_RETRY_TEMPLATES (-100)  // private to this file: the template rows of a cluster search outgrew their reservation
-static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_table** out, hawk_timing* timing);
+
+// The slots of hawk_ctx::ev a search records, each named for the interval it opens or closes.
+enum SearchEvent {
+  EV_BEGIN, EV_COUNT_DONE, EV_OFFSETS_DONE, EV_EMIT_BEGIN, EV_EMIT_END, EV_LIST_EMIT_END,  // every search
+  EV_VIEW_COUNT_BEGIN, EV_VIEW_EMIT_BEGIN,                                                 // a view of an expansion plan
+  EV_TEMPLATES_DONE, EV_REF_ROWS_PACKED,                                                   // ... searched per cluster
+  EV_SLOTS
+};
+static_assert(EV_SLOTS == sizeof(hawk_ctx::ev) / sizeof(hipEvent_t), "hawk_ctx::ev holds exactly the search's events");
+
+// One attempt of hawk_search: what its stages share.  search_classify .. search_view_args fill it, the stages behind them read it.
+struct SearchRun {
+  hawk_hapset* hs; hawk_ctx* ctx; hipStream_t st;
+  const hawk_xplan* vx;           // the plan a view is searched from (nullptr: a set with planes, every row through the plane kernels)
+  bool by_cluster;                // ... per distinct cluster (hawk_csearch.hip); false: per dirty word (hawk_vsearch.hip)
+  HapSetDev d; ScanParams sp; GuideParams gp; RefInfo ri; VcArgs va; ClDict cd;
+  uint64_t ntile, nscan;          // tiles of all rows; entries of the offset scan
+  uint32_t plane_tiles, v_tiles;  // tiles the plane kernels take; tiles left to the per-word search
+  uint64_t tcap, t_rows_used;     // cluster search: template rows reserved, and produced
+  uint64_t stage_cap;             // ... rows of REF staged as columns: at most every window start of both strands
+  unsigned long long* shards;     // hs->misc on the device (SearchMisc): the shard sums ...
+  SearchStatusBlock* blk;         // ... and the status block every launcher is handed its fields of
+  SearchStatusBlock* h;           // the status block as last read back (hawk_ctx::pinned)
+  uint64_t* table_cap;            // rows the set's table holds: hs->rows_cap for a cluster search, else hs->cols_cap
+};
+
+// Parameter checks, and which path runs.  A view of an expansion plan (hawk_xplan_view) holds no planes: its REF row runs through the
+// plane kernels on the plan's REF planes (hand-over lists included); every other row per distinct cluster when the plan's dictionary
+// is usable (hawk_csearch.hip: the scan then runs over REF's tiles + one count per cluster instance), else - or with
+// HAWK_VIEW_SEARCH=words, read per call - per dirty word (hawk_vsearch.hip).
+static int search_classify(hawk_hapset* hs, const hawk_search_params* p, SearchRun* r) {
+  if (!hs || !p || !hs->has_meta || p->score_cfdon > 2) return HAWK_E_INVALID;
+  if (p->score_cfdon && (p->right || !p->cfd_mm || !p->cfd_pam || p->pamlen < 2)) return HAWK_E_INVALID;
+  r->hs = hs; r->ctx = hs->ctx; r->st = hs->ctx->stream; r->vx = hs->vplan;
+  HIPCHK(hipSetDevice(r->ctx->device));
+  const int rc = make_scan_params(hs, p->pam_fwd, p->pam_rev, p->pamlen, p->guidelen, p->right, true, &r->sp);
+  if (rc) return rc;
+  r->d = make_dev(hs);
+  ++hs->cols_gen;  // the columns are about to be rewritten: earlier tables of this set become stale
+  const hawk_xplan* vx = r->vx;
+  if (vx && (hs->ref_index != 0 || hs->n_ref_rows != 1)) return HAWK_E_INVALID;  // a plan's rows: REF first, once
+  r->by_cluster = vx && vx->cl.built && vx->cl.usable;
+  if (r->by_cluster) { const char* e = getenv("HAWK_VIEW_SEARCH"); if (e && e[0] == 'w') r->by_cluster = false; }
+  r->ntile = (uint64_t)hs->n_hap * r->sp.bph;
+  // what the offset scan runs over: the plane kernels' tiles, then - for a cluster search - one entry per 64 consecutive cluster
+  // instances (a wave of the count / emit kernels: its rows are one contiguous stretch of the table), else the view's tiles
+  r->nscan = r->by_cluster ? (uint64_t)r->sp.bph + ((uint64_t)vx->cl.n_inst + 63) / 64 : r->ntile;
+  r->plane_tiles = vx ? r->sp.bph : (uint32_t)r->ntile;
+  r->v_tiles = (uint32_t)r->ntile - r->plane_tiles;
+  r->stage_cap = r->by_cluster ? 2ull * hs->hap_len[hs->ref_index] + 64 : 0;
+  r->table_cap = r->by_cluster ? &hs->rows_cap : &hs->cols_cap;
+  r->tcap = r->t_rows_used = 0;
+  return HAWK_OK;
+}
+// The workspaces every path needs, and what points into them.  Hand-over lists (2 KB per tile): the count pass leaves each small
+// tile's valid survivors for the emit pass.  A REF tile takes one work-list entry per 512 survivors (<= 128 per tile), any other big tile one.
+static int search_reserve(SearchRun* r, const hawk_search_params* p) {
+  hawk_hapset* hs = r->hs;
+  const ScanParams& sp = r->sp;
+  const uint64_t n_ref_tiles = (uint64_t)sp.bph * hs->n_ref_rows;
+  int rc;
+  if ((rc = hs->counts.reserve(r->nscan * 4)) || (rc = hs->offsets.reserve((r->nscan + 1) * 8)) || (rc = hs->misc.reserve(sizeof(SearchMisc))) ||
+      (rc = hs->cfd.reserve(336 * 8)) || (rc = hs->partial.reserve((r->nscan / 1024 + 2) * 8)) ||
+      (rc = hs->lists.reserve((size_t)r->plane_tiles * HAWK_LIST_CAP * 4 + 16)) || (rc = hs->big.reserve(((size_t)r->plane_tiles + 128 * n_ref_tiles) * 8 + 16)))
+    return rc;
+  r->shards = &hs->misc.as<SearchMisc>()->shards[0][0];
+  r->blk = &hs->misc.as<SearchMisc>()->blk;
+  r->h = static_cast<SearchStatusBlock*>(r->ctx->pinned);
+  GuideParams& gp = r->gp;
+  gp.pamlen = sp.pamlen; gp.guidelen = sp.guidelen; gp.right = sp.right; gp.L = sp.L;
+  gp.score_cfdon = (int32_t)p->score_cfdon;  // 1: a non-ACGT base under a lookup is HAWK_E_CFD; 2: it scores NaN ("NA")
+  gp.cfd_mm = hs->cfd.as<double>(); gp.cfd_pam = hs->cfd.as<double>() + 320; gp.bph = sp.bph;
+  return HAWK_OK;
+}
+// The CFD tables go up once; later searches with the same tables find them in HBM.
+static int search_upload_cfd(SearchRun* r, const hawk_search_params* p) {
+  hawk_hapset* hs = r->hs;
+  if (!p->score_cfdon) return HAWK_OK;
+  if (hs->cfd_host.size() == 336 && memcmp(hs->cfd_host.data(), p->cfd_mm, 320 * 8) == 0 && memcmp(hs->cfd_host.data() + 320, p->cfd_pam, 16 * 8) == 0) return HAWK_OK;
+  hs->cfd_host.assign(336, 0.0);
+  memcpy(hs->cfd_host.data(), p->cfd_mm, 320 * 8);
+  memcpy(hs->cfd_host.data() + 320, p->cfd_pam, 16 * 8);
+  HIPCHK(hipMemcpyAsync(hs->cfd.p, hs->cfd_host.data(), 336 * 8, hipMemcpyHostToDevice, r->st));
+  HIPCHK(hipStreamSynchronize(r->st));
+  return HAWK_OK;
+}
+// Where REF has guides a haplotype row can be grouped with (RefInfo) and, cached on the set, REF's candidate windows as bitmaps
+// (k_ref_bits) + for a view REF's PAM hits and prefix counts (k_ref_hits: what the clean stretches of a plan's rows are counted
+// from).  Both are rebuilt only when the PAM / guide geometry or REF's range changed.
+static int search_ref(SearchRun* r, const hawk_search_params* p) {
+  hawk_hapset* hs = r->hs;
+  const ScanParams& sp = r->sp;
+  RefInfo& ri = r->ri;
+  ri.index = hs->ref_index; ri.startp = hs->ref_startp;
+  ri.bits[0] = ri.bits[1] = nullptr; ri.n_bits = 0;
+  for (int s = 0; s < 2; ++s) {
+    ri.lo[s] = 0; ri.hi[s] = 0;
+    if (hs->ref_index < 0) continue;
+    // same arithmetic as the kernel's phase A, for the REF haplotype
+    const bool pamfirst = (sp.right != 0) != (s != 0);
+    const int po = pamfirst ? 0 : sp.guidelen;
+    const int haplen = (int)hs->hap_len[hs->ref_index];
+    // REF's own scan range, or - for a tile of a larger region - the region's scan range as far as this tile's REF string
+    // reaches (hawk_hapset_set_ref_partner_range)
+    const int rs = hs->has_partner ? hs->partner_start : hs->scan_start[hs->ref_index];
+    const int re = hs->has_partner ? hs->partner_stop : hs->scan_stop[hs->ref_index];
+    ri.lo[s] = std::max(rs - po, HAWK_PAD);
+    ri.hi[s] = std::min(re - po, haplen - sp.L - HAWK_PAD + 1);
+  }
+  if (hs->ref_index < 0) return HAWK_OK;
+  const uint64_t key[6] = {p->pam_fwd, p->pam_rev, ((uint64_t)p->pamlen << 32) | p->guidelen, (uint64_t)(p->right ? 1 : 0),
+                           ((uint64_t)(uint32_t)ri.lo[0] << 32) | (uint32_t)ri.hi[0], ((uint64_t)(uint32_t)ri.lo[1] << 32) | (uint32_t)ri.hi[1]};
+  int rc;
+  if ((rc = hs->refbits.reserve((size_t)hs->S * 4 * 2))) return rc;
+  ri.bits[0] = hs->refbits.as<uint32_t>(); ri.bits[1] = hs->refbits.as<uint32_t>() + hs->S;
+  ri.n_bits = hs->S * 32u;
+  if (r->vx && ((rc = hs->refhp.reserve(((size_t)hs->S + 1) * 8 * 2)) || (rc = hs->vcnt0.reserve(r->by_cluster ? 16 : r->ntile * 4)))) return rc;
+  if (hs->refbits_valid && memcmp(hs->refbits_key, key, sizeof(key)) == 0) return HAWK_OK;
+  hawk_launch_ref_bits(r->st, r->d, sp, ri, hs->refbits.as<uint32_t>(), hs->refbits.as<uint32_t>() + hs->S);
+  if (r->vx) hawk_launch_ref_hits(r->st, r->d, sp, hs->ref_index, hs->refhp.p);
+  HIPCHK(hipGetLastError());
+  memcpy(hs->refbits_key, key, sizeof(key));
+  hs->refbits_valid = true;
+  return HAWK_OK;
+}
+// What a view's kernels read beside the rows' metadata: the plan's records (VcArgs) and, for a cluster search, the dictionary
+// (ClDict) with the room for this search's template rows.
+static int search_view_args(SearchRun* r) {
+  hawk_hapset* hs = r->hs;
+  const hawk_xplan* vx = r->vx;
+  VcArgs& va = r->va; ClDict& cd = r->cd;
+  memset(&va, 0, sizeof(va)); memset(&cd, 0, sizeof(cd));
+  if (!vx) return HAWK_OK;
+  for (int pl = 0; pl < 4; ++pl) va.ref[pl] = vx->ref5[pl].as<uint32_t>();
+  va.ref_S = hs->S; va.hp = hs->refhp.as<uint4>();
+  va.recs_ = vx->recs.p; va.alt_codes = vx->codes.as<uint8_t>(); va.hv_off = vx->off.as<uint64_t>(); va.tiles_ = vx->tiles.p;
+  if (!r->by_cluster) return HAWK_OK;
+  const auto& cl = vx->cl;
+  cd.n_inst = cl.n_inst; cd.n_uniq = cl.n_uniq;
+  cd.inst_uid = cl.inst_uid.as<uint32_t>(); cd.inst_o = cl.inst_o.as<int32_t>(); cd.inst_row = cl.inst_row.as<uint32_t>();
+  cd.inst_pa = cl.inst_pa.as<int32_t>(); cd.inst_rb = cl.inst_rb.as<int32_t>();
+  cd.u_rec = cl.u_rec.as<uint32_t>(); cd.u_n = cl.u_n.as<uint32_t>(); cd.u_row = cl.u_row.as<uint32_t>(); cd.u_o = cl.u_o.as<int32_t>();
+  cd.u_seg = cl.u_seg.as<uint32_t>();
+  // template rows: packed as the search produces them.  Their number is bounded by the window starts of the distinct clusters
+  // (cl.slots: 2 strands x every start), but a PAM keeps a few per cent of those: reserve 16 rows per distinct cluster, and
+  // if a search needs more it produces no table (k_cs_count sees the counter), says so and is rerun with the bound reserved
+  const char* e0 = getenv("HAWK_CLUSTER_ROWS0");  // tests: a first reservation small enough to overflow (read per call)
+  const uint64_t first = e0 ? strtoull(e0, nullptr, 10) : 16ull * cl.n_uniq + 65536;
+  r->tcap = std::max<uint64_t>(std::min<uint64_t>(cl.slots, std::max<uint64_t>(hs->cs_tcap, first)), 1);
+  // (cs_res, 32 bytes per distinct cluster: {rows per strand, hits, candidates} {first template row, REF's hits before / behind it})
+  const size_t n_uniq = std::max<uint32_t>(cl.n_uniq, 1), n_inst = std::max<uint32_t>(cl.n_inst, 1);
+  int rc;
+  if ((rc = hs->cs_res.reserve(n_uniq * 32)) || (rc = hs->cs_tbase.reserve(n_uniq * 4)) || (rc = hs->cs_trows.reserve((size_t)r->tcap * hawk_cs_row_bytes())) ||
+      (rc = hs->cs_itb.reserve(n_inst * 4)) || (rc = hs->cs_icnt.reserve(n_inst * 4)))
+    return rc;
+  return HAWK_OK;
+}
+// The count side: the plane kernels' tiles, then the view's share - templates + a count per cluster instance, or pass 0 of the
+// per-word search - then the offset scan, which leaves the totals in the status block.
+static int search_count(SearchRun* r) {
+  hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
+  SearchStatusBlock* blk = r->blk; uint32_t* counts = hs->counts.as<uint32_t>();
+  HIPCHK(hipEventRecord(ev[EV_BEGIN], st));
+  hawk_launch_search(st, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
+                     &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
+  if (r->vx) HIPCHK(hipEventRecord(ev[EV_VIEW_COUNT_BEGIN], st));
+  if (r->by_cluster) {
+    hawk_launch_cs_templates(st, r->d, r->va, r->cd, r->sp, r->gp, r->ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, &blk->template_rows,
+                             r->tcap, &blk->status);
+    (void)hipEventRecord(ev[EV_TEMPLATES_DONE], st);
+    hawk_launch_cs_count(st, r->d, r->va, r->cd, r->sp, hs->cs_res.p, &blk->template_rows, r->tcap, counts + r->plane_tiles, hs->cs_icnt.as<uint32_t>(),
+                         hs->cs_itb.as<uint32_t>(), r->shards);
+  } else if (r->vx) {
+    hawk_launch_vsearch(st, 0, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, hs->vcnt0.as<uint32_t>(), r->shards, nullptr, GuideCols{}, &blk->status,
+                        r->plane_tiles, r->v_tiles);
+  }
+  HIPCHK(hipEventRecord(ev[EV_COUNT_DONE], st));
+  hawk_launch_mscan(st, counts, r->nscan, hs->partial.as<unsigned long long>(), r->shards, hs->offsets.as<uint64_t>(), &blk->totals);
+  HIPCHK(hipEventRecord(ev[EV_OFFSETS_DONE], st));
+  HIPCHK(hipGetLastError());
+  return HAWK_OK;
+}
+// Reserve for `cap` rows: `cols` is what the column emitters write, `table` what the finished table is
+static int search_reserve_table(SearchRun* r, uint64_t cap, GuideCols* cols, GuideCols* table) {
+  hawk_hapset* hs = r->hs;
+  int rc;
+  if ((rc = hawk_reserve_cols(hs->colsA, r->by_cluster ? r->stage_cap : cap, cols))) return rc;
+  *table = *cols;
+  if (!r->by_cluster) return HAWK_OK;
+  if ((rc = hs->rowsA.reserve(cap * 64))) return rc;  // colsA then stages REF's rows only
+  memset(table, 0, sizeof(*table));
+  table->rows = hs->rowsA.as<uint4>(); table->cap = cap; table->startp = r->ri.startp;
+  return HAWK_OK;
+}
+// The emit side, between its two events (`launch` false: a table of no rows).  Plane kernels (all rows of a set with planes; REF's
+// rows of a view) and the per-word search of a view write columns; the cluster search writes packed rows (k_cs_emit_rows), and REF's
+// rows - staged as columns - are packed in front of them.  The kernels take their offsets from HBM and refuse to write past the capacity.
+static int search_emit(SearchRun* r, const GuideCols& cols, const GuideCols& packed, bool launch) {
+  hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
+  SearchStatusBlock* blk = r->blk; const uint64_t* offsets = hs->offsets.as<uint64_t>();
+  HIPCHK(hipEventRecord(ev[EV_EMIT_BEGIN], st));
+  if (launch) {
+    hawk_launch_search(st, 1, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), r->shards, offsets, cols, &blk->status, hs->lists.as<uint32_t>(),
+                       &blk->big_count, hs->big.as<unsigned long long>(), ev[EV_LIST_EMIT_END], r->plane_tiles);
+    if (r->vx) (void)hipEventRecord(ev[EV_VIEW_EMIT_BEGIN], st);
+    if (r->by_cluster) {
+      hawk_launch_rows_pack(st, cols, offsets + r->plane_tiles, 0, std::min<uint64_t>(r->stage_cap, packed.cap), packed.rows, packed.startp, &blk->status);
+      (void)hipEventRecord(ev[EV_REF_ROWS_PACKED], st);
+      hawk_launch_cs_emit_rows(st, r->cd, hs->cs_icnt.as<uint32_t>(), hs->cs_itb.as<uint32_t>(), hs->cs_trows.p, offsets + r->plane_tiles, &blk->template_rows,
+                               r->tcap, packed.rows, packed.cap, &blk->status);
+    } else if (r->vx) {
+      hawk_launch_vsearch(st, 1, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), hs->vcnt0.as<uint32_t>(), r->shards, offsets, cols,
+                          &blk->status, r->plane_tiles, r->v_tiles);
+    }
+  }
+  HIPCHK(hipEventRecord(ev[EV_EMIT_END], st));
+  HIPCHK(hipGetLastError());
+  return HAWK_OK;
+}
+// The status block after the count side (and a speculative emit): totals, status, and the template rows a cluster search used.
+// If those outgrew their reservation the rerun reserves what this search asked for (+ 1/8), at most the plan's bound.
+static int search_read_block(SearchRun* r) {
+  HIPCHK(hipMemcpyAsync(r->h, r->blk, sizeof(SearchStatusBlock), hipMemcpyDeviceToHost, r->st));
+  HIPCHK(hipStreamSynchronize(r->st));
+  if (!r->by_cluster) return HAWK_OK;
+  const uint64_t tcu = r->h->template_rows;
+  if (tcu > r->tcap) { r->hs->cs_tcap = std::min<uint64_t>(r->vx->cl.slots, tcu + tcu / 8 + 64); return HAWK_RETRY_TEMPLATES; }
+  r->t_rows_used = tcu;
+  return HAWK_OK;
+}
+
+static void search_timing(const SearchRun* r, uint64_t nrows, hawk_timing* timing) {
+  const hawk_hapset* hs = r->hs; hipEvent_t* ev = r->ctx->ev;
+  memset(timing, 0, sizeof(*timing));
+  (void)hipEventElapsedTime(&timing->count_ms, ev[EV_BEGIN], ev[EV_COUNT_DONE]);
+  (void)hipEventElapsedTime(&timing->offsets_ms, ev[EV_COUNT_DONE], ev[EV_OFFSETS_DONE]);
+  (void)hipEventElapsedTime(&timing->emit_ms, ev[EV_EMIT_BEGIN], ev[EV_EMIT_END]);
+  if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, ev[EV_EMIT_BEGIN], ev[EV_LIST_EMIT_END]);
+  (void)hipEventElapsedTime(&timing->total_ms, ev[EV_BEGIN], ev[EV_EMIT_END]);
+  if (r->vx) {
+    (void)hipEventElapsedTime(&timing->v_count_ms, ev[EV_VIEW_COUNT_BEGIN], ev[EV_COUNT_DONE]);
+    if (nrows) (void)hipEventElapsedTime(&timing->v_emit_ms, ev[EV_VIEW_EMIT_BEGIN], ev[EV_EMIT_END]);
+    timing->v_path = r->by_cluster ? 2u : 1u;
+    if (r->by_cluster) (void)hipEventElapsedTime(&timing->v_templates_ms, ev[EV_VIEW_COUNT_BEGIN], ev[EV_TEMPLATES_DONE]);
+    if (r->by_cluster && nrows) (void)hipEventElapsedTime(&timing->v_emit_rows_ms, ev[EV_REF_ROWS_PACKED], ev[EV_EMIT_END]);
+  }
+  uint64_t pos = 0;
+  for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
+  timing->scanned_positions = pos;
+}
+
+static int search_make_table(const SearchRun* r, const hawk_search_params* p, const GuideCols& tc, hawk_table** out) {
+  hawk_table* t = new (std::nothrow) hawk_table();
+  if (!t) return HAWK_E_INVALID;
+  const ScanTotals& tot = r->h->totals;
+  t->hs = r->hs; t->ctx = r->ctx; t->gen = r->hs->cols_gen;
+  t->n_rows = tot.n_keep; t->n_cand = tot.n_cand; t->n_hits = tot.n_hits; t->cols = tc; t->cap = tc.cap;
+  t->guidelen = p->guidelen; t->pamlen = p->pamlen; t->right = p->right ? 1 : 0; t->n_groups = 0; t->collapsed = false;
+  t->by_cluster = r->by_cluster; t->plane_tiles = r->plane_tiles; t->t_rows = r->by_cluster ? r->t_rows_used : 0;
+  *out = t;
+  return HAWK_OK;
+}
+
+// One attempt: the count side, then the table.  Its recovery rule, in one place:
+//  * a table an earlier search on this set reserved takes a SPECULATIVE emit straight behind the offset scan, instead of waiting for
+//    the row count to cross PCIe.  The status block then decides: template rows beyond their reservation - no table,
+//    HAWK_RETRY_TEMPLATES (hawk_search reruns the attempt with more reserved); the rows fit the speculative emit - finished; else
+//    reserve for the rows and emit (again);
+//  * only the capacity refusal of a speculative emit is answered by emitting again.  Any other status was raised by the count side
+//    (a strict-mode CFD error, an unsupported coordinate range) and stands - the kernels keep the FIRST status they raise.
+static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_table** out, hawk_timing* timing) {
+  if (!out) return HAWK_E_INVALID;
+  SearchRun r;
+  int rc;
+  if ((rc = search_classify(hs, p, &r)) || (rc = search_reserve(&r, p)) || (rc = search_upload_cfd(&r, p))) return rc;
+  HIPCHK(hipMemsetAsync(r.hs->misc.p, 0, sizeof(SearchMisc), r.st));
+  if ((rc = search_ref(&r, p)) || (rc = search_view_args(&r)) || (rc = search_count(&r))) return rc;
+  uint64_t& table_cap = *r.table_cap;
+  const bool speculative = table_cap != 0;
+  GuideCols cols, table;
+  if (speculative && ((rc = search_reserve_table(&r, table_cap, &cols, &table)) || (rc = search_emit(&r, cols, table, true)))) return rc;
+  if ((rc = search_read_block(&r))) return rc;
+  const uint64_t nrows = r.h->totals.n_keep;
+  if (!speculative || nrows > table_cap) {
+    const int status = r.h->status;
+    if (status && !(speculative && status == HAWK_E_CAPACITY)) return status;
+    if (speculative) HIPCHK(hipMemsetAsync(&r.blk->status, 0, sizeof(int), r.st));
+    if ((rc = search_reserve_table(&r, std::max<uint64_t>(std::max<uint64_t>(nrows, 1), table_cap), &cols, &table))) return rc;
+    table_cap = table.cap;
+    if ((rc = search_emit(&r, cols, table, nrows != 0))) return rc;
+    HIPCHK(hipMemcpyAsync(&r.h->status, &r.blk->status, sizeof(int), hipMemcpyDeviceToHost, r.st));
+    HIPCHK(hipStreamSynchronize(r.st));
+  }
+  if (timing) search_timing(&r, nrows, timing);
+  if (r.h->status) return r.h->status;
+  return search_make_table(&r, p, table, out);
+}
+
+extern "C" {
+
 int hawk_search(hawk_hapset* hs, const hawk_search_params* p, hawk_table** out, hawk_timing* timing) {
   int rc = hawk_search_once(hs, p, out, timing);
   if (rc == HAWK_RETRY_TEMPLATES) rc = hawk_search_once(hs, p, out, timing);  // now reserved for the bound: cannot recur
   return rc == HAWK_RETRY_TEMPLATES ? HAWK_E_CAPACITY : rc;
-}
-static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_table** out, hawk_timing* timing) {
-  if (!hs || !p || !out || !hs->has_meta) return HAWK_E_INVALID;
-  if (p->score_cfdon > 2) return HAWK_E_INVALID;
-  if (p->score_cfdon && (p->right || !p->cfd_mm || !p->cfd_pam || p->pamlen < 2)) return HAWK_E_INVALID;
-  hawk_ctx* ctx = hs->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  ScanParams sp;
-  int rc = make_scan_params(hs, p->pam_fwd, p->pam_rev, p->pamlen, p->guidelen, p->right, true, &sp);
-  if (rc) return rc;
-  const HapSetDev d = make_dev(hs);
-  ++hs->cols_gen;  // the columns are about to be rewritten: earlier tables of this set become stale
-  const uint64_t ntile = (uint64_t)hs->n_hap * sp.bph;
-  // A view of a plan whose cluster dictionary is usable is searched per distinct cluster (hawk_csearch.hip): the scan then runs
-  // over REF's tiles + one count per cluster instance.  HAWK_VIEW_SEARCH=words keeps the per-word search (hawk_vsearch.hip).
-  bool by_cluster = hs->vplan && hs->vplan->cl.built && hs->vplan->cl.usable && hs->ref_index == 0;
-  if (by_cluster) { const char* e = getenv("HAWK_VIEW_SEARCH"); if (e && e[0] == 'w') by_cluster = false; }
-  // what the offset scan runs over: the plane kernels' tiles, then - for a cluster search - one entry per 64 consecutive cluster
-  // instances (a wave of the count / emit kernels: its rows are one contiguous stretch of the table), else the view's tiles
-  const uint64_t nscan = by_cluster ? (uint64_t)sp.bph + ((uint64_t)hs->vplan->cl.n_inst + 63) / 64 : ntile;
-  if ((rc = hs->counts.reserve(nscan * 4)) || (rc = hs->offsets.reserve((nscan + 1) * 8)) ||
-      (rc = hs->misc.reserve(512 * 8 + 64)) ||
-      (rc = hs->cfd.reserve(336 * 8)) || (rc = hs->partial.reserve((nscan / 1024 + 2) * 8)))
-    return rc;
-  // A view of an expansion plan (hawk_xplan_view) holds no planes: its REF row runs through the plane kernels below on the
-  // plan's REF planes (hand-over lists included), every other row through hawk_vsearch.hip or hawk_csearch.hip.
-  const hawk_xplan* vx = hs->vplan;
-  const uint32_t plane_tiles = vx ? sp.bph * (hs->ref_index == 0 ? 1u : 0u) : (uint32_t)ntile;  // tiles the plane kernels take
-  if (vx && (hs->ref_index != 0 || hs->n_ref_rows != 1)) return HAWK_E_INVALID;                 // a plan's rows: REF first, once
-  // hand-over lists (2 KB per tile): the count pass leaves each small tile's valid survivors for the emit pass.
-  // A REF tile takes one work-list entry per 512 survivors (<= 128 per tile), any other big tile one.
-  const uint64_t n_ref_tiles = (uint64_t)sp.bph * hs->n_ref_rows;
-  if ((rc = hs->lists.reserve((size_t)plane_tiles * HAWK_LIST_CAP * 4 + 16)) || (rc = hs->big.reserve(((size_t)plane_tiles + 128 * n_ref_tiles) * 8 + 16))) return rc;
-  uint32_t* const d_lists = hs->lists.as<uint32_t>();
-  unsigned long long* const d_big = hs->big.as<unsigned long long>();
-  if (p->score_cfdon) {  // the tables go up once; later searches with the same tables find them in HBM
-    if (hs->cfd_host.size() != 336 || memcmp(hs->cfd_host.data(), p->cfd_mm, 320 * 8) != 0 ||
-        memcmp(hs->cfd_host.data() + 320, p->cfd_pam, 16 * 8) != 0) {
-      hs->cfd_host.assign(336, 0.0);
-      memcpy(hs->cfd_host.data(), p->cfd_mm, 320 * 8);
-      memcpy(hs->cfd_host.data() + 320, p->cfd_pam, 16 * 8);
-      HIPCHK(hipMemcpyAsync(hs->cfd.p, hs->cfd_host.data(), 336 * 8, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-  }
-  HIPCHK(hipMemsetAsync(hs->misc.p, 0, 512 * 8 + 64, ctx->stream));
-  unsigned long long* d_shards = hs->misc.as<unsigned long long>();          // [256][2] candidate / hit partial sums
-  int* d_status = reinterpret_cast<int*>(hs->misc.as<char>() + 512 * 8);
-  uint32_t* d_big_count = reinterpret_cast<uint32_t*>(hs->misc.as<char>() + 512 * 8 + 16);  // zeroed with misc
-  unsigned long long* d_tcount = reinterpret_cast<unsigned long long*>(hs->misc.as<char>() + 512 * 8 + 8);  // template rows handed out (hawk_csearch.hip)
-  // status (4 B) | work-list count | totals share one 64-byte block: a single copy into page-locked memory per search
-  static_assert(sizeof(ScanTotals) == 32, "status block layout");
-  ScanTotals* d_totals = reinterpret_cast<ScanTotals*>(hs->misc.as<char>() + 512 * 8 + 32);
-  const char* d_block = hs->misc.as<char>() + 512 * 8;
-  char* h_block = static_cast<char*>(ctx->pinned);
-  GuideParams gp;
-  gp.pamlen = sp.pamlen; gp.guidelen = sp.guidelen; gp.right = sp.right; gp.L = sp.L;
-  gp.score_cfdon = (int32_t)p->score_cfdon;  // 1: a non-ACGT base under a lookup is HAWK_E_CFD; 2: it scores NaN ("NA")
-  gp.cfd_mm = hs->cfd.as<double>(); gp.cfd_pam = hs->cfd.as<double>() + 320; gp.bph = sp.bph;
-  RefInfo ri;
-  ri.index = hs->ref_index; ri.startp = hs->ref_startp;
-  for (int s = 0; s < 2; ++s) {
-    ri.lo[s] = 0; ri.hi[s] = 0;
-    if (hs->ref_index >= 0) {  // same arithmetic as the kernel's phase A, for the REF haplotype
-      const bool pamfirst = (sp.right != 0) != (s != 0);
-      const int po = pamfirst ? 0 : sp.guidelen;
-      const int haplen = (int)hs->hap_len[hs->ref_index];
-      // where REF has guides a haplotype row can be grouped with: REF's own scan range, or - for a tile of a larger
-      // region - the region's scan range as far as this tile's REF string reaches (hawk_hapset_set_ref_partner_range)
-      const int rs = hs->has_partner ? hs->partner_start : hs->scan_start[hs->ref_index];
-      const int re = hs->has_partner ? hs->partner_stop : hs->scan_stop[hs->ref_index];
-      ri.lo[s] = std::max(rs - po, HAWK_PAD);
-      ri.hi[s] = std::min(re - po, haplen - sp.L - HAWK_PAD + 1);
-    }
-  }
-  ri.bits[0] = ri.bits[1] = nullptr;
-  ri.n_bits = 0;
-  if (hs->ref_index >= 0) {
-    // REF's candidate windows as bitmaps (k_ref_bits): rebuilt only when the PAM / guide geometry or REF's range changed
-    const uint64_t key[6] = {p->pam_fwd, p->pam_rev, ((uint64_t)p->pamlen << 32) | p->guidelen, (uint64_t)(p->right ? 1 : 0),
-                             ((uint64_t)(uint32_t)ri.lo[0] << 32) | (uint32_t)ri.hi[0], ((uint64_t)(uint32_t)ri.lo[1] << 32) | (uint32_t)ri.hi[1]};
-    if ((rc = hs->refbits.reserve((size_t)hs->S * 4 * 2))) return rc;
-    ri.bits[0] = hs->refbits.as<uint32_t>();
-    ri.bits[1] = hs->refbits.as<uint32_t>() + hs->S;
-    ri.n_bits = hs->S * 32u;
-    if (vx && ((rc = hs->refhp.reserve(((size_t)hs->S + 1) * 8 * 2)) || (rc = hs->vcnt0.reserve(by_cluster ? 16 : ntile * 4)))) return rc;
-    if (!hs->refbits_valid || memcmp(hs->refbits_key, key, sizeof(key)) != 0) {
-      hawk_launch_ref_bits(ctx->stream, d, sp, ri, hs->refbits.as<uint32_t>(), hs->refbits.as<uint32_t>() + hs->S);
-      // REF's PAM hits + prefix counts: what the clean stretches of a plan's rows are counted from
-      if (vx) hawk_launch_ref_hits(ctx->stream, d, sp, hs->ref_index, hs->refhp.p);
-      HIPCHK(hipGetLastError());
-      memcpy(hs->refbits_key, key, sizeof(key));
-      hs->refbits_valid = true;
-    }
-  }
-  VcArgs va;
-  memset(&va, 0, sizeof(va));
-  if (vx) {
-    for (int pl = 0; pl < 4; ++pl) va.ref[pl] = vx->ref5[pl].as<uint32_t>();
-    va.ref_S = hs->S;
-    va.recs_ = vx->recs.p; va.alt_codes = vx->codes.as<uint8_t>(); va.hv_off = vx->off.as<uint64_t>(); va.tiles_ = vx->tiles.p;
-    va.hp = hs->refhp.as<uint4>();
-  }
-  const uint32_t v_tiles = vx ? (uint32_t)ntile - plane_tiles : 0u;
-  ClDict cd;
-  memset(&cd, 0, sizeof(cd));
-  uint64_t tcap = 0, t_rows_used = 0;
-  if (by_cluster) {
-    const auto& cl = vx->cl;
-    cd.n_inst = cl.n_inst; cd.n_uniq = cl.n_uniq;
-    cd.inst_uid = cl.inst_uid.as<uint32_t>(); cd.inst_o = cl.inst_o.as<int32_t>(); cd.inst_row = cl.inst_row.as<uint32_t>();
-    cd.inst_pa = cl.inst_pa.as<int32_t>(); cd.inst_rb = cl.inst_rb.as<int32_t>();
-    cd.u_rec = cl.u_rec.as<uint32_t>(); cd.u_n = cl.u_n.as<uint32_t>(); cd.u_row = cl.u_row.as<uint32_t>(); cd.u_o = cl.u_o.as<int32_t>();
-    cd.u_seg = cl.u_seg.as<uint32_t>();
-    // template rows: packed as the search produces them.  Their number is bounded by the window starts of the distinct clusters
-    // (cl.slots: 2 strands x every start), but a PAM keeps a few per cent of those: reserve 16 rows per distinct cluster, and
-    // if a search needs more it produces no table (k_cs_count sees the counter), says so and is rerun with the bound reserved
-    const char* e0 = getenv("HAWK_CLUSTER_ROWS0");  // tests: a first reservation small enough to overflow
-    const uint64_t first = e0 ? strtoull(e0, nullptr, 10) : 16ull * cl.n_uniq + 65536;
-    tcap = std::max<uint64_t>(std::min<uint64_t>(cl.slots, std::max<uint64_t>(hs->cs_tcap, first)), 1);
-    // (cs_res, 32 bytes per distinct cluster: {rows per strand, hits, candidates} {first template row, REF's hits before / behind it})
-    if ((rc = hs->cs_res.reserve((size_t)std::max<uint32_t>(cl.n_uniq, 1) * 32)) || (rc = hs->cs_tbase.reserve((size_t)std::max<uint32_t>(cl.n_uniq, 1) * 4)) ||
-        (rc = hs->cs_trows.reserve((size_t)tcap * hawk_cs_row_bytes())) || (rc = hs->cs_itb.reserve((size_t)std::max<uint32_t>(cl.n_inst, 1) * 4)) ||
-        (rc = hs->cs_icnt.reserve((size_t)std::max<uint32_t>(cl.n_inst, 1) * 4)))
-      return rc;
-  }
-  // the view's share of the two passes: per dirty word of every row, or per distinct cluster + a copy per instance
-  uint32_t* const d_counts_v = hs->counts.as<uint32_t>() + plane_tiles;
-  auto view_count = [&]() {
-    if (by_cluster) {
-      hawk_launch_cs_templates(ctx->stream, d, va, cd, sp, gp, ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, d_tcount, tcap, d_status);
-      (void)hipEventRecord(ctx->ev[8], ctx->stream);
-      hawk_launch_cs_count(ctx->stream, d, va, cd, sp, hs->cs_res.p, d_tcount, tcap, d_counts_v, hs->cs_icnt.as<uint32_t>(),
-                           hs->cs_itb.as<uint32_t>(), d_shards);
-    } else {
-      hawk_launch_vsearch(ctx->stream, 0, d, va, sp, gp, ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), hs->vcnt0.as<uint32_t>(), d_shards, nullptr,
-                          GuideCols{}, d_status, plane_tiles, v_tiles);
-    }
-  };
-  // the emit side.  Plane kernels (all rows of a set with planes; REF's rows of a view) and the per-word search of a view write
-  // columns; the cluster search writes packed rows (k_cs_emit_rows), and REF's rows - staged as columns - are packed in front of them
-  const uint64_t stage_cap = by_cluster ? 2ull * hs->hap_len[hs->ref_index] + 64 : 0;  // REF keeps at most every window start of both strands
-  auto emit_all = [&](const GuideCols& cols, const GuideCols& packed) {
-    hawk_launch_search(ctx->stream, 1, d, sp, gp, ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), d_shards,
-                       hs->offsets.as<uint64_t>(), cols, d_status, d_lists, d_big_count, d_big, ctx->ev[5], plane_tiles);
-    if (!vx) return;
-    (void)hipEventRecord(ctx->ev[7], ctx->stream);
-    if (by_cluster) {
-      hawk_launch_rows_pack(ctx->stream, cols, hs->offsets.as<uint64_t>() + plane_tiles, 0, std::min<uint64_t>(stage_cap, packed.cap), packed.rows,
-                            packed.startp, d_status);
-      (void)hipEventRecord(ctx->ev[9], ctx->stream);
-      hawk_launch_cs_emit_rows(ctx->stream, cd, hs->cs_icnt.as<uint32_t>(), hs->cs_itb.as<uint32_t>(), hs->cs_trows.p, hs->offsets.as<uint64_t>() + plane_tiles,
-                               d_tcount, tcap, packed.rows, packed.cap, d_status);
-    } else {
-      hawk_launch_vsearch(ctx->stream, 1, d, va, sp, gp, ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), hs->vcnt0.as<uint32_t>(), d_shards,
-                          hs->offsets.as<uint64_t>(), cols, d_status, plane_tiles, v_tiles);
-    }
-  };
-  // reserve for `cap` rows: `cols` is what the column emitters write, `table` what the finished table is
-  auto reserve_table = [&](uint64_t cap, GuideCols* cols, GuideCols* table) -> int {
-    int r;
-    if (!by_cluster) {
-      if ((r = hawk_reserve_cols(hs->colsA, cap, cols))) return r;
-      *table = *cols;
-      return HAWK_OK;
-    }
-    if ((r = hawk_reserve_cols(hs->colsA, stage_cap, cols)) || (r = hs->rowsA.reserve(cap * 64))) return r;
-    memset(table, 0, sizeof(*table));
-    table->rows = hs->rowsA.as<uint4>(); table->cap = cap; table->startp = ri.startp;
-    return HAWK_OK;
-  };
-  uint64_t& table_cap = by_cluster ? hs->rows_cap : hs->cols_cap;
-  GuideCols none = {};
-  hipEvent_t* ev = ctx->ev;
-  HIPCHK(hipEventRecord(ev[0], ctx->stream));
-  hawk_launch_search(ctx->stream, 0, d, sp, gp, ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), d_shards, nullptr, none, d_status, d_lists, d_big_count, d_big,
-                     nullptr, plane_tiles);
-  if (vx) HIPCHK(hipEventRecord(ev[6], ctx->stream));
-  if (vx) view_count();
-  HIPCHK(hipEventRecord(ev[1], ctx->stream));
-  hawk_launch_mscan(ctx->stream, hs->counts.as<uint32_t>(), nscan, hs->partial.as<unsigned long long>(), d_shards,
-                    hs->offsets.as<uint64_t>(), d_totals);
-  HIPCHK(hipEventRecord(ev[2], ctx->stream));
-  HIPCHK(hipGetLastError());
-  ScanTotals tot;
-  GuideCols ca, tc;
-  int status = 0;
-  uint64_t nrows = 0;
-  bool emitted = false;
-  // the status block after the count side (and a speculative emit): totals, status, and the template rows a cluster search
-  // used.  If those outgrew their reservation the rerun reserves what this search asked for (+ 1/8), at most the plan's bound
-  auto read_block = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(h_block, d_block, 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    memcpy(&tot, h_block + 32, sizeof(tot));
-    memcpy(&status, h_block, 4);
-    if (!by_cluster) return HAWK_OK;
-    uint64_t tcu;
-    memcpy(&tcu, h_block + 8, 8);
-    if (tcu > tcap) { hs->cs_tcap = std::min<uint64_t>(vx->cl.slots, tcu + tcu / 8 + 64); return HAWK_RETRY_TEMPLATES; }
-    t_rows_used = tcu;
-    return HAWK_OK;
-  };
-  if (table_cap) {
-    // The table of an earlier search on this set is still reserved: launch the emit pass straight behind the offset
-    // scan instead of waiting for the row count to cross PCIe (the kernels take their offsets from HBM and refuse to
-    // write past the capacity).  If the table turns out larger, the normal path below runs after a reserve.
-    if ((rc = reserve_table(table_cap, &ca, &tc))) return rc;
-    HIPCHK(hipEventRecord(ev[3], ctx->stream));
-    emit_all(ca, tc);
-    HIPCHK(hipEventRecord(ev[4], ctx->stream));
-    HIPCHK(hipGetLastError());
-    if ((rc = read_block())) return rc;
-    nrows = tot.n_keep;
-    emitted = nrows <= table_cap;
-    if (!emitted) {
-      // only the capacity refusal of the emit pass is answered by emitting again; any other status was raised by the count side
-      // (a strict-mode CFD error, an unsupported coordinate range) and stands - the kernels keep the FIRST status they raise
-      if (status && status != HAWK_E_CAPACITY) return status;
-      status = 0;
-      HIPCHK(hipMemsetAsync(d_status, 0, 4, ctx->stream));
-    }
-  } else {
-    if ((rc = read_block())) return rc;
-    if (status) return status;
-    nrows = tot.n_keep;
-  }
-  if (!emitted) {
-    if ((rc = reserve_table(std::max<uint64_t>(std::max<uint64_t>(nrows, 1), table_cap), &ca, &tc))) return rc;
-    table_cap = tc.cap;
-    HIPCHK(hipEventRecord(ev[3], ctx->stream));
-    if (nrows) emit_all(ca, tc);
-    HIPCHK(hipEventRecord(ev[4], ctx->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_block, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    memcpy(&status, h_block, 4);
-  }
-  if (timing) {
-    memset(timing, 0, sizeof(*timing));
-    (void)hipEventElapsedTime(&timing->count_ms, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&timing->offsets_ms, ev[1], ev[2]);
-    (void)hipEventElapsedTime(&timing->emit_ms, ev[3], ev[4]);
-    if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, ev[3], ev[5]);
-    (void)hipEventElapsedTime(&timing->total_ms, ev[0], ev[4]);
-    if (vx) {
-      (void)hipEventElapsedTime(&timing->v_count_ms, ev[6], ev[1]);
-      if (nrows) (void)hipEventElapsedTime(&timing->v_emit_ms, ev[7], ev[4]);
-      timing->v_path = by_cluster ? 2u : 1u;
-      if (by_cluster) (void)hipEventElapsedTime(&timing->v_templates_ms, ev[6], ev[8]);
-      if (by_cluster && nrows) (void)hipEventElapsedTime(&timing->v_emit_rows_ms, ev[9], ev[4]);
-    }
-    uint64_t pos = 0;
-    for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
-    timing->scanned_positions = pos;
-  }
-  if (status) return status;
-  hawk_table* t = new (std::nothrow) hawk_table();
-  if (!t) return HAWK_E_INVALID;
-  t->hs = hs; t->ctx = ctx; t->gen = hs->cols_gen;
-  t->n_rows = nrows; t->n_cand = tot.n_cand; t->n_hits = tot.n_hits; t->cols = tc; t->cap = tc.cap;
-  t->guidelen = p->guidelen; t->pamlen = p->pamlen; t->right = p->right ? 1 : 0; t->n_groups = 0; t->collapsed = false;
-  t->by_cluster = by_cluster; t->plane_tiles = plane_tiles; t->t_rows = by_cluster ? t_rows_used : 0;
-  *out = t;
-  return HAWK_OK;
 }
 
 void hawk_table_destroy(hawk_table* t) {  // columns live in the hapset's workspace, or in own[] for a merged table

@@ -14,6 +14,9 @@
 
 #include "hawk_host.h"
 
+// The slots of hawk_ctx::ev this file records: the kernels a call times for its caller (kernel_ms), and the dictionary build (build_ms).
+enum XplanEvent { EV_KERNELS_BEGIN = 0, EV_KERNELS_END = 1, EV_BUILD_BEGIN = 8, EV_BUILD_END = 9 };
+
 extern "C" {
 
 // ---------------------------------------------------------------------------- f1 haplotype expansion
@@ -160,12 +163,12 @@ int hawk_xplan_run(hawk_xplan* x, hawk_hapset** out, uint64_t* hash_out, float* 
   if (hs->S != x->S) { hawk_hapset_destroy(hs); return HAWK_E_INVALID; }
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemsetAsync(x->hash.p, 0, (size_t)x->n_hap * 16, st);
-  if (e == hipSuccess) e = hipEventRecord(ctx->ev[0], st);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[EV_KERNELS_BEGIN], st);
   if (e == hipSuccess) {
     hawk_launch_hx_build(st, x->ref_plane, x->ref_S, x->recs.p, x->codes.as<uint8_t>(), x->off.as<uint64_t>(), hs->d_hap_len, x->n_hap,
                          hs->S, hs->plane, x->tiles.p);
     if (hash_out) hawk_launch_hx_hash(st, hs->plane, x->n_hap, hs->S, x->hash.as<unsigned long long>());
-    e = hipEventRecord(ctx->ev[1], st);
+    e = hipEventRecord(ctx->ev[EV_KERNELS_END], st);
   }
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess && hash_out) e = hipMemcpyAsync(hash_out, x->hash.p, (size_t)x->n_hap * 16, hipMemcpyDeviceToHost, st);
@@ -179,7 +182,7 @@ int hawk_xplan_run(hawk_xplan* x, hawk_hapset** out, uint64_t* hash_out, float* 
     hawk_hapset_destroy(hs);
     return HAWK_E_HIP;
   }
-  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]);
+  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[EV_KERNELS_BEGIN], ctx->ev[EV_KERNELS_END]);
   *out = hs;
   return HAWK_OK;
 }
@@ -247,7 +250,7 @@ static int xplan_build_dict(hawk_xplan* x) {
   int32_t* const t_o = cl.inst_o.as<int32_t>();
   int32_t* const t_pa = cl.inst_pa.as<int32_t>();
   int32_t* const t_rb = cl.inst_rb.as<int32_t>();
-  HIPCHK(hipEventRecord(ctx->ev[8], st));
+  HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_BEGIN], st));
   HIPCHK(hipMemsetAsync(d_zero, 0, z_end, st));
   // chunks per row -> their offsets and rows, then the instances every chunk opens and how many of them go on the list of the
   // clusters that are more than their variant (the number of chunks is only known on the device - rows that scan nothing have
@@ -285,7 +288,7 @@ static int xplan_build_dict(hawk_xplan* x) {
                           t_uid, t_row, x->m_seg_off.as<uint32_t>(), x->m_seg_rel.as<uint32_t>(), cl.u_rec.as<uint32_t>(), cl.u_n.as<uint32_t>(),
                           cl.u_row.as<uint32_t>(), cl.u_o.as<int32_t>(), cl.u_seg.as<uint32_t>(), d_span2, d_status);
     HIPCHK(hipMemcpyAsync(res, d_results, 64, hipMemcpyDeviceToHost, st));  // {instances, the table's clusters, the variants that are clusters, template rows, status}
-    HIPCHK(hipEventRecord(ctx->ev[9], st));
+    HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_END], st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     n_inst = (uint32_t)res[0]; status = (uint32_t)res[4];
@@ -302,7 +305,7 @@ static int xplan_build_dict(hawk_xplan* x) {
   if (n_inst == 0) { cl.status = 4; return HAWK_OK; }
   if (n_inst > inst_bound) { snprintf(hawk_hip_err_buf(), 256, "hawk_xplan_view: instance count beyond its bound"); return HAWK_E_HIP; }
   cl.n_inst = n_inst; cl.n_uniq = n_uniq; cl.n_real = n_real; cl.last_uniq = (uint32_t)res[1];
-  (void)hipEventElapsedTime(&cl.build_ms, ctx->ev[8], ctx->ev[9]);
+  (void)hipEventElapsedTime(&cl.build_ms, ctx->ev[EV_BUILD_BEGIN], ctx->ev[EV_BUILD_END]);
   cl.slots = n_uniq ? res[3] : 0;
   cl.status = status;
   // worth it when clusters are shared (the template rows are extra traffic otherwise) and the templates fit a sane budget
@@ -486,14 +489,14 @@ int hawk_xplan_text(hawk_xplan* x, uint32_t n_rows, const uint32_t* rows, const 
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemcpyAsync(d_rows, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_off, rel.data(), (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  HIPCHK(hipEventRecord(ctx->ev[EV_KERNELS_BEGIN], st));
   hawk_launch_hx_text(st, x->ref_plane, x->ref_S, x->recs.p, x->codes.as<uint8_t>(), x->off.as<uint64_t>(), x->hlen.as<uint32_t>(), x->S,
                       x->tiles.p, n_rows, d_rows, d_off, d_text);
-  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  HIPCHK(hipEventRecord(ctx->ev[EV_KERNELS_END], st));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out + out_off[0], d_text + phase, (size_t)total, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));  // `rel` and the temporaries live until here
-  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]);
+  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[EV_KERNELS_BEGIN], ctx->ev[EV_KERNELS_END]);
   return HAWK_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <memory>
 #include <vector>
@@ -25,9 +26,30 @@ char* hawk_hip_err_buf();  // thread-local text of the last HIP failure (hawk_la
 struct hawk_ctx {
   int device;
   hipStream_t stream;
+  // Scratch of the call that is running: every C-ABI call records the events it times with and reads them before it returns.
+  // No call may read an event another call recorded (two calls use the same slots for different intervals).
   hipEvent_t ev[10];
-  void* pinned = nullptr;  // 256 B of page-locked host memory: the per-search totals + status come back in one copy
+  void* pinned = nullptr;  // 256 B of page-locked host memory: hawk_search reads the device's SearchStatusBlock back into it
 };
+
+// What hs->misc holds while hawk_search runs.  The host and the kernels' launchers share the status block; the host reads it back
+// whole (64 bytes, one copy into hawk_ctx::pinned).  The offsets are what the device side has always been handed.
+struct SearchStatusBlock {
+  int status;                        // the FIRST status a kernel raised (0: none)
+  int pad0;
+  unsigned long long template_rows;  // template rows a cluster search handed out (hawk_csearch.hip)
+  uint32_t big_count;                // entries of the emit pass's work list
+  uint32_t pad1[3];
+  ScanTotals totals;
+};
+struct SearchMisc {
+  unsigned long long shards[256][2];  // candidate / hit partial sums
+  SearchStatusBlock blk;
+};
+static_assert(sizeof(SearchStatusBlock) == 64 && sizeof(SearchMisc) == 4096 + 64, "status block layout");
+static_assert(offsetof(SearchMisc, shards) == 0 && offsetof(SearchMisc, blk) == 4096, "status block layout");
+static_assert(offsetof(SearchStatusBlock, status) == 0 && offsetof(SearchStatusBlock, template_rows) == 8 &&
+              offsetof(SearchStatusBlock, big_count) == 16 && offsetof(SearchStatusBlock, totals) == 32, "status block layout");
 
 // Caching device allocator, one per device: a freed block goes to a free list and is handed to the next request of a
 // similar size, so a per-tile loop (expand -> search -> collapse, tile after tile) allocates its planes, columns and
@@ -120,7 +142,7 @@ struct hawk_hapset {
   DevBuf refhp;               // REF's PAM hits + prefix counts per strand (k_ref_hits), keyed like refbits
   uint64_t cs_tcap = 0;       // template rows a search of this view may need (raised to the plan's bound after an overflow)
   DevBuf cs_res, cs_tbase, cs_trows, cs_itb, cs_icnt;  // per distinct cluster 32 B {rows per strand, hits, candidates} {first template row, REF hits before / behind}, first template row; template rows; per instance its first template row
-  DevBuf cmini[8], cm_gid;   // hawk_table_collapse of such a table: REF's rows + the template rows as a table of their own, their groups  // the cluster search of a view: per distinct cluster {rows per strand, hits, candidates}, first template row; template rows
+  DevBuf cmini[8], cm_gid;   // hawk_table_collapse of such a table: REF's rows + the template rows as a table of their own, their groups
   DevBuf colsA[8];
   DevBuf rowsA;               // packed rows of a cluster-searched table (colsA then stages REF's rows only)
   uint64_t rows_cap = 0;

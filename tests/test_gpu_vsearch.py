@@ -95,7 +95,8 @@ def _same_table(reg, pam_s, guidelen, right, cfd=True, na_on_ambiguous=False, or
         assert np.array_equal(ca[k], cc[k]), k
     assert np.array_equal(ca["win"], cc["win"])
     assert np.array_equal(ca["cfdon"], cc["cfdon"], equal_nan=True)
-    # a second search on the view (cached REF bitmaps, reserved columns) and a different geometry after it
+    # a second search on the view with the same geometry: cached REF bitmaps, and the table the first one reserved takes the emit
+    # before the row count is known (another geometry behind it: test_search_emits_again_...)
     b2 = view.search(bits, bitsrc, len(pam_s), guidelen, right, mm, pt, cfd_na_on_ambiguous=na_on_ambiguous)
     assert b2.n_rows == a.n_rows and np.array_equal(b2.start, c.start) and np.array_equal(b2.win, c.win)
     with pytest.raises(_lib.HawkStatusError):
@@ -206,6 +207,108 @@ def test_cluster_search_reruns_when_the_template_rows_outgrow_their_reservation(
     monkeypatch.setenv("HAWK_CLUSTER_ROWS0", "64")
     a = _same_table(reg, "NGN", 20, False)
     assert a.n_rows > 64
+
+
+# ---- the recovery paths of the search driver (hawk_api_search.hip): a table reserved by an earlier search on the set takes the
+# emit pass before the row count is known; the status block then says whether that was enough
+V_PATHS = {0: "planes", 2: "cluster", 1: "words"}  # hawk_timing.v_path
+
+
+def _seam_panel(iupac=False):
+    if iupac:  # ambiguity codes in the reference: a strict CFD lookup on them is an error
+        reg = synth.make_region(8501, "chrN", 60_000, 500, 58_000, iupac_frac=0.01)
+        synth.add_phased_variants(reg, 8502, 900, 4, af_min=0.1, af_max=0.6)
+    else:
+        reg = synth.make_region(8601, "chrT", 40_000, 1_000, 38_000)
+        synth.add_phased_variants(reg, 8602, 900, 4, af_min=0.2, af_max=0.7)
+    return reg
+
+
+class _Searcher:
+    """a fresh set of the panel (v_path 0: with planes) or a fresh view of its plan (2: per cluster, 1: per dirty word)"""
+
+    def __init__(self, reg, v_path):
+        self.v_path = v_path
+        self.ds, _info, _ms, _kept = expand_on_device(reg, 3, keep_plan=True)
+        self.on = self.ds if v_path == 0 else self.ds.plan.view()
+
+    def search(self, pam_s, na_on_ambiguous=False):
+        bits, bitsrc, _, _ = ora.pam_encode(pam_s)
+        mm, pt = synth.cfd_tables()
+        old = os.environ.pop("HAWK_VIEW_SEARCH", None)
+        if self.v_path == 1:
+            os.environ["HAWK_VIEW_SEARCH"] = "words"
+        try:
+            t = self.on.search(bits, bitsrc, len(pam_s), 20, False, mm, pt, cfd_na_on_ambiguous=na_on_ambiguous)
+        finally:
+            os.environ.pop("HAWK_VIEW_SEARCH", None)
+            if old is not None:
+                os.environ["HAWK_VIEW_SEARCH"] = old
+        assert t.timing["v_path"] == self.v_path
+        return t
+
+    def close(self):
+        self.ds.plan.close()
+        self.ds.close()
+
+
+_FRESH = {}
+
+
+def _fresh(v_path, pam_s, iupac=False):
+    """the table of the FIRST search on a fresh set / view (nothing reserved, nothing cached): computed once per module"""
+    key = (v_path, pam_s, iupac)
+    if key not in _FRESH:
+        s = _Searcher(_seam_panel(iupac), v_path)
+        _FRESH[key] = s.search(pam_s, na_on_ambiguous=iupac)
+        s.close()
+    return _FRESH[key]
+
+
+def _identical(t, want):
+    assert (t.n_rows, t.n_candidates, t.n_hits) == (want.n_rows, want.n_candidates, want.n_hits)
+    for c in COLS:
+        assert np.array_equal(getattr(t, c), getattr(want, c)), c
+    assert np.array_equal(t.win, want.win)
+    assert np.array_equal(t.cfdon, want.cfdon, equal_nan=True)
+
+
+@pytest.mark.parametrize("v_path", list(V_PATHS), ids=list(V_PATHS.values()))
+def test_search_emits_again_when_the_reserved_table_was_too_small(v_path):
+    # NGG reserves a table; NGN's rows do not fit it: its speculative emit is refused (capacity), the table grows and the emit
+    # runs again; NGG after it fits the larger table speculatively.  Every table as on a fresh set, bit for bit.
+    s = _Searcher(_seam_panel(), v_path)
+    first, larger, again = s.search("NGG"), s.search("NGN"), s.search("NGG")
+    assert larger.n_rows > first.n_rows
+    _identical(first, _fresh(v_path, "NGG"))
+    _identical(larger, _fresh(v_path, "NGN"))
+    _identical(again, _fresh(v_path, "NGG"))
+    s.close()
+
+
+def test_cluster_search_reruns_for_template_rows_while_a_table_is_reserved(monkeypatch):
+    # the template rows outgrow their reservation in a search whose table is already reserved: the attempt has emitted
+    # speculatively before the counter is read, produces no table, and the rerun (emit, too small, emit again) the right one
+    s = _Searcher(_seam_panel(), 2)
+    s.search("NGG")
+    monkeypatch.setenv("HAWK_CLUSTER_ROWS0", "64")
+    t = s.search("NGN")
+    assert t.n_rows > 64
+    _identical(t, _fresh(2, "NGN"))
+    s.close()
+
+
+@pytest.mark.parametrize("v_path", list(V_PATHS), ids=list(V_PATHS.values()))
+def test_cfd_status_outlives_a_speculative_emit(v_path):
+    # a reference with IUPAC codes: after a successful search (NA on ambiguous bases) the table is reserved; the strict search
+    # then emits speculatively and its CFD error must still come back; the set is as good as new afterwards
+    s = _Searcher(_seam_panel(iupac=True), v_path)
+    _identical(s.search("NGG", na_on_ambiguous=True), _fresh(v_path, "NGG", iupac=True))
+    with pytest.raises(_lib.HawkStatusError) as e:
+        s.search("NGG", na_on_ambiguous=False)
+    assert e.value.status == _lib.HAWK_E_CFD
+    _identical(s.search("NGG", na_on_ambiguous=True), _fresh(v_path, "NGG", iupac=True))
+    s.close()
 
 
 def test_cluster_dictionary_against_a_host_count():
