@@ -232,7 +232,7 @@ class GenomeIndex:
 
     # ---- bulged sites (the -bDNA / -bRNA arguments of the reference's CRISPRitz call, offtargets.py:264-268) -------------
     def scan_bulges(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int, brna: int, cap: int = 1 << 20,
-                    max_derived: int = 1 << 20) -> List["BulgeHit"]:
+                    max_derived: int = 1 << 20, engine: str = "derived") -> List["BulgeHit"]:
         """Sites that pair with a guide once `b` bases are bulged out - of the DNA (the site's spacer is b bases longer, b <= bdna)
         or of the RNA (b bases shorter, b <= brna) - with at most `max_mm` mismatches among the paired bases.  A bulged alignment
         is a mismatch-only alignment of a DERIVED guide: the guide with b interior bases deleted (RNA bulge), or with b bases
@@ -241,7 +241,12 @@ class GenomeIndex:
         (ties: the lexicographically smallest bulge positions) - the definitions of oracle/hawk_oracle.c: ora_offtargets_bulges.
         Bulges of up to 2 bases are enumerated (CRISPRitz's own limit).  A family is derived and scanned for consecutive slices
         of the guides, at most `max_derived` derived guides per scan (a DNA bulge of 2 turns a 20-mer into 3040 of them); rows
-        never depend on other guides, so the slicing does not change them."""
+        never depend on other guides, so the slicing does not change them.
+        `engine`: "derived" is the route above; "device" selects the placement where the site is (hawk_offtarget_bulges, k_ot_bulge:
+        one call per (type, size) over the guides as they are - no derived guides, no duplicates, no host selection) and returns
+        the same rows in the same order."""
+        if engine not in ("derived", "device"):
+            raise ValueError(f"engine {engine!r}: 'derived' or 'device'")
         if not (0 <= bdna <= 2 and 0 <= brna <= 2):
             raise ValueError("bulges of 0..2 bases are enumerated")
         if bdna > self.max_bulge:
@@ -249,8 +254,12 @@ class GenomeIndex:
         G = self.guidelen
         guides = [g.upper() for g in guides]
         out: List[BulgeHit] = []
+        self.last_bulge_timing = []  # engine="device": the timing block of every (type, size) call
         for dna, bmax in ((True, bdna), (False, brna)):
             for b in range(1, bmax + 1):
+                if engine == "device":
+                    out += self._bulge_rows_device(guides, pam, right, max_mm, b, dna, cap)
+                    continue
                 step = max(1, int(max_derived) // max(1, derived_per_guide(G, b, dna)))
                 Gs = G + b if dna else G - b
                 for g0 in range(0, len(guides), step):
@@ -276,11 +285,7 @@ class GenomeIndex:
         G, P = self.guidelen, self.pamlen
         L = Gs + P
         # the windows as bytes [n, L] (guide orientation, N for ambiguous bases) and their spacers
-        sh = (2 * np.arange(L, dtype=np.uint64))[None, :]
-        codes = ((h["code"][:, None] >> sh) & np.uint64(3)).astype(np.uint8)
-        amb = ((h["nmask"][:, None].astype(np.uint64) >> np.arange(L, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        win = np.frombuffer(b"ACGT", dtype=np.uint8)[codes]
-        win[amb] = ord("N")
+        win = self._windows(h, L)
         site = win[:, P:] if right else win[:, :Gs]
         g_of = owner[h["guide"]]
         gp = gaps[h["guide"]]
@@ -311,27 +316,87 @@ class GenomeIndex:
         key = np.stack([g_of[order].astype(np.int64), h["row"][order].astype(np.int64), h["q"][order].astype(np.int64), h["strand"][order].astype(np.int64)], axis=1)
         first = np.ones(len(order), dtype=bool)
         first[1:] = (key[1:] != key[:-1]).any(axis=1)
-        rows = []
-        for i in order[first].tolist():
-            name, off, _ = self.rows[int(h["row"][i])]
-            g = int(g_of[i])
-            sp_site = site[i].tobytes().decode("ascii")
-            pam_site = (win[i, :P] if right else win[i, Gs:]).tobytes().decode("ascii")
-            gbits = int(gp[i])
-            cr, dn = [], []
-            si = gi = 0
-            while si < Gs or gi < G:
-                if dna and si < Gs and (gbits >> si) & 1:
-                    cr.append("-"); dn.append(sp_site[si]); si += 1
-                elif (not dna) and gi < G and (gbits >> gi) & 1:
-                    cr.append(guides[g][gi]); dn.append("-"); gi += 1
-                else:
-                    t, q = sp_site[si], guides[g][gi]
-                    cr.append(q); dn.append(t if t == q else t.lower())
-                    si += 1; gi += 1
-            rows.append(BulgeHit(g, name, off + int(h["q"][i]), "-" if h["strand"][i] else "+", int(mm[i]), "DNA" if dna else "RNA", b,
-                                 "".join(cr), "".join(dn), pam_site, gbits))
-        return rows
+        return [self._bulge_hit(h, i, win, guides, int(g_of[i]), int(mm[i]), int(gp[i]), Gs, b, dna, right) for i in order[first].tolist()]
+
+    def _bulge_hit(self, h, i: int, win, guides, g: int, mm: int, gbits: int, Gs: int, b: int, dna: bool, right: bool) -> "BulgeHit":
+        """Row i of the scan columns `h` (win[i]: its window's bytes in guide orientation, N for ambiguous bases) as the BulgeHit
+        of guide g with the bulges at `gbits`: the crRNA / DNA strings with '-' where the other has no partner, mismatches of the
+        DNA in lower case, the site's own PAM."""
+        G, P = self.guidelen, self.pamlen
+        name, off, _ = self.rows[int(h["row"][i])]
+        sp_site = (win[i, P:] if right else win[i, :Gs]).tobytes().decode("ascii")
+        pam_site = (win[i, :P] if right else win[i, Gs:]).tobytes().decode("ascii")
+        cr, dn = [], []
+        si = gi = 0
+        while si < Gs or gi < G:
+            if dna and si < Gs and (gbits >> si) & 1:
+                cr.append("-"); dn.append(sp_site[si]); si += 1
+            elif (not dna) and gi < G and (gbits >> gi) & 1:
+                cr.append(guides[g][gi]); dn.append("-"); gi += 1
+            else:
+                t, q = sp_site[si], guides[g][gi]
+                cr.append(q); dn.append(t if t == q else t.lower())
+                si += 1; gi += 1
+        return BulgeHit(g, name, off + int(h["q"][i]), "-" if h["strand"][i] else "+", mm, "DNA" if dna else "RNA", b,
+                        "".join(cr), "".join(dn), pam_site, gbits)
+
+    def _windows(self, h, L: int):
+        """the windows of scan columns as bytes [n, L]: guide orientation, N for ambiguous bases"""
+        sh = (2 * np.arange(L, dtype=np.uint64))[None, :]
+        codes = ((h["code"][:, None] >> sh) & np.uint64(3)).astype(np.uint8)
+        amb = ((h["nmask"][:, None].astype(np.uint64) >> np.arange(L, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        win = np.frombuffer(b"ACGT", dtype=np.uint8)[codes]
+        win[amb] = ord("N")
+        return win
+
+    def bulge_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, b: int, dna: bool, cap: int = 1 << 20):
+        """One hawk_offtarget_bulges over this rank's rows - the bulged sites of one (type, size), the placement chosen on the
+        device: ({guide, row (global), q, strand, mm, code, nmask, gaps} arrays in no particular order, timing).  The windows
+        (code / nmask) have guidelen + b (DNA bulge) or guidelen - b (RNA bulge) + pamlen bases; the scan ranges are left set
+        for them (scan_bulges puts the index's own back)."""
+        G = self.guidelen
+        if not 1 <= b <= 2:
+            raise ValueError("bulges of 1..2 bases are enumerated")
+        if G - b < 3:
+            raise ValueError(f"guides of {G} bases leave no interior base to pair beside a bulge of {b}")
+        if dna and b > self.max_bulge:
+            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        Gs = G + b if dna else G - b
+        self._set_window(Gs)
+        g2 = encode_guides(guides)
+        if len(g2) and len(guides[0]) != G:
+            raise ValueError(f"guides of {len(guides[0])} bases on an index built for {G}")
+        cols = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
+                ("nmask", np.uint32), ("gaps", np.uint64))
+        if self.ds is None or len(g2) == 0:
+            return {k: np.zeros(0, t) for k, t in cols}, dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+        par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), G, int(bool(right)), max_mm)
+        while True:
+            o = {k: np.empty(cap, t) for k, t in cols}
+            n = C.c_uint64(0)
+            tm = _lib.OtTiming()
+            rc = self.ds._L.hawk_offtarget_bulges(self.ds._h, C.byref(par), _p(g2), len(g2), 1 if dna else 2, int(b), *[_p(o[k]) for k, _t in cols],
+                                                  C.c_uint64(cap), C.byref(n), C.byref(tm))
+            if rc == _lib.HAWK_E_CAPACITY:
+                cap = int(n.value) + 1024
+                continue
+            _lib.check(rc, "hawk_offtarget_bulges")
+            break
+        self.last_timing = {k: getattr(tm, k) for k, _ in tm._fields_}
+        k = int(n.value)
+        hits = {name: o[name][:k].copy() for name, _t in cols}
+        hits["row"] = hits["row"] + np.uint32(self.row_lo)
+        return hits, self.last_timing
+
+    def _bulge_rows_device(self, guides, pam, right: bool, max_mm: int, b: int, dna: bool, cap: int) -> List["BulgeHit"]:
+        h, tm = self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)
+        self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
+        if len(h["guide"]) == 0:
+            return []
+        Gs = self.guidelen + b if dna else self.guidelen - b
+        win = self._windows(h, Gs + self.pamlen)
+        return [self._bulge_hit(h, i, win, guides, int(h["guide"][i]), int(h["mm"][i]), int(h["gaps"][i]), Gs, b, dna, right)
+                for i in range(len(h["guide"]))]
 
     def hits_from_arrays(self, h) -> List["OffTargetHit"]:
         """Arrays of scan_arrays (of this rank, or gathered from every rank) -> sorted OffTargetHit list."""

@@ -54,14 +54,14 @@ def crispritz_bulge_line(hit, pamlen: int, right: bool) -> str:
 def search(genome: GenomeIndex, guides_seqs: List[str], pam: PAM, right: bool, mm: int, verbosity: int, debug: bool,
            bdna: int = 0, brna: int = 0) -> List[str]:
     """The CRISPRitz call's replacement (`crispritz.py search ... -mm M -bDNA B -bRNA R`, offtargets.py:264-268): report lines
-    for every hit of every unique spacer - the un-bulged sites, then the DNA- / RNA-bulged ones (genome.GenomeIndex.scan_bulges:
-    bulges of up to 2 bases, one row per (guide, site, type, size); CRISPRitz itself is absent, so its output beyond the field
+    for every hit of every unique spacer - the un-bulged sites, then the DNA- / RNA-bulged ones (genome.GenomeIndex.scan_bulges with
+    engine="device", the placement chosen per (site, guide) in k_ot_bulge: bulges of up to 2 bases, one row per (guide, site, type, size); CRISPRitz itself is absent, so its output beyond the field
     set the reference parses is unpinned)."""
     if bdna < 0 or brna < 0 or bdna > 2 or brna > 2:
         exception_handler(CrisprHawkOffTargetsError, f"DNA / RNA bulges of 0..2 bases are enumerated (got {bdna} / {brna})", os.EX_DATAERR, debug)
     try:
         hits = genome.scan(guides_seqs, pam, right, mm)
-        bulged = genome.scan_bulges(guides_seqs, pam, right, mm, bdna, brna) if (bdna or brna) else []
+        bulged = genome.scan_bulges(guides_seqs, pam, right, mm, bdna, brna, engine="device") if (bdna or brna) else []
     except ValueError as e:
         exception_handler(CrisprHawkOffTargetsError, f"Off-targets search failed: {e}", os.EX_DATAERR, debug, e)
     return [crispritz_report_line(h, guides_seqs[h.guide], len(pam), right) for h in hits] + \

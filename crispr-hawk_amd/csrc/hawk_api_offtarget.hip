@@ -69,7 +69,8 @@ struct OtFront {
   OtSeeds sd;
   OtPairSeeds ps;
 };
-static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, OtFront* f) {
+// `want_seeds` false: all pairs whatever the guide count, no bucketed tables (hawk_offtarget_bulges, whose p->guidelen is the SITE's spacer).
+static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, OtFront* f, bool want_seeds = true) {
   if (!hs || !p || !hs->has_meta || (n_guides && !guides2)) return HAWK_E_INVALID;
   if (hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
   if (p->guidelen + p->pamlen > 32 || p->guidelen == 0) return HAWK_E_UNSUPPORTED;  // window code = 2 bits x 32
@@ -97,7 +98,7 @@ static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* gu
   const char* e_all = getenv("HAWK_OT_ALLPAIRS");
   const int G = f->G = (int)p->guidelen, nb = (int)p->max_mm + 1;
   f->sp0 = p->right ? (int)p->pamlen : 0;
-  const bool seeded = f->seeded = !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
+  const bool seeded = f->seeded = want_seeds && !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
   const bool pairs = f->pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
   OtSeeds& sd = f->sd;
   OtPairSeeds& ps = f->ps;
@@ -218,6 +219,64 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
     if (out_mm) out_mm[i] = (uint8_t)hh[i].mm;
     if (out_code) out_code[i] = ss[i].code;
     if (out_nmask) out_nmask[i] = ss[i].nmask;
+  }
+  return HAWK_OK;
+}
+
+int hawk_offtarget_bulges(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, uint32_t bulge_type,
+                          uint32_t bulge_size, uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand,
+                          uint8_t* out_mm, uint64_t* out_code, uint32_t* out_nmask, uint64_t* out_gaps, uint64_t cap, uint64_t* n_out,
+                          hawk_ot_timing* timing) {
+  if (!n_out || !p || !hs) return HAWK_E_INVALID;
+  if (bulge_type < 1 || bulge_type > 2 || bulge_size < 1 || bulge_size > 2) return HAWK_E_INVALID;
+  const bool dna = bulge_type == 1;
+  const uint32_t G = p->guidelen;
+  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;  // a guide code is 2 bits x 32; two end bases and one interior base stay paired
+  hawk_ot_params ps = *p;
+  const uint32_t Gs = ps.guidelen = dna ? G + bulge_size : G - bulge_size;  // the site's spacer: what the window scan is about
+  if (Gs + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
+  // the rows' scan ranges must be those of windows of Gs + pamlen bases (hawk_hapset_set_meta): a window that starts inside a
+  // range set for a shorter window would reach past its row
+  if (!hs->has_meta) return HAWK_E_INVALID;
+  for (uint32_t h = 0; h < hs->n_hap; ++h)
+    if (hs->scan_stop[h] > hs->scan_start[h] && (int64_t)hs->scan_stop[h] - 1 + Gs + p->pamlen > (int64_t)hs->hap_len[h]) return HAWK_E_INVALID;
+  OtFront f;
+  int rc = ot_front(hs, &ps, guides2, n_guides, &f, false);
+  if (rc) return rc;
+  hawk_ctx* ctx = f.ctx;
+  hipEvent_t* ev = ctx->ev;
+  const uint64_t nsites = f.nsites;
+  // sized by the rows asked for and (ot_front) by the guides: nothing here grows with the placements
+  if ((rc = hs->hits.reserve(std::max<uint64_t>(cap, 1) * sizeof(OtBulgeHit)))) return rc;
+  unsigned long long* d_nhits = hs->misc.as<unsigned long long>();
+  hawk_launch_ot_bulge(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, (int)G, f.sp0, (int)p->max_mm,
+                       dna ? 1 : 0, (int)bulge_size, hs->hits.as<OtBulgeHit>(), cap, d_nhits);
+  HIPCHK(hipEventRecord(ev[4], ctx->stream));
+  HIPCHK(hipGetLastError());
+  unsigned long long nh = 0;
+  HIPCHK(hipMemcpyAsync(&nh, d_nhits, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *n_out = nh;
+  ot_timing(hs, nsites, timing);
+  if (nh > cap) return HAWK_E_CAPACITY;
+  if (!nh) return HAWK_OK;
+  std::vector<OtBulgeHit> hh(nh);
+  std::vector<OtSite> ss(nh);
+  if ((rc = hs->othit.reserve(nh * sizeof(OtSite)))) return rc;
+  hawk_launch_ot_bulge_gather(ctx->stream, hs->sites.as<OtSite>(), hs->hits.as<OtBulgeHit>(), nh, hs->othit.as<OtSite>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hh.data(), hs->hits.p, nh * sizeof(OtBulgeHit), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ss.data(), hs->othit.p, nh * sizeof(OtSite), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (uint64_t i = 0; i < nh; ++i) {
+    if (out_guide) out_guide[i] = hh[i].guide;
+    if (out_row) out_row[i] = ss[i].row;
+    if (out_q) out_q[i] = ss[i].q & 0x7fffffffu;
+    if (out_strand) out_strand[i] = (uint8_t)(ss[i].q >> 31);
+    if (out_mm) out_mm[i] = (uint8_t)hh[i].mm;
+    if (out_code) out_code[i] = ss[i].code;
+    if (out_nmask) out_nmask[i] = ss[i].nmask;
+    if (out_gaps) out_gaps[i] = hh[i].gaps;
   }
   return HAWK_OK;
 }

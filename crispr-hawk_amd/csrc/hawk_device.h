@@ -243,6 +243,14 @@ void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n
                                  const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
                                  OtHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const OtHit* hits, uint64_t n_hits, OtSite* out);
+// Bulged sites (hawk_otbulge.hip: k_ot_bulge).  `sites`: the records of a scan whose window is Gs + pamlen bases, Gs = guidelen +
+// bsize (dna) or guidelen - bsize (RNA bulge); one launch per (type, size).  A row per (site, guide) whose best placement of the
+// bsize gaps has <= max_mm mismatches; gaps: bit i = position i (of the site spacer for DNA bulges, of the guide for RNA bulges)
+// faces nothing.  *n_hits (zeroed) counts past cap.
+struct OtBulgeHit { uint64_t site; uint32_t guide, mm, gaps, pad; };
+void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
+                          int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits);
+void hawk_launch_ot_bulge_gather(hipStream_t st, const OtSite* sites, const OtBulgeHit* hits, uint64_t n_hits, OtSite* out);
 // The match kernels with the summary's hit sink (hawk_offtarget.hip: OtSumSink): where a hit goes instead of hits[].
 struct OtSummary {
   const OtSite* sites;

@@ -463,6 +463,22 @@ int hawk_genome_finalize(hawk_hapset* rows);
 int hawk_offtarget_scan(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
                         uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm,
                         uint64_t* out_code, uint32_t* out_nmask, uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing);
+/* Bulged sites (-bDNA / -bRNA of the CRISPRitz call), one call per (type, size), selected on the device (k_ot_bulge).
+ * p->guidelen is the GUIDE's length G; bulge_type 1 = DNA bulge (the site's spacer has Gs = G + bulge_size bases, bulge_size of
+ * its interior positions 1 .. Gs - 2 face no guide base), 2 = RNA bulge (Gs = G - bulge_size, bulge_size interior guide positions
+ * 1 .. G - 2 face no site base); bulge_size 1..2.  The rows' scan ranges (hawk_hapset_set_meta) must be those of windows of
+ * Gs + pamlen bases.  At most one row per (guide, site, strand): the placement with the fewest mismatches among the paired
+ * bases, ties to the lexicographically smallest tuple of bulge positions in guide orientation, reported when that minimum is
+ * <= max_mm.  An aligned ambiguous site base counts as a mismatch; an ambiguous site base is never bulged out.
+ * Output columns as hawk_offtarget_scan (code / nmask: the window of Gs + pamlen bases) plus out_gaps: bit i = position i is
+ * bulged (of the site spacer for DNA bulges, of the guide for RNA bulges).  Rows are unordered.  cap / *n_out / HAWK_E_CAPACITY
+ * as hawk_offtarget_scan.  HAWK_E_INVALID: type or size out of range, scan ranges that let a window of Gs + pamlen bases reach
+ * past its row; HAWK_E_UNSUPPORTED: G - bulge_size < 3, G > 32, Gs + pamlen > 32.  Device memory is sized by n_guides and cap,
+ * never by the placements. */
+int hawk_offtarget_bulges(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
+                          uint32_t bulge_type, uint32_t bulge_size, uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q,
+                          uint8_t* out_strand, uint8_t* out_mm, uint64_t* out_code, uint32_t* out_nmask, uint64_t* out_gaps,
+                          uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing);
 /* The same scan with every hit consumed inside the match kernel instead of listed: per-guide aggregates, mismatch-only, and no
  * memory on host or device that grows with the number of hits (no capacity, no retry).
  *   out_hist[g][m]  (row stride max_mm + 1) hits of guide g with m mismatches - the on-target site included
