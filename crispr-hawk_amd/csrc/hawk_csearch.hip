@@ -16,8 +16,8 @@
 //       variants.  An instance whose windows could meet a row-specific bound (scan range, row ends) is a cluster of its own; one
 //       wholly outside the scan range carries no cluster at all.
 //   per search:  k_cs_templates builds each distinct cluster's rows ONCE, on its representative row, with the string
-//       builder, PAM match, filters and classification of hawk_vsearch.hip (64-byte template rows, strand 0 / strand 1
-//       regions in position order); k_cs_count gives every instance its row count and adds up the job's totals
+//       builder, PAM match and filters of hawk_vsearch.hip and the row rules of hawk_rows.h (64-byte template rows, CsRow there;
+//       strand 0 / strand 1 regions in position order); k_cs_count gives every instance its row count and adds up the job's totals
 //       (candidates, hits: the cluster's own + REF's hits under the shift of the clean stretch in front of it) and adds a wave's
 //       rows up (the offset scan runs over one entry per 64 instances); k_cs_emit_rows then copies template rows into the guide
 //       table - packed 64-byte rows, one linear write stream - a wave per 256 consecutive instances, patching haplotype row
@@ -33,10 +33,6 @@
 #define CL_MAXWALK 4096      // records per cluster the dictionary accepts (longer chains: the per-word search takes the plan)
 #define CS_G 8               // lanes per distinct cluster in k_cs_templates: one 32-window word each per round
 
-// a template row, 64 bytes = one L2 sector pair: {position relative to the cluster's first allele, strand | flags << 1,
-// start - REF's first position, stop - start} {cfdon, win0} {win1, win2} {win3, win4}
-struct __attribute__((aligned(16))) CsRow { uint4 a, b, c, d; };
-static_assert(sizeof(CsRow) == 64, "template row layout");
 size_t hawk_cs_row_bytes() { return sizeof(CsRow); }
 
 __device__ __forceinline__ uint64_t cl_mix(uint64_t h, uint64_t v) {
@@ -672,7 +668,8 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
   const uint32_t back = (uint64_t)r0 > va.hv_off[h] ? 1u : 0u;  // the record in front of the cluster sets the REF shift it starts from
   const HxVar* __restrict__ sv = recs + r0 - back;
   const int nrec = (int)(nc + back);
-  const int L = p.L;
+  const RowGeom geom = row_geom(p, gp);
+  const int L = geom.L;
   const int32_t haplen = (int32_t)hs.hap_len[h];
   const int32_t o_first = live ? cd.u_o[u] : 0;
   const int32_t o_end = live ? recs[r0 + nc - 1].o + (int32_t)recs[r0 + nc - 1].alt_len : 0;
@@ -693,11 +690,6 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
   const int32_t rb_front = back ? (int32_t)sv[0].rs - (sv[0].o + (int32_t)sv[0].alt_len) : 0;
   const uint32_t h_front = hits_before((int64_t)o_first + rb_front - (L - 1)), h_behind = hits_before((int64_t)recs[r0 + nc - 1].rs);
   const int poF = p.right ? 0 : p.guidelen, poR = p.right ? p.guidelen : 0;
-  const uint32_t mlo = L >= 32 ? 0xffffffffu : ((1u << L) - 1u), mhi = L <= 32 ? 0u : ((1u << (L - 32)) - 1u);
-  const int W = L + 2 * HAWK_PAD;
-  const uint32_t whi = W >= 64 ? 0xffffffffu : ((1u << (W - 32)) - 1u);
-  const int ncfd = gp.guidelen < 20 ? gp.guidelen : 20;
-  const uint32_t cfdmask = (1u << ncfd) - 1u;
   auto ref32 = [&](int pl, uint32_t r) -> uint32_t {
     const uint32_t w = (r >> 5) < va.ref_S - 2 ? (r >> 5) : va.ref_S - 2;
     return ext32_glb(va.ref[pl], (w << 5) | (r & 31u));
@@ -742,7 +734,8 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
     kF = f & E;
     kR = rv & E;
   };
-  // which kept starts are rows: not the REF guide at the same (start, strand) again (remove_redundant_guides)
+  // which kept starts are rows: not the REF guide at the same (start, strand) again (remove_redundant_guides).  REF's core is
+  // asked for only where REF has a guide: a second round trip, but for few of a long cluster's many starts
   auto classify = [&](int32_t q0, const uint32_t (&X)[5][3], uint32_t kF, uint32_t kR, uint32_t& vF, uint32_t& vR) {
     vF = 0; vR = 0;
 #pragma unroll 1
@@ -751,26 +744,20 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
       while (m) {
         const uint32_t bpos = (uint32_t)__builtin_ctz(m);
         m &= m - 1u;
-        const int64_t start = posmap_hint(hs, seg0, seg_end, (uint32_t)q0 + bpos);
-        const int64_t qr64 = start - ri.startp;
-        const bool inr = qr64 >= 0 && qr64 < (int64_t)ri.n_bits;
-        const uint32_t qr = inr ? (uint32_t)qr64 : 0u;
-        const bool has_ref = inr && (((s ? ri.bits[1] : ri.bits[0])[qr >> 5] >> (qr & 31u)) & 1u);
-        bool same = has_ref;
-        if (has_ref) {
-#pragma unroll
-          for (int pl = 0; pl < 4; ++pl) {
-            W2 wn = ext96(X[pl][0], X[pl][1], X[pl][2], bpos);
-            wn.hi &= whi;
-            const uint32_t clo = fsh(wn.lo, wn.hi, HAWK_PAD) & mlo, chi = (wn.hi >> HAWK_PAD) & mhi;
-            const W2 rc = ext_glb(va.ref[pl], qr);
-            same = same && (rc.lo & mlo) == clo && (rc.hi & mhi) == chi;
-          }
+        RefProbe pr = ref_probe_bit(ri, posmap_hint(hs, seg0, seg_end, (uint32_t)q0 + bpos), (uint32_t)s);
+        bool same = false;
+        if (probe_has_ref(pr)) {
+          W2 win[5], core[4], rcore[4];
+          bool has_ref;
+          ref_probe_cores(pr, va.ref);
+          row_slices([&](int pl, int k) { return X[pl][k]; }, bpos, geom, win, core);
+          same = ref_verdict(pr, core, geom, rcore, has_ref);
         }
         if (!same) { if (s) vR |= 1u << bpos; else vF |= 1u << bpos; }
       }
     }
   };
+  // one row per start classify kept: slices -> probe -> verdict -> store (pass 2 of a short cluster does the same from LDS)
   auto write = [&](int32_t q0, const uint32_t (&X)[5][3], uint32_t vF, uint32_t vR, uint64_t at0, uint64_t at1) {
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
@@ -779,45 +766,14 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
         const uint32_t bpos = (uint32_t)__builtin_ctz(m);
         m &= m - 1u;
         const uint32_t q = (uint32_t)q0 + bpos;
-        const uint64_t k = s ? at1++ : at0++;
-        if (k >= t_cap) { atomicExch(status, -3 /* HAWK_E_CAPACITY: more rows than window starts */); continue; }
-        W2 win[5], core[4], rcore[4];
-#pragma unroll
-        for (int pl = 0; pl < 5; ++pl) {
-          win[pl] = ext96(X[pl][0], X[pl][1], X[pl][2], bpos);
-          win[pl].hi &= whi;
-          if (pl < 4) {
-            core[pl].lo = fsh(win[pl].lo, win[pl].hi, HAWK_PAD) & mlo;
-            core[pl].hi = (win[pl].hi >> HAWK_PAD) & mhi;
-          }
-        }
         const int64_t start = posmap_hint(hs, seg0, seg_end, q), stop = posmap_hint(hs, seg0, seg_end, q + (uint32_t)L);
-        const int64_t qr64 = start - ri.startp;
-        const bool inr = qr64 >= 0 && qr64 < (int64_t)ri.n_bits;
-        const uint32_t qr = inr ? (uint32_t)qr64 : 0u;
-        const bool has_ref = inr && (((s ? ri.bits[1] : ri.bits[0])[qr >> 5] >> (qr & 31u)) & 1u);
-#pragma unroll
-        for (int pl = 0; pl < 4; ++pl) {
-          rcore[pl] = ext_glb(va.ref[pl], qr);
-          rcore[pl].lo &= mlo; rcore[pl].hi &= mhi;
-          if (!has_ref) rcore[pl] = core[pl];
-        }
-        double score = __longlong_as_double(0x7ff8000000000000ll);  // NaN -> "NA"
-        if (gp.score_cfdon && has_ref) {
-          bool err;
-          score = cfdon_from_slices(core, rcore, (uint32_t)s, L, cfdmask, s_cfd, err);
-          if (err && gp.score_cfdon == 1) atomicExch(status, -5 /* HAWK_E_CFD */);
-        }
-        const bool pamfirst = (p.right != 0) != (s != 0);
-        const int64_t ds = start - ri.startp, de = stop - start;
-        if (ds < INT32_MIN || ds > INT32_MAX || de < INT32_MIN || de > INT32_MAX) atomicExch(status, -7 /* HAWK_E_UNSUPPORTED */);
-        const uint64_t sc = (uint64_t)__double_as_longlong(score);
-        uint4* __restrict__ tp = reinterpret_cast<uint4*>(trows + k);
-        tp[0] = make_uint4((uint32_t)((int32_t)(pamfirst ? q : q + (uint32_t)p.guidelen) - o_first), (uint32_t)s | (has_ref ? 2u : 0u),
-                           (uint32_t)(int32_t)ds, (uint32_t)(int32_t)de);
-        tp[1] = make_uint4((uint32_t)sc, (uint32_t)(sc >> 32), win[0].lo, win[0].hi);
-        tp[2] = make_uint4(win[1].lo, win[1].hi, win[2].lo, win[2].hi);
-        tp[3] = make_uint4(win[3].lo, win[3].hi, win[4].lo, win[4].hi);
+        const RefProbe pr = ref_probe(ri, va.ref, start, (uint32_t)s);
+        W2 win[5], core[4], rcore[4];
+        bool has_ref;
+        row_slices([&](int pl, int k) { return X[pl][k]; }, bpos, geom, win, core);
+        ref_verdict(pr, core, geom, rcore, has_ref);  // (classify kept only starts that are rows)
+        const double score = row_cfdon(gp, has_ref, core, rcore, (uint32_t)s, geom, s_cfd, status);
+        template_row_store(trows, s ? at1++ : at0++, t_cap, q, o_first, (uint32_t)s, start, stop, ri.startp, has_ref, win, score, p, status);
       }
     }
   };
@@ -909,54 +865,16 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
       const uint32_t bpos = select_bit(s_k[sd][src], jj - ((s_e[src] >> sh16) & 0xffffu));
       const uint32_t q = (uint32_t)(qa + 32 * (int32_t)l) + bpos;
       W2 win[5], core[4], rcore[4];
-#pragma unroll
-      for (int pl = 0; pl < 5; ++pl) {
-        win[pl] = ext96(s_X[pl * 3 + 0][src], s_X[pl * 3 + 1][src], s_X[pl * 3 + 2][src], bpos);
-        win[pl].hi &= whi;
-        if (pl < 4) {
-          core[pl].lo = fsh(win[pl].lo, win[pl].hi, HAWK_PAD) & mlo;
-          core[pl].hi = (win[pl].hi >> HAWK_PAD) & mhi;
-        }
-      }
+      row_slices([&](int pl, int k) { return s_X[pl * 3 + k][src]; }, bpos, geom, win, core);
       const int64_t start = posmap_hint(hs, seg0, seg_end, q), stop = posmap_hint(hs, seg0, seg_end, q + (uint32_t)L);
-      const int64_t qr64 = start - ri.startp;
-      const bool inr = qr64 >= 0 && qr64 < (int64_t)ri.n_bits;
-      const uint32_t qr = inr ? (uint32_t)qr64 : 0u;
-      const uint32_t rw = (sd ? ri.bits[1] : ri.bits[0])[qr >> 5];
-#pragma unroll
-      for (int pl = 0; pl < 4; ++pl) rcore[pl] = ext_glb(va.ref[pl], qr);  // fetched whether or not REF has a guide there: one round trip
-      const bool has_ref = inr && ((rw >> (qr & 31u)) & 1u);
-      bool same = has_ref;
-#pragma unroll
-      for (int pl = 0; pl < 4; ++pl) {
-        rcore[pl].lo &= mlo; rcore[pl].hi &= mhi;
-        same = same && rcore[pl].lo == core[pl].lo && rcore[pl].hi == core[pl].hi;
-        if (!has_ref) rcore[pl] = core[pl];
-      }
-      const bool valid = act && !same;
+      const RefProbe pr = ref_probe(ri, va.ref, start, (uint32_t)sd);  // REF's core whether or not REF has a guide there: one round trip
+      bool has_ref;
+      const bool valid = act && !ref_verdict(pr, core, geom, rcore, has_ref);
       const uint32_t vinc = group_incl_scan(valid ? 1u : 0u, gl);
       const uint32_t vtot = (uint32_t)__shfl((int)vinc, CS_G - 1, CS_G);
       if (valid && live) {
-        const uint64_t k = tb + done + ns + (vinc - 1u);
-        if (k >= t_cap) atomicExch(status, -3 /* HAWK_E_CAPACITY */);
-        else {
-          double score = __longlong_as_double(0x7ff8000000000000ll);  // NaN -> "NA"
-          if (gp.score_cfdon && has_ref) {
-            bool err;
-            score = cfdon_from_slices(core, rcore, (uint32_t)sd, L, cfdmask, s_cfd, err);
-            if (err && gp.score_cfdon == 1) atomicExch(status, -5 /* HAWK_E_CFD */);
-          }
-          const bool pamfirst = (p.right != 0) != (sd != 0);
-          const int64_t ds = start - ri.startp, de = stop - start;
-          if (ds < INT32_MIN || ds > INT32_MAX || de < INT32_MIN || de > INT32_MAX) atomicExch(status, -7 /* HAWK_E_UNSUPPORTED */);
-          const uint64_t sc = (uint64_t)__double_as_longlong(score);
-          uint4* __restrict__ tp = reinterpret_cast<uint4*>(trows + k);
-          tp[0] = make_uint4((uint32_t)((int32_t)(pamfirst ? q : q + (uint32_t)p.guidelen) - o_first), (uint32_t)sd | (has_ref ? 2u : 0u),
-                             (uint32_t)(int32_t)ds, (uint32_t)(int32_t)de);
-          tp[1] = make_uint4((uint32_t)sc, (uint32_t)(sc >> 32), win[0].lo, win[0].hi);
-          tp[2] = make_uint4(win[1].lo, win[1].hi, win[2].lo, win[2].hi);
-          tp[3] = make_uint4(win[3].lo, win[3].hi, win[4].lo, win[4].hi);
-        }
+        const double score = row_cfdon(gp, has_ref, core, rcore, (uint32_t)sd, geom, s_cfd, status);
+        template_row_store(trows, tb + done + ns + (vinc - 1u), t_cap, q, o_first, (uint32_t)sd, start, stop, ri.startp, has_ref, win, score, p, status);
       }
       ns += vtot;
     }
@@ -1053,8 +971,7 @@ __device__ __forceinline__ void nt_store4(uint32_t* q, const uint4& v) {
   __builtin_nontemporal_store(v.z, q + 2); __builtin_nontemporal_store(v.w, q + 3);
 }
 // ---- packed rows (round 4): the guide table of a cluster search as ONE array of 64-byte rows -----------------------------
-// {pos, strand | flags << 1 | haplotype row << 9, start - startp, stop - start} {cfdon, win0} {win1, win2} {win3, win4}: a template
-// row with two words patched.  A wave's rows are contiguous, four lanes move one row (16 bytes each), so every store
+// A template row (CsRow, hawk_rows.h: the field order is written down there) with two words patched: pos and the haplotype row.  A wave's rows are contiguous, four lanes move one row (16 bytes each), so every store
 // instruction writes 1 KB of consecutive addresses and the whole table is a single linear write stream - twelve column
 // streams whose relative placement decided the speed before (profiles/r03_csearch_ablation.txt).
 // NI x 64 consecutive instances per wave, their rows one contiguous stretch of the table.  What bounds the pass is not bytes but
@@ -1182,7 +1099,8 @@ void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va,
                      group_counts, counts, inst_tb, shards);
 }
 
-// columns -> packed rows (REF's rows, which the plane kernels write as columns; a columnar table before an exchange) and back
+// columns -> packed rows (REF's rows, which the plane kernels write as columns; a columnar table before an exchange) and back:
+// the field order of CsRow (hawk_rows.h)
 __global__ __launch_bounds__(256) void k_rows_pack(GuideCols c, const uint64_t* __restrict__ n_dev, uint64_t n_host, uint4* __restrict__ rows, int64_t startp,
                                                    int* status) {
   const uint64_t n = n_dev ? *n_dev : n_host;
@@ -1239,7 +1157,7 @@ __global__ __launch_bounds__(256) void k_cc_ucnt(const uint4* __restrict__ res, 
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   if (u < nu) { const uint4 r = res[2 * u]; cnt[u] = r.x + r.y; }
 }
-// mini row r0 + moff[u] + k is row k of distinct cluster u: template row tbase[u] + k
+// mini row r0 + moff[u] + k is row k of distinct cluster u: template row tbase[u] + k (CsRow, hawk_rows.h)
 __global__ __launch_bounds__(256) void k_cc_mini(GuideCols c, uint64_t r0, const CsRow* __restrict__ trows, uint64_t t_rows,
                                                  const uint64_t* __restrict__ moff, const uint32_t* __restrict__ tbase, uint32_t nu, int64_t startp,
                                                  GuideCols m) {

@@ -190,12 +190,9 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
     // PASS 1 on one round of a REF tile (round_only >= 0): every survivor of a REF tile is a row, so round b starts
     // b * CAP rows into the tile and the rounds of one tile can run in different workgroups
     uint64_t row_base = PASS == 1 ? offsets[tile] + (round_only >= 0 ? (uint64_t)round_only * CAP : 0ull) : 0;
-    const int L = p.L;
-    const int W = L + 2 * HAWK_PAD;
-    const uint32_t mlo = L >= 32 ? 0xffffffffu : ((1u << L) - 1u), mhi = L <= 32 ? 0u : ((1u << (L - 32)) - 1u);
-    const uint32_t wlo = 0xffffffffu, whi = W >= 64 ? 0xffffffffu : ((1u << (W - 32)) - 1u);  // W = L + 20 > 32
-    const int ncfd = gp.guidelen < 20 ? gp.guidelen : 20;
-    const uint32_t cfdmask = (1u << ncfd) - 1u;
+    const RowGeom geom = row_geom(p, gp);
+    const int L = geom.L;
+    const uint32_t mlo = geom.mlo, mhi = geom.mhi;
 
     const uint32_t base_lo = (PASS == 1 && round_only >= 0) ? (uint32_t)round_only * CAP : 0u;
     const uint32_t base_hi = (PASS == 1 && round_only >= 0) ? (base_lo + CAP < T ? base_lo + CAP : T) : T;
@@ -265,14 +262,7 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
           }
           ql = (4 * lo + kw) * 32 + bpos;
           const uint32_t q = tile_q0 + ql;
-          if (ovf) {  // workgroup-uniform, rare: more than NSEG segments in the tile
-            c_start = posmap_global(hs, h, q);
-          } else {    // unused slots of s_segrel hold 0xffffffff: a fixed six-step search needs no bounds
-            uint32_t sj = 0;
-#pragma unroll
-            for (uint32_t step = NSEG / 2; step; step >>= 1) sj += (s_segrel[sj + step] <= q) ? step : 0u;
-            c_start = s_seggen[sj] + (int64_t)(q - s_segrel[sj]);
-          }
+          c_start = ovf ? posmap_global(hs, h, q) : posmap_staged(s_segrel, s_seggen, q);  // ovf: workgroup-uniform, rare: > NSEG segments in the tile
           c_valid = 1;
           c_has_ref = isref;
           if (dedup) {  // workgroup-uniform
@@ -280,11 +270,9 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
             // the per-strand bitmaps k_ref_bits left in HBM (2 x 125 KB on C3, L2-resident).  The survivor is redundant
             // iff the four code planes agree as well: the planes the PAM names (just streamed, L2-hot) are compared for
             // every lane, the others only in the rare wave where those agree.
-            const int64_t qr64 = c_start - ri.startp;
-            const bool inr = qr64 >= 0 && qr64 < (int64_t)ri.n_bits;
-            const uint32_t qr = inr ? (uint32_t)qr64 : 0u;
-            const uint32_t rw = (s ? ri.bits[1] : ri.bits[0])[qr >> 5];
-            c_has_ref = inr && ((rw >> (qr & 31u)) & 1u);
+            const RefProbe pr = ref_probe_bit(ri, c_start, s);
+            const uint32_t qr = pr.qr;
+            c_has_ref = probe_has_ref(pr);
             bool same = c_has_ref;
 #pragma unroll
             for (int pl = 0; pl < 4; ++pl)
@@ -319,12 +307,7 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
             start = posmap_global(hs, h, q);
             if (PASS == 1) stop = posmap_global(hs, h, q + (uint32_t)L);
           } else {
-            const int j = seg_find(s_segrel, nloc, q);
-            start = s_seggen[j] + (int64_t)(q - s_segrel[j]);
-            if (PASS == 1) {  // search_guides.py:260-280: stop = posmap[q + L]
-              if (j + 1 >= nloc || s_segrel[j + 1] > q + (uint32_t)L) stop = start + L;
-              else { const int j2 = seg_find(s_segrel, nloc, q + (uint32_t)L); stop = s_seggen[j2] + (int64_t)(q + (uint32_t)L - s_segrel[j2]); }
-            }
+            posmap_staged_span(s_segrel, s_seggen, nloc, q, L, start, stop);
           }
           valid = 1;
           if (PASS == 0) {
@@ -395,29 +378,14 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
           uint32_t tot;
           const uint32_t ex = block_excl_scan<HAWK_BLOCK / WAVE>(valid, s_w, &tot);
           if (valid) {
-            const uint64_t o = row_base + ex;
-            if (o >= out.cap) { atomicExch(status, -3 /* HAWK_E_CAPACITY: offsets and counts disagree */); continue; }
-            const bool pamfirst = (p.right != 0) != (s != 0);
-            const uint32_t q = tile_q0 + ql;
-            out.hap[o] = h;
-            out.pos[o] = pamfirst ? q : q + (uint32_t)p.guidelen;
-            out.strand[o] = (uint8_t)s;
-            out.start[o] = start;
-            out.stop[o] = stop;
-            out.flags[o] = has_ref ? 1 : 0;
+            const double score = row_cfdon(gp, has_ref, core, rcore, s, geom, s_cfd, status);
+            W2 win[5];  // (cut out behind the scoring: five windows held across it cost the kernel a wave per SIMD)
 #pragma unroll
             for (int pl = 0; pl < HAWK_PLANES; ++pl) {
-              W2 w = ext_lds(s_pl[pl], (int)ql - HAWK_PAD);
-              w.lo &= wlo; w.hi &= whi;
-              out.win[(size_t)pl * out.cap + o] = (uint64_t)w.lo | ((uint64_t)w.hi << 32);
+              win[pl] = ext_lds(s_pl[pl], (int)ql - HAWK_PAD);
+              win[pl].hi &= geom.whi;
             }
-            double score = __longlong_as_double(0x7ff8000000000000ll);  // NaN -> "NA"
-            if (gp.score_cfdon && has_ref) {
-              bool err;
-              score = cfdon_from_slices(core, rcore, s, L, cfdmask, s_cfd, err);
-              if (err && gp.score_cfdon == 1) atomicExch(status, -5 /* HAWK_E_CFD; score_cfdon == 2 leaves NaN = "NA" */);
-            }
-            out.cfdon[o] = score;
+            cols_store(out, row_base + ex, h, tile_q0 + ql, s, start, stop, has_ref, win, score, p, status);
           }
           row_base += tot;
         }
@@ -553,12 +521,8 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_emit_list(HapSetDev hs, ScanPara
   __syncthreads();
   const int nloc = (int)s_nloc;
   const size_t refbase = ri.index >= 0 ? (size_t)ri.index * hs.S : 0;
-  const int L = p.L;
-  const int W = L + 2 * HAWK_PAD;
-  const uint32_t mlo = L >= 32 ? 0xffffffffu : ((1u << L) - 1u), mhi = L <= 32 ? 0u : ((1u << (L - 32)) - 1u);
-  const uint32_t whi = W >= 64 ? 0xffffffffu : ((1u << (W - 32)) - 1u);  // W = L + 20 > 32
-  const int ncfd = gp.guidelen < 20 ? gp.guidelen : 20;
-  const uint32_t cfdmask = (1u << ncfd) - 1u;
+  const RowGeom geom = row_geom(p, gp);
+  const int L = geom.L;
   const uint64_t row0 = offsets[tile];
 
 #pragma unroll 1
@@ -574,47 +538,25 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_emit_list(HapSetDev hs, ScanPara
       start = posmap_global(hs, h, q);
       stop = posmap_global(hs, h, q + (uint32_t)L);
     } else {  // search_guides.py:260-280: start = posmap[q], stop = posmap[q + L]
-      const int j = seg_find(s_segrel, nloc, q);
-      start = s_seggen[j] + (int64_t)(q - s_segrel[j]);
-      if (j + 1 >= nloc || s_segrel[j + 1] > q + (uint32_t)L) stop = start + L;
-      else { const int j2 = seg_find(s_segrel, nloc, q + (uint32_t)L); stop = s_seggen[j2] + (int64_t)(q + (uint32_t)L - s_segrel[j2]); }
+      posmap_staged_span(s_segrel, s_seggen, nloc, q, L, start, stop);
     }
-    const uint64_t o = row0 + i;
-    if (o >= out.cap) { atomicExch(status, -3 /* HAWK_E_CAPACITY: offsets and counts disagree */); continue; }
-    const bool pamfirst = (p.right != 0) != (s != 0);
-    out.hap[o] = h;
-    out.pos[o] = pamfirst ? q : q + (uint32_t)p.guidelen;
-    out.strand[o] = (uint8_t)s;
-    out.start[o] = start;
-    out.stop[o] = stop;
-    out.flags[o] = has_ref ? 1 : 0;
-    W2 core[4], rcore[4];
+    W2 win[5], core[4], rcore[4];
 #pragma unroll
     for (int pl = 0; pl < HAWK_PLANES; ++pl) {
-      W2 w = ext_lds(s_pl[pl], (int)ql - HAWK_PAD);
-      w.hi &= whi;
-      out.win[(size_t)pl * out.cap + o] = (uint64_t)w.lo | ((uint64_t)w.hi << 32);
-      if (pl < 4) {  // the spacer+PAM core is the window without its pads
-        core[pl].lo = fsh(w.lo, w.hi, HAWK_PAD) & mlo;
-        core[pl].hi = (w.hi >> HAWK_PAD) & mhi;
-        rcore[pl] = core[pl];
-      }
+      win[pl] = ext_lds(s_pl[pl], (int)ql - HAWK_PAD);
+      win[pl].hi &= geom.whi;
+      if (pl < 4) rcore[pl] = core[pl] = core_of_window(win[pl], geom);
     }
-    double score = __longlong_as_double(0x7ff8000000000000ll);  // NaN -> "NA"
-    if (gp.score_cfdon && has_ref) {
-      if (!isref) {
-        const uint32_t qr = (uint32_t)(start - ri.startp);  // REF's position map is the identity
+    if (gp.score_cfdon && has_ref && !isref) {
+      const uint32_t qr = (uint32_t)(start - ri.startp);  // REF's position map is the identity
 #pragma unroll
-        for (int pl = 0; pl < 4; ++pl) {
-          rcore[pl] = ext_glb(hs.plane[pl] + refbase, qr);
-          rcore[pl].lo &= mlo; rcore[pl].hi &= mhi;
-        }
+      for (int pl = 0; pl < 4; ++pl) {
+        rcore[pl] = ext_glb(hs.plane[pl] + refbase, qr);
+        rcore[pl].lo &= geom.mlo; rcore[pl].hi &= geom.mhi;
       }
-      bool err;
-      score = cfdon_from_slices(core, rcore, s, L, cfdmask, s_cfd, err);
-      if (err && gp.score_cfdon == 1) atomicExch(status, -5 /* HAWK_E_CFD; score_cfdon == 2 leaves NaN = "NA" */);
     }
-    out.cfdon[o] = score;
+    const double score = row_cfdon(gp, has_ref, core, rcore, s, geom, s_cfd, status);
+    cols_store(out, row0 + i, h, q, s, start, stop, has_ref, win, score, p, status);
   }
 }
 

@@ -1,6 +1,7 @@
 // hawk_vc.h - device helpers of the searches that run straight from an expansion plan (hawk_vsearch.hip: per dirty word of
 // every row; hawk_csearch.hip: per distinct variant cluster): 96-bit strings of the five planes built in registers from REF
-// and the carried-variant records, the PAM match on them, REF's hit-prefix tables for the clean stretches.
+// and the carried-variant records, the PAM match on them, REF's hit-prefix tables for the clean stretches.  What a surviving
+// window start of those strings becomes is in hawk_rows.h, shared with the plane search (hawk_search.hip).
 #pragma once
 #include "hawk_hx.h"
 #include "hawk_rows.h"
@@ -15,8 +16,6 @@ __device__ __forceinline__ uint32_t ext32_glb(const uint32_t* __restrict__ row, 
   const U2 t = *reinterpret_cast<const U2*>(row + (bp >> 5));
   return fsh(t.a, t.b, bp & 31u);
 }
-// 64 bits starting at bit `off` (0 <= off < 32) of a 96-bit string held as three words
-__device__ __forceinline__ W2 ext96(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t off) { return W2{fsh(x0, x1, off), fsh(x1, x2, off)}; }
 // position of the j-th set bit of x (j < popc(x)): halving search on popcounts
 __device__ __forceinline__ uint32_t select_bit(uint32_t x, uint32_t j) {
   uint32_t bpos = 0;

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
     first -= back < VC_BACK ? back : VC_BACK;
   }
   const int avail = (int)(vrecs + va.hv_off[h + 1] - first);  // the row's records from `first` on
-  const int L = p.L;
+  const RowGeom geom = row_geom(p, gp);
+  const int L = geom.L;
   if (tid == 0) s_n = 0;
   if (tid < 32) s_bm[tid] = 0;
   __syncthreads();
@@ -155,11 +156,6 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
     rg.lo[1] = rg.slo[1] > qmin ? rg.slo[1] : qmin; rg.hi[1] = rg.shi[1] < qmax ? rg.shi[1] : qmax;
   }
   const int poF = p.right ? 0 : p.guidelen, poR = p.right ? p.guidelen : 0;
-  const uint32_t mlo = L >= 32 ? 0xffffffffu : ((1u << L) - 1u), mhi = L <= 32 ? 0u : ((1u << (L - 32)) - 1u);
-  const int W = L + 2 * HAWK_PAD;
-  const uint32_t whi = W >= 64 ? 0xffffffffu : ((1u << (W - 32)) - 1u);  // W = L + 20 > 32
-  const int ncfd = gp.guidelen < 20 ? gp.guidelen : 20;
-  const uint32_t cfdmask = (1u << ncfd) - 1u;
   // the REF planes for the general word builder; reads of bits no word keeps are clamped
   auto ref32 = [&](int pl, uint32_t r) -> uint32_t {
     const uint32_t w = (r >> 5) < va.ref_S - 2 ? (r >> 5) : va.ref_S - 2;
@@ -271,17 +267,18 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
     // by round trips per resident wave, not by bytes or instructions.
 #pragma unroll 1
     for (uint32_t base = 0; base < T; base += 2 * VC_BLOCK) {
-      uint32_t valid[2] = {0, 0}, sst[2] = {0, 0}, qq[2] = {0, 0}, qrr[2] = {0, 0};
+      uint32_t valid[2] = {0, 0}, sst[2] = {0, 0}, qq[2] = {0, 0};
       int64_t startv[2] = {0, 0};
-      bool inrv[2] = {false, false}, has_refv[2] = {false, false};
+      bool has_refv[2] = {false, false};
       W2 win[2][5], core[2][4], rcore[2][4];
-      uint32_t rw[2] = {0, 0};
+      RefProbe pr[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
 #pragma unroll
         for (int pl = 0; pl < 5; ++pl) win[u][pl] = W2{0, 0};
 #pragma unroll
-        for (int pl = 0; pl < 4; ++pl) { core[u][pl] = W2{0, 0}; rcore[u][pl] = W2{0, 0}; }
+        for (int pl = 0; pl < 4; ++pl) { core[u][pl] = W2{0, 0}; pr[u].rcore[pl] = W2{0, 0}; }
+        pr[u].inr = false; pr[u].qr = 0; pr[u].rw = 0;
       }
       // LDS work of both survivors, then every gather of both
 #pragma unroll
@@ -297,51 +294,17 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
           for (uint32_t step = VC_SLOTS / 2; step; step >>= 1) slot += (((s_ex[slot + step] >> sh16) & 0xffffu) <= target) ? step : 0u;
           const uint32_t bpos = select_bit(s_kw[s][slot], target - ((s_ex[slot] >> sh16) & 0xffffu));
           const uint32_t q = tile_q0 + 32u * s_wl[slot] + bpos;
-          int64_t start;
-          if (ovf) {
-            start = posmap_global(hs, h, q);
-          } else {
-            uint32_t sj = 0;
-#pragma unroll
-            for (uint32_t step = NSEG / 2; step; step >>= 1) sj += (s_segrel[sj + step] <= q) ? step : 0u;
-            start = s_seggen[sj] + (int64_t)(q - s_segrel[sj]);
-          }
+          const int64_t start = ovf ? posmap_global(hs, h, q) : posmap_staged(s_segrel, s_seggen, q);
           // the padded window [q - PAD, q + L + PAD) sits at bits [bpos, bpos + W) of the slot's string
-#pragma unroll
-          for (int pl = 0; pl < 5; ++pl) {
-            win[u][pl] = ext96(s_str[pl][0][slot], s_str[pl][1][slot], s_str[pl][2][slot], bpos);
-            win[u][pl].hi &= whi;
-            if (pl < 4) {
-              core[u][pl].lo = fsh(win[u][pl].lo, win[u][pl].hi, HAWK_PAD) & mlo;
-              core[u][pl].hi = (win[u][pl].hi >> HAWK_PAD) & mhi;
-            }
-          }
-          // a REF guide shares (start, strand) iff REF has a candidate window starting at qr = start - startp (k_ref_bits);
-          // the row is redundant iff the four code planes agree as well (search_guides.py:340-369).  REF's core is fetched
-          // whether or not the bit turns out set: one round trip instead of two.
-          const int64_t qr64 = start - ri.startp;
-          const bool inr = qr64 >= 0 && qr64 < (int64_t)ri.n_bits;
-          const uint32_t qr = inr ? (uint32_t)qr64 : 0u;
-          rw[u] = (s ? ri.bits[1] : ri.bits[0])[qr >> 5];
-#pragma unroll
-          for (int pl = 0; pl < 4; ++pl) rcore[u][pl] = ext_glb(va.ref[pl], qr);
-          sst[u] = s; qq[u] = q; qrr[u] = qr; startv[u] = start; inrv[u] = inr;
+          row_slices([&](int pl, int k) { return s_str[pl][k][slot]; }, bpos, geom, win[u], core[u]);
+          pr[u] = ref_probe(ri, va.ref, start, s);  // both survivors' probes before either verdict
+          sst[u] = s; qq[u] = q; startv[u] = start;
           valid[u] = i < T ? 1u : 0u;
         }
       }
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const bool has_ref = inrv[u] && ((rw[u] >> (qrr[u] & 31u)) & 1u);
-        bool same = has_ref;
-#pragma unroll
-        for (int pl = 0; pl < 4; ++pl) {
-          rcore[u][pl].lo &= mlo; rcore[u][pl].hi &= mhi;
-          same = same && rcore[u][pl].lo == core[u][pl].lo && rcore[u][pl].hi == core[u][pl].hi;
-          if (!has_ref) rcore[u][pl] = core[u][pl];
-        }
-        has_refv[u] = has_ref;
-        if (same) valid[u] = 0;
-      }
+      for (int u = 0; u < 2; ++u)
+        if (ref_verdict(pr[u], core[u], geom, rcore[u], has_refv[u])) valid[u] = 0;
       if (PASS == 0) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -360,36 +323,10 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
           if (!valid[u]) continue;
           const uint32_t s = sst[u], q = qq[u];
           const uint32_t rk = u == 0 ? (s ? (ex >> 8) & 0xffu : ex & 0xffu) : (s ? t0R + (ex >> 24) : t0F + ((ex >> 16) & 0xffu));
-          const uint64_t o = (s ? row1 : row0) + rk;
-          if (o >= out.cap) {
-            atomicExch(status, -3 /* HAWK_E_CAPACITY: offsets and counts disagree */);
-            continue;
-          }
-          int64_t stop;  // search_guides.py:260-280: stop = posmap[q + L]
-          if (ovf) {
-            stop = posmap_global(hs, h, q + (uint32_t)L);
-          } else {
-            uint32_t sj = 0;
-#pragma unroll
-            for (uint32_t step = NSEG / 2; step; step >>= 1) sj += (s_segrel[sj + step] <= q + (uint32_t)L) ? step : 0u;
-            stop = s_seggen[sj] + (int64_t)(q + (uint32_t)L - s_segrel[sj]);
-          }
-          const bool pamfirst = (p.right != 0) != (s != 0);
-          out.hap[o] = h;
-          out.pos[o] = pamfirst ? q : q + (uint32_t)p.guidelen;
-          out.strand[o] = (uint8_t)s;
-          out.start[o] = startv[u];
-          out.stop[o] = stop;
-          out.flags[o] = has_refv[u] ? 1 : 0;
-#pragma unroll
-          for (int pl = 0; pl < HAWK_PLANES; ++pl) out.win[(size_t)pl * out.cap + o] = (uint64_t)win[u][pl].lo | ((uint64_t)win[u][pl].hi << 32);
-          double score = __longlong_as_double(0x7ff8000000000000ll);  // NaN -> "NA"
-          if (gp.score_cfdon && has_refv[u]) {
-            bool err;
-            score = cfdon_from_slices(core[u], rcore[u], s, L, cfdmask, s_cfd, err);
-            if (err && gp.score_cfdon == 1) atomicExch(status, -5 /* HAWK_E_CFD; score_cfdon == 2 leaves NaN = "NA" */);
-          }
-          out.cfdon[o] = score;
+          // search_guides.py:260-280: stop = posmap[q + L]
+          const int64_t stop = ovf ? posmap_global(hs, h, q + (uint32_t)L) : posmap_staged(s_segrel, s_seggen, q + (uint32_t)L);
+          const double score = row_cfdon(gp, has_refv[u], core[u], rcore[u], s, geom, s_cfd, status);
+          cols_store(out, (s ? row1 : row0) + rk, h, q, s, startv[u], stop, has_refv[u], win[u], score, p, status);
         }
         row0 += t0F + t1F; row1 += t0R + t1R;
       }

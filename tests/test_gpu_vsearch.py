@@ -168,6 +168,40 @@ def test_view_search_crowded_tiles_long_deletions_long_insertion():
     _same_table(reg, "NNGRRT", 21, False, cfd=False)
 
 
+def _long_cluster_region():
+    """~8 kb, 3 samples, sample 0 carrying every variant: a 400-nt insertion (its cluster owns ceil((400 + L - 1) / 32) = 14 words of
+    window starts at L = 23 - more than the 8 lanes of a cluster's group, so its rows are counted, then written, word by word), a
+    1 500-nt deletion, SNVs every 20 nt over 600 nt (closer than L - 1: one cluster of 30 records and more than 256 window starts
+    on the haplotype that carries them all) and a few isolated SNVs (short clusters: survivors dealt to the group's lanes)"""
+    reg = synth.make_region(8361, "chrL", 10_000, 1_000, 9_000)
+    rng = np.random.default_rng(8362)
+    seq = reg.contig_seq
+    reg.samples = [f"S{i:04d}" for i in range(3)]
+
+    def gt():
+        g = (rng.random((3, 2)) < 0.5).astype(np.uint8)
+        g[0, 0] = 1
+        return g
+
+    def snv(pos, step):
+        refb = seq[pos - 1]
+        return synth.VariantSite(pos, refb, "ACGT"[("ACGT".index(refb) + step) % 4], 0.5, gt())
+    sites = [snv(pos, 1) for pos in range(1_500, 2_100, 20)]
+    sites.append(synth.VariantSite(3_000, seq[2_999], seq[2_999] + "".join("ACGT"[b] for b in rng.integers(0, 4, 400)), 0.5, gt()))
+    sites.append(synth.VariantSite(4_000, seq[3_999:5_500], seq[3_999], 0.5, gt()))
+    sites += [snv(pos, 2) for pos in (5_800, 6_300, 6_800, 7_300)]  # (in front of where a row that carries the deletion ends)
+    reg.variants = sites
+    return reg
+
+
+def test_long_clusters_against_the_oracle():
+    # the plane path and the cluster path share their row rules (hawk_rows.h): a long cluster's table is held to the ORACLE, not
+    # only to the other path (test_view_search_crowded_tiles_... compares the two with each other)
+    reg = _long_cluster_region()
+    _same_table(reg, "NGG", 20, False, oracle=True)
+    _same_table(reg, "TTTV", 23, True, cfd=False, oracle=True)
+
+
 def test_view_search_variants_at_the_very_ends():
     # variants within the first / last bases of the region string: the first word's string has nothing in front of it
     reg = synth.make_region(8401, "chrE", 3000, 700, 1500)
