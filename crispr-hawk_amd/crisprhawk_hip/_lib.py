@@ -35,6 +35,7 @@ EXPORTS = [
     "hawk_xplan_destroy", "hawk_hapset_set_ref_partner_range", "hawk_xplan_set_ref_partner_range", "hawk_table_collapse_ex", "hawk_table_collapse_export", "hawk_comm_unique_id", "hawk_comm_init",
     "hawk_comm_destroy", "hawk_comm_last_error", "hawk_comm_allgather_u64", "hawk_comm_gatherv", "hawk_table_gather", "hawk_host_ragged_join", "hawk_host_tsv_write", "hawk_host_vcf_index", "hawk_host_polish_rows", "hawk_host_variant_window", "hawk_host_polish_windows", "hawk_host_group_join", "hawk_host_group_samples", "hawk_gbt_predict", "hawk_gt_from_codes",
     "hawk_annot_create", "hawk_annot_query", "hawk_annot_download", "hawk_annot_free", "hawk_xplan_text",
+    "hawk_offtarget_text", "hawk_offtarget_text_download", "hawk_host_offtarget_text",
 ]
 
 
@@ -86,6 +87,11 @@ class OtParams(C.Structure):
 class AnnotTiming(C.Structure):
     _fields_ = [("upload_ms", C.c_float), ("count_ms", C.c_float), ("scan_ms", C.c_float), ("fill_ms", C.c_float),
                 ("reserved", C.c_float), ("total_ms", C.c_float), ("out_bytes", C.c_uint64), ("walk_steps", C.c_uint64)]
+
+
+class OtTextTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("len_ms", C.c_float), ("scan_ms", C.c_float), ("fill_ms", C.c_float),
+                ("reserved", C.c_float), ("total_ms", C.c_float), ("out_bytes", C.c_uint64), ("n_rows", C.c_uint64)]
 
 
 class OtTiming(C.Structure):

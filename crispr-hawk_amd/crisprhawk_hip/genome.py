@@ -398,6 +398,89 @@ class GenomeIndex:
         return [self._bulge_hit(h, i, win, guides, int(h["guide"][i]), int(h["mm"][i]), int(h["gaps"][i]), Gs, b, dna, right)
                 for i in range(len(h["guide"]))]
 
+    # ---- the off-targets table without an object per site (hawk_offtarget_text) ------------------------------------------
+    OT_COLUMNS = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
+                  ("nmask", np.uint32), ("gaps", np.uint64), ("kind", np.uint8), ("size", np.uint8))
+
+    def offtarget_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int = 0, brna: int = 0, cap: int = 1 << 20):
+        """Every hit of `guides` as columns - one scan_arrays, one bulge_arrays per (type, size), concatenated with `kind`
+        (0 = X, 1 = DNA, 2 = RNA) and `size` columns (gaps = 0 for un-bulged hits) - in the order the product's file has: the
+        un-bulged hits in scan()'s order, then the bulged ones in scan_bulges()' order (guide, type, size, contig, position,
+        strand), by one lexsort of integer keys.  No OffTargetHit / BulgeHit is built.  The index's own window is put back."""
+        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
+            raise ValueError("bulges of 0..2 bases are enumerated")
+        if bdna > self.max_bulge:
+            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        guides = [g.upper() for g in guides]
+        parts = []
+        h, _tm = self.scan_arrays(guides, pam, right, max_mm, cap)
+        n0 = len(h["guide"])
+        parts.append(dict(h, gaps=np.zeros(n0, np.uint64), kind=np.zeros(n0, np.uint8), size=np.zeros(n0, np.uint8)))
+        self.last_bulge_timing = []
+        try:
+            for dna, bmax in ((True, bdna), (False, brna)):
+                for b in range(1, bmax + 1):
+                    hb, tm = self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)
+                    self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
+                    nb = len(hb["guide"])
+                    parts.append(dict(hb, kind=np.full(nb, 1 if dna else 2, np.uint8), size=np.full(nb, b, np.uint8)))
+        finally:
+            self._set_window(self.guidelen)
+        cols = {k: np.concatenate([pt[k] for pt in parts]).astype(t, copy=False) for k, t in self.OT_COLUMNS}
+        # rows of a contig ascend with their offsets and own disjoint starts: (row, q) orders as (contig, position) does
+        order = np.lexsort((cols["strand"], cols["q"], cols["row"], cols["size"], cols["kind"], cols["guide"], cols["kind"] != 0))
+        return {k: np.ascontiguousarray(v[order]) for k, v in cols.items()}
+
+    def row_table(self):
+        """(contig id uint32[rows], offset uint64[rows], names blob uint8[], name offsets uint64[contigs + 1], names) of ALL rows"""
+        t = getattr(self, "_row_table", None)
+        if t is None:
+            names = list(dict.fromkeys(r[0] for r in self.rows))
+            cid = {n: i for i, n in enumerate(names)}
+            enc = [n.encode("ascii") for n in names]
+            noff = np.zeros(len(enc) + 1, dtype=np.uint64)
+            np.cumsum([len(b) for b in enc], out=noff[1:])
+            blob = np.frombuffer(b"".join(enc), dtype=np.uint8) if noff[-1] else np.zeros(1, np.uint8)
+            t = self._row_table = (np.array([cid[r[0]] for r in self.rows], dtype=np.uint32), np.array([r[1] for r in self.rows], dtype=np.uint64),
+                                   blob, noff, names)
+        return t
+
+    def rows_text(self, arrays, guides: Sequence[str], pam, right: bool, order=None, cfd_tables=None):
+        """The hits of offtarget_arrays as rows of offtargets_*.tsv, written on the device (hawk_offtarget_text: k_ot_text_len,
+        the 64-bit scan, k_ot_text_fill): (reports.Ragged - row i = the eleven tab-joined fields of hit order[i], or of hit i -,
+        cfd_e4 int64[n] = the rows' CFD in units of 1e-4 or -1, n_unscorable).  `cfd_tables` = (mm[20,4,4], pam[16]) or None
+        (the cfd column is NA).  The rows come down into page-locked blocks (_lib.pinned_empty)."""
+        from .reports import Ragged
+        n = len(arrays["guide"])
+        cols = [np.ascontiguousarray(arrays[k], dtype=t) for k, t in self.OT_COLUMNS]
+        if any(len(c) != n for c in cols):
+            raise ValueError("rows_text: the hit columns disagree on their length")
+        g2 = encode_guides([g.upper() for g in guides])
+        rc, roff, nblob, noff, names = self.row_table()
+        od = None if order is None else np.ascontiguousarray(order, dtype=np.uint64)
+        if od is not None and len(od) != n:
+            raise ValueError("rows_text: `order` must name every row once")
+        mm = pt = None
+        if cfd_tables is not None:
+            mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
+            pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
+        device = self.ds.device if self.ds is not None else None
+        L, ctx = _lib.lib(), _lib.context(device)
+        par = _lib.OtParams(0, 0, len(pam), self.guidelen, int(bool(right)), 0)
+        nbytes, nuns, tm, dl = C.c_uint64(0), C.c_uint64(0), _lib.OtTextTiming(), C.c_float(0)
+        byname = dict(zip((k for k, _t in self.OT_COLUMNS), cols))
+        _lib.check(L.hawk_offtarget_text(ctx, C.c_uint64(n), *[_p(byname[k]) for k in ("guide", "row", "q", "strand", "mm", "code", "nmask", "gaps", "kind", "size")],
+                                         _p(g2), C.c_uint32(len(g2)), C.byref(par), _p(rc), _p(roff), C.c_uint32(len(rc)), _p(nblob), _p(noff),
+                                         C.c_uint32(len(names)), pam.pam.encode("ascii"),
+                                         _p(od), _p(mm), _p(pt), C.byref(nbytes), C.byref(nuns), C.byref(tm)), "hawk_offtarget_text")
+        off = _lib.pinned_empty(n + 1, np.uint64, device)
+        blob = _lib.pinned_empty(int(nbytes.value), np.uint8, device)
+        cfd = _lib.pinned_empty(n, np.int64, device)
+        _lib.check(L.hawk_offtarget_text_download(ctx, _p(blob), _p(off), _p(cfd), C.byref(dl)), "hawk_offtarget_text_download")
+        self.last_text_timing = {k: float(getattr(tm, k)) for k in ("upload_ms", "len_ms", "scan_ms", "fill_ms", "total_ms")}
+        self.last_text_timing.update(download_ms=float(dl.value), out_bytes=int(nbytes.value), n_rows=n)
+        return Ragged(blob, off), cfd, int(nuns.value)
+
     def hits_from_arrays(self, h) -> List["OffTargetHit"]:
         """Arrays of scan_arrays (of this rank, or gathered from every rank) -> sorted OffTargetHit list."""
         order = np.lexsort((h["strand"], h["q"], h["row"], h["guide"]))

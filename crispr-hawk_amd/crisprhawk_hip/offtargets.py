@@ -7,7 +7,11 @@ When only the guide report's two columns are wanted (``pipeline.search_files(off
 ``specificity_by_spacer`` takes them from ``GenomeIndex.summary``: the match kernels sum, per guide, the hits
 and their CFD rounded to 4 decimals as integers, and no site is listed, rendered, parsed or scored on the host.
 With `annotations` the off-targets table gets one column per BED file (offtargets.py:407-483), joined on the device
-(bedannot.AnnotTable: one handle per file and contig of the table).  Elevation is out of scope."""
+(bedannot.AnnotTable: one handle per file and contig of the table).  Elevation is out of scope.
+``estimate_offtargets_spacers`` - the stage as ``pipeline.search_files`` runs it - keeps the hits as columns from the scan to the
+file by default (``engine="device"``: ``GenomeIndex.offtarget_arrays`` / ``rows_text``, the rows' CFD and text written by
+``hawk_offtarget_text``); the route over one ``Offtarget`` per site is its ``engine="objects"`` and what ``search`` /
+``report_offtargets`` / ``estimate_offtargets``, the reference's signatures, run."""
 import os
 from typing import Dict, List, Set
 
@@ -241,11 +245,115 @@ def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen:
     return {sp: (int(c), str(round_score(100 / (100 + e4 / 1e4)))) for sp, c, e4 in zip(uniq, counts, sums)}
 
 
+def _annotation_columns_device(annotations, anncolnames, chrom_names, chrom_of_row, pos, stop, debug: bool, device=None):
+    """annotate_offtargets (offtargets.py:447-483) for rows sorted by (chrom, position), as columns: per file one Ragged, row =
+    the labels of the features overlapping (chrom, position, stop) or NA.  The rows of a contig are consecutive, so a file's
+    column is its per-contig query results back to back.  (names, columns)."""
+    from .bedannot import BedAnnotation
+    from .reports import Ragged
+    names = list(anncolnames) if anncolnames else [f"annotation_{i + 1}" for i in range(len(annotations))]
+    n = len(pos)
+    cuts = np.flatnonzero(np.diff(chrom_of_row)) + 1 if n else np.zeros(0, np.int64)
+    lo = np.concatenate([[0], cuts]).astype(np.int64) if n else np.zeros(0, np.int64)
+    hi = np.concatenate([cuts, [n]]).astype(np.int64) if n else np.zeros(0, np.int64)
+    out = []
+    for fann in annotations:
+        bedann = fann if isinstance(fann, BedAnnotation) else BedAnnotation(fann, 0, debug)
+        blobs, offs, base = [], [np.zeros(1, np.uint64)], 0
+        try:
+            for a, b in zip(lo.tolist(), hi.tolist()):
+                col = bedann.table(chrom_names[int(chrom_of_row[a])], 0, device).query(pos[a:b], stop[a:b])
+                nb = int(col.off[-1])
+                blobs.append(np.asarray(col.blob[:nb]))
+                offs.append(col.off[1:] + np.uint64(base))
+                base += nb
+        finally:
+            if bedann is not fann:
+                bedann.close()
+        out.append(Ragged(np.concatenate(blobs) if blobs else np.zeros(0, np.uint8), np.concatenate(offs)))
+    return names, out
+
+
+def _estimate_device(uniq, pam: PAM, genome: GenomeIndex, region, mm: int, bdna: int, brna: int, right: bool, outdir: str, debug: bool,
+                     annotations, anncolnames, device):
+    """estimate_offtargets_spacers on arrays: the hits stay columns from the scan to the file.  Returns None when a label or a
+    column name would need csv quoting (the caller takes the `objects` engine, which writes through pandas)."""
+    from .bedannot import plain_labels
+    from .crisprhawk_error import CrisprHawkCfdScoreError
+    from .reports import write_report_tsv
+    from .utils import round_score
+    if bdna < 0 or brna < 0 or bdna > 2 or brna > 2:
+        exception_handler(CrisprHawkOffTargetsError, f"DNA / RNA bulges of 0..2 bases are enumerated (got {bdna} / {brna})", os.EX_DATAERR, debug)
+    tables = None
+    if pam.cas_system in (SPCAS9, XCAS9):
+        from .scoring import _tables
+        tables = _tables(debug)
+    try:
+        arr = genome.offtarget_arrays(uniq, pam, right, mm, bdna, brna)
+    except ValueError as e:
+        exception_handler(CrisprHawkOffTargetsError, f"Off-targets search failed: {e}", os.EX_DATAERR, debug, e)
+    n = len(arr["guide"])
+    rc, roff, _nblob, _noff, names = genome.row_table()
+    # the table's order: (chrom as a string, position), ties in the order of the hits (pandas' stable two-key sort)
+    srank = np.empty(len(names), dtype=np.int64)
+    srank[np.array(sorted(range(len(names)), key=lambda i: names[i]), dtype=np.int64)] = np.arange(len(names))
+    chrom = rc[arr["row"]]
+    pos = (roff[arr["row"]] + arr["q"].astype(np.uint64)).astype(np.int64)
+    order = np.lexsort((pos, srank[chrom]))
+    text, cfd_rows, n_uns = genome.rows_text(arr, uniq, pam, right, order, tables)
+    if n_uns > 0:  # before any file is written
+        exception_handler(CrisprHawkCfdScoreError, "CFDon score calculation failed", os.EX_DATAERR, debug)
+    if outdir:
+        cols = {"\t".join(OTREPCNAMES): text}
+        if annotations:
+            glen = genome.guidelen + len(pam)
+            stop = pos + glen + np.where(arr["kind"] == 1, arr["size"], 0).astype(np.int64)  # + len(spacer field): '-' counts
+            anames, acols = _annotation_columns_device(annotations, anncolnames, names, chrom[order], pos[order], stop[order], debug, device)
+            if any(ch in x for x in anames for ch in '"\t\n\r') or not all(plain_labels(c) for c in acols):
+                return None
+            cols.update(zip(anames, acols))
+        fname = os.path.join(outdir, f"offtargets_{region.contig}_{region.start + PADDING}_{region.stop - PADDING}.tsv")
+        try:
+            if n == 0:
+                with open(fname, "w") as f:
+                    f.write("\t".join(cols) + "\n")
+            else:
+                write_report_tsv(fname, cols, np.arange(n, dtype=np.uint64))
+        except (OSError, RuntimeError) as e:
+            exception_handler(CrisprHawkOffTargetsError, f"Failed writing off-targets report for region {region}", os.EX_IOERR, debug, e)
+    # per guide: rows, and the CFD sum accumulated one row after the other in the order of the hits - Python's sum over the
+    # guide's Offtarget list, which numpy's pairwise sum does not reproduce in the last digit (cumsum is sequential)
+    cfd_hit = np.empty(n, dtype=np.int64)
+    cfd_hit[order] = cfd_rows
+    val = np.where(cfd_hit < 0, 0, cfd_hit) / 1e4
+    counts = np.bincount(arr["guide"], minlength=len(uniq))
+    by_guide = np.argsort(arr["guide"], kind="stable")
+    ends = np.cumsum(counts)
+    res = {}
+    for gi, sp in enumerate(uniq):
+        a, b = int(ends[gi] - counts[gi]), int(ends[gi])
+        tot = float(np.cumsum(val[by_guide[a:b]])[-1]) if b > a else 0
+        res[sp] = (int(counts[gi]), str(round_score(100 / (100 + tot))))
+    return res
+
+
 def estimate_offtargets_spacers(spacers, pam: PAM, crispritz_index, region, mm: int, bdna: int, brna: int, guidelen: int, right: bool,
-                                outdir: str, verbosity: int, debug: bool, annotations=None, anncolnames=None, device=None) -> Dict[str, tuple]:
+                                outdir: str, verbosity: int, debug: bool, annotations=None, anncolnames=None, device=None,
+                                engine: str = "device") -> Dict[str, tuple]:
     """estimate_offtargets for the columnar report (pipeline.search_files): the same stage - unique spacers -> device scan
-    -> CFD -> offtargets_*.tsv -> per-spacer aggregates - without Guide objects."""
+    -> CFD -> offtargets_*.tsv -> per-spacer aggregates - without Guide objects.
+    `engine`: "device" keeps the hits as columns from the scan to the file - GenomeIndex.offtarget_arrays, the rows' text and
+    CFD written by hawk_offtarget_text, the file by hawk_host_tsv_write, the aggregates from arrays; "objects" is the route
+    over one Offtarget per site (search -> report_offtargets -> offtargets_by_spacer).  Same file, same result; a label or
+    column name csv quoting reacts to sends the device engine's call to "objects"."""
+    if engine not in ("device", "objects"):
+        raise ValueError(f"engine {engine!r}: 'device' or 'objects'")
     uniq = sorted({sp.upper() for sp in spacers})
+    if engine == "device" and uniq:
+        crispritz_index = _genome_index(crispritz_index, guidelen, len(pam), bdna)
+        res = _estimate_device(uniq, pam, crispritz_index, region, mm, bdna, brna, right, outdir, debug, annotations or [], anncolnames or [], device)
+        if res is not None:
+            return res
     lines = search(_genome_index(crispritz_index, guidelen, len(pam), bdna), uniq, pam, right, mm, verbosity, debug, bdna, brna) if uniq else []
     ots = report_offtargets(lines, region, pam, guidelen, annotations or [], anncolnames or [], False, right, outdir, verbosity, debug, device)
     return offtargets_by_spacer(ots, uniq)

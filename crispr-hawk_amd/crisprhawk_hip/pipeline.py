@@ -103,7 +103,8 @@ def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir
         return specificity_by_spacer(spacers, pam, ot["genome"], ot["mm"], guidelen, right, debug)
     ann = ot.get("ann")
     return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug,
-                                       ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None)
+                                       ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None,
+                                       engine=ot.get("engine", "device"))
 
 
 def _plan_row_variants(info, vt) -> List[bytes]:

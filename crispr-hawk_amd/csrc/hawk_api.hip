@@ -165,6 +165,7 @@ void hawk_destroy(hawk_ctx* ctx) {
   }
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  hawk_ottext_forget(ctx);  // rows of a hawk_offtarget_text nobody downloaded
   for (auto& e : ctx->ev) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);

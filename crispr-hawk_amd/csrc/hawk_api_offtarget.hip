@@ -1,4 +1,4 @@
-// hawk_api_offtarget.hip - C ABI: the off-target scan (K7) and its per-guide summary
+// hawk_api_offtarget.hip - C ABI: the off-target scan (K7), its per-guide summary and its hits as the rows of the off-targets table
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -338,6 +338,152 @@ int hawk_offtarget_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint6
     else if (out_cfd_e4) memset(out_cfd_e4, 0, (size_t)n_guides * 8);
   }
   ot_timing(hs, f.nsites, timing, 5);
+  return HAWK_OK;
+}
+
+// ---------------------------------------------------------------------------- the off-targets table as text (hawk_ottext.hip)
+// The rows of the last hawk_offtarget_text of a context, in HBM until hawk_offtarget_text_download fetches them.
+namespace {
+struct OtTextState {
+  DevBuf off, out, cfd, partial, cnt;
+  uint64_t n = 0, bytes = 0;
+  bool has_result = false;
+};
+std::mutex g_ott_mu;
+std::map<hawk_ctx*, OtTextState> g_ott;
+OtTextState* ott_state(hawk_ctx* ctx) {
+  std::lock_guard<std::mutex> g(g_ott_mu);
+  return &g_ott[ctx];
+}
+}  // namespace
+
+}  // extern "C"
+void hawk_ottext_forget(hawk_ctx* ctx) {
+  std::lock_guard<std::mutex> g(g_ott_mu);
+  auto it = g_ott.find(ctx);
+  if (it == g_ott.end()) return;
+  for (DevBuf* b : {&it->second.off, &it->second.out, &it->second.cfd, &it->second.partial, &it->second.cnt}) b->release();
+  g_ott.erase(it);
+}
+extern "C" {
+
+int hawk_offtarget_text(hawk_ctx* ctx, uint64_t n, const uint32_t* guide, const uint32_t* row, const uint32_t* q, const uint8_t* strand,
+                        const uint8_t* mm, const uint64_t* code, const uint32_t* nmask, const uint64_t* gaps, const uint8_t* kind,
+                        const uint8_t* size, const uint64_t* guides2, uint32_t n_guides, const hawk_ot_params* p,
+                        const uint32_t* row_contig, const uint64_t* row_off, uint32_t n_table_rows, const uint8_t* name_blob,
+                        const uint64_t* name_off, uint32_t n_contigs, const char* pam_text, const uint64_t* order, const double* cfd_mm,
+                        const double* cfd_pam, uint64_t* n_bytes, uint64_t* n_unscorable, hawk_ot_text_timing* timing) {
+  if (!ctx || !p || !n_bytes || !n_unscorable || !cfd_mm != !cfd_pam || (p->pamlen && !pam_text)) return HAWK_E_INVALID;
+  if (n && (!guides2 || !row_off)) return HAWK_E_INVALID;
+  if (p->guidelen == 0 || p->guidelen > 32 || p->guidelen + p->pamlen > 32) return HAWK_E_UNSUPPORTED;  // a window code is 2 bits x 32
+  if (cfd_mm && p->pamlen < 2) return HAWK_E_UNSUPPORTED;  // as hawk_offtarget_summary: the PAM table is keyed by PAM[-2:]
+  OtTextFmt fmt;
+  memset(&fmt, 0, sizeof(fmt));
+  fmt.G = p->guidelen; fmt.P = p->pamlen; fmt.right = p->right ? 1u : 0u;
+  for (uint32_t k = 0; k < p->pamlen; ++k) fmt.pam[k] = (uint8_t)pam_text[k];
+  // every index a kernel would follow is checked here, before anything is written
+  const OtTextCols cols = {guide, row, q, nmask, code, gaps, strand, mm, kind, size};
+  if (!ot_text_check(n, cols, fmt, n_guides, row_contig, n_table_rows, name_blob, name_off, n_contigs, order)) return HAWK_E_INVALID;
+  OtTextState* S = ott_state(ctx);
+  S->has_result = false;
+  *n_bytes = 0;
+  *n_unscorable = 0;
+  if (timing) memset(timing, 0, sizeof(*timing));
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  hipEvent_t* ev = ctx->ev;
+  int rc;
+  if ((rc = S->off.reserve((n + 1) * 8)) || (rc = S->cfd.reserve(std::max<uint64_t>(n, 1) * 8)) ||
+      (rc = S->partial.reserve(std::max<uint64_t>(hawk_ann_scan_blocks(n), 1) * 8)) || (rc = S->cnt.reserve(8)))
+    return rc;
+  if (!n) {
+    HIPCHK(hipMemsetAsync(S->off.p, 0, 8, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S->n = 0; S->bytes = 0; S->has_result = true;
+    return HAWK_OK;
+  }
+  // the inputs of this call: back to the pool when it returns (the stream is drained by then)
+  PoolScope tmp;
+  OtTextDev A;
+  memset(&A, 0, sizeof(A));
+  A.fmt = fmt;
+  A.n = n;
+  const uint64_t nbytes_names = name_off[n_contigs];
+  uint32_t *d_guide, *d_row, *d_q, *d_nmask, *d_rc;
+  uint64_t *d_code, *d_gaps, *d_order = nullptr, *d_g2, *d_roff, *d_noff;
+  uint8_t *d_strand, *d_mm, *d_kind, *d_size, *d_names;
+  double* d_tab = nullptr;
+  TEMPCHK(tmp, &d_guide, n * 4); TEMPCHK(tmp, &d_row, n * 4); TEMPCHK(tmp, &d_q, n * 4); TEMPCHK(tmp, &d_nmask, n * 4);
+  TEMPCHK(tmp, &d_code, n * 8); TEMPCHK(tmp, &d_gaps, n * 8);
+  TEMPCHK(tmp, &d_strand, n); TEMPCHK(tmp, &d_mm, n); TEMPCHK(tmp, &d_kind, n); TEMPCHK(tmp, &d_size, n);
+  if (order) TEMPCHK(tmp, &d_order, n * 8);
+  TEMPCHK(tmp, &d_g2, (size_t)n_guides * 8);
+  TEMPCHK(tmp, &d_rc, (size_t)n_table_rows * 4); TEMPCHK(tmp, &d_roff, (size_t)n_table_rows * 8);
+  TEMPCHK(tmp, &d_names, std::max<uint64_t>(nbytes_names, 1)); TEMPCHK(tmp, &d_noff, ((size_t)n_contigs + 1) * 8);
+  if (cfd_mm) TEMPCHK(tmp, &d_tab, 336 * 8);
+  HIPCHK(hipMemsetAsync(S->cnt.p, 0, 8, st));
+  HIPCHK(hipEventRecord(ev[0], st));
+#define OTT_UP(dstp, srcp, bytes) HIPCHK(hipMemcpyAsync((dstp), (srcp), (bytes), hipMemcpyHostToDevice, st))
+  OTT_UP(d_guide, guide, n * 4); OTT_UP(d_row, row, n * 4); OTT_UP(d_q, q, n * 4); OTT_UP(d_nmask, nmask, n * 4);
+  OTT_UP(d_code, code, n * 8); OTT_UP(d_gaps, gaps, n * 8);
+  OTT_UP(d_strand, strand, n); OTT_UP(d_mm, mm, n); OTT_UP(d_kind, kind, n); OTT_UP(d_size, size, n);
+  if (order) OTT_UP(d_order, order, n * 8);
+  OTT_UP(d_g2, guides2, (size_t)n_guides * 8);
+  OTT_UP(d_rc, row_contig, (size_t)n_table_rows * 4); OTT_UP(d_roff, row_off, (size_t)n_table_rows * 8);
+  if (nbytes_names) OTT_UP(d_names, name_blob, nbytes_names);
+  OTT_UP(d_noff, name_off, ((size_t)n_contigs + 1) * 8);
+  if (cfd_mm) { OTT_UP(d_tab, cfd_mm, 320 * 8); OTT_UP(d_tab + 320, cfd_pam, 16 * 8); }
+#undef OTT_UP
+  A.guide = d_guide; A.row = d_row; A.q = d_q; A.nmask = d_nmask; A.code = d_code; A.gaps = d_gaps;
+  A.strand = d_strand; A.mm = d_mm; A.kind = d_kind; A.size = d_size; A.order = d_order; A.guides2 = d_g2;
+  A.row_contig = d_rc; A.row_off = d_roff; A.names = d_names; A.name_off = d_noff; A.tab = d_tab;
+  HIPCHK(hipEventRecord(ev[1], st));
+  hawk_launch_ot_text_len(st, A, S->off.as<uint64_t>(), S->cfd.as<int64_t>(), S->cnt.as<unsigned long long>());
+  HIPCHK(hipEventRecord(ev[2], st));
+  hawk_launch_ann_offsets(st, S->off.as<uint64_t>(), n, S->partial.as<uint64_t>());
+  HIPCHK(hipEventRecord(ev[3], st));
+  HIPCHK(hipGetLastError());
+  uint64_t tot[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(&tot[0], S->off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&tot[1], S->cnt.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // the blob's size decides its allocation
+  if ((rc = S->out.reserve(std::max<uint64_t>(tot[0], 1)))) return rc;
+  HIPCHK(hipEventRecord(ev[4], st));
+  hawk_launch_ot_text_fill(st, A, S->off.as<uint64_t>(), S->out.as<uint8_t>());
+  HIPCHK(hipEventRecord(ev[5], st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  S->n = n; S->bytes = tot[0]; S->has_result = true;
+  *n_bytes = tot[0];
+  *n_unscorable = tot[1];
+  if (timing) {
+    (void)hipEventElapsedTime(&timing->upload_ms, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&timing->len_ms, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&timing->scan_ms, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&timing->fill_ms, ev[4], ev[5]);
+    (void)hipEventElapsedTime(&timing->total_ms, ev[0], ev[5]);
+    timing->out_bytes = tot[0];
+    timing->n_rows = n;
+  }
+  return HAWK_OK;
+}
+
+int hawk_offtarget_text_download(hawk_ctx* ctx, uint8_t* blob, uint64_t* off, int64_t* cfd_e4, float* download_ms) {
+  if (!ctx || !off) return HAWK_E_INVALID;
+  OtTextState* S = ott_state(ctx);
+  if (!S->has_result || (S->bytes && !blob) || (S->n && !cfd_e4)) return HAWK_E_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  if (S->bytes) HIPCHK(hipMemcpyAsync(blob, S->out.p, S->bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(off, S->off.p, (S->n + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (S->n) HIPCHK(hipMemcpyAsync(cfd_e4, S->cfd.p, S->n * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (download_ms) (void)hipEventElapsedTime(download_ms, ctx->ev[0], ctx->ev[1]);
+  // the workspace goes back to the caching allocator: the table of a bulged search is tens of MB
+  S->has_result = false;
+  S->out.release(); S->off.release(); S->cfd.release(); S->partial.release();
   return HAWK_OK;
 }
 

@@ -366,3 +366,25 @@ void hawk_launch_ann_count(hipStream_t st, const AnnDev& A, const int64_t* qs, c
 // off[nq + 1] <- exclusive 64-bit sums of off[0..nq), in place
 void hawk_launch_ann_offsets(hipStream_t st, uint64_t* off, uint64_t nq, uint64_t* partial);
 void hawk_launch_ann_fill(hipStream_t st, const AnnDev& A, const int64_t* qs, const int64_t* qe, uint64_t nq, const uint64_t* off, uint8_t* out);
+
+// ---- the off-targets table as text (hawk_ottext.hip; the row itself: ot_text_row, hawk_ottext.h)
+#include "hawk_ottext.h"
+struct OtTextDev {
+  // the hit columns, n records (device)
+  const uint32_t *guide, *row, *q, *nmask;
+  const uint64_t *code, *gaps;
+  const uint8_t *strand, *mm, *kind, *size;
+  const uint64_t* order;       // output row i = record order[i]; NULL: input order
+  const uint64_t* guides2;     // the guides' 2-bit codes
+  const uint32_t* row_contig;  // per genome row: contig id ...
+  const uint64_t* row_off;     // ... and offset on it
+  const uint8_t* names;        // contig c = names[name_off[c], name_off[c + 1])
+  const uint64_t* name_off;
+  const double* tab;           // mm[20][4][4] + pam[16], or NULL
+  OtTextFmt fmt;
+  uint64_t n;
+};
+// len[i] <- bytes of output row i, cfd_e4[i] <- its CFD in 1e-4 units (-1: NA or unscorable), *n_unscorable += the unscorable rows
+void hawk_launch_ot_text_len(hipStream_t st, const OtTextDev& A, uint64_t* len, int64_t* cfd_e4, unsigned long long* n_unscorable);
+// row i at out[off[i], off[i + 1]) (off: the exclusive sums of len, off[n] = bytes of the blob)
+void hawk_launch_ot_text_fill(hipStream_t st, const OtTextDev& A, const uint64_t* off, uint8_t* out);

@@ -225,6 +225,7 @@ inline bool hawk_table_stale(const hawk_table* t) { return t->hs && t->gen != t-
 int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c);
 
 // shared by the C-ABI translation units (hawk_api_*.hip)
+void hawk_ottext_forget(hawk_ctx* ctx);  // hawk_api_offtarget.hip: the context's undelivered hawk_offtarget_text result goes back to the pool
 int hapset_create_impl(hawk_ctx* ctx, uint32_t n_hap, const uint32_t* hap_len, bool zero_planes, hawk_hapset** out, bool alloc_planes = true);
 HapSetDev make_dev(const hawk_hapset* hs);
 int make_scan_params(const hawk_hapset* hs, uint64_t pam_fwd, uint64_t pam_rev, uint32_t pamlen, uint32_t guidelen,

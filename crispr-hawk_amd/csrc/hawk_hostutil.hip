@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/hawk.h"
+#include "hawk_ottext.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -664,6 +665,57 @@ int hawk_host_polish_windows(uint64_t n, uint32_t L, const uint8_t* cores, const
   });
   if (bad.load()) return HAWK_E_INVALID;
   polish_compact(n, cand_off, cnt, out_off, out_var);
+  return HAWK_OK;
+}
+
+
+// ---- the rows of the off-targets table on the host ---------------------------------------------------------------------------
+// hawk_offtarget_text without a device: the same checks, the same ot_text_row (hawk_ottext.h), one thread.  It is what holds the
+// emitter to the fixtures on a machine without a GPU; the product writes its table through the kernels.
+int hawk_host_offtarget_text(uint64_t n, const uint32_t* guide, const uint32_t* row, const uint32_t* q, const uint8_t* strand,
+                             const uint8_t* mm, const uint64_t* code, const uint32_t* nmask, const uint64_t* gaps, const uint8_t* kind,
+                             const uint8_t* size, const uint64_t* guides2, uint32_t n_guides, const hawk_ot_params* p,
+                             const uint32_t* row_contig, const uint64_t* row_off, uint32_t n_table_rows, const uint8_t* name_blob,
+                             const uint64_t* name_off, uint32_t n_contigs, const char* pam_text, const uint64_t* order,
+                             const double* cfd_mm, const double* cfd_pam, uint8_t* blob, uint64_t blob_cap, uint64_t* off, int64_t* cfd_e4,
+                             uint64_t* n_bytes, uint64_t* n_unscorable) {
+  if (!p || !off || !n_bytes || !n_unscorable || !cfd_mm != !cfd_pam || (p->pamlen && !pam_text)) return HAWK_E_INVALID;
+  if (n && (!guides2 || !row_off || !cfd_e4)) return HAWK_E_INVALID;
+  if (p->guidelen == 0 || p->guidelen > 32 || p->guidelen + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
+  if (cfd_mm && p->pamlen < 2) return HAWK_E_UNSUPPORTED;
+  OtTextFmt fmt;
+  memset(&fmt, 0, sizeof(fmt));
+  fmt.G = p->guidelen; fmt.P = p->pamlen; fmt.right = p->right ? 1u : 0u;
+  for (uint32_t k = 0; k < p->pamlen; ++k) fmt.pam[k] = (uint8_t)pam_text[k];
+  const OtTextCols cols = {guide, row, q, nmask, code, gaps, strand, mm, kind, size};
+  if (!ot_text_check(n, cols, fmt, n_guides, row_contig, n_table_rows, name_blob, name_off, n_contigs, order)) return HAWK_E_INVALID;
+  double tab[336];
+  if (cfd_mm) { memcpy(tab, cfd_mm, 320 * sizeof(double)); memcpy(tab + 320, cfd_pam, 16 * sizeof(double)); }
+  const double* tb = cfd_mm ? tab : nullptr;
+  // the length pass and the fill pass: one function, two sinks
+  auto emit = [&](uint64_t i, auto& sink) {
+    const OtTextRec r = ot_text_rec(cols, order ? order[i] : i);
+    const uint32_t c = row_contig[r.row];
+    return ot_text_row(r, guides2[r.guide], name_blob + name_off[c], name_off[c + 1] - name_off[c], row_off[r.row] + r.q, fmt, tb, sink);
+  };
+  uint64_t total = 0, uns = 0;
+  off[0] = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    OtTextCount cnt;
+    const long long u = emit(i, cnt);
+    cfd_e4[i] = u < 0 ? -1 : u;
+    uns += u == OT_TEXT_UNSCORABLE;
+    total += cnt.n;
+    off[i + 1] = total;
+  }
+  *n_bytes = total;
+  *n_unscorable = uns;
+  if (!blob || blob_cap < total) return total ? HAWK_E_CAPACITY : HAWK_OK;
+  for (uint64_t i = 0; i < n; ++i) {
+    OtTextBytes w;
+    w.w = blob + off[i];
+    (void)emit(i, w);
+  }
   return HAWK_OK;
 }
 

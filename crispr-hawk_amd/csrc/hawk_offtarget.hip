@@ -119,18 +119,8 @@ struct OtListSink {
   }
 };
 
-// round(x, 4) of Python as an integer number of 1e-4 units: the nearest integer to the EXACT product x * 1e4, exact ties to
-// even (float_round -> dtoa mode 3 is correctly rounded on the binary value).  With k = floor(fl(x * 1e4)) the answer is k or
-// k + 1, decided by the sign of x * 1e4 - (k + 0.5), which one fma gives exactly in sign (the difference of two doubles below
-// 2^53 is far above the underflow range, so a non-zero exact residual never rounds to zero); zero is a true tie.
-__device__ __forceinline__ long long ot_round_e4(double x) {
-  const double k = floor(x * 1e4);
-  const double r = fma(x, 1e4, -(k + 0.5));
-  const long long ki = (long long)k;
-  if (r > 0.0) return ki + 1;
-  if (r < 0.0) return ki;
-  return ki + (ki & 1);
-}
+// ot_round_e4 - round(x, 4) of Python as an integer number of 1e-4 units - is hawk_ottext.h's: the rows of the off-targets table
+// round with the same function.
 
 // The summary's sink.  Per hit: hist[guide][mm] += 1 and, with tables, cfd_e4[guide] += round(CFD(guide, site), 4) * 1e4 with the CFD
 // formed as compute_cfd forms it (cfdscore.py:53-95; the string form is k_cfd, hawk_kernels.hip): a left-to-right fp64 product

@@ -495,6 +495,55 @@ int hawk_offtarget_summary(hawk_hapset* rows, const hawk_ot_params* p, const uin
                            const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
                            uint64_t* n_hits, uint64_t* n_unscorable, hawk_ot_timing* timing);
 
+/* The hits of hawk_offtarget_scan / hawk_offtarget_bulges as the rows of offtargets_{contig}_{start}_{stop}.tsv (offtargets.py:
+ * 41-53, 530-544), written on the device: per row the eleven fields chrom, position, strand, grna, spacer, pam, mm, bulge_size,
+ * bulg_type, cfd, elevation joined by tabs, no newline - byte for byte what the package's host chain prints for the hit
+ * (GenomeIndex._bulge_hit / hits_from_arrays -> crispritz_bulge_line / crispritz_report_line -> Offtarget.report_line -> the
+ * float columns of offtargets_table).  One statement of the row serves device and host (csrc/hawk_ottext.h).
+ *   records     n entries per column (host arrays): guide, row, q, strand, mm, code, nmask as the scans return them, gaps (0 for
+ *               un-bulged hits), kind 0 = X / 1 = DNA / 2 = RNA, size 0 / 1..2.  The window (code / nmask) has Gs + pamlen bases,
+ *               Gs = guidelen + size (DNA), guidelen - size (RNA) or guidelen; p->guidelen is the GUIDE's length.
+ *   guides2     the guides' 2-bit codes (n_guides); p: pamlen, guidelen, right (pam_fwd / pam_rev / max_mm are not read)
+ *   row table   row_contig[r] / row_off[r]: contig id and 64-bit offset of genome row r (n_table_rows); position = row_off + q
+ *   contigs     contig c's name is name_blob[name_off[c], name_off[c + 1]) (n_contigs)
+ *   pam_text    the NOMINAL PAM, pamlen bytes: the pam field, and the PAM of the grna field (in front when p->right)
+ *   order       optional: output row i is record order[i] (any order, repeats allowed); NULL keeps input order
+ *   cfd_mm / cfd_pam   mm[20][4][4] + pam[16] as hawk_cfd takes them, or both NULL: the cfd field is NA
+ * cfd: compute_cfd as hawk_cfd forms it on the row's own strings - a left-to-right fp64 product over the first min(columns, 20)
+ * ALIGNMENT columns, those with equal bases or a '-' on either side skipped, the table's position being the alignment column (a
+ * DNA bulge moves every later mismatch by one), times the entry of the spacer field's last two characters - rounded as Python's
+ * round(x, 4) and printed as repr() prints the rounded value (0.0, 1.0, 0.0312, 12.3456).  A row with an ambiguous base under a
+ * lookup (hawk_cfd's HAWK_E_CFD) prints NA and is counted in *n_unscorable.  elevation is NA.
+ * The rows stay in HBM: *n_bytes = bytes of their blob.  hawk_offtarget_text_download copies them into the caller's buffers -
+ * blob[n_bytes], off = uint64[n + 1] (row i = blob[off[i], off[i + 1])), cfd_e4 = int64[n], the rows' CFD in units of 1e-4
+ * (-1: NA or unscorable) - and returns the workspace to the caching allocator; once per hawk_offtarget_text of the context.
+ * n = 0 is HAWK_OK (an empty blob, off[0] = 0).  All offsets are 64 bits.  HAWK_E_INVALID, with nothing written and the context
+ * usable as before: kind or size out of range (or a bulge without size / a size without bulge), gaps with a bit outside the
+ * interior positions 1 .. span - 2 (span = Gs for DNA, guidelen for RNA bulges) or a popcount that is not size, a window beyond 32
+ * bases, a guide index >= n_guides, a row index >= n_table_rows, a contig id >= n_contigs, an order entry >= n.
+ * HAWK_E_UNSUPPORTED: guidelen + pamlen > 32, CFD tables with pamlen < 2. */
+typedef struct {
+  float upload_ms, len_ms, scan_ms, fill_ms, reserved, total_ms; /* HIP events around the stages of one call */
+  uint64_t out_bytes, n_rows;
+} hawk_ot_text_timing;
+int hawk_offtarget_text(hawk_ctx* ctx, uint64_t n, const uint32_t* guide, const uint32_t* row, const uint32_t* q, const uint8_t* strand,
+                        const uint8_t* mm, const uint64_t* code, const uint32_t* nmask, const uint64_t* gaps, const uint8_t* kind,
+                        const uint8_t* size, const uint64_t* guides2, uint32_t n_guides, const hawk_ot_params* p,
+                        const uint32_t* row_contig, const uint64_t* row_off, uint32_t n_table_rows, const uint8_t* name_blob,
+                        const uint64_t* name_off, uint32_t n_contigs, const char* pam_text, const uint64_t* order, const double* cfd_mm,
+                        const double* cfd_pam, uint64_t* n_bytes, uint64_t* n_unscorable, hawk_ot_text_timing* timing);
+int hawk_offtarget_text_download(hawk_ctx* ctx, uint8_t* blob, uint64_t* off, int64_t* cfd_e4, float* download_ms);
+/* The same rows made on the host by the same function, single-threaded, no device (the CPU tests hold the statement to the
+ * fixtures with it).  Same arguments, checks and statuses; off[n + 1], cfd_e4[n], *n_bytes and *n_unscorable are always written,
+ * the bytes when `blob` is non-NULL and blob_cap suffices - else HAWK_E_CAPACITY with the required size in *n_bytes. */
+int hawk_host_offtarget_text(uint64_t n, const uint32_t* guide, const uint32_t* row, const uint32_t* q, const uint8_t* strand,
+                             const uint8_t* mm, const uint64_t* code, const uint32_t* nmask, const uint64_t* gaps, const uint8_t* kind,
+                             const uint8_t* size, const uint64_t* guides2, uint32_t n_guides, const hawk_ot_params* p,
+                             const uint32_t* row_contig, const uint64_t* row_off, uint32_t n_table_rows, const uint8_t* name_blob,
+                             const uint64_t* name_off, uint32_t n_contigs, const char* pam_text, const uint64_t* order,
+                             const double* cfd_mm, const double* cfd_pam, uint8_t* blob, uint64_t blob_cap, uint64_t* off, int64_t* cfd_e4,
+                             uint64_t* n_bytes, uint64_t* n_unscorable);
+
 /* ---- K4 stand-alone: compute_cfd() (scores/cfdscore/cfdscore.py:53-95) on n triples --------
  * wt / sg: n spacers of `len` characters each (host, contiguous, any case, T or U); pam2: n
  * two-character strings (the caller passes guide.pam[-2:], crisprhawk_scores.py:84-86).
