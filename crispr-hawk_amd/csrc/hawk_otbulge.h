@@ -1,5 +1,5 @@
-// hawk_otbulge.h - the placement selection of a bulged (site, guide) pair, shared by k_ot_bulge (hawk_otbulge.hip) and by host
-// code that wants to check it (plain C++: no device types).
+// hawk_otbulge.h - the placement selection of a bulged (site, guide) pair, shared by k_ot_bulge (hawk_otbulge.hip) and by the host
+// program that checks it against a plain walk over the placements (otbulge_check_main.cpp; plain C++: no device types).
 //
 // A bulge of b bases aligns a LONGER sequence of span = n + b positions (DNA bulge: the site spacer; RNA bulge: the guide) with a
 // SHORTER one of n positions (DNA: the guide; RNA: the site spacer); b interior positions 1 .. span - 2 of the longer one - the

@@ -183,3 +183,184 @@ def place(g: list, start: int, spacer: str, pam: str, right: bool, minus: bool) 
     w = "".join(_COMP[c] if c in _COMP else c for c in reversed(w)) if minus else w
     g[start:start + len(w)] = list(w)
     return len(w)
+
+
+# ---- the wave queue of k_ot_bulge without a device: which inputs fill it --------------------------------------------------------------
+def sites_np(genome: str, pam: str, right: bool, spacer: int):
+    """sites() as a list, the PAM test vectorised (tests/test_bulge_refs.py holds the two to each other)"""
+    import numpy as np
+    P, g = len(pam), genome.upper()
+    L = spacer + P
+    nw = len(g) - L + 1
+    if nw <= 0:
+        return []
+    a = np.frombuffer(g.encode("ascii"), dtype=np.uint8)
+    ok = [np.ones(nw, dtype=bool), np.ones(nw, dtype=bool)]
+    for k, q in enumerate(pam):
+        if q == "N":
+            continue
+        o = k if right else spacer + k  # strand 1: the window read backwards, base for base complemented
+        ok[0] &= np.isin(a[o:o + nw], [ord(c) for c in _IUPAC[q]])
+        ok[1] &= np.isin(a[L - 1 - o:L - 1 - o + nw], [ord(_COMP[c]) for c in _IUPAC[q]])
+    out = []
+    for w in np.flatnonzero(ok[0] | ok[1]).tolist():
+        for strand in (0, 1):
+            if ok[strand][w]:
+                win = g[w:w + L] if strand == 0 else revcomp(g[w:w + L])
+                out.append((w, strand, "".join(c if c in _CODE else "N" for c in (win[P:] if right else win[:spacer]))))
+    return out
+
+
+def device_site_order(contigs, pam: str, right: bool, spacer: int):
+    """(contig, start, strand, site spacer) of every site of an index over `contigs` in the order k_ot_sites writes the site
+    records of one launch: strand (+ first), then row - rows follow the contigs and their pieces - then window start"""
+    rows = [(strand, ci, w, name, sp) for ci, (name, seq) in enumerate(contigs.items()) for w, strand, sp in sites_np(seq, pam, right, spacer)]
+    return [(name, w, strand, sp) for strand, _ci, w, name, sp in sorted(rows)]
+
+
+def prune_survivors(site_spacers: Sequence[str], guides: Sequence[str], b: int, dna: bool, max_mm: int):
+    """bool [sites, guides]: prune_floor(shift_vectors(site, guide)) <= max_mm, for all pairs at once on numpy uint64 (two bits per
+    base, the fold to one bit per base at the even positions)"""
+    import numpy as np
+    G = len(guides[0])
+    n = G if dna else G - b
+    enc = [encode(sp) for sp in site_spacers]
+    spread = lambda v: sum(1 << (2 * j) for j in range(32) if (v >> j) & 1)
+    even = np.uint64(spread(low(n)))
+    gc = np.array([encode(g.upper())[0] for g in guides], dtype=np.uint64)[None, :]
+    acc = np.full((len(enc), len(guides)), even, dtype=np.uint64)
+    for k in range(b + 1):
+        sc = np.array([(c >> (2 * k)) if dna else c for c, _nm in enc], dtype=np.uint64)[:, None]
+        nk = np.array([spread((nm >> k) if dna else nm) for _c, nm in enc], dtype=np.uint64)[:, None]
+        x = (gc ^ sc) if dna else (sc ^ (gc >> np.uint64(2 * k)))
+        acc &= (x | (x >> np.uint64(1))) | nk
+    if hasattr(np, "bitwise_count"):
+        cnt = np.bitwise_count(acc)
+    else:
+        cnt = np.unpackbits(acc.view(np.uint8).reshape(acc.shape + (8,)), axis=-1).sum(axis=-1)
+    return cnt <= max_mm
+
+
+def queue_walk(site_spacers: Sequence[str], guides: Sequence[str], b: int, dna: bool, max_mm: int, wave: int = 64, chunk: int = 1024):
+    """The arithmetic of k_ot_bulge's wave queue alone, for the sites of one (type, size) launch in the device's order: per wave of
+    64 sites and chunk of 1024 guides, a guide adds its survivors of the prune to qn and a queue of 64 or more is flushed
+    (qn -= 64); what is left at the end of a chunk is that chunk's remainder.  Returns
+      flushes       full-queue flushes
+      flush_zero    ... that left 0 / flush_rest ... that left something
+      remainders    [(wave, chunk, qn at the chunk's end)] for every wave and chunk
+      peak          the largest qn a queue held (before its flush)
+      carried       waves that end the first chunk with 1..63 queued and have survivors in the second chunk too"""
+    keep = prune_survivors(site_spacers, guides, b, dna, max_mm) if len(site_spacers) else None
+    out = dict(flushes=0, flush_zero=0, flush_rest=0, remainders=[], peak=0, carried=0, sites=len(site_spacers))
+    for wv, s0 in enumerate(range(0, len(site_spacers), wave)):
+        per_guide = keep[s0:s0 + wave].sum(axis=0).tolist()
+        first_rem = 0
+        for ch, g0 in enumerate(range(0, len(guides), chunk)):
+            qn = 0
+            for c in per_guide[g0:g0 + chunk]:
+                qn += c
+                out["peak"] = max(out["peak"], qn)
+                if qn >= wave:
+                    qn -= wave
+                    out["flushes"] += 1
+                    out["flush_zero" if qn == 0 else "flush_rest"] += 1
+            out["remainders"].append((wv, ch, qn))
+            if ch == 0:
+                first_rem = qn
+            elif ch == 1 and 0 < first_rem < wave and sum(per_guide[g0:g0 + chunk]) > 0:
+                out["carried"] += 1
+    return out
+
+
+# ---- dense panels: a tandem of near-copies of two guides against a guide list that holds their families ----------------------------------
+def family_base(rng, G: int = 20) -> str:
+    """a guide without GG or CC that neither starts nor ends with G or C: a tandem of its near-copies, each followed by TGG, has
+    hardly a PAM on either strand beside the planted ones"""
+    while True:
+        s = random_seq(rng, G)
+        if "GG" not in s and "CC" not in s and s[0] in "AT" and s[-1] in "AT":
+            return s
+
+
+def dense_contig(rng, bases: Sequence[str], weights: Sequence[float], n_units: int, max_mm: int, stretch=None, flank: int = 6) -> str:
+    """`n_units` units base-with-0..max_mm-substitutions-and-a-bulge + TGG back to back, base and kind drawn per unit, a few
+    non-site bases at either end; the + strand sites are the units in position order.  `stretch` = (unit index, kind, b, units):
+    from that unit on, `units` units of that one kind without substitutions, every 16th of bases[1], the others of bases[0] -
+    any 64 consecutive ones are 60 and 4."""
+    kinds = (("DNA", 1), ("DNA", 2), ("RNA", 1), ("RNA", 2))
+    units = []
+    for u in range(n_units):
+        if stretch is not None and stretch[0] <= u < stretch[0] + stretch[3]:
+            base, (kind, b), n_mm = bases[1 if (u - stretch[0]) % 16 == 7 else 0], stretch[1:3], 0
+        else:
+            base = bases[int(rng.choice(len(bases), p=weights))]
+            kind, b = kinds[int(rng.integers(0, 4))]
+            n_mm = int(rng.integers(0, max_mm + 1))
+        units.append(mutate(rng, base, kind, b, n_mm) + "TGG")
+    return "ATTATA"[:flank] + "".join(units) + "ATATTA"[:flank]
+
+
+def family_guides(rng, n: int, families) -> List[str]:
+    """`n` random guides; `families` = [(base, indices)]: every index holds the base with 0 or 1 substitutions"""
+    G = len(families[0][0])
+    guides = [random_seq(rng, G) for _ in range(n)]
+    for base, idx in families:
+        for i in idx:
+            guides[i] = mutate(rng, base, "", 0, int(rng.integers(0, 2)))
+    return guides
+
+
+_KINDS = ((True, 1), (True, 2), (False, 1), (False, 2))
+
+
+def dense_panel(seed: int = 5):
+    """(guides, contigs) of the dense family panel, NGG, G = 20, max_mm = 2.  1100 guides (over the 1024-guide chunk): random ones,
+    near-copies of A at 3..39 and 1000..1059, of B at 500..519 and 1020..1029 - but 1023 and 1024 hold one and the same near-copy
+    of A across the chunk seam, and 0 and 1099 the same third base R, which a few units are made of.  c1: 60 units and a stretch
+    of 96 RNA-2 units without substitutions (any wave inside it queues 60 sites per A-family guide), c2: its reverse complement
+    (the same on the - strand), c3: 258 units, so the + strand alone has more than 256 sites."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    A, B, R = family_base(rng), family_base(rng), family_base(rng)
+    fam_a = [i for i in list(range(3, 40)) + list(range(1000, 1060)) if not 1020 <= i <= 1029] + [1023, 1024]
+    fam_b = [i for i in list(range(500, 520)) + list(range(1020, 1030)) if i not in (1023, 1024)]
+    guides = family_guides(rng, 1100, [(A, fam_a), (B, fam_b)])
+    guides[0] = guides[1099] = R
+    guides[1024] = guides[1023]
+    weights = (0.62, 0.30, 0.08)
+    c1 = dense_contig(rng, (A, B, R), weights, 60 + 96, 2, stretch=(30, "RNA", 2, 96))
+    c3 = dense_contig(rng, (A, B, R), weights, 258, 2)
+    return guides, {"c1": c1, "c2": revcomp(c1), "c3": c3}, sorted(fam_a), sorted(fam_b)
+
+
+def every_pair_panel(seed: int = 9):
+    """(guides, contigs): a 2 kb tandem and 70 guides for max_mm = G = 20, where no pair is pruned; three N inside spacers"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    A, B = family_base(rng), family_base(rng)
+    guides = family_guides(rng, 70, [(A, range(3, 20)), (B, range(40, 50))])
+    g = list(dense_contig(rng, (A, B), (0.6, 0.4), 87, 2))
+    for p in (200, 777, 1503):
+        while g[p] == "G" or "G" in g[p - 1:p + 2]:  # not in or next to a PAM: the site list keeps its size
+            p += 1
+        g[p] = "N"
+    return guides, {"t": "".join(g)}
+
+
+def queue_figures(contigs, guides: Sequence[str], pam: str, right: bool, max_mm: int, bdna: int, brna: int):
+    """{(type 'DNA' / 'RNA', size): queue_walk(...)} for the launches scan_bulges(engine="device") makes over an index of `contigs`"""
+    G = len(guides[0])
+    out = {}
+    for dna, b in _KINDS:
+        if b <= (bdna if dna else brna):
+            order = device_site_order(contigs, pam, right, G + b if dna else G - b)
+            out[("DNA" if dna else "RNA", b)] = queue_walk([s[3] for s in order], guides, b, dna, max_mm)
+    return out
+
+
+def assert_queue_is_exercised(figures) -> None:
+    """the conditions a dense panel has to meet - on the reference's arithmetic, before any device call"""
+    for kind, q in figures.items():
+        assert q["flushes"] >= 10 and q["flush_zero"] >= 1 and q["flush_rest"] >= 5, (kind, q["flushes"], q["flush_zero"], q["flush_rest"])
+        assert q["carried"] >= 1, kind
+    assert max(q["peak"] for q in figures.values()) >= 100
