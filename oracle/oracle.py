@@ -27,6 +27,7 @@ ERRORS = {
     -5: "capacity",
     -6: "variant beyond original region length (haplotype.py:199-201 clamp)",
     -7: "duplicate REF guide",
+    -8: "scan range reads past the haplotype (IndexError in scan_haplotype, search_guides.py:87-99)",
 }
 
 
@@ -113,8 +114,10 @@ def scan(nibbles: np.ndarray, start: int, stop: int, bits: int, bitsrc: int, pam
     fwd = np.empty(n + 1, dtype=np.int32)
     rev = np.empty(n + 1, dtype=np.int32)
     nf, nr = C.c_int64(), C.c_int64()
-    lib().ora_scan(_p(nibbles), C.c_int64(start), C.c_int64(stop), C.c_uint64(bits), C.c_uint64(bitsrc),
-                   pamlen, _p(fwd), C.byref(nf), _p(rev), C.byref(nr))
+    rc = lib().ora_scan(_p(nibbles), C.c_int64(len(nibbles)), C.c_int64(start), C.c_int64(stop), C.c_uint64(bits), C.c_uint64(bitsrc),
+                        pamlen, _p(fwd), C.byref(nf), _p(rev), C.byref(nr))
+    if rc:
+        raise OracleError(rc)
     return fwd[: nf.value].copy(), rev[: nr.value].copy()
 
 
