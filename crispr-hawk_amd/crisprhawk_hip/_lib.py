@@ -36,6 +36,8 @@ EXPORTS = [
     "hawk_comm_destroy", "hawk_comm_last_error", "hawk_comm_allgather_u64", "hawk_comm_gatherv", "hawk_table_gather", "hawk_host_ragged_join", "hawk_host_tsv_write", "hawk_host_vcf_index", "hawk_host_polish_rows", "hawk_host_variant_window", "hawk_host_polish_windows", "hawk_host_group_join", "hawk_host_group_samples", "hawk_gbt_predict", "hawk_gt_from_codes",
     "hawk_annot_create", "hawk_annot_query", "hawk_annot_download", "hawk_annot_free", "hawk_xplan_text",
     "hawk_offtarget_text", "hawk_offtarget_text_download", "hawk_host_offtarget_text",
+    "hawk_gnomad_scan", "hawk_gnomad_records", "hawk_gnomad_text", "hawk_gnomad_text_download", "hawk_gnomad_destroy",
+    "hawk_host_gnomad_lines", "hawk_host_f32_repr",
 ]
 
 
@@ -94,6 +96,12 @@ class OtTextTiming(C.Structure):
                 ("reserved", C.c_float), ("total_ms", C.c_float), ("out_bytes", C.c_uint64), ("n_rows", C.c_uint64)]
 
 
+class GnomadTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("scan_ms", C.c_float), ("len_ms", C.c_float), ("prefix_ms", C.c_float),
+                ("fill_ms", C.c_float), ("total_ms", C.c_float), ("n_records", C.c_uint64), ("n_kept", C.c_uint64),
+                ("out_bytes", C.c_uint64)]
+
+
 class OtTiming(C.Structure):
     _fields_ = [("scan_ms", C.c_float), ("sites_ms", C.c_float), ("match_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_sites", C.c_uint64), ("scanned_positions", C.c_uint64)]
@@ -126,6 +134,7 @@ def lib() -> C.CDLL:
         L.hawk_comm_destroy.restype = None
         L.hawk_host_free.restype = None
         L.hawk_annot_free.restype = None
+        L.hawk_gnomad_destroy.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)

@@ -52,3 +52,7 @@ class CrisprHawkAnnotationError(CrisprHawkError):
 
 class CrisprHawkOffTargetsError(CrisprHawkError):
     pass
+
+
+class CrisprHawkConverterError(CrisprHawkError):
+    pass

@@ -486,19 +486,78 @@ def write_vcf(path: str, contig: str, samples: List[str], rows: List[List[str]],
             f.write(data)
 
 
+def _bgzf_member(chunk: bytes) -> bytes:
+    import struct
+    import zlib
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    body = c.compress(chunk) + c.flush()
+    bsize = 12 + 6 + len(body) + 8 - 1
+    return (b"\x1f\x8b\x08\x04" + b"\x00" * 4 + b"\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize) + body +
+            struct.pack("<II", zlib.crc32(chunk) & 0xffffffff, len(chunk)))
+
+
 def write_bgzf(path: str, data: bytes, block: int = 0xff00) -> None:
     """bgzip's container: independent deflate members of <= 64 KB of text each, the member size in a BC extra field,
     an empty member as the end marker (SAM spec §4.1)."""
-    import struct
-    import zlib
-
-    def member(chunk: bytes) -> bytes:
-        c = zlib.compressobj(6, zlib.DEFLATED, -15)
-        body = c.compress(chunk) + c.flush()
-        bsize = 12 + 6 + len(body) + 8 - 1
-        return (b"\x1f\x8b\x08\x04" + b"\x00" * 4 + b"\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize) + body +
-                struct.pack("<II", zlib.crc32(chunk) & 0xffffffff, len(chunk)))
     with open(path, "wb") as f:
         for i in range(0, len(data), block):
-            f.write(member(data[i:i + block]))
-        f.write(member(b""))
+            f.write(_bgzf_member(data[i:i + block]))
+        f.write(_bgzf_member(b""))
+
+
+class BgzfWriter:
+    """write_bgzf for text that arrives piece by piece (a converted chromosome is never resident): `write` cuts what it is
+    given - bytes or a uint8 array, copied before it returns - into members of `block` bytes, deflates them on `threads` host
+    threads (zlib releases the interpreter lock) and writes them in order; `close` writes the tail and the end marker."""
+
+    def __init__(self, path: str, threads: int = 1, block: int = 0xff00) -> None:
+        from concurrent.futures import ThreadPoolExecutor
+        self._f = open(path, "wb")
+        self._block = block
+        self._tail = b""
+        self._threads = max(1, int(threads))
+        self._pool = ThreadPoolExecutor(self._threads) if self._threads > 1 else None
+
+    def _emit(self, chunks) -> None:
+        if self._pool is None:
+            for c in chunks:
+                self._f.write(_bgzf_member(c))
+            return
+        wave = 8 * self._threads  # members in flight: bounded memory, order kept
+        for i in range(0, len(chunks), wave):
+            for m in self._pool.map(_bgzf_member, chunks[i:i + wave]):
+                self._f.write(m)
+
+    def write(self, data) -> None:
+        mv = memoryview(data).cast("B") if not isinstance(data, (bytes, bytearray)) else memoryview(data)
+        blk, chunks, pos = self._block, [], 0
+        if self._tail:
+            take = min(blk - len(self._tail), len(mv))
+            self._tail += bytes(mv[:take])
+            pos = take
+            if len(self._tail) < blk:
+                return
+            chunks.append(self._tail)
+            self._tail = b""
+        full = pos + (len(mv) - pos) // blk * blk
+        chunks += [bytes(mv[i:i + blk]) for i in range(pos, full, blk)]
+        self._tail = bytes(mv[full:])
+        self._emit(chunks)
+
+    def close(self) -> None:
+        if self._f is None:
+            return
+        if self._tail:
+            self._f.write(_bgzf_member(self._tail))
+            self._tail = b""
+        self._f.write(_bgzf_member(b""))
+        self.abort()
+
+    def abort(self) -> None:
+        """close the file without finishing the stream (the caller removes it)"""
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+        if self._f is not None:
+            self._f.close()
+            self._f = None

@@ -380,3 +380,74 @@ def write_region_files(reg: SynthRegion, directory: str, stem: str = "region"):
             f.write(head + g.reshape(-1).tobytes()[:-1] + b"\n")
     return fa, bed, vcf
 
+
+
+# ---------------------------------------------------------------------------------------------- gnomAD sites records
+GNOMAD_POPS = ["afr", "ami", "amr", "asj", "eas", "fin", "nfe", "mid", "sas", "remaining"]
+_GN_COUNTS = ["0", "00", "5", "0,0,5", "-3", "2147483647", "3,.", "0", "0", "12", "1", "0,0", "7,0"]
+_GN_FILTERS = ["PASS", "PASS", "PASS", ".", "AC0", "AC0;PASS", "PASSED", "NOPASS", "AS_VQSR;AC0"]
+_GN_QUALS = [".", "1234", "0.1", "57.25", "1e3", "100000", "3.4e-05", "0"]
+
+
+def gnomad_sites_header(joint: bool) -> List[str]:
+    """The header lines of a sites VCF as gnomad_sites_lines fills it (no FORMAT, no samples)."""
+    af = "AF_joint" if joint else "AF"
+    return ["##fileformat=VCFv4.2", '##FILTER=<ID=AC0,Description="Allele count is zero">',
+            f'##INFO=<ID={af},Number=A,Type=Float,Description="Alternate allele frequency">',
+            '##INFO=<ID=AC_afr,Number=A,Type=Integer,Description="Alternate allele count, African">', "##contig=<ID=chr21,length=46709983>",
+            "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"]
+
+
+def gnomad_sites_lines(seed: int, n_records: int, joint: bool, info_keys: int = 150) -> List[str]:
+    """Data lines of a gnomAD-like sites VCF, every one convertible: the ten allele-count keys of the file's kind with counts
+    of every accepted form, and around them the keys that must NOT be taken for them - `AC_afr_XX`, `XAC_afr`, `nhomalt_afr`,
+    the other kind's `AC_joint_afr` / `AC_afr`, an `AC_afr=5` inside another entry's value, flags without '=' - each with a count
+    opposite to the real key's, up to about `info_keys` entries in shuffled order.  FILTER, QUAL, AF (absent, '.', lists; a
+    joint file has `AF_joint` and no `AF`) and the number of ALT alleles vary; positions ascend on chr21."""
+    rng = np.random.default_rng(seed)
+    real = [f"AC_joint_{p}" if joint else f"AC_{p}" for p in GNOMAD_POPS]
+    other = [f"AC_{p}" if joint else f"AC_joint_{p}" for p in GNOMAD_POPS]
+    lines, pos = [], 5_000_000
+    for r in range(n_records):
+        pos += int(rng.integers(1, 400))
+        n_alt = int(rng.choice([1, 1, 1, 1, 2, 3]))
+        ref = random_sequence(rng, int(rng.choice([1, 1, 1, 2, 5])))
+        alts = []
+        while len(alts) < n_alt:
+            a = random_sequence(rng, int(rng.choice([1, 1, 1, 3, 9])))
+            if a != ref and a not in alts:
+                alts.append(a)
+        entries = []
+        for k, (key, okey, p) in enumerate(zip(real, other, GNOMAD_POPS)):
+            val = _GN_COUNTS[int(rng.integers(0, len(_GN_COUNTS)))]
+            seen = any(int(e) > 0 for e in val.split(",") if e != ".") if val != "3,." else True
+            decoy = "0" if seen else "9"
+            entries.append(f"{key}={val}")
+            entries += [f"{key}_XX={decoy}", f"X{key}={decoy}", f"{okey}={decoy}", f"nhomalt_{p}={decoy}", f"AN_{p}={int(rng.integers(2, 90000))}",
+                        f"note{k}={key}={decoy}"]
+        af_kind = int(rng.integers(0, 6))
+        af_key = "AF_joint" if joint else "AF"
+        if af_kind == 1:
+            entries.append(f"{af_key}=.")
+        elif af_kind == 2:
+            entries.append(f"{af_key}=0.5,.")
+        elif af_kind >= 3:
+            entries.append(f"{af_key}=" + ",".join(f"{float(rng.random()) * 10 ** -int(rng.integers(0, 7)):.5e}" for _ in range(n_alt)))
+        k = 0
+        while len(entries) < info_keys:
+            kind = int(rng.integers(0, 4))
+            if kind == 0:
+                entries.append(f"flag{k}")
+            elif kind == 1:
+                entries.append(f"faf95_{k}={float(rng.random()):.6e}")
+            elif kind == 2:
+                entries.append(f"vep{k}=" + "|".join(random_sequence(rng, int(rng.integers(1, 12))) for _ in range(int(rng.integers(1, 9)))))
+            else:
+                entries.append(f"AN_grp{k}={int(rng.integers(0, 200000))}")
+            k += 1
+        order = rng.permutation(len(entries))
+        info = ";".join(entries[int(i)] for i in order)
+        vid = f"rs{int(rng.integers(1, 10 ** 9))}" if rng.random() < 0.5 else "."
+        lines.append("\t".join(["chr21", str(pos), vid, ref, ",".join(alts), _GN_QUALS[int(rng.integers(0, len(_GN_QUALS)))],
+                                _GN_FILTERS[int(rng.integers(0, len(_GN_FILTERS)))], info]))
+    return lines

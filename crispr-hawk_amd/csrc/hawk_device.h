@@ -388,3 +388,29 @@ struct OtTextDev {
 void hawk_launch_ot_text_len(hipStream_t st, const OtTextDev& A, uint64_t* len, int64_t* cfd_e4, unsigned long long* n_unscorable);
 // row i at out[off[i], off[i + 1]) (off: the exclusive sums of len, off[n] = bytes of the blob)
 void hawk_launch_ot_text_fill(hipStream_t st, const OtTextDev& A, const uint64_t* off, uint8_t* out);
+
+// ---- gnomAD sites records -> population-genotype lines (hawk_gnomad.hip; the rules themselves: hawk_gnomad.h)
+#include "hawk_gnomad.h"
+struct GnDev {
+  const uint8_t* text;       // the batch's data lines
+  const uint64_t* line_off;  // [n + 1]
+  uint64_t n;
+  const uint8_t* keys;       // key k = keys[key_off[k], key_off[k + 1])
+  const uint32_t* key_off;   // [n_keys + 1]
+  uint32_t n_keys, keep;
+  // per record: what k_gn_scan writes and the text kernels read
+  uint32_t* mask;
+  uint8_t* flags;
+  uint32_t* field_off;  // [n][8]
+  uint32_t* qual_span;  // [n][2]
+  uint32_t* af_span;    // [n][2]
+};
+void hawk_launch_gn_scan(hipStream_t st, const GnDev& G);
+// kept[i] <- 1 for a record without flags, else 0 (the input of the scan that numbers the kept records)
+void hawk_launch_gn_kept(hipStream_t st, const GnDev& G, uint64_t* kept);
+// len[i] <- bytes of record i's output line (0 for a record with flags); kidx: the exclusive sums of kept; pool entry j =
+// pool[pool_off[j], pool_off[j + 1]), QUAL of kept record k at k, its AF at n_kept + k
+void hawk_launch_gn_text_len(hipStream_t st, const GnDev& G, const uint64_t* kidx, const uint8_t* pool, const uint64_t* pool_off, uint64_t n_kept,
+                             uint64_t* len);
+void hawk_launch_gn_text_fill(hipStream_t st, const GnDev& G, const uint64_t* kidx, const uint8_t* pool, const uint64_t* pool_off, uint64_t n_kept,
+                              const uint64_t* off, uint8_t* out);

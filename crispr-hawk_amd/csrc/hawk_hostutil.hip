@@ -2,7 +2,10 @@
 // `samples` and `haplotype_id` columns list every carrier of every report row (C3: 28 M entries, ~330 MB of text);
 // joining them is a ragged byte gather that Python cannot do at memory speed, so it lives here, multi-threaded.
 #include <algorithm>
+#include <charconv>
+#include <cmath>
 #include <cstdlib>
+#include <string>
 #include <cstring>
 #include <thread>
 #include <atomic>
@@ -10,6 +13,7 @@
 
 #include "../../include/hawk.h"
 #include "hawk_ottext.h"
+#include "hawk_gnomad.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -715,6 +719,229 @@ int hawk_host_offtarget_text(uint64_t n, const uint32_t* guide, const uint32_t* 
     OtTextBytes w;
     w.w = blob + off[i];
     (void)emit(i, w);
+  }
+  return HAWK_OK;
+}
+
+// ---- gnomAD sites records -> population-genotype lines on the host ------------------------------------------------------------
+// hawk_gnomad_scan + hawk_gnomad_text without a device: the same checks and the same functions of hawk_gnomad.h, one thread, one
+// record after the other.  Where the kernel finds entry starts by sweeping chunks, this walks INFO from ';' to ';'; what an entry
+// start, a key match, a value, a flag and a line ARE is the header's.
+namespace {
+struct GnHostRec {
+  uint32_t fo[8], mask, flags, qual[2], af[2];
+};
+inline GnHostRec gn_host_scan(const uint8_t* text, uint64_t lo, uint64_t end, const uint8_t* key_blob, const uint64_t* key_off, uint32_t n_keys,
+                              uint32_t keep) {
+  GnHostRec R;
+  uint64_t hi = end;
+  while (hi > lo && (text[hi - 1] == '\n' || text[hi - 1] == '\r')) --hi;
+  const uint8_t* rec = text + lo;
+  const uint32_t len = (uint32_t)(hi - lo);
+  for (uint32_t& f : R.fo) f = len;
+  R.fo[0] = 0;
+  uint32_t tabs = 0, info_hi = len, commas = 0;
+  for (uint32_t p = 0; p < len; ++p) {
+    if (rec[p] == '\t') {
+      if (++tabs < 8) R.fo[tabs] = p + 1;
+      else { info_hi = p; break; }
+    } else if (tabs == 4 && rec[p] == ',') ++commas;
+  }
+  const bool full = tabs >= 7;
+  uint32_t pos[32];
+  for (uint32_t& q : pos) q = GN_ABSENT;
+  const uint8_t afkey[2] = {'A', 'F'};
+  if (full) {
+    uint32_t p = R.fo[7];
+    while (p < info_hi) {  // an entry starts at p: behind the tab that opens INFO or behind a ';'
+      for (uint32_t j = 0; j < n_keys; ++j)
+        if (pos[j] == GN_ABSENT && gn_key_at(rec, p, len, key_blob + key_off[j], (uint32_t)(key_off[j + 1] - key_off[j]))) pos[j] = p;
+      if (pos[31] == GN_ABSENT && gn_key_at(rec, p, len, afkey, 2)) pos[31] = p;
+      while (p < info_hi && rec[p] != ';') ++p;
+      ++p;
+    }
+  }
+  bool absent = false, bad = false;
+  uint32_t mask = 0;
+  for (uint32_t j = 0; full && j < n_keys; ++j) {
+    if (pos[j] == GN_ABSENT) { absent = true; continue; }
+    const uint32_t kl = (uint32_t)(key_off[j + 1] - key_off[j]);
+    const int v = gn_key_at(rec, pos[j], len, key_blob + key_off[j], kl) == 1 ? gn_value(rec, (uint64_t)pos[j] + kl + 1, len) : 2;
+    if (v == 1) mask |= 1u << j;
+    if (v == 2) bad = true;
+  }
+  R.flags = full ? gn_record_flags(rec, R.fo, keep, absent, bad) : GN_FEW_FIELDS;
+  R.mask = R.flags ? 0u : mask;
+  gn_spans(rec, R.fo, len, full, pos[31], commas, R.qual, R.af);
+  return R;
+}
+}  // namespace
+
+int hawk_host_gnomad_lines(const uint8_t* text, uint64_t text_len, const uint64_t* line_off, uint64_t n_lines, const uint8_t* key_blob,
+                           const uint64_t* key_off, uint32_t n_keys, int keep, uint32_t* mask, uint8_t* flags, uint32_t* field_off,
+                           uint32_t* qual_span, uint32_t* af_span, const uint8_t* pool_blob, const uint64_t* pool_off, uint8_t* blob,
+                           uint64_t blob_cap, uint64_t* off, uint64_t* n_bytes, uint64_t* n_kept) {
+  if (!n_bytes || !n_kept || !gn_args_ok(text, text_len, line_off, n_lines, key_blob, key_off, n_keys)) return HAWK_E_INVALID;
+  std::vector<GnHostRec> recs(n_lines);
+  uint64_t kept = 0;
+  for (uint64_t i = 0; i < n_lines; ++i) {
+    recs[i] = gn_host_scan(text, line_off[i], line_off[i + 1], key_blob, key_off, n_keys, keep ? 1u : 0u);
+    kept += recs[i].flags == 0;
+  }
+  if (pool_off) {  // checked before anything is written
+    if (pool_off[0] != 0) return HAWK_E_INVALID;
+    for (uint64_t j = 0; j < 2 * kept; ++j)
+      if (pool_off[j + 1] < pool_off[j]) return HAWK_E_INVALID;
+    if (pool_off[2 * kept] && !pool_blob) return HAWK_E_INVALID;
+  }
+  for (uint64_t i = 0; i < n_lines; ++i) {
+    const GnHostRec& R = recs[i];
+    if (mask) mask[i] = R.mask;
+    if (flags) flags[i] = (uint8_t)R.flags;
+    if (field_off) memcpy(field_off + i * 8, R.fo, 32);
+    if (qual_span) memcpy(qual_span + i * 2, R.qual, 8);
+    if (af_span) memcpy(af_span + i * 2, R.af, 8);
+  }
+  *n_kept = kept;
+  *n_bytes = 0;
+  if (!pool_off) return HAWK_OK;
+  // the length pass and the fill pass: one function, two sinks
+  auto emit = [&](uint64_t i, uint64_t k, auto& sink) {
+    const GnHostRec& R = recs[i];
+    gn_line(text + line_off[i], R.fo, R.mask, n_keys, pool_blob + pool_off[k], pool_off[k + 1] - pool_off[k], pool_blob + pool_off[kept + k],
+            pool_off[kept + k + 1] - pool_off[kept + k], R.af[1] != GN_ABSENT, R.af[0], sink);
+  };
+  uint64_t total = 0, k = 0;
+  std::vector<uint64_t> o(n_lines + 1, 0);
+  for (uint64_t i = 0; i < n_lines; ++i) {
+    if (recs[i].flags == 0) {
+      GnCount c;
+      emit(i, k++, c);
+      total += c.n;
+    }
+    o[i + 1] = total;
+  }
+  if (off) memcpy(off, o.data(), (n_lines + 1) * 8);
+  *n_bytes = total;
+  if (!blob || blob_cap < total) return total ? HAWK_E_CAPACITY : HAWK_OK;
+  k = 0;
+  for (uint64_t i = 0; i < n_lines; ++i) {
+    if (recs[i].flags) continue;
+    GnBytes w;
+    w.w = blob + o[i];
+    emit(i, k++, w);
+  }
+  return HAWK_OK;
+}
+
+// ---- float32 text as Python prints it -----------------------------------------------------------------------------------------
+namespace {
+// str(float(numpy.float32(float(entry)))) appended to `out`; false when entry is no finite decimal number
+inline bool f32_repr_one(const uint8_t* s, uint32_t n, std::string& out) {
+  if (n == 0 || n > 400) return false;
+  char buf[408];
+  bool digit = false;
+  for (uint32_t k = 0; k < n; ++k) {
+    const char c = (char)s[k];
+    if (!((c >= '0' && c <= '9') || c == '+' || c == '-' || c == '.' || c == 'e' || c == 'E')) return false;  // no nan, inf, hex, blanks
+    digit |= c >= '0' && c <= '9';
+    buf[k] = c;
+  }
+  if (!digit) return false;
+  buf[n] = 0;
+  char* end = nullptr;
+  const double parsed = strtod(buf, &end);
+  if (end != buf + n) return false;
+  const float f = (float)parsed;
+  if (!std::isfinite(f)) return false;
+  const double d = (double)f;
+  char sci[40];
+  const auto r = std::to_chars(sci, sci + sizeof(sci) - 1, d, std::chars_format::scientific);  // shortest digits that round-trip
+  if (r.ec != std::errc()) return false;
+  *r.ptr = 0;
+  // [-]d[.ddd]e[+-]XX -> the digits and the position of the decimal point behind the first of them
+  const char* p = sci;
+  if (*p == '-') { out.push_back('-'); ++p; }
+  char dig[24];
+  int nd = 0;
+  for (; p < r.ptr && *p != 'e'; ++p)
+    if (*p != '.') dig[nd++] = *p;
+  const int decpt = (int)strtol(p + 1, nullptr, 10) + 1;
+  while (nd > 1 && dig[nd - 1] == '0') --nd;
+  if (decpt > -4 && decpt <= 16) {  // repr's fixed notation, ".0" behind integers
+    if (decpt <= 0) {
+      out.append("0.");
+      out.append((size_t)-decpt, '0');
+      out.append(dig, (size_t)nd);
+    } else if (decpt >= nd) {
+      out.append(dig, (size_t)nd);
+      out.append((size_t)(decpt - nd), '0');
+      out.append(".0");
+    } else {
+      out.append(dig, (size_t)decpt);
+      out.push_back('.');
+      out.append(dig + decpt, (size_t)(nd - decpt));
+    }
+  } else {
+    out.push_back(dig[0]);
+    if (nd > 1) { out.push_back('.'); out.append(dig + 1, (size_t)(nd - 1)); }
+    const int e = decpt - 1, ae = e < 0 ? -e : e;
+    out.push_back('e');
+    out.push_back(e < 0 ? '-' : '+');
+    if (ae < 10) out.push_back('0');
+    out.append(std::to_string(ae));
+  }
+  return true;
+}
+}  // namespace
+
+int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_t* len, uint64_t n, const char* missing, uint8_t* out,
+                       uint64_t out_cap, uint64_t* out_off, uint8_t* status, uint32_t threads) {
+  if (!out_off || (n && (!start || !len || !status || !missing))) return HAWK_E_INVALID;
+  for (uint64_t i = 0; i < n; ++i)
+    if (len[i] != 0xffffffffu && len[i] && !text) return HAWK_E_INVALID;
+  unsigned nt = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
+  nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min(nt, 32u), n / 2048 + 1));
+  const uint64_t per = (n + nt - 1) / nt;
+  std::vector<std::string> part(nt);
+  auto work = [&](unsigned t) {
+    std::string& o = part[t];
+    const uint64_t i0 = std::min<uint64_t>(n, t * per), i1 = std::min<uint64_t>(n, i0 + per);
+    for (uint64_t i = i0; i < i1; ++i) {
+      const size_t at = o.size();
+      bool ok = true;
+      if (len[i] != 0xffffffffu) {
+        const uint8_t* s = text + start[i];
+        uint32_t p = 0;
+        for (;;) {  // one comma entry [p, q)
+          uint32_t q = p;
+          while (q < len[i] && s[q] != ',') ++q;
+          if (q - p == 1 && s[p] == '.') o.append(missing);
+          else if (!f32_repr_one(s + p, q - p, o)) { ok = false; break; }
+          if (q >= len[i]) break;
+          o.push_back(',');
+          p = q + 1;
+        }
+      }
+      if (!ok) o.resize(at);
+      status[i] = ok ? 0 : 1;
+      out_off[i + 1] = o.size() - at;
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+  }
+  out_off[0] = 0;
+  for (uint64_t i = 0; i < n; ++i) out_off[i + 1] += out_off[i];
+  const uint64_t total = out_off[n];
+  if (!out || out_cap < total) return total ? HAWK_E_CAPACITY : HAWK_OK;
+  uint64_t at = 0;
+  for (unsigned t = 0; t < nt; ++t) {
+    memcpy(out + at, part[t].data(), part[t].size());
+    at += part[t].size();
   }
   return HAWK_OK;
 }

@@ -624,6 +624,71 @@ int hawk_annot_query(hawk_annot* annot, const int64_t* qstart, const int64_t* qs
 int hawk_annot_download(hawk_annot* annot, uint8_t* blob, uint64_t* off, float* download_ms);
 void hawk_annot_free(hawk_annot* annot);
 
+/* ---- gnomAD sites VCF -> population-genotype VCF (converter.py:129-265 of the reference: _asses_genotype, _format_vrecord and
+ * the keep rule of _convert, per data line) ------------------------------------------------------------------------------------
+ * `text` holds whole data lines of a sites VCF (no '#' lines), record i = text[line_off[i], line_off[i + 1]) ending in '\n'
+ * (a '\r' before it is dropped).  Key k (a population's allele-count key, e.g. AC_afr) is key_blob[key_off[k], key_off[k + 1]);
+ * at most 31 keys of at most 255 bytes and 2048 bytes in all, none empty or holding ';', '=' or a tab.  The rules are stated once, in
+ * csrc/hawk_gnomad.h, for the kernels and for hawk_host_gnomad_lines.
+ *
+ * hawk_gnomad_scan uploads the text once and runs k_gn_scan; hawk_gnomad_records downloads, per record (a NULL argument skips
+ * that array):
+ *   mask       uint32     bit k: key k's value holds a count > 0 (read left to right up to the first such count)
+ *   flags      uint8      HAWK_GN_DROPPED (keep == 0 and FILTER has no token PASS; nothing else of the record is examined),
+ *                         HAWK_GN_KEY_ABSENT, HAWK_GN_BAD_VALUE ('.' before a positive count, an empty value, the key without '=',
+ *                         an entry that is no optionally signed run of 1..10 digits), HAWK_GN_FEW_FIELDS (fewer than eight),
+ *                         HAWK_GN_ALT_MISSING (ALT is "."), HAWK_GN_BAD_POS (POS empty or not all digits)
+ *   field_off  uint32[8]  where the first eight fields start, relative to the record (the record's length for a field it lacks)
+ *   qual_span  uint32[2]  offset and length of QUAL
+ *   af_span    uint32[2]  offset and length of the value of the INFO entry whose key is exactly AF; when there is none the
+ *                         length is 0xffffffff and the first word holds the number of ALT alleles (commas in ALT plus one)
+ * hawk_gnomad_text writes the output line of every record whose flags are 0 ("CHROM POS ID REF ALT QUAL FILTER AF=<af> GT" and
+ * one 0/1 or 0/0 per key, tab-joined, ended by '\n'; FILTER "." becomes the empty string) and leaves the lines in HBM.  QUAL
+ * and AF are printed from the caller's pool, entry j = pool_blob[pool_off[j], pool_off[j + 1]): entry k is the QUAL text of
+ * the k-th kept record, entry n_kept + k its AF text (ignored when the record has no AF entry: "0.0" per ALT allele is
+ * printed).  pool_off has 2 * n_kept + 1 entries; *n_kept and *n_bytes are written in any case, so a call with pool_off == NULL
+ * reports n_kept and does nothing else.  hawk_gnomad_text_download copies the lines: blob[n_bytes], off = uint64[n_lines + 1]
+ * (line i = blob[off[i], off[i + 1]), empty for a record with flags); either may be NULL.
+ * HAWK_E_INVALID with nothing written: n_keys > 31, a malformed key, a text that does not end in '\n', offsets that are not
+ * whole lines inside the text, a record longer than 2^32 - 1 bytes.  n_lines = 0 is HAWK_OK with an empty blob.  All offsets
+ * are 64 bits. */
+#define HAWK_GN_DROPPED 1
+#define HAWK_GN_KEY_ABSENT 2
+#define HAWK_GN_BAD_VALUE 4
+#define HAWK_GN_FEW_FIELDS 8
+#define HAWK_GN_ALT_MISSING 16
+#define HAWK_GN_BAD_POS 32
+typedef struct hawk_gnomad hawk_gnomad;
+typedef struct {
+  float upload_ms, scan_ms, len_ms, prefix_ms, fill_ms, total_ms; /* HIP events around the stages of one call */
+  uint64_t n_records, n_kept, out_bytes;
+} hawk_gnomad_timing;
+int hawk_gnomad_scan(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, uint64_t n_lines,
+                     const uint8_t* key_blob, const uint64_t* key_off, uint32_t n_keys, int keep, hawk_gnomad** out,
+                     hawk_gnomad_timing* timing);
+int hawk_gnomad_records(hawk_gnomad* g, uint32_t* mask, uint8_t* flags, uint32_t* field_off, uint32_t* qual_span, uint32_t* af_span);
+int hawk_gnomad_text(hawk_gnomad* g, const uint8_t* pool_blob, const uint64_t* pool_off, uint64_t* n_bytes, uint64_t* n_kept,
+                     hawk_gnomad_timing* timing);
+int hawk_gnomad_text_download(hawk_gnomad* g, uint8_t* blob, uint64_t* off);
+void hawk_gnomad_destroy(hawk_gnomad* g);
+/* The same on the host by the same header, single-threaded, no device.  The per-record arrays (those that are not NULL) and
+ * *n_kept are always written; with pool_off == NULL the call ends there (*n_bytes = 0).  Otherwise off[n_lines + 1] (if not
+ * NULL) and *n_bytes are written, the lines when `blob` is non-NULL and blob_cap suffices - else HAWK_E_CAPACITY with the
+ * required size in *n_bytes. */
+int hawk_host_gnomad_lines(const uint8_t* text, uint64_t text_len, const uint64_t* line_off, uint64_t n_lines, const uint8_t* key_blob,
+                           const uint64_t* key_off, uint32_t n_keys, int keep, uint32_t* mask, uint8_t* flags, uint32_t* field_off,
+                           uint32_t* qual_span, uint32_t* af_span, const uint8_t* pool_blob, const uint64_t* pool_off, uint8_t* blob,
+                           uint64_t blob_cap, uint64_t* off, uint64_t* n_bytes, uint64_t* n_kept);
+/* What pysam hands Python for a Float field, printed as Python prints it: string i = text[start[i], start[i] + len[i]) is a
+ * comma list; every entry is read with strtod, narrowed to float32, widened again and printed as str() prints that double
+ * (shortest digits that round-trip; fixed notation while the decimal exponent is in -4 .. 15, ".0" appended to integers, else
+ * d.ddde-05 with at least two exponent digits).  An entry that is exactly "." prints as `missing`.  len[i] == 0xffffffff
+ * gives the empty string.  status[i] = 1 when an entry is empty, is no decimal number in full, or is not finite as a float32
+ * (its output is then empty).  out_off[n + 1] is always written; the bytes when `out` is non-NULL and out_cap suffices, else
+ * HAWK_E_CAPACITY with the required size in out_off[n].  `threads` host threads (0: one per core, at most 32). */
+int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_t* len, uint64_t n, const char* missing, uint8_t* out,
+                       uint64_t out_cap, uint64_t* out_off, uint8_t* status, uint32_t threads);
+
 #ifdef __cplusplus
 }
 #endif
