@@ -38,6 +38,8 @@ EXPORTS = [
     "hawk_offtarget_text", "hawk_offtarget_text_download", "hawk_host_offtarget_text",
     "hawk_gnomad_scan", "hawk_gnomad_records", "hawk_gnomad_text", "hawk_gnomad_text_download", "hawk_gnomad_destroy",
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
+    "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
+    "hawk_host_effects", "hawk_host_round4",
 ]
 
 
@@ -102,6 +104,24 @@ class GnomadTiming(C.Structure):
                 ("out_bytes", C.c_uint64)]
 
 
+class EffectsColumns(C.Structure):
+    _fields_ = [("n_groups", C.c_uint64), ("win_stride", C.c_uint64), ("start", C.c_void_p), ("stop", C.c_void_p), ("strand", C.c_void_p),
+                ("win", C.c_void_p), ("cfdon", C.c_void_p), ("member_off", C.c_void_p), ("member_hap", C.c_void_p), ("hap_is_ref", C.c_void_p),
+                ("hap_off", C.c_void_p), ("sample_id", C.c_void_p), ("rank", C.c_void_p), ("n_hap", C.c_uint32), ("n_sample_ids", C.c_uint32),
+                ("guidelen", C.c_uint32), ("pamlen", C.c_uint32), ("right", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EffectsOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("score", "delta", "abs_delta", "n_samples", "type", "dup", "position", "pos_ref", "pos_worst",
+                                          "pos_nvalid", "pos_first_rank", "chosen", "alt_off", "alt_group", "counts")]
+
+
+class EffectsTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("groups_ms", C.c_float), ("samples_ms", C.c_float), ("positions_ms", C.c_float),
+                ("topk_ms", C.c_float), ("alts_ms", C.c_float), ("total_ms", C.c_float), ("reserved", C.c_float),
+                ("n_groups", C.c_uint64), ("n_positions", C.c_uint64), ("n_long", C.c_uint64)]
+
+
 class OtTiming(C.Structure):
     _fields_ = [("scan_ms", C.c_float), ("sites_ms", C.c_float), ("match_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_sites", C.c_uint64), ("scanned_positions", C.c_uint64)]
@@ -135,6 +155,7 @@ def lib() -> C.CDLL:
         L.hawk_host_free.restype = None
         L.hawk_annot_free.restype = None
         L.hawk_gnomad_destroy.restype = None
+        L.hawk_effects_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)

@@ -56,3 +56,11 @@ class CrisprHawkOffTargetsError(CrisprHawkError):
 
 class CrisprHawkConverterError(CrisprHawkError):
     pass
+
+
+class CrisprHawkGraphicalReportsError(CrisprHawkError):
+    pass
+
+
+class CrisprHawkCandidateGuideError(CrisprHawkError):
+    pass

@@ -170,10 +170,13 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
     return path
 
 
+# Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
+# candidate_guides and figures sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, device: Optional[int] = None,
                  debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
-                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, annotations: Optional[List[str]] = None,
+                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, graphical_reports: bool = False,
+                 candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
                  tables: Optional[Dict[str, str]] = None) -> Dict[str, str]:
@@ -195,7 +198,16 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     haplotypes_table_{contig}_{start}_{stop}.tsv per BED interval (padded coordinates): id, haplotype, variants, samples of every
     haplotype searched, REF first, `id` being the guide report's haplotype_id.  The strings of a device-built plan are fetched
     as text in batches (haplotypes.haplotypes_table; HAWK_HAPTEXT_BATCH_BYTES, default 256 MiB).  The returned dict stays
-    {str(coordinate): report path}; pass a dict as `tables` and it is filled in place with {str(coordinate): table path}."""
+    {str(coordinate): report path}; pass a dict as `tables` and it is filled in place with {str(coordinate): table path}.
+    `graphical_reports=True` (the data behind the reference's --graphical-reports; no plot is drawn) runs the variant-effect stage
+    on the collapsed table while it is still in HBM (graphical_reports.py: hawk_effects_*) and writes, per interval,
+    figures/{contig}_{start}_{stop}_{score}_delta.tsv for every score column with numbers in it and
+    figures/{contig}_{start}_{stop}_guides_type.tsv; `candidate_guides` ('contig:position:strand' strings, the reference's
+    --candidate-guides) are forced into the delta tables and each gets its sub-report
+    crisprhawk_candidate_guides__{contig}_{position}_{pam}_{guidelen}.tsv (candidate_guides.subset_reports).  Pass a dict as
+    `figures` and it is filled with {str(coordinate): [paths]}.  Intervals whose haplotypes are built on the host (unphased
+    VCFs, records the device expansion declines) have no device table: asking for the stage there is a ValueError.  (Everything
+    from `timings` on is meant to be passed by keyword.)"""
     import time as _time
     check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
@@ -245,21 +257,31 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
         if ot is not None:
             ot["ann"] = ann
         lap("open annotation BED files")
+    fx = None
+    if graphical_reports or candidate_guides:
+        from .candidate_guides import initialize_candidate_guides
+        fx = dict(on=bool(graphical_reports), cgs=initialize_candidate_guides(list(candidate_guides or []), guidelen, debug),
+                  figures=figures if figures is not None else {})
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
-                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables)
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx)
     finally:
         if ann is not None:
             ann.close()
 
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
-                      deepcpf1_weights, paths, lap, tables=None) -> Dict[str, str]:
+                      deepcpf1_weights, paths, lap, tables=None, fx=None) -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
+    def no_table():
+        if fx is not None and (fx["on"] or fx["cgs"]):
+            raise ValueError("graphical_reports / candidate_guides: this interval's haplotypes are built on the host, so there is no collapsed "
+                             "table on the device for the variant-effect stage")
     for coord in bed:
         seq = fastas[coord.contig].fetch(coord).sequence
         v = vcf_by_contig.get(coord.contig)
         if v is not None and not v.phased:
+            no_table()
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
                                                    pt if score else None, debug, ot, ann, lap, tables)
             continue
@@ -272,6 +294,7 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         except HaplotypeBuildError:
             # records the device expansion does not take (overlapping records on one chromosome copy, deletions with a
             # multi-base alt): the host builder mirrors the reference's own construction, the search stays on the device
+            no_table()
             paths[str(coord)] = _search_host_built(coord, seq, v, True, pam, guidelen, right, outdir, mmt if score else None,
                                                    pt if score else None, debug, ot, ann, lap, tables)
             continue
@@ -289,8 +312,24 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         deepcpf1_on = pam.cas_system == CPF1 and deepcpf1_weights is not None
         tab.collapse((4, 3) if (azimuth_on or deepcpf1_on) else (0, 0), download_perm=False)
         groups = tab.export_groups()
-        tab.close()
+        keep_table = fx is not None and fx["on"]  # the effects stage ranks the table's groups in HBM; candidates alone need only the columns
+        if not keep_table:
+            tab.close()
         lap("dictionary + search + collapse + export of the groups")
+        try:
+            _finish_interval(coord, tab if keep_table else None, groups, ds, plan, labels, info, vt, kept, seq, pam, guidelen, right, outdir, score, debug, ot, ann,
+                             azimuth_on, deepcpf1_on, bed_start, bed_stop, paths, lap, tables, fx)
+        finally:
+            if keep_table:
+                tab.close()
+    return paths
+
+
+def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, pam, guidelen, right, outdir, score, debug, ot, ann, azimuth_on, deepcpf1_on,
+                     bed_start, bed_stop, paths, lap, tables, fx) -> None:
+    """One interval from its exported groups to its files: scorers, annotation join, report, the optional tables.  `tab`: the
+    collapsed table, still in HBM, when the variant-effect stage is on (the caller closes it whatever happens here)."""
+    if True:
         # model-based scorers run once per report row, on the group representatives (scoring.py:749-813), when the
         # caller has supplied their parameters
         scores = {}
@@ -310,6 +349,18 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         cols, order, plain = reports.group_columns(groups, labels, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", scores, score,
                                                    is_ref_hap=np.asarray(ds.is_ref, dtype=bool), offtargets=otcb, annotations=anncols)
         lap("report assembly")
+        if fx is not None:  # the table is still collapsed in HBM: the effects stage ranks its groups there, by the report's row order
+            from . import candidate_guides as cg_mod, graphical_reports as gr_mod
+            made = []
+            if tab is not None:
+                made += gr_mod.compute_graphical_reports(tab, labels, (cols, order, plain), coord, outdir, fx["cgs"], scores,
+                                                         is_ref_hap=np.asarray(ds.is_ref, dtype=bool), debug=debug)
+            if fx["cgs"]:
+                from .coordinate import Coordinate
+                made += list(cg_mod.subset_reports(fx["cgs"], {Coordinate(coord.contig, bed_start, bed_stop, 0): (cols, order, plain)}, pam, guidelen,
+                                                   outdir, debug).values())
+            fx["figures"][str(coord)] = made
+            lap("variant effects: delta, type and candidate tables")
         if tables is not None:  # the plan's metadata is finished; its rows as text, batch by batch, straight into the file
             from . import haplotypes as hap_mod
             hap_ids, hap_samples = [labels.ids[r] for r in kept], [labels.samples[r] for r in kept]
@@ -328,4 +379,3 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         reports.write_report_tsv(path, cols, order, plain)
         paths[str(coord)] = path
         lap("TSV text + write")
-    return paths

@@ -259,10 +259,15 @@ class TiledRegionSearch:
 
     # ---- the whole region ---------------------------------------------------------------------------
     def run(self, cfd=None, flank_key: Tuple[int, int] = (0, 0), cfd_na_on_ambiguous: bool = True, keep_plans: bool = False,
-            haplotype_table: bool = False):
+            haplotype_table: bool = False, graphical_reports: bool = False):
         """All tiles; returns a MergedGroups (report groups of the whole region, seam groups merged).  There is no haplotypes
         table of a tiled region: rows are haplotypes of ONE tile (two samples that share a tile's variants are one row there and
-        two in the next), so the region has no single row set to list - `haplotype_table=True` is a ValueError."""
+        two in the next), so the region has no single row set to list - `haplotype_table=True` is a ValueError.  Nor is there
+        one collapsed table in HBM for the variant-effect stage to rank (graphical_reports.py): `graphical_reports=True` is a
+        ValueError as well."""
+        if graphical_reports:
+            raise ValueError("graphical_reports: a tiled region search has no single collapsed table on the device (every tile has its own, "
+                             "and a position's groups may sit in two of them); use pipeline.search_files on an interval that fits one plan")
         if haplotype_table:
             raise ValueError("haplotype_table: a tiled region search has no whole-region haplotypes (haplotype identity is per tile); "
                              "use pipeline.search_files on an interval that fits one plan")

@@ -17,6 +17,7 @@ IUPACTABLE = {"A": "A", "C": "C", "G": "G", "T": "T", "R": "AG", "Y": "CT", "M":
               "W": "AT", "H": "ACT", "B": "CGT", "V": "ACG", "D": "AGT", "N": "ACGT"}
 IUPAC_ENCODER = {perm: k for k, v in IUPACTABLE.items() for perm in {"".join(p) for p in permutations(v)}}
 STRAND = [0, 1]
+CANDIDATEGUIDESREPORTPREFIX = "crisprhawk_candidate_guides"  # utils.py:113
 _RC_TRANS = str.maketrans("".join(RC.keys()), "".join(RC.values()))
 
 

@@ -414,3 +414,37 @@ void hawk_launch_gn_text_len(hipStream_t st, const GnDev& G, const uint64_t* kid
                              uint64_t* len);
 void hawk_launch_gn_text_fill(hipStream_t st, const GnDev& G, const uint64_t* kidx, const uint8_t* pool, const uint64_t* pool_off, uint64_t n_kept,
                               const uint64_t* off, uint8_t* out);
+
+// ---- variant effects on the report groups (hawk_effects.hip; the rules themselves: hawk_effects.h)
+#include "hawk_effects.h"
+struct FxDev {
+  FxCols c;  // device pointers
+  // score-independent, per group (hawk_launch_fx_groups / _samples)
+  uint32_t* head;
+  uint8_t* type;
+  uint8_t* dup;
+  uint32_t* n_samples;
+  uint32_t* long_list;         // groups whose sample list takes a wave; their number is counts[6]
+  unsigned long long* counts;  // [8]
+  // per score (hawk_launch_fx_positions)
+  const double* score;
+  double *rs, *delta, *abs_delta;
+  uint32_t *pos_ref, *pos_nvalid, *pos_first_rank;
+  double* pos_worst;
+  // the selection
+  const int64_t* cand_start;
+  const uint8_t* cand_strand;
+  uint32_t n_cand, K;
+  uint32_t* chosen;     // [2 * FX_MAX_K + 1]: the candidates' heads, then the K - n_cand best others; at FX_MAX_K their valid-alternative counts; last their number
+  FxEntry* part;        // [blocks][FX_MAX_K] per-workgroup candidates of the selection
+  uint64_t* alt_off;    // [K + 1]
+  uint32_t* alt_group;
+};
+#define FX_TOPK_MAX_BLOCKS 1024u
+void hawk_launch_fx_isref_gather(hipStream_t st, const uint8_t* hap_is_ref, const uint32_t* member_hap, const uint64_t* member_off, uint64_t n_groups, uint8_t* out);
+void hawk_launch_fx_groups(hipStream_t st, const FxDev& F);
+void hawk_launch_fx_samples(hipStream_t st, const FxDev& F);
+void hawk_launch_fx_positions(hipStream_t st, const FxDev& F, int family);
+uint32_t hawk_fx_topk_blocks(uint64_t n_groups);
+void hawk_launch_fx_topk(hipStream_t st, const FxDev& F, int family);
+void hawk_launch_fx_alts(hipStream_t st, const FxDev& F, int family, uint32_t n_chosen);

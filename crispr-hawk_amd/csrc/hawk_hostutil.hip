@@ -14,6 +14,7 @@
 #include "../../include/hawk.h"
 #include "hawk_ottext.h"
 #include "hawk_gnomad.h"
+#include "hawk_effects.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -943,6 +944,128 @@ int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_
     memcpy(out + at, part[t].data(), part[t].size());
     at += part[t].size();
   }
+  return HAWK_OK;
+}
+
+// ---- variant effects on the host: the loops of k_fx_* over host arrays, every rule from hawk_effects.h
+static FxCols fx_cols_of(const hawk_effects_columns* c) {
+  FxCols f;
+  f.n_groups = c->n_groups; f.win_stride = c->win_stride; f.start = c->start; f.stop = c->stop; f.strand = c->strand; f.win = c->win;
+  f.member_off = c->member_off; f.member_hap = c->member_hap; f.is_ref = nullptr; f.hap_off = c->hap_off; f.sample_id = c->sample_id;
+  f.rank = c->rank; f.n_hap = c->n_hap; f.n_sample_ids = c->n_sample_ids; f.guidelen = c->guidelen; f.pamlen = c->pamlen; f.right = c->right;
+  return f;
+}
+
+int hawk_host_round4(const double* x, uint64_t n, double* out) {
+  if (n && (!x || !out)) return HAWK_E_INVALID;
+  for (uint64_t i = 0; i < n; ++i) out[i] = fx_round4(x[i]);
+  return HAWK_OK;
+}
+
+int hawk_host_effects(const hawk_effects_columns* cols, int family, const double* score, const int64_t* cand_start,
+                      const uint8_t* cand_strand, uint32_t n_cand, uint32_t K, const hawk_effects_out* out, uint64_t alt_cap,
+                      uint32_t* n_chosen, uint64_t* n_alts) {
+  if (!cols || !out || !n_chosen || !n_alts) return HAWK_E_INVALID;
+  *n_chosen = 0; *n_alts = 0;
+  if ((family != FX_SIGNED && family != FX_ABSOLUTE) || K < 1 || K > FX_MAX_K || n_cand > K || (n_cand && (!cand_start || !cand_strand)))
+    return HAWK_E_INVALID;
+  FxCols c = fx_cols_of(cols);
+  const int bad = fx_check_cols(c);
+  if (bad) return bad == 2 ? HAWK_E_UNSUPPORTED : HAWK_E_INVALID;
+  const uint64_t G = c.n_groups;
+  if (G && !cols->hap_is_ref) return HAWK_E_INVALID;
+  std::vector<uint8_t> origin(G);
+  for (uint64_t g = 0; g < G; ++g) origin[g] = cols->hap_is_ref[c.member_hap[c.member_off[g]]];
+  c.is_ref = origin.data();
+  if (!score) score = cols->cfdon;
+  if (G && !score) return HAWK_E_INVALID;
+  uint64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<uint32_t> head(G), pref(G, FX_NONE), pnv(G, 0), pfr(G, FX_NONE);
+  std::vector<double> pworst(G, 0.0), rs(G);
+  std::vector<uint64_t> seen((c.n_sample_ids + 63) / 64 + 1);
+  for (uint64_t g = 0; g < G; ++g) {
+    const uint64_t h = fx_head(c, g);
+    head[g] = (uint32_t)h;
+    const bool ref = fx_is_ref(c, g);
+    const uint8_t type = fx_guide_type(ref, fx_case_bits(c, g));
+    const bool dup = fx_is_dup(c, g, h);
+    if (!dup) ++counts[type == FX_TYPE_UNKNOWN ? 4 : type];
+    if (h == g) ++counts[5];
+    uint32_t ns = 0;
+    if (!ref) {  // distinct samples over the member rows' labels
+      uint64_t entries = 0;
+      for (uint64_t m = c.member_off[g]; m < c.member_off[g + 1]; ++m)
+        for (uint64_t e = c.hap_off[c.member_hap[m]]; e < c.hap_off[c.member_hap[m] + 1]; ++e, ++entries) {
+          const uint32_t id = c.sample_id[e];
+          if (!((seen[id >> 6] >> (id & 63)) & 1)) { seen[id >> 6] |= 1ull << (id & 63); ++ns; }
+        }
+      for (uint64_t m = c.member_off[g]; m < c.member_off[g + 1]; ++m)
+        for (uint64_t e = c.hap_off[c.member_hap[m]]; e < c.hap_off[c.member_hap[m] + 1]; ++e) seen[c.sample_id[e] >> 6] = 0;
+      if (c.member_off[g + 1] - c.member_off[g] > FX_SHORT_LIST || entries > FX_SHORT_LIST) ++counts[6];
+    }
+    rs[g] = fx_round4(score[g]);
+    if (out->n_samples) out->n_samples[g] = ns;
+    if (out->type) out->type[g] = type;
+    if (out->dup) out->dup[g] = dup ? 1 : 0;
+    if (out->position) out->position[g] = (uint32_t)h;
+    if (out->score) out->score[g] = rs[g];
+  }
+  std::vector<FxEntry> ranked;
+  for (uint64_t h = 0; h < G; ++h) {
+    if (head[h] != h) continue;
+    const uint64_t e = fx_end(c, h);
+    const FxPosition p = fx_position(c, score, family, h, e);
+    pref[h] = p.ref; pworst[h] = p.worst; pnv[h] = p.n_valid; pfr[h] = p.first_rank;
+    for (uint64_t j = h; j < e; ++j) {
+      const double d = p.ref == FX_NONE ? 0.0 : fx_delta(rs[j], p.ref_score);
+      if (out->delta) out->delta[j] = d;
+      if (out->abs_delta) out->abs_delta[j] = fabs(d);
+    }
+    if (p.ref == FX_NONE) continue;
+    bool is_cand = false;
+    for (uint32_t k = 0; k < n_cand; ++k) is_cand = is_cand || (cand_start[k] == c.start[h] && cand_strand[k] == c.strand[h]);
+    if (!is_cand) ranked.push_back(FxEntry{fx_key(family, p.worst), p.first_rank, (uint32_t)h});
+  }
+  for (uint64_t g = 0; g < G; ++g) {
+    if (out->pos_ref) out->pos_ref[g] = pref[g];
+    if (out->pos_worst) out->pos_worst[g] = pworst[g];
+    if (out->pos_nvalid) out->pos_nvalid[g] = pnv[g];
+    if (out->pos_first_rank) out->pos_first_rank[g] = pfr[g];
+  }
+  const size_t take = std::min<size_t>(K - n_cand, ranked.size());
+  std::partial_sort(ranked.begin(), ranked.begin() + take, ranked.end(), fx_before);
+  std::vector<uint32_t> chosen;
+  for (uint32_t k = 0; k < n_cand; ++k) {
+    uint32_t at = FX_NONE;
+    for (uint64_t h = 0; h < G; ++h)
+      if (head[h] == h && pref[h] != FX_NONE && cand_start[k] == c.start[h] && cand_strand[k] == c.strand[h]) at = (uint32_t)h;
+    chosen.push_back(at);
+  }
+  for (size_t i = 0; i < take; ++i) chosen.push_back(ranked[i].head);
+  *n_chosen = (uint32_t)chosen.size();
+  uint64_t total = 0;
+  for (uint32_t h : chosen) total += h == FX_NONE ? 0 : pnv[h];
+  *n_alts = total;
+  if (out->counts) memcpy(out->counts, counts, sizeof(counts));
+  for (size_t i = 0; i < chosen.size(); ++i)
+    if (out->chosen) out->chosen[i] = chosen[i];
+  if (out->alt_group && total > alt_cap) return HAWK_E_CAPACITY;
+  uint64_t at = 0;
+  for (size_t i = 0; i < chosen.size(); ++i) {
+    if (out->alt_off) out->alt_off[i] = at;
+    const uint32_t h = chosen[i];
+    if (h == FX_NONE) continue;
+    std::vector<uint32_t> alts;
+    const double ref_score = rs[pref[h]];
+    for (uint64_t j = h, e = fx_end(c, h); j < e; ++j)
+      if (!fx_is_ref(c, j) && fx_valid_alt(family, rs[j], ref_score)) alts.push_back((uint32_t)j);
+    std::sort(alts.begin(), alts.end(), [&](uint32_t a, uint32_t b) { return c.rank[a] < c.rank[b]; });
+    for (uint32_t j : alts) {
+      if (out->alt_group) out->alt_group[at] = j;
+      ++at;
+    }
+  }
+  if (out->alt_off) out->alt_off[chosen.size()] = at;
   return HAWK_OK;
 }
 

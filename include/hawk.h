@@ -689,6 +689,98 @@ int hawk_host_gnomad_lines(const uint8_t* text, uint64_t text_len, const uint64_
 int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_t* len, uint64_t n, const char* missing, uint8_t* out,
                        uint64_t out_cap, uint64_t* out_off, uint8_t* status, uint32_t threads);
 
+/* ---- variant effects: the data stage behind the reference's --graphical-reports (graphical_reports.py: _compute_delta_table,
+ * _count_guide_type) on the report GROUPS of a collapsed table, which stay in HBM.  The rules are stated once, in
+ * csrc/hawk_effects.h, for the kernels (k_fx_*) and for hawk_host_effects: the score as the report prints it (round(x, 4)), the
+ * delta against the REF group of the same (start, strand), the valid alternatives, the worst delta per position, the ranking
+ * and the guide types.  ONE order is this project's own: inside a run of equal worst deltas, where pandas' unstable sort leaves
+ * the reference's order undefined, positions rank by their first appearance in report order.
+ *
+ * Groups come in collapse order (start, strand, group) - hawk_table_collapse_download documents it - so the groups of one
+ * position are contiguous; a POSITION is named by the index of its first group (its head), and per-position results sit at the
+ * head's index of arrays of n_groups entries (other entries hold HAWK_FX_NONE / 0).  `rank[g]` is the report rank of group g (the
+ * inverse of the row order the report is written in): it orders the alternatives, breaks ties and decides which of two groups
+ * showing the same guide counts.  Haplotype rows name their samples through a CSR (hap_off[n_hap + 1], sample_id[], REF rows
+ * empty); ids lie in [0, n_sample_ids) and n_sample_ids may be at most HAWK_FX_SAMPLE_CAP (one bit per sample in 8 KiB of LDS):
+ * more is HAWK_E_UNSUPPORTED, never a wrong count.  guidelen + pamlen + 20 may be at most 64, as for every table.
+ *
+ * hawk_effects_create runs the group export of a collapsed table on the device and then the score-independent passes
+ * (k_fx_groups: position heads, guide type, the duplicate rule, the four type counts; k_fx_samples_*: distinct samples per group);
+ * nothing of the table is downloaded, and the handle keeps its own copies, so it outlives the table and later searches.
+ * hawk_effects_create_columns does the same from host arrays (tests; callers whose groups were merged on the host).
+ * hawk_effects_rank, once per score on the same handle: `family` HAWK_FX_SIGNED (score_cfdon) or HAWK_FX_ABSOLUTE (azimuth, rs3,
+ * deepcpf1); `score` = double[n_groups], or NULL for the table's CFDon; candidates are positions (start, strand), they come
+ * first in the order given, then the best K - n_cand other positions that have a REF group.  1 <= K <= HAWK_FX_MAX_K and
+ * n_cand <= K, else HAWK_E_INVALID.  A candidate whose position is absent or has no REF group is reported as HAWK_FX_NONE in
+ * `chosen` (the caller raises).  *n_chosen and *n_alts size the download.
+ * hawk_effects_download copies what is not NULL in `out`:
+ *   per group     score (rounded), delta, abs_delta (double), n_samples (uint32; REF 0), type (uint8: 0 ref, 1 spacer+PAM,
+ *                 2 spacer, 3 PAM, HAWK_FX_TYPE_UNKNOWN neither), dup (uint8: an earlier group in report order shows the same guide), position
+ *                 (uint32: the head)
+ *   per position  pos_ref (uint32 group or HAWK_FX_NONE), pos_worst (double), pos_nvalid, pos_first_rank (uint32)
+ *   chosen        uint32[n_chosen] heads in rank order; alt_off uint64[n_chosen + 1], alt_group uint32[n_alts]: the valid
+ *                 alternatives of every chosen position in report order
+ *   counts        uint64[8]: groups of type 0..3 and of type HAWK_FX_TYPE_UNKNOWN that are no duplicates, positions, groups whose sample
+ *                 list went to the wave path, 0 */
+#define HAWK_FX_SIGNED 0
+#define HAWK_FX_ABSOLUTE 1
+#define HAWK_FX_MAX_K 64
+#define HAWK_FX_SAMPLE_CAP 65536
+#define HAWK_FX_NONE 0xffffffffu       /* "no group" / "no position" in pos_ref, chosen, pos_first_rank */
+#define HAWK_FX_TYPE_UNKNOWN 255        /* an alternative without a lower-case base in spacer or PAM */
+typedef struct hawk_effects hawk_effects;
+typedef struct {
+  uint64_t n_groups, win_stride;
+  const int64_t* start;
+  const int64_t* stop;
+  const uint8_t* strand;
+  const uint64_t* win;        /* [5][win_stride] window slices */
+  const double* cfdon;        /* may be NULL when every rank call brings its scores */
+  const uint64_t* member_off; /* [n_groups + 1] */
+  const uint32_t* member_hap;
+  const uint8_t* hap_is_ref;  /* [n_hap] */
+  const uint64_t* hap_off;    /* [n_hap + 1] */
+  const uint32_t* sample_id;
+  const uint32_t* rank;
+  uint32_t n_hap, n_sample_ids, guidelen, pamlen, right, reserved;
+} hawk_effects_columns;
+typedef struct {
+  double* score;
+  double* delta;
+  double* abs_delta;
+  uint32_t* n_samples;
+  uint8_t* type;
+  uint8_t* dup;
+  uint32_t* position;
+  uint32_t* pos_ref;
+  double* pos_worst;
+  uint32_t* pos_nvalid;
+  uint32_t* pos_first_rank;
+  uint32_t* chosen;
+  uint64_t* alt_off;
+  uint32_t* alt_group;
+  uint64_t* counts;
+} hawk_effects_out;
+typedef struct {
+  float upload_ms, groups_ms, samples_ms, positions_ms, topk_ms, alts_ms, total_ms; /* HIP events around the stages of one call */
+  float reserved;
+  uint64_t n_groups, n_positions, n_long;
+} hawk_effects_timing;
+int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap_off, const uint32_t* sample_id, uint32_t n_hap,
+                        uint32_t n_sample_ids, hawk_effects** out, hawk_effects_timing* timing);
+int hawk_effects_create_columns(hawk_ctx* ctx, const hawk_effects_columns* cols, hawk_effects** out, hawk_effects_timing* timing);
+int hawk_effects_rank(hawk_effects* fx, int family, const double* score, const int64_t* cand_start, const uint8_t* cand_strand,
+                      uint32_t n_cand, uint32_t K, uint32_t* n_chosen, uint64_t* n_alts, hawk_effects_timing* timing);
+int hawk_effects_download(hawk_effects* fx, const hawk_effects_out* out);
+void hawk_effects_free(hawk_effects* fx);
+/* The same on the host by the same header, single-threaded, no device: every array of `out` that is not NULL is written
+ * (alt_group holds up to alt_cap entries, else HAWK_E_CAPACITY with the need in *n_alts).  Same refusals. */
+int hawk_host_effects(const hawk_effects_columns* cols, int family, const double* score, const int64_t* cand_start,
+                      const uint8_t* cand_strand, uint32_t n_cand, uint32_t K, const hawk_effects_out* out, uint64_t alt_cap,
+                      uint32_t* n_chosen, uint64_t* n_alts);
+/* round(x, 4) as Python computes it (csrc/hawk_effects.h: fx_round4), element by element */
+int hawk_host_round4(const double* x, uint64_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif
