@@ -4,7 +4,9 @@
 // at every offset around a 4096-byte sweep, its value across it, records of 4095 .. 70001 bytes, the shortest record, the key
 // first and last with every line end - each in a text buffer of EXACTLY its size and into a blob of EXACTLY the size the length
 // pass named (a byte read or written beyond either is a heap overflow the sanitizer sees); then every value and flag case
-// against the flags they must give, the refused arguments with the outputs untouched, and the float texts.  Not part of the library.
+// against the flags they must give, the refused arguments with the outputs untouched, and the float texts.  Then the long fields:
+// every field starting at 4095 / 4096 / 4097, an ALT of 5000 alleles and one of 100 000 bytes, field offsets, spans and lines
+// held to a naive splitter written here.  Not part of the library.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -99,6 +101,61 @@ std::string gts(uint32_t mask) {
   for (int k = 0; k < 10; ++k) s += (mask >> k) & 1 ? "\t0/1" : "\t0/0";
   return s + "\n";
 }
+// ---- the naive splitter the long-field cases are held to
+std::vector<std::string> split(const std::string& s, char d) {
+  std::vector<std::string> out(1);
+  for (char c : s) {
+    if (c == d) out.emplace_back();
+    else out.back().push_back(c);
+  }
+  return out;
+}
+std::string rep(const std::string& unit, size_t n) {
+  std::string s;
+  while (s.size() < n) s += unit;
+  return s.substr(0, n);
+}
+std::string alt_of_len(size_t n) { return n & 1 ? "G" + rep(",T", n - 1) : "GA" + rep(",T", n - 2); }
+std::string filter_of_len(size_t n) { return (n - 4) & 1 ? "PASS;qq" + rep(";q", n - 7) : "PASS" + rep(";q", n - 4); }
+// a record of eight fields whose field f starts at byte o: the field in front of it lengthened (ALT in front of FILTER: QUAL stays short)
+std::string long_record(int f, size_t o, bool* has_af) {
+  std::vector<std::string> fl = {"1", "1", ".", "A", "G", ".", "PASS"};
+  const int how = f - 1 == 5 ? 4 : f - 1;
+  size_t start = 0, between = 0;
+  for (int k = 0; k < how; ++k) start += fl[k].size() + 1;
+  for (int k = how + 1; k < f; ++k) between += fl[k].size() + 1;
+  const size_t n = o - start - 1 - between;
+  fl[how] = how == 0 ? rep("chrX", n) : how == 1 ? rep("1234567890", n) : how == 2 ? rep("rs77", n) : how == 3 ? rep("ACGT", n) : how == 4 ? alt_of_len(n) : filter_of_len(n);
+  *has_af = how != 4;
+  std::string s;
+  for (const std::string& x : fl) s += x + "\t";
+  s += "AC_afr=0";
+  for (int i = 1; i < 10; ++i) s += std::string(";AC_") + POPS[i] + "=5";
+  return *has_af ? s + ";AF=0.5" : s;
+}
+// record i of R against the splitter: field offsets, QUAL and AF spans, mask, the line
+void check_long(const Result& R, uint64_t i, const std::string& line, uint32_t mask, const std::string& what) {
+  const std::vector<std::string> f = split(line, '\t');
+  if (f.size() < 8) { fail(what + ": the case has no eight fields"); return; }
+  uint32_t fo[8], p = 0;
+  for (int k = 0; k < 8; ++k) { fo[k] = p; p += (uint32_t)f[k].size() + 1; }
+  for (int k = 0; k < 8; ++k)
+    if (R.fo[i * 8 + k] != fo[k]) fail(what + ": field " + std::to_string(k) + " at " + std::to_string(R.fo[i * 8 + k]) + ", expected " + std::to_string(fo[k]));
+  if (R.qs[i * 2] != fo[5] || R.qs[i * 2 + 1] != f[5].size()) fail(what + ": QUAL span");
+  const uint32_t n_alt = (uint32_t)split(f[4], ',').size();
+  std::string af;
+  uint32_t a0 = n_alt, a1 = 0xffffffffu, q = fo[7];
+  for (const std::string& e : split(f[7], ';')) {
+    if (e.rfind("AF=", 0) == 0) { a0 = q + 3; a1 = (uint32_t)e.size() - 3; af = e.substr(3); break; }
+    q += (uint32_t)e.size() + 1;
+  }
+  if (R.as[i * 2] != a0 || R.as[i * 2 + 1] != a1) fail(what + ": AF span " + std::to_string(R.as[i * 2]) + ", expected " + std::to_string(a0));
+  if (a1 == 0xffffffffu)
+    for (uint32_t a = 0; a < n_alt; ++a) af += a ? ",0.0" : "0.0";
+  else if (af != "0.5") { fail(what + ": the case's AF is not 0.5"); return; }
+  const std::string want = f[0] + "\t" + f[1] + "\t" + f[2] + "\t" + f[3] + "\t" + f[4] + "\t.\t" + (f[6] == "." ? "" : f[6]) + "\tAF=" + af + "\tGT" + gts(mask);
+  if (R.flags[i] != 0 || R.mask[i] != mask || line_of(R, i) != want) fail(what + ": flags, mask or line");
+}
 }  // namespace
 
 int main() {
@@ -178,6 +235,32 @@ int main() {
     const char* afs[6] = {"AF=0.0\t", "AF=0.0,0.0\t", "AF=0.0,0.0,0.0\t", "AF=None\t", "AF=0.5,None\t", "AF=0.125,9.999999747378752e-06,3.0\t"};
     for (int i = 0; i < 6; ++i)
       if (R.rc != HAWK_OK || line_of(R, i).find(afs[i]) == std::string::npos) fail(std::string("AF case ") + afs[i]);
+  }
+  // ---- long fields: every field start at 4095 / 4096 / 4097, 5000 alleles, a 100 000-byte ALT
+  {
+    std::vector<std::string> lines, names;
+    for (int f = 1; f <= 7; ++f)
+      for (size_t o : {4095u, 4096u, 4097u}) {
+        bool has_af;
+        lines.push_back(long_record(f, o, &has_af));
+        names.push_back("field " + std::to_string(f) + " at " + std::to_string(o));
+        if (split(lines.back(), '\t').size() != 8 || lines.back()[o - 1] != '\t') fail(names.back() + ": not built so");
+        lines.push_back(lines.back() + "\tAC_afr=5;AF=0.9");  // a ninth field the scan must not read
+        names.push_back(names.back() + ", a ninth field");
+      }
+    std::string many;
+    for (int a = 0; a < 5000; ++a) many += std::string(a ? "," : "") + (a % 3 == 0 ? "G" : a % 3 == 1 ? "TA" : "CAT");
+    for (const std::string& alt : {many, rep("ACGT", 100000)}) {
+      std::string s = "1\t1\t.\tA\t" + alt + "\t.\tPASS\tAC_afr=0";
+      for (int i = 1; i < 10; ++i) s += std::string(";AC_") + POPS[i] + "=5";
+      lines.push_back(s);
+      names.push_back("ALT of " + std::to_string(alt.size()) + " bytes");
+    }
+    const Result R = run(lines, {}, K, 0);
+    if (R.rc != HAWK_OK || R.n_kept != lines.size()) fail("long fields");
+    else
+      for (uint64_t i = 0; i < lines.size(); ++i) check_long(R, i, lines[i], 0x3fe, names[i]);
+    records += lines.size();
   }
   // ---- refused arguments: nothing written
   {
