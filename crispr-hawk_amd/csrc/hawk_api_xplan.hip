@@ -253,30 +253,36 @@ static int xplan_build_dict(hawk_xplan* x) {
   HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_BEGIN], st));
   HIPCHK(hipMemsetAsync(d_zero, 0, z_end, st));
   // chunks per row -> their offsets and rows, then the instances every chunk opens and how many of them go on the list of the
-  // clusters that are more than their variant (the number of chunks is only known on the device - rows that scan nothing have
+  // clusters that are more than their variant - and, from a large job's first chunks, the variants they describe (the number of
+  // chunks is only known on the device - rows that scan nothing have
   // none: the count pass and its scan run over the bound; chunks beyond the last one open nothing)
   hawk_launch_cl_chunks(st, x->off.as<uint64_t>(), x->m_is_ref.as<uint8_t>(), x->m_ss.as<int32_t>(), x->m_se.as<int32_t>(), n, d_ch_off, d_ch_row);
   hawk_launch_cl_count(st, x->heads.p, x->off.as<uint64_t>(), x->hlen.as<uint32_t>(), x->m_ss.as<int32_t>(), x->m_se.as<int32_t>(), d_ch_off, d_ch_row, n,
-                       n_var, ch_bound, d_cnt, d_lcnt);
-  hawk_launch_scan2_u32(st, d_cnt, d_lcnt, ch_bound, d_base, d_lbase);
+                       n_var, ch_bound, d_cnt, d_lcnt, d_vdesc);
+  if (hawk_cl_head_chunks(ch_bound))  // (beside the scan, in its launch: the bitmap of the variants the first chunks described)
+    hawk_launch_scan2_u32(st, d_cnt, d_lcnt, ch_bound, d_base, d_lbase, d_vdesc, d_claim, n_var);
+  else
+    hawk_launch_scan2_u32(st, d_cnt, d_lcnt, ch_bound, d_base, d_lbase);
   const uint32_t* const d_n_inst = d_base + ch_bound;
   const uint32_t* const d_n_list = d_lbase + ch_bound;
   // One pass = cut the rows (a one-record shareable instance is its variant; the rest goes on the list), the listed instances through
   // the table, the distinct clusters' descriptions, the listed instances that share a cluster - queued without a read-back in
   // between.  The host reads the counts once, at the end, and repeats the pass if the small table gave up.
-  unsigned long long res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // (read back into the context's page-locked block, behind the 64 bytes a search's status block takes: a copy into pageable memory is staged)
+  unsigned long long* const res = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->pinned) + 128);
+  for (int k = 0; k < 8; ++k) res[k] = 0;
   uint32_t status = 0, n_inst = 0, n_uniq = 0, n_real = 0;
   auto pass = [&](uint32_t tsz, uint32_t max_probe, uint32_t fail_bit, bool first) -> int {
     const uint32_t u_bound = n_var + std::min<uint32_t>(tsz, inst_bound);  // the variants, then what the table can hold
     uint32_t* d_span2 = reinterpret_cast<uint32_t*>(d_zero + z_span2);
     void* d_tab = d_zero + z_tab;
-    if (!first) {  // the repeat: its own, larger table and bounds; everything cleared again
+    if (!first) {  // the repeat: its own, larger table and bounds, the counters cleared again.  The variants' bitmap and describers stay:
+      // the counting pass and the scan, which are not repeated, left the first rows' there, and who describes a variant does not depend on the table
       TEMPCHK(tmp, &d_span2, (size_t)u_bound * 4);
       TEMPCHK(tmp, &d_tab, (size_t)tsz * hawk_cl_slot_bytes());
       HIPCHK(hipMemsetAsync(d_tab, 0, (size_t)tsz * hawk_cl_slot_bytes(), st));
       HIPCHK(hipMemsetAsync(d_span2, 0, (size_t)u_bound * 4, st));
       HIPCHK(hipMemsetAsync(d_zero + z_counters, 0, z_cnt - z_counters, st));               // counters, results
-      HIPCHK(hipMemsetAsync(d_zero + z_claim, 0, z_span2 - z_claim, st));                   // the variants' bitmap and describers
     }
     int rc2;
     if ((rc2 = cl.u_rec.reserve((size_t)u_bound * 4)) || (rc2 = cl.u_n.reserve((size_t)u_bound * 4)) || (rc2 = cl.u_row.reserve((size_t)u_bound * 4)) ||

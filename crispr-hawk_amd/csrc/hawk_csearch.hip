@@ -10,7 +10,8 @@
 //
 //   dictionary (once per plan; hawk_xplan_view):  k_cl_chunks / k_cl_count / k_cl_fill cut every row's records into cluster instances.
 //       An instance of ONE record whose windows can meet no bound of its row IS its variant: its distinct cluster is the variant's
-//       index in the plan's table - nothing to look up, nothing to compare.  Every other instance with a cluster goes on a list and
+//       index in the plan's table - nothing to look up, nothing to compare (the counting pass describes the variants of the
+//       first rows, the cutting pass - one launch - what they left).  Every other instance with a cluster goes on a list and
 //       through a hash table of the variant identities (k_cl_enter), and is compared record by record with the instance that
 //       opened its cluster (k_cl_uid: exactly - same hash is not same cluster until then); those clusters are numbered behind the
 //       variants.  An instance whose windows could meet a row-specific bound (scan range, row ends) is a cluster of its own; one
@@ -188,7 +189,7 @@ __device__ __forceinline__ uint4 shfl_down4(const uint4& v, int d) {
 __global__ __launch_bounds__(256) void k_cl_count(const HxHead* __restrict__ recs, const uint64_t* __restrict__ hv_off, const uint32_t* __restrict__ hap_len,
                                                   const int32_t* __restrict__ ss_, const int32_t* __restrict__ se_, const uint32_t* __restrict__ ch_off,
                                                   const uint32_t* __restrict__ ch_row, uint32_t n_rows, uint32_t n_var, uint32_t* __restrict__ cnt,
-                                                  uint32_t* __restrict__ lcnt) {
+                                                  uint32_t* __restrict__ lcnt, unsigned long long* __restrict__ var_desc, uint32_t n_head) {
   __shared__ uint32_t s_w[256 / WAVE];
   const uint32_t b = blockIdx.x;
   if (b >= ch_off[n_rows]) return;  // (launched over the bound on the chunks: their number is only known on the device; workgroup-uniform)
@@ -212,8 +213,13 @@ __global__ __launch_bounds__(256) void k_cl_count(const HxHead* __restrict__ rec
       const uint64_t j = b0 + u * 256 + threadIdx.x;
       if (!(j < hi && (j == lo || (int32_t)r0[u].x - ((int32_t)rp[u].x + (int32_t)rp[u].z) > CL_LINK))) return;
       const ClCut k = cl_cut(recs, lo, hi, j, r0[u], rp[u], nx1, nx2, lane, ss, se, hl, row);
-      const bool simple = k.n == 1 && k.cls == 1 && r0[u].w < n_var;
+      const uint32_t v = r0[u].w;
+      const bool simple = k.n == 1 && k.cls == 1 && v < n_var;
       c += 1u + ((k.cls != 0 && !simple) ? 0x10000u : 0u);
+      // the first rows describe what they carry, before the cutting pass and its crowd: one aligned 64-bit store, whichever lands last
+      // is whole (row >= 1: never 0).  Which variants are described goes into the bitmap beside the scan (hawk_launch_scan2_u32): an
+      // atomic OR per instance here, as the head launch of the cutting pass once did it, cost this pass 13 us on C3
+      if (simple && b < n_head) var_desc[v] = (unsigned long long)(uint32_t)j | ((unsigned long long)row << 32);
     };
     static_assert(CL_ROW_U == 4, "one call per slice");
     one(0); one(1); one(2); one(3);
@@ -223,10 +229,10 @@ __global__ __launch_bounds__(256) void k_cl_count(const HxHead* __restrict__ rec
   if (threadIdx.x == 0) { cnt[b] = (tot & 0xffffu) + (b + 1 == ch_off[row + 1] ? 1u : 0u); lcnt[b] = tot >> 16; }
 }
 
-// Cuts chunks [b_first, ...) of the rows into instances.  A one-record shareable instance IS its variant (uid = the variant's index);
+// Cuts the rows' chunks into instances.  A one-record shareable instance IS its variant (uid = the variant's index);
 // any other instance with a cluster goes on the list for k_cl_enter / k_cl_uid.  No atomic that anybody waits for:
-// places in the instance arrays and on the list come from the counting pass; the variants the FIRST rows describe set a bit, and
-// the later launch reads those bits through LDS (a chunk's records are consecutive variants-in-a-row, ascending: one window of
+// places in the instance arrays and on the list come from the counting pass; the variants the FIRST rows described there (k_cl_count)
+// have their bit set (k_scan2_u32), and this pass reads those bits through LDS (a chunk's records are consecutive variants-in-a-row, ascending: one window of
 // the bitmap, C3: all 4 KB of it, loaded once per workgroup) and describes what they left.
 #define CL_BM_WORDS 4096  // the window's LDS words (16 KB); a chunk that spans more variants asks the bitmap in HBM directly
 __global__ __launch_bounds__(256) void k_cl_fill(const HxHead* __restrict__ recs, const uint64_t* __restrict__ hv_off,
@@ -234,12 +240,12 @@ __global__ __launch_bounds__(256) void k_cl_fill(const HxHead* __restrict__ recs
                                                  const int32_t* __restrict__ se_, const uint32_t* __restrict__ ch_off,
                                                  const uint32_t* __restrict__ ch_row, const uint32_t* __restrict__ inst_base,
                                                  const uint32_t* __restrict__ list_base, ClInst ci, unsigned long long* __restrict__ var_desc,
-                                                 uint32_t* claim_bits, uint32_t n_var, ClListed* __restrict__ cx_list, uint32_t* __restrict__ status,
-                                                 uint32_t b_first, uint32_t n_rows, uint32_t head) {
+                                                 const uint32_t* __restrict__ claim_bits, uint32_t n_var, ClListed* __restrict__ cx_list, uint32_t* __restrict__ status,
+                                                 uint32_t n_rows) {
   __shared__ uint32_t s_c[256 / WAVE][CL_ROW_U];  // cluster starts per wave and record slice
   __shared__ uint32_t s_l[256 / WAVE][CL_ROW_U];  // ... and how many of them are listed
   __shared__ uint32_t s_bm[CL_BM_WORDS];
-  const uint32_t b = b_first + blockIdx.x;
+  const uint32_t b = blockIdx.x;
   if (b >= ch_off[n_rows]) return;  // (launched over the bound on the chunks; workgroup-uniform)
   const uint32_t row = ch_row[b];
   const uint64_t lo = hv_off[row], hi = hv_off[row + 1];
@@ -249,11 +255,11 @@ __global__ __launch_bounds__(256) void k_cl_fill(const HxHead* __restrict__ recs
   const uint32_t at = inst_base[b], lat = list_base[b];
   uint32_t round_tot = 0;
   if (hi > lo) {
-    // the chunk's window of the variants' bitmap (the head launch writes the bitmap and reads nothing of it)
+    // the chunk's window of the variants' bitmap (the first chunks' variants, described by the counting pass; nothing here writes it)
     const uint64_t b1 = b0 + CL_CHUNK < hi ? b0 + CL_CHUNK : hi;
     const uint32_t v_lo = recs[b0].var, v_hi = recs[b1 - 1].var;
     const uint32_t w_lo = v_lo >> 5, n_w = v_hi >= v_lo && v_hi < n_var ? (v_hi >> 5) - w_lo + 1u : 0u;
-    const bool bm_lds = !head && n_w != 0u && n_w <= CL_BM_WORDS;  // workgroup-uniform
+    const bool bm_lds = n_w != 0u && n_w <= CL_BM_WORDS;  // workgroup-uniform
     if (bm_lds) for (uint32_t w = threadIdx.x; w < n_w; w += 256) s_bm[w] = claim_bits[w_lo + w];
     // CL_ROW_U slices of 256 consecutive records: every thread's record and the one before it, asked for at once
     uint4 r0[CL_ROW_U], rp[CL_ROW_U];
@@ -304,13 +310,8 @@ __global__ __launch_bounds__(256) void k_cl_fill(const HxHead* __restrict__ recs
         if (simple) {
           ci.uid[i] = v;
           const uint32_t bit = 1u << (v & 31u);
-          const unsigned long long desc = (unsigned long long)(uint32_t)j | ((unsigned long long)row << 32);  // (row >= 1: never 0)
-          if (head) {  // the first rows describe what they carry and say so
-            var_desc[v] = desc;
-            (void)__hip_atomic_fetch_or(&claim_bits[v >> 5], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else if (!((bm_lds ? s_bm[(v >> 5) - w_lo] : claim_bits[v >> 5]) & bit)) {
-            var_desc[v] = desc;  // whichever of these lands last is whole: one aligned 64-bit store
-          }
+          if (!((bm_lds ? s_bm[(v >> 5) - w_lo] : claim_bits[v >> 5]) & bit))  // nobody among the first rows carries it as a cluster of its own
+            var_desc[v] = (unsigned long long)(uint32_t)j | ((unsigned long long)row << 32);  // (row >= 1: never 0; whichever lands last is whole: one aligned 64-bit store)
         }
         listed[u] = k.cls != 0 && !simple;
         ea[u] = make_uint4(i, (uint32_t)k.key, (uint32_t)(k.key >> 32), (uint32_t)j);
@@ -548,24 +549,28 @@ void hawk_launch_cl_chunks(hipStream_t st, const uint64_t* hv_off, const uint8_t
                            uint32_t* ch_off, uint32_t* ch_row) {
   hipLaunchKernelGGL(k_cl_chunks, dim3(1), dim3(1024), 0, st, hv_off, is_ref, ss, se, n_rows, ch_off, ch_row);
 }
-void hawk_launch_cl_count(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
-                          const uint32_t* ch_off, const uint32_t* ch_row, uint32_t n_rows, uint32_t n_var, uint32_t ch_bound, uint32_t* cnt /* zeroed */,
-                          uint32_t* lcnt /* zeroed */) {
-  if (ch_bound)
-    hipLaunchKernelGGL(k_cl_count, dim3(ch_bound), dim3(256), 0, st, static_cast<const HxHead*>(recs), hv_off, hap_len, ss, se, ch_off, ch_row, n_rows,
-                       n_var, cnt, lcnt);
-}
-// Two launches: the first chunks (a few dozen rows), then the rest - and likewise the head of the list, then the rest.  A common
-// cluster has thousands of instances, half of which are in flight at once in a single launch: in the table passes they all find
-// their slot empty and all go to the atomic - thousands of device-scope atomics queued at one address (60-90 us, whatever the
-// panel's size); in the cutting pass they would all describe the cluster.  After the head launch every common cluster is there.
+// The first CL_HEAD_CHUNKS chunks (a few dozen rows) describe the variants they carry in the COUNTING pass, which cuts them anyway;
+// the launch of the scan turns the describers into the bitmap, and the cutting pass - one launch - describes what they left.  A
+// common variant has thousands of instances, half of which are in flight at once: without the bitmap they would all describe it.
+// Likewise the table passes run the head of the list as a launch of its own, then the rest: in a single launch the instances of a
+// common cluster all find their slot empty and all go to the atomic - thousands of device-scope atomics queued at one address
+// (60-90 us, whatever the panel's size).
+// A small job - a stretch of a region on one of several GPUs - has no crowd to keep away from one address: no bitmap, no head.
 // The launches run over BOUNDS (the numbers of chunks and of listed instances are on the device only; surplus workgroups leave at once).
 #define CL_HEAD_CHUNKS 96
 #define CL_HEAD_LISTED 16384
+uint32_t hawk_cl_head_chunks(uint32_t ch_bound) { return ch_bound < 16 * CL_HEAD_CHUNKS ? 0u : CL_HEAD_CHUNKS; }
+void hawk_launch_cl_count(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
+                          const uint32_t* ch_off, const uint32_t* ch_row, uint32_t n_rows, uint32_t n_var, uint32_t ch_bound, uint32_t* cnt /* zeroed */,
+                          uint32_t* lcnt /* zeroed */, void* var_desc) {
+  if (ch_bound)
+    hipLaunchKernelGGL(k_cl_count, dim3(ch_bound), dim3(256), 0, st, static_cast<const HxHead*>(recs), hv_off, hap_len, ss, se, ch_off, ch_row, n_rows,
+                       n_var, cnt, lcnt, static_cast<unsigned long long*>(var_desc), hawk_cl_head_chunks(ch_bound));
+}
 void hawk_launch_cl_fill(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
                          uint32_t n_rows, const uint32_t* ch_off, const uint32_t* ch_row, uint32_t ch_bound, const uint32_t* inst_base,
                          const uint32_t* list_base, int32_t* o, uint32_t* row, int32_t* pa, int32_t* rb, uint32_t* inst_uid, void* var_desc,
-                         uint32_t* claim_bits, uint32_t n_var, void* cx_list, uint32_t* status) {
+                         const uint32_t* claim_bits, uint32_t n_var, void* cx_list, uint32_t* status) {
   ClInst ci{o, row, pa, rb, inst_uid};
 #ifdef HAWK_TEST_HOOKS
   {
@@ -574,16 +579,9 @@ void hawk_launch_cl_fill(hipStream_t st, const void* recs, const uint64_t* hv_of
     (void)hipMemcpyToSymbol(HIP_SYMBOL(cl_weak_hash), &weak, sizeof(weak));
   }
 #endif
-  // (a small job - a stretch of a region on one of several GPUs - has no crowd to keep away from one address, and two launches
-  // of pure latency to save: everything in the second launch, where every instance whose variant nobody described writes it)
-  const uint32_t n_head = ch_bound < 16 * CL_HEAD_CHUNKS ? 0u : CL_HEAD_CHUNKS;
-  if (n_head)
-    hipLaunchKernelGGL(k_cl_fill, dim3(n_head), dim3(256), 0, st, static_cast<const HxHead*>(recs), hv_off, hap_len, ss, se, ch_off, ch_row, inst_base,
-                       list_base, ci, static_cast<unsigned long long*>(var_desc), claim_bits, n_var, static_cast<ClListed*>(cx_list), status, 0u, n_rows, 1u);
-  if (ch_bound > n_head)
-    hipLaunchKernelGGL(k_cl_fill, dim3(ch_bound - n_head), dim3(256), 0, st, static_cast<const HxHead*>(recs), hv_off, hap_len, ss, se, ch_off, ch_row,
-                       inst_base, list_base, ci, static_cast<unsigned long long*>(var_desc), claim_bits, n_var, static_cast<ClListed*>(cx_list), status,
-                       n_head, n_rows, 0u);
+  if (ch_bound)
+    hipLaunchKernelGGL(k_cl_fill, dim3(ch_bound), dim3(256), 0, st, static_cast<const HxHead*>(recs), hv_off, hap_len, ss, se, ch_off, ch_row, inst_base,
+                       list_base, ci, static_cast<unsigned long long*>(var_desc), claim_bits, n_var, static_cast<ClListed*>(cx_list), status, n_rows);
 }
 // after the cutting pass: the listed instances through the table, the distinct clusters' descriptions, then the listed instances
 // that share a cluster.  counters: [0] the table's distinct clusters, [1] the variants that are clusters of their own, [4..5] the

@@ -154,19 +154,23 @@ struct ClDict {
   const uint32_t* u_seg;     // a position-map segment of that row in force in front of every position a search of the cluster maps
 };
 size_t hawk_cs_row_bytes();
-void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b);  // two arrays, one launch
+void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b,
+                           const void* desc = nullptr, uint32_t* desc_bits = nullptr, uint32_t n_desc = 0);  // two arrays, one launch; beside it, if asked for:
+                           // which of n_desc 64-bit words are not 0, as a bitmap of n_desc / 32 + 1 words
 void hawk_launch_hx_heads(hipStream_t st, const void* recs, const uint32_t* hv_idx, uint64_t n, void* heads);  // {o, rs, alt_len, variant} per record
 // (the hawk_launch_cl_* passes take the HEADS as `recs`)
 uint32_t hawk_cl_chunk_bound(uint64_t n_records, uint32_t n_rows);  // room for ch_row / the chunks' counts
 void hawk_launch_cl_chunks(hipStream_t st, const uint64_t* hv_off, const uint8_t* is_ref, const int32_t* ss, const int32_t* se, uint32_t n_rows,
                            uint32_t* ch_off, uint32_t* ch_row);
+uint32_t hawk_cl_head_chunks(uint32_t ch_bound);  // the first chunks, whose variants the counting pass describes (0: a small job, none)
 void hawk_launch_cl_count(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
                           const uint32_t* ch_off, const uint32_t* ch_row, uint32_t n_rows, uint32_t n_var, uint32_t ch_bound, uint32_t* cnt /* zeroed */,
-                          uint32_t* lcnt /* zeroed */);  // per chunk: the instances it opens, and how many of them go on the list
+                          uint32_t* lcnt /* zeroed */, void* var_desc /* 8 B per variant, zeroed */);  // per chunk: the instances it opens, and how
+                          // many of them go on the list; the first hawk_cl_head_chunks() chunks also describe the variants they carry
 void hawk_launch_cl_fill(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
                          uint32_t n_rows, const uint32_t* ch_off, const uint32_t* ch_row, uint32_t ch_bound, const uint32_t* inst_base,
                          const uint32_t* list_base, int32_t* o, uint32_t* row, int32_t* pa, int32_t* rb, uint32_t* inst_uid,
-                         void* var_desc /* 8 B per variant, zeroed */, uint32_t* claim_bits /* n_var bits, zeroed */, uint32_t n_var,
+                         void* var_desc /* as hawk_launch_cl_count left it */, const uint32_t* claim_bits /* n_var bits: who is described */, uint32_t n_var,
                          void* cx_list /* hawk_cl_listed_bytes() per listed instance */, uint32_t* status);
 size_t hawk_cl_slot_bytes();    // a slot of the table of the listed instances' clusters
 size_t hawk_cl_listed_bytes();  // a list entry

@@ -29,7 +29,8 @@ struct hawk_ctx {
   // Scratch of the call that is running: every C-ABI call records the events it times with and reads them before it returns.
   // No call may read an event another call recorded (two calls use the same slots for different intervals).
   hipEvent_t ev[10];
-  void* pinned = nullptr;  // 256 B of page-locked host memory: hawk_search reads the device's SearchStatusBlock back into it
+  void* pinned = nullptr;  // 256 B of page-locked host memory: hawk_search reads the device's SearchStatusBlock back into it ([0, 64)),
+                           // the cluster dictionary's build its result block ([128, 192))
 };
 
 // What hs->misc holds while hawk_search runs.  The host and the kernels' launchers share the status block; the host reads it back

@@ -92,10 +92,20 @@ __global__ __launch_bounds__(1024) void k_scan_u32(const uint32_t* __restrict__ 
 // A thread takes sixteen CONSECUTIVE counts of either array (four 16-byte loads each, all in flight at once), scans them in
 // registers, and the workgroup scans the threads' sums once per 16384 counts: a scan of 1.5 x 10^4 counts is latency and nothing
 // else, so it is one round trip and one pair of barriers instead of fifteen.  Arrays and offsets 16-byte aligned, as the pool's are.
+// Workgroups behind the first do a job that only has to be done before the cutting pass and would otherwise be a launch of its own,
+// or an atomic per instance in the counting pass: the bitmap of the variants that pass described (desc: their 64-bit describers).
 __global__ __launch_bounds__(1024) void k_scan2_u32(const uint32_t* __restrict__ cnt_a, const uint32_t* __restrict__ cnt_b, uint32_t n,
-                                                    uint32_t* __restrict__ off_a, uint32_t* __restrict__ off_b) {
+                                                    uint32_t* __restrict__ off_a, uint32_t* __restrict__ off_b,
+                                                    const unsigned long long* __restrict__ desc, uint32_t* __restrict__ desc_bits, uint32_t n_desc) {
   __shared__ uint32_t s_w[2][1024 / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  if (blockIdx.x) {  // which of n_desc 64-bit words are set, as a bitmap of n_desc / 32 + 1 words: a wave per 64 of them
+    const uint32_t v = (blockIdx.x - 1) * 1024 + threadIdx.x;
+    const unsigned long long set = __ballot(v < n_desc && desc[v] != 0ull);
+    const uint32_t w = v >> 5, n_w = n_desc / 32 + 1;
+    if (lane == 0) { if (w < n_w) desc_bits[w] = (uint32_t)set; if (w + 1 < n_w) desc_bits[w + 1] = (uint32_t)(set >> 32); }
+    return;
+  }
   uint32_t carry_a = 0, carry_b = 0;
   for (uint32_t b0 = 0; b0 < n; b0 += 16 * 1024) {
     const uint32_t i0 = b0 + threadIdx.x * 16;
@@ -236,8 +246,10 @@ void hawk_launch_segments(hipStream_t st, const uint64_t* ioff, const uint32_t* 
     hipLaunchKernelGGL(k_seg_fill, dim3(n_rows), dim3(256), 0, st, ioff, indel, hv_idx, hv_o, v_r0, v_chain, hap_len, startp, seg_off, seg_rel, seg_gen);
   }
 }
-void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b) {
-  hipLaunchKernelGGL(k_scan2_u32, dim3(1), dim3(1024), 0, st, cnt_a, cnt_b, n, off_a, off_b);
+void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b,
+                           const void* desc, uint32_t* desc_bits, uint32_t n_desc) {
+  hipLaunchKernelGGL(k_scan2_u32, dim3(1 + (desc ? (n_desc + 1023) / 1024 : 0u)), dim3(1024), 0, st, cnt_a, cnt_b, n, off_a, off_b,
+                     static_cast<const unsigned long long*>(desc), desc_bits, n_desc);
 }
 void hawk_launch_rev_lookup(hipStream_t st, const uint32_t* seg_off, const uint32_t* seg_rel, const int64_t* seg_gen, const uint32_t* hap_len,
                             uint32_t n_rows, int64_t g0, int64_t g1, int64_t* out0, int64_t* out1) {
