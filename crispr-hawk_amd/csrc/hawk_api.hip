@@ -146,7 +146,9 @@ int hawk_init(int device, hawk_ctx** out) {
   if (!ctx) return HAWK_E_INVALID;
   ctx->device = device;
   HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-  for (auto& e : ctx->ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+  for (int i = 0; i < (int)(sizeof(ctx->ev) / sizeof(ctx->ev[0])); ++i)
+    HIPCHK(i < HAWK_EV_TIMED ? hipEventCreate(&ctx->ev[i]) : hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
   HIPCHK(hipHostMalloc(&ctx->pinned, 256, hipHostMallocDefault));
   g_ctx_of[device] = ctx; g_ctx_refs[device] = 1;
   *out = ctx;
@@ -165,8 +167,10 @@ void hawk_destroy(hawk_ctx* ctx) {
   }
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  (void)hipStreamSynchronize(ctx->side);  // (every search joined it before it returned)
   hawk_ottext_forget(ctx);  // rows of a hawk_offtarget_text nobody downloaded
   for (auto& e : ctx->ev) (void)hipEventDestroy(e);
+  (void)hipStreamDestroy(ctx->side);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   delete ctx;

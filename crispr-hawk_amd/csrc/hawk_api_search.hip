@@ -28,18 +28,24 @@ int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c) {
 
 #define HAWK_RETRY_TEMPLATES (-100)  // private to this file: the template rows of a cluster search outgrew their reservation
 
-// The slots of hawk_ctx::ev a search records, each named for the interval it opens or closes.
+// The slots of hawk_ctx::ev a search records, each named for the interval it opens or closes.  A recorded event is a packet of its
+// own between two kernels of its stream (5-6 us on the main stream of a C3 search, profiles/ref_overlap.md): an interval that begins
+// where another one ends shares that event instead of recording a second one behind it.
 enum SearchEvent {
   EV_BEGIN, EV_COUNT_DONE, EV_OFFSETS_DONE, EV_EMIT_BEGIN, EV_EMIT_END, EV_LIST_EMIT_END,  // every search
   EV_VIEW_COUNT_BEGIN, EV_VIEW_EMIT_BEGIN,                                                 // a view of an expansion plan
-  EV_TEMPLATES_DONE, EV_REF_ROWS_PACKED,                                                   // ... searched per cluster
+  EV_TEMPLATES_DONE,                                                                       // ... searched per cluster
+  // ordering only: REF's passes on the side stream are done (the forks wait on the event that opens the stage on the main stream)
+  EV_COUNT_JOIN = HAWK_EV_TIMED, EV_EMIT_JOIN,
   EV_SLOTS
 };
-static_assert(EV_SLOTS == sizeof(hawk_ctx::ev) / sizeof(hipEvent_t), "hawk_ctx::ev holds exactly the search's events");
+static_assert(EV_SLOTS == sizeof(hawk_ctx::ev) / sizeof(hipEvent_t), "hawk_ctx::ev ends with the search's ordering events");
+static_assert(EV_TEMPLATES_DONE < HAWK_EV_TIMED, "the slots in front of the joins carry timestamps");
 
 // One attempt of hawk_search: what its stages share.  search_classify .. search_view_args fill it, the stages behind them read it.
 struct SearchRun {
   hawk_hapset* hs; hawk_ctx* ctx; hipStream_t st;
+  hipStream_t side;               // where REF's plane passes of a cluster search run, beside the cluster passes on st
   const hawk_xplan* vx;           // the plan a view is searched from (nullptr: a set with planes, every row through the plane kernels)
   bool by_cluster;                // ... per distinct cluster (hawk_csearch.hip); false: per dirty word (hawk_vsearch.hip)
   HapSetDev d; ScanParams sp; GuideParams gp; RefInfo ri; VcArgs va; ClDict cd;
@@ -51,6 +57,7 @@ struct SearchRun {
   SearchStatusBlock* blk;         // ... and the status block every launcher is handed its fields of
   SearchStatusBlock* h;           // the status block as last read back (hawk_ctx::pinned)
   uint64_t* table_cap;            // rows the set's table holds: hs->rows_cap for a cluster search, else hs->cols_cap
+  SearchEvent emit_begin;         // what opened the last emit: EV_OFFSETS_DONE straight behind the scan (a speculative emit), else EV_EMIT_BEGIN
 };
 
 // Parameter checks, and which path runs.  A view of an expansion plan (hawk_xplan_view) holds no planes: its REF row runs through the
@@ -60,7 +67,7 @@ struct SearchRun {
 static int search_classify(hawk_hapset* hs, const hawk_search_params* p, SearchRun* r) {
   if (!hs || !p || !hs->has_meta || p->score_cfdon > 2) return HAWK_E_INVALID;
   if (p->score_cfdon && (p->right || !p->cfd_mm || !p->cfd_pam || p->pamlen < 2)) return HAWK_E_INVALID;
-  r->hs = hs; r->ctx = hs->ctx; r->st = hs->ctx->stream; r->vx = hs->vplan;
+  r->hs = hs; r->ctx = hs->ctx; r->st = hs->ctx->stream; r->side = hs->ctx->side; r->vx = hs->vplan;
   HIPCHK(hipSetDevice(r->ctx->device));
   const int rc = make_scan_params(hs, p->pam_fwd, p->pam_rev, p->pamlen, p->guidelen, p->right, true, &r->sp);
   if (rc) return rc;
@@ -79,6 +86,7 @@ static int search_classify(hawk_hapset* hs, const hawk_search_params* p, SearchR
   r->stage_cap = r->by_cluster ? 2ull * hs->hap_len[hs->ref_index] + 64 : 0;
   r->table_cap = r->by_cluster ? &hs->rows_cap : &hs->cols_cap;
   r->tcap = r->t_rows_used = 0;
+  r->emit_begin = EV_EMIT_BEGIN;
   return HAWK_OK;
 }
 // The workspaces every path needs, and what points into them.  Hand-over lists (2 KB per tile): the count pass leaves each small
@@ -184,15 +192,30 @@ static int search_view_args(SearchRun* r) {
     return rc;
   return HAWK_OK;
 }
+// The side stream's work behind a fork is done -> the main stream goes on.  Nothing between a fork and its join returns: if the join
+// cannot be queued the host waits for the side stream instead, so no caller ever meets REF's kernels still in flight.
+static hipError_t search_join(SearchRun* r, SearchEvent done) {
+  hipError_t e = hipEventRecord(r->ctx->ev[done], r->side);
+  if (e == hipSuccess) e = hipStreamWaitEvent(r->st, r->ctx->ev[done], 0);
+  if (e != hipSuccess) (void)hipStreamSynchronize(r->side);
+  return e;
+}
 // The count side: the plane kernels' tiles, then the view's share - templates + a count per cluster instance, or pass 0 of the
-// per-word search - then the offset scan, which leaves the totals in the status block.
+// per-word search - then the offset scan, which leaves the totals in the status block.  A cluster search forks: REF's tiles are
+// counted on the side stream (counts[0, plane_tiles), the hand-over lists, the work list) while the main stream makes the templates
+// and counts the instances (counts[plane_tiles, ..)); the shard sums and the status take atomics from both.  The scan reads both
+// halves: the join stands right in front of it, behind EV_COUNT_DONE, so the cluster passes' brackets hold nothing but their kernels
+// (and begin at EV_BEGIN: the main stream has nothing in front of them).
 static int search_count(SearchRun* r) {
   hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
   SearchStatusBlock* blk = r->blk; uint32_t* counts = hs->counts.as<uint32_t>();
+  const bool fork = r->by_cluster;
   HIPCHK(hipEventRecord(ev[EV_BEGIN], st));
-  hawk_launch_search(st, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
-                     &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
-  if (r->vx) HIPCHK(hipEventRecord(ev[EV_VIEW_COUNT_BEGIN], st));
+  if (!fork) {
+    hawk_launch_search(st, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
+                       &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
+    if (r->vx) HIPCHK(hipEventRecord(ev[EV_VIEW_COUNT_BEGIN], st));
+  }
   if (r->by_cluster) {
     hawk_launch_cs_templates(st, r->d, r->va, r->cd, r->sp, r->gp, r->ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, &blk->template_rows,
                              r->tcap, &blk->status);
@@ -204,6 +227,13 @@ static int search_count(SearchRun* r) {
                         r->plane_tiles, r->v_tiles);
   }
   HIPCHK(hipEventRecord(ev[EV_COUNT_DONE], st));
+  if (fork) {
+    // the main stream's kernels are queued first: at the head of a search the device is waiting for the host
+    HIPCHK(hipStreamWaitEvent(r->side, ev[EV_BEGIN], 0));  // (nothing is queued on the side stream yet)
+    hawk_launch_search(r->side, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
+                       &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
+    HIPCHK(search_join(r, EV_COUNT_JOIN));
+  }
   hawk_launch_mscan(st, counts, r->nscan, hs->partial.as<unsigned long long>(), r->shards, hs->offsets.as<uint64_t>(), &blk->totals);
   HIPCHK(hipEventRecord(ev[EV_OFFSETS_DONE], st));
   HIPCHK(hipGetLastError());
@@ -221,22 +251,31 @@ static int search_reserve_table(SearchRun* r, uint64_t cap, GuideCols* cols, Gui
   table->rows = hs->rowsA.as<uint4>(); table->cap = cap; table->startp = r->ri.startp;
   return HAWK_OK;
 }
-// The emit side, between its two events (`launch` false: a table of no rows).  Plane kernels (all rows of a set with planes; REF's
+// The emit side, between its two events (`launch` false: a table of no rows); `behind_scan`: nothing has been queued since the offset
+// scan, whose event then opens the emit as well.  Plane kernels (all rows of a set with planes; REF's
 // rows of a view) and the per-word search of a view write columns; the cluster search writes packed rows (k_cs_emit_rows), and REF's
 // rows - staged as columns - are packed in front of them.  The kernels take their offsets from HBM and refuse to write past the capacity.
-static int search_emit(SearchRun* r, const GuideCols& cols, const GuideCols& packed, bool launch) {
+// A cluster search forks here too: REF's emit chain and its packing run on the side stream and write the table's rows
+// [0, offsets[plane_tiles]) (through the staging columns, which nothing else touches); k_cs_emit_rows, the only kernel on the main stream,
+// writes every row behind them.  The join stands in front of EV_EMIT_END, and so in front of whatever reads the status block or the table.
+static int search_emit(SearchRun* r, const GuideCols& cols, const GuideCols& packed, bool launch, bool behind_scan) {
   hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
   SearchStatusBlock* blk = r->blk; const uint64_t* offsets = hs->offsets.as<uint64_t>();
-  HIPCHK(hipEventRecord(ev[EV_EMIT_BEGIN], st));
+  r->emit_begin = behind_scan ? EV_OFFSETS_DONE : EV_EMIT_BEGIN;
+  if (!behind_scan) HIPCHK(hipEventRecord(ev[EV_EMIT_BEGIN], st));
   if (launch) {
-    hawk_launch_search(st, 1, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), r->shards, offsets, cols, &blk->status, hs->lists.as<uint32_t>(),
-                       &blk->big_count, hs->big.as<unsigned long long>(), ev[EV_LIST_EMIT_END], r->plane_tiles);
-    if (r->vx) (void)hipEventRecord(ev[EV_VIEW_EMIT_BEGIN], st);
-    if (r->by_cluster) {
-      hawk_launch_rows_pack(st, cols, offsets + r->plane_tiles, 0, std::min<uint64_t>(r->stage_cap, packed.cap), packed.rows, packed.startp, &blk->status);
-      (void)hipEventRecord(ev[EV_REF_ROWS_PACKED], st);
+    const hipStream_t ref_st = r->by_cluster ? r->side : st;
+    if (r->by_cluster) {  // the main stream's kernel first, then the fork (nothing is queued on the side stream yet)
       hawk_launch_cs_emit_rows(st, r->cd, hs->cs_icnt.as<uint32_t>(), hs->cs_itb.as<uint32_t>(), hs->cs_trows.p, offsets + r->plane_tiles, &blk->template_rows,
                                r->tcap, packed.rows, packed.cap, &blk->status);
+      HIPCHK(hipStreamWaitEvent(r->side, ev[r->emit_begin], 0));
+    }
+    hawk_launch_search(ref_st, 1, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), r->shards, offsets, cols, &blk->status, hs->lists.as<uint32_t>(),
+                       &blk->big_count, hs->big.as<unsigned long long>(), ev[EV_LIST_EMIT_END], r->plane_tiles);
+    if (r->vx) (void)hipEventRecord(ev[EV_VIEW_EMIT_BEGIN], ref_st);
+    if (r->by_cluster) {
+      hawk_launch_rows_pack(ref_st, cols, offsets + r->plane_tiles, 0, std::min<uint64_t>(r->stage_cap, packed.cap), packed.rows, packed.startp, &blk->status);
+      HIPCHK(search_join(r, EV_EMIT_JOIN));
     } else if (r->vx) {
       hawk_launch_vsearch(st, 1, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), hs->vcnt0.as<uint32_t>(), r->shards, offsets, cols,
                           &blk->status, r->plane_tiles, r->v_tiles);
@@ -260,18 +299,21 @@ static int search_read_block(SearchRun* r) {
 
 static void search_timing(const SearchRun* r, uint64_t nrows, hawk_timing* timing) {
   const hawk_hapset* hs = r->hs; hipEvent_t* ev = r->ctx->ev;
+  const hipEvent_t emit_begin = ev[r->emit_begin];
   memset(timing, 0, sizeof(*timing));
   (void)hipEventElapsedTime(&timing->count_ms, ev[EV_BEGIN], ev[EV_COUNT_DONE]);
   (void)hipEventElapsedTime(&timing->offsets_ms, ev[EV_COUNT_DONE], ev[EV_OFFSETS_DONE]);
-  (void)hipEventElapsedTime(&timing->emit_ms, ev[EV_EMIT_BEGIN], ev[EV_EMIT_END]);
-  if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, ev[EV_EMIT_BEGIN], ev[EV_LIST_EMIT_END]);
+  (void)hipEventElapsedTime(&timing->emit_ms, emit_begin, ev[EV_EMIT_END]);
+  if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, emit_begin, ev[EV_LIST_EMIT_END]);
   (void)hipEventElapsedTime(&timing->total_ms, ev[EV_BEGIN], ev[EV_EMIT_END]);
   if (r->vx) {
-    (void)hipEventElapsedTime(&timing->v_count_ms, ev[EV_VIEW_COUNT_BEGIN], ev[EV_COUNT_DONE]);
+    // a cluster search: the main stream holds the cluster passes alone, their brackets open with the stage's
+    const hipEvent_t v_count_begin = ev[r->by_cluster ? EV_BEGIN : EV_VIEW_COUNT_BEGIN];
+    (void)hipEventElapsedTime(&timing->v_count_ms, v_count_begin, ev[EV_COUNT_DONE]);
     if (nrows) (void)hipEventElapsedTime(&timing->v_emit_ms, ev[EV_VIEW_EMIT_BEGIN], ev[EV_EMIT_END]);
     timing->v_path = r->by_cluster ? 2u : 1u;
-    if (r->by_cluster) (void)hipEventElapsedTime(&timing->v_templates_ms, ev[EV_VIEW_COUNT_BEGIN], ev[EV_TEMPLATES_DONE]);
-    if (r->by_cluster && nrows) (void)hipEventElapsedTime(&timing->v_emit_rows_ms, ev[EV_REF_ROWS_PACKED], ev[EV_EMIT_END]);
+    if (r->by_cluster) (void)hipEventElapsedTime(&timing->v_templates_ms, v_count_begin, ev[EV_TEMPLATES_DONE]);
+    if (r->by_cluster && nrows) (void)hipEventElapsedTime(&timing->v_emit_rows_ms, emit_begin, ev[EV_EMIT_END]);
   }
   uint64_t pos = 0;
   for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
@@ -296,7 +338,9 @@ static int search_make_table(const SearchRun* r, const hawk_search_params* p, co
 //    HAWK_RETRY_TEMPLATES (hawk_search reruns the attempt with more reserved); the rows fit the speculative emit - finished; else
 //    reserve for the rows and emit (again);
 //  * only the capacity refusal of a speculative emit is answered by emitting again.  Any other status was raised by the count side
-//    (a strict-mode CFD error, an unsupported coordinate range) and stands - the kernels keep the FIRST status they raise.
+//    (a strict-mode CFD error, an unsupported coordinate range) and stands - the kernels keep the FIRST status they raise;
+//  * a cluster search runs REF's plane passes on the context's side stream (search_count, search_emit): each fork is joined into the
+//    main stream before the stage returns, on its error paths too, so every return below leaves nothing in flight beside the main stream.
 static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_table** out, hawk_timing* timing) {
   if (!out) return HAWK_E_INVALID;
   SearchRun r;
@@ -307,7 +351,7 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
   uint64_t& table_cap = *r.table_cap;
   const bool speculative = table_cap != 0;
   GuideCols cols, table;
-  if (speculative && ((rc = search_reserve_table(&r, table_cap, &cols, &table)) || (rc = search_emit(&r, cols, table, true)))) return rc;
+  if (speculative && ((rc = search_reserve_table(&r, table_cap, &cols, &table)) || (rc = search_emit(&r, cols, table, true, true)))) return rc;
   if ((rc = search_read_block(&r))) return rc;
   const uint64_t nrows = r.h->totals.n_keep;
   if (!speculative || nrows > table_cap) {
@@ -316,7 +360,7 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
     if (speculative) HIPCHK(hipMemsetAsync(&r.blk->status, 0, sizeof(int), r.st));
     if ((rc = search_reserve_table(&r, std::max<uint64_t>(std::max<uint64_t>(nrows, 1), table_cap), &cols, &table))) return rc;
     table_cap = table.cap;
-    if ((rc = search_emit(&r, cols, table, nrows != 0))) return rc;
+    if ((rc = search_emit(&r, cols, table, nrows != 0, false))) return rc;
     HIPCHK(hipMemcpyAsync(&r.h->status, &r.blk->status, sizeof(int), hipMemcpyDeviceToHost, r.st));
     HIPCHK(hipStreamSynchronize(r.st));
   }

@@ -1098,11 +1098,15 @@ void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va,
 }
 
 // columns -> packed rows (REF's rows, which the plane kernels write as columns; a columnar table before an exchange) and back:
-// the field order of CsRow (hawk_rows.h)
-__global__ __launch_bounds__(256) void k_rows_pack(GuideCols c, const uint64_t* __restrict__ n_dev, uint64_t n_host, uint4* __restrict__ rows, int64_t startp,
-                                                   int* status) {
+// the field order of CsRow (hawk_rows.h).  `max_rows`: what `rows` holds.  The row count comes from the device, and a speculative
+// emit packs into a table an earlier search reserved: REF alone can have more rows than that table (a one-base PAM behind NGG on a
+// panel of few variants).  Like every other writer of a table the kernel then refuses instead of writing past the end - the launch is
+// rounded up to 256 threads, and those between max_rows and the next multiple used to write up to 255 rows behind the allocation.
+__global__ __launch_bounds__(256) void k_rows_pack(GuideCols c, const uint64_t* __restrict__ n_dev, uint64_t n_host, uint64_t max_rows, uint4* __restrict__ rows,
+                                                   int64_t startp, int* status) {
   const uint64_t n = n_dev ? *n_dev : n_host;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n > max_rows) { if (i == 0) atomicCAS(status, 0, -3 /* HAWK_E_CAPACITY */); return; }
   if (i >= n) return;
   const int64_t start = c.start[i], ds = start - startp, de = c.stop[i] - start;
   const uint32_t h = c.hap[i];
@@ -1141,7 +1145,7 @@ __global__ __launch_bounds__(256) void k_rows_unpack(const uint4* __restrict__ r
 void hawk_launch_rows_pack(hipStream_t st, const GuideCols& src, const uint64_t* n_dev, uint64_t n_host, uint64_t max_rows, uint4* rows, int64_t startp,
                            int* status) {
   if (!max_rows) return;
-  hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((max_rows + 255) / 256)), dim3(256), 0, st, src, n_dev, n_host, rows, startp, status);
+  hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((max_rows + 255) / 256)), dim3(256), 0, st, src, n_dev, n_host, max_rows, rows, startp, status);
 }
 void hawk_launch_rows_unpack(hipStream_t st, const uint4* rows, uint64_t n, int64_t startp, const GuideCols& dst) {
   if (!n) return;

@@ -23,12 +23,16 @@ char* hawk_hip_err_buf();  // thread-local text of the last HIP failure (hawk_la
     }                                                                                        \
   } while (0)
 
+#define HAWK_EV_TIMED 10  // slots [0, HAWK_EV_TIMED) of hawk_ctx::ev carry timestamps; the slots behind them only order two streams
 struct hawk_ctx {
   int device;
   hipStream_t stream;
+  // A cluster search runs REF's plane passes here, beside the cluster passes on `stream` (hawk_api_search.hip).  Whatever a call
+  // queues on it is joined into `stream` - or waited for - before the call returns: to every other call the context has one stream.
+  hipStream_t side = nullptr;
   // Scratch of the call that is running: every C-ABI call records the events it times with and reads them before it returns.
   // No call may read an event another call recorded (two calls use the same slots for different intervals).
-  hipEvent_t ev[10];
+  hipEvent_t ev[12];
   void* pinned = nullptr;  // 256 B of page-locked host memory: hawk_search reads the device's SearchStatusBlock back into it ([0, 64)),
                            // the cluster dictionary's build its result block ([128, 192))
 };

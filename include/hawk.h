@@ -202,7 +202,9 @@ typedef struct {
   const double* cfd_pam;     /* [16]: PAM[-2:] dinucleotide, 4*b0+b1 over A,C,G,T */
 } hawk_search_params;
 
-typedef struct {          /* kernel times of the last hawk_search (HIP events on the ctx stream), ms */
+typedef struct {          /* kernel times of the last hawk_search (HIP events on the ctx stream), ms.  A cluster search of a plan view
+                             (v_path 2) runs the REF row's plane kernels on a second stream beside the cluster kernels: the intervals
+                             below are the main stream's, and the waits for REF's kernels fall into offsets_ms and emit_ms */
   float count_ms;   /* k_search_count: scan + filters + redundancy classification -> tile counts + hand-over lists */
   float offsets_ms; /* k_mscan1-3: tile counts -> row offsets */
   float emit_ms;    /* k_emit_list + k_search_emit: finished rows (coordinates, windows, CFDon) */
@@ -210,11 +212,12 @@ typedef struct {          /* kernel times of the last hawk_search (HIP events on
   uint64_t scanned_positions; /* sum over haplotypes of (scan_stop - scan_start) */
   float emit_list_ms; /* k_emit_list alone (0 when the hand-over lists are switched off) */
   float v_count_ms;   /* a plan view (hawk_xplan_view): its count side alone (v_path 1: k_vsearch<0>; 2: k_cs_templates + k_cs_count) -
-                         count_ms also holds the REF row's plane kernel */
+                         count_ms also holds the REF row's plane kernel (v_path 1; v_path 2 runs it beside them: the same interval) */
   float v_emit_ms;    /* ... its emit side alone (k_vsearch<1> / k_rows_pack + k_cs_emit_rows) */
   float v_templates_ms; /* the cluster path of a view: k_cs_templates alone (v_count_ms: templates + k_cs_count) */
   uint32_t v_path;    /* 0: planes, 1: a view searched per dirty word (k_vsearch), 2: a view searched per distinct cluster (hawk_csearch.hip) */
-  float v_emit_rows_ms; /* the cluster path: k_cs_emit_rows alone (v_emit_ms also holds k_rows_pack, which packs REF's staged rows) */
+  float v_emit_rows_ms; /* the cluster path: k_cs_emit_rows, the main stream's one emit kernel (= emit_ms; v_emit_ms begins on the second
+                           stream, where k_rows_pack packs REF's staged rows) */
   float reserved;
 } hawk_timing;
 
