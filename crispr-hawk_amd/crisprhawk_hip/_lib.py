@@ -40,6 +40,7 @@ EXPORTS = [
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
     "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
     "hawk_host_effects", "hawk_host_round4",
+    "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
 ]
 
 
@@ -156,6 +157,7 @@ def lib() -> C.CDLL:
         L.hawk_annot_free.restype = None
         L.hawk_gnomad_destroy.restype = None
         L.hawk_effects_free.restype = None
+        L.hawk_plm_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)

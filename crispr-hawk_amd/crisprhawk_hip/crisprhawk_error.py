@@ -46,6 +46,10 @@ class CrisprHawkElevationScoreError(CrisprHawkScoreError):
     pass
 
 
+class CrisprHawkPlmCrisprScoreError(CrisprHawkScoreError):
+    pass
+
+
 class CrisprHawkAnnotationError(CrisprHawkError):
     pass
 

@@ -173,8 +173,8 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 # Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
 # candidate_guides and figures sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
-                 cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, device: Optional[int] = None,
-                 debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
+                 cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
+                 device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
                  timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
@@ -183,7 +183,11 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     """One report per BED interval; returns {str(coordinate): path}.  `cfd_tables = (mm[20,4,4], pam[16])` adds the
     CFDon column for SpCas9-class PAMs (scoring.py:352-387); `azimuth_model` (a fitted sklearn GBR or the flattened
     dict of scoring.azimuth_model_from_sklearn) and `deepcpf1_weights` (scoring.set_deepcpf1_weights layout) switch
-    their score columns on - the reference reads those parameters from files it downloads.  `estimate_offtargets` (the
+    their score columns on - the reference reads those parameters from files it downloads.  `plmcrispr_model` (keyword only in
+    practice, like everything behind `outdir`): a pair (state_dict by name, {cas_system: (L, 1280) embedding}) as
+    scoring.set_plmcrispr_model takes them, or True for the model that is already set; for SpCas9 / xCas9-class PAMs it fills
+    `score_plmcrispr` for the group representatives (their guide + PAM 23-mers), and guidelen + len(pam) != 23 is a
+    CrisprHawkPlmCrisprScoreError before any search - the reference fails on every such run.  `estimate_offtargets` (the
     reference's --estimate-offtargets with its --crispritz-index: a genome.GenomeIndex, a {contig: sequence} dict or a
     FASTA path) runs the off-target stage per region: the `offtargets` / `cfd` columns of the guide report
     (reports.py:292-333, 612-660) and offtargets_{contig}_{start}_{stop}.tsv next to it (offtargets.py:486-558); `mm`,
@@ -236,6 +240,15 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
         scoring.set_deepcpf1_weights(deepcpf1_weights)
     pam = PAM(pam_seq, right, debug)
     pam.encode(0)
+    plm_on = plmcrispr_model is not None and plmcrispr_model is not False and pam.cas_system in (SPCAS9, XCAS9)
+    if plm_on:
+        if guidelen + len(pam_seq) != 23:
+            from .crisprhawk_error import CrisprHawkPlmCrisprScoreError
+            from .exception_handlers import exception_handler
+            exception_handler(CrisprHawkPlmCrisprScoreError, f"PLM-CRISPR scores guide + PAM of 23 nt, got {guidelen} + {len(pam_seq)}",
+                              os.EX_DATAERR, debug)
+        if plmcrispr_model is not True:
+            scoring.set_plmcrispr_model(*plmcrispr_model)
     fa = Fasta(fasta, 0, debug)
     fastas = {fa.contig: fa}
     vcf_by_contig = {}
@@ -264,14 +277,14 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                   figures=figures if figures is not None else {})
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
-                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx)
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on)
     finally:
         if ann is not None:
             ann.close()
 
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
-                      deepcpf1_weights, paths, lap, tables=None, fx=None) -> Dict[str, str]:
+                      deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False) -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
     def no_table():
         if fx is not None and (fx["on"] or fx["cgs"]):
@@ -318,7 +331,7 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         lap("dictionary + search + collapse + export of the groups")
         try:
             _finish_interval(coord, tab if keep_table else None, groups, ds, plan, labels, info, vt, kept, seq, pam, guidelen, right, outdir, score, debug, ot, ann,
-                             azimuth_on, deepcpf1_on, bed_start, bed_stop, paths, lap, tables, fx)
+                             azimuth_on, deepcpf1_on, bed_start, bed_stop, paths, lap, tables, fx, plm_on)
         finally:
             if keep_table:
                 tab.close()
@@ -326,19 +339,21 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
 
 
 def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, pam, guidelen, right, outdir, score, debug, ot, ann, azimuth_on, deepcpf1_on,
-                     bed_start, bed_stop, paths, lap, tables, fx) -> None:
+                     bed_start, bed_stop, paths, lap, tables, fx, plm_on=False) -> None:
     """One interval from its exported groups to its files: scorers, annotation join, report, the optional tables.  `tab`: the
     collapsed table, still in HBM, when the variant-effect stage is on (the caller closes it whatever happens here)."""
     if True:
         # model-based scorers run once per report row, on the group representatives (scoring.py:749-813), when the
         # caller has supplied their parameters
         scores = {}
-        if groups.n_groups and (azimuth_on or deepcpf1_on):
+        if groups.n_groups and (azimuth_on or deepcpf1_on or plm_on):
             kmers = reports.group_kmers(groups)
             if azimuth_on:
                 scores["score_azimuth"] = np.asarray(scoring.azimuth(kmers, debug), dtype=np.float64)
             if deepcpf1_on:
                 scores["score_deepcpf1"] = np.asarray(scoring.deepcpf1(kmers, debug), dtype=np.float64)
+            if plm_on:  # guide + PAM of the 4 + 23 + 3 k-mer (left-PAM systems only reach here)
+                scores["score_plmcrispr"] = np.asarray(scoring.plmcrispr([k[4:27] for k in kmers], pam.cas_system, debug), dtype=np.float64)
         anncols = None
         if ann:  # one join per file over the groups' (start, stop), while the table is closed and before the report's own threads start
             anncols = ann.columns(coord.contig)(np.asarray(groups.start, dtype=np.int64), np.asarray(groups.stop, dtype=np.int64))

@@ -11,10 +11,12 @@ from typing import Dict, List, Optional, Tuple, Union
 import numpy as np
 
 from . import _lib
-from .crisprhawk_error import CrisprHawkAzimuthScoreError, CrisprHawkCfdScoreError, CrisprHawkDeepCpf1ScoreError
+from .crisprhawk_error import (CrisprHawkAzimuthScoreError, CrisprHawkCfdScoreError, CrisprHawkDeepCpf1ScoreError,
+                               CrisprHawkPlmCrisprScoreError)
 from .exception_handlers import exception_handler
 from .guide import GUIDESEQPAD, Guide
 from .pam import CPF1, PAM, SPCAS9, XCAS9
+from .synth import PLMCRISPR_SHAPES
 from .utils import VERBOSITYLVL, flatten_list, print_verbosity
 
 _CFD_TABLES: Optional[Tuple[np.ndarray, np.ndarray]] = None
@@ -197,6 +199,120 @@ def deepcpf1_score(guides: List[Guide], threads: int, verbosity: int, debug: boo
     for g, s in zip(guides, deepcpf1(_extract_guide_sequences(guides), debug)):
         g.deepcpf1_score = s
     return guides
+
+
+# ---------------------------------------------------------------------------- PLM-CRISPR
+# One device handle per Cas system (hawk_plm_create): the 83 MB of parameters and the protein branch's vector stay in HBM.
+_PLM: Dict[int, C.c_void_p] = {}
+_PLM_GUIDEPAM = 23  # spacer + PAM; the wrapper appends its 36-nt scaffold to reach the network's 59 (plm_crispr.py:29-35)
+
+
+def pack_plmcrispr_params(params: Dict[str, np.ndarray]) -> np.ndarray:
+    """The state_dict of the reference's sgrna_net as the one fp32 block hawk_plm_create takes (include/hawk.h)."""
+    parts = []
+    for name, shp in PLMCRISPR_SHAPES:
+        if name not in params:
+            raise ValueError(f"PLM-CRISPR parameter {name} is missing")
+        a = np.ascontiguousarray(params[name], dtype=np.float32)
+        if a.shape != shp:
+            raise ValueError(f"PLM-CRISPR parameter {name} has shape {a.shape}, expected {shp}")
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+def clear_plmcrispr_model() -> None:
+    """Forget the PLM-CRISPR model and free its device handles."""
+    while _PLM:
+        _, h = _PLM.popitem()
+        _lib.lib().hawk_plm_free(h)
+
+
+def set_plmcrispr_model(params: Dict[str, np.ndarray], proteins: Dict[int, np.ndarray]) -> None:
+    """params: the state_dict of sgrna_net (scores/plm_crispr/train_general.py:12-51) by name, torch layout
+    (synth.PLMCRISPR_SHAPES); proteins: {cas_system: (L, 1280) per-residue ESM embedding} for SPCAS9 (3) and / or XCAS9 (4),
+    L >= 13.  The embedding is rounded through fp16 on the device as the reference's loader does.  One handle per Cas system;
+    a model set earlier is freed first."""
+    block = pack_plmcrispr_params(params)
+    embs = {}
+    for cas, emb in proteins.items():
+        if cas not in (SPCAS9, XCAS9):
+            raise ValueError(f"PLM-CRISPR scores SpCas9 ({SPCAS9}) and xCas9 ({XCAS9}) only, got Cas system {cas}")
+        e = np.ascontiguousarray(emb, dtype=np.float32)
+        if e.ndim != 2 or e.shape[1] != 1280 or e.shape[0] < 13:
+            raise ValueError(f"PLM-CRISPR protein embedding has shape {e.shape}, expected (L >= 13, 1280)")
+        embs[cas] = e
+    if not embs:
+        raise ValueError("PLM-CRISPR needs the protein embedding of at least one Cas system")
+    clear_plmcrispr_model()
+    for cas, e in embs.items():
+        h = C.c_void_p()
+        rc = _lib.lib().hawk_plm_create(_lib.context(), block.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p),
+                                        C.c_uint32(e.shape[0]), C.byref(h))
+        if rc != _lib.HAWK_OK:
+            clear_plmcrispr_model()
+        _lib.check(rc, "hawk_plm_create")
+        _PLM[cas] = h
+
+
+def plmcrispr_protein_vector(cas_system: int) -> np.ndarray:
+    """out_protein of the loaded model: sigmoid(relu(lin4(text_cnn(embedding)))), 256 values (hawk_plm_protein)."""
+    out = np.empty(256, dtype=np.float32)
+    _lib.check(_lib.lib().hawk_plm_protein(_PLM[cas_system], out.ctypes.data_as(C.c_void_p)), "hawk_plm_protein")
+    return out
+
+
+_PLM_LEGAL = np.zeros(256, dtype=bool)
+_PLM_LEGAL[np.frombuffer(b"ATCGNatcgn", dtype=np.uint8)] = True
+
+
+def _plmcrispr_check_inputs(guidepams: List[str]) -> bytes:
+    """What the reference's _build_input_sequences / _encode_sequences refuse (plm_crispr.py:152-158, 199): a guide that
+    does not reach 59 symbols with the scaffold (ValueError), a symbol outside A T C G N after upper-casing (KeyError).
+    Returns the guides as one byte string, as hawk_plm_score takes them."""
+    for gp in guidepams:
+        if len(gp) != _PLM_GUIDEPAM:
+            raise ValueError(f"PLM-CRISPR input sequence has length {len(gp) + 36}, expected 59. Guide='{gp}' (len={len(gp)})")
+    joined = "".join(guidepams)
+    text = joined.encode("ascii", "replace")  # a symbol outside ASCII becomes '?', which is refused below
+    bad = np.flatnonzero(~_PLM_LEGAL[np.frombuffer(text, dtype=np.uint8)])
+    if len(bad):
+        raise KeyError(joined[int(bad[0])].upper())
+    return text
+
+
+def plmcrispr(guidepams: List[str], cas_system: int, debug: bool = True, batch: Optional[int] = None) -> List[float]:
+    """scores/plm_crispr/plm_crispr.py:203-258 on the GPU: spacer+PAM 23-mers -> fp32 scores.  `batch` guides share the
+    device workspace at a time (None: the library's default, 8192); a guide's score does not depend on it."""
+    if cas_system not in _PLM:
+        exception_handler(CrisprHawkPlmCrisprScoreError, "PLM-CRISPR model not loaded for this Cas system "
+                          "(scoring.set_plmcrispr_model)", os.EX_NOINPUT, debug)
+    n = len(guidepams)
+    if n == 0:
+        return []
+    try:
+        text = _plmcrispr_check_inputs(guidepams)
+    except (ValueError, KeyError) as e:
+        exception_handler(CrisprHawkPlmCrisprScoreError, "PLM-CRISPR score calculation failed", os.EX_DATAERR, debug, e)
+    out = np.empty(n, dtype=np.float32)
+    rc = _lib.lib().hawk_plm_score(_PLM[cas_system], text, C.c_uint32(_PLM_GUIDEPAM), C.c_uint64(n), C.c_uint32(batch or 0),
+                                   out.ctypes.data_as(C.c_void_p))
+    if rc in (_lib.HAWK_E_IUPAC, _lib.HAWK_E_INVALID):
+        exception_handler(CrisprHawkPlmCrisprScoreError, "PLM-CRISPR score calculation failed", os.EX_DATAERR, debug)
+    _lib.check(rc, "hawk_plm_score")
+    return out.astype(np.float64).tolist()
+
+
+def plmcrispr_score(guides: List[Guide], cas_system: int, threads: int, verbosity: int, debug: bool) -> List[Guide]:
+    """scoring.py:526-567 (one call on the device; ``threads`` is ignored)."""
+    if not guides:
+        return guides
+    print_verbosity("Computing PLM-CRISPR score", verbosity, VERBOSITYLVL[3])
+    for g, s in zip(guides, plmcrispr([g.guidepam for g in guides], cas_system, debug)):
+        g.plmcrispr_score = s
+    return guides
+
+
+_plmcrispr_score = plmcrispr_score  # the reference's name
 
 
 # ---------------------------------------------------------------------------- Azimuth (K5)
@@ -395,6 +511,13 @@ def rs3_score(guides: List[Guide], threads: int, verbosity: int, debug: bool) ->
 
 
 # ---------------------------------------------------------------------------------------------- model files (f4)
+class _Loaded(dict):
+    """load_models' result: a scorer whose file was not there reads False, whether or not it has an entry"""
+
+    def __missing__(self, key):
+        return False
+
+
 def load_models(models_dir: str, debug: bool = True) -> Dict[str, bool]:
     """Load whatever scorer parameters `models_dir` holds and make them current.  Accepted files:
 
@@ -403,11 +526,14 @@ def load_models(models_dir: str, debug: bool = True) -> Dict[str, bool]:
         azimuth_model.npz                     tree_off, feature, left, right, threshold, value, init, learning_rate
         deepcpf1_weights.npz                  conv_w, conv_b, w1, b1, w2, b2, w3, b3, w4, b4 (torch layout)
         rs3_model.txt                         LightGBM text model (needs scoring.set_rs3_model's featuriser separately)
+        plmcrispr_model.npz                   the state_dict of PLM-CRISPR's sgrna_net by name (synth.PLMCRISPR_SHAPES) plus
+                                              protein_spcas9 and / or protein_xcas9, the (L, 1280) ESM embeddings
 
     The .npz files are what tools/convert_models.py writes from the reference's own downloads (the sklearn pickle and the
     Keras .h5 need scikit-learn / h5py, which only the machine that fetched the models is sure to have).
-    Returns which scorers are now available."""
-    have = {"cfd": False, "azimuth": False, "deepcpf1": False, "rs3_model": False}
+    Returns which scorers are now available; `plmcrispr` has its entry only when its file was read (have["plmcrispr"] is
+    False without it all the same), so the four long-standing entries are the whole dict where there is no such file."""
+    have = _Loaded({"cfd": False, "azimuth": False, "deepcpf1": False, "rs3_model": False})
     j = lambda f: os.path.join(models_dir, f)
     if os.path.exists(j("cfd_tables.npz")):
         z = np.load(j("cfd_tables.npz"))
@@ -426,20 +552,25 @@ def load_models(models_dir: str, debug: bool = True) -> Dict[str, bool]:
         have["deepcpf1"] = True
     if os.path.exists(j("rs3_model.txt")):
         have["rs3_model"] = True
+    if os.path.exists(j("plmcrispr_model.npz")):
+        z = np.load(j("plmcrispr_model.npz"))
+        proteins = {cas: z[k] for cas, k in ((SPCAS9, "protein_spcas9"), (XCAS9, "protein_xcas9")) if k in z.files}
+        set_plmcrispr_model({name: z[name] for name, _ in PLMCRISPR_SHAPES}, proteins)
+        have["plmcrispr"] = True
     return have
 
 
-# Scorers the reference calls that have no counterpart here (external checkpoints / conda environments).
+# Scorers the reference calls that have no counterpart here (conda environments of their own).
 # Their columns keep "NA"; they are listed so that scoring_guides documents, in code, what it leaves out.
-OUT_OF_SCOPE_SCORERS = ("plmcrispr", "crispron", "sgdesigner")
+OUT_OF_SCOPE_SCORERS = ("crispron", "sgdesigner")
 _SKIP: set = set()
 
 
 def skip_scorers(*names: str) -> None:
-    """Opt out of in-scope scorers by name ("azimuth", "rs3", "cfdon", "deepcpf1") for callers that do not hold their
+    """Opt out of in-scope scorers by name ("azimuth", "rs3", "plmcrispr", "cfdon", "deepcpf1") for callers that do not hold their
     parameters.  Nothing is skipped by default: like the reference, scoring_guides calls every scorer of the Cas system
     and a scorer without its model raises its CrisprHawk*ScoreError.  skip_scorers() with no argument clears the set."""
-    bad = set(names) - {"azimuth", "rs3", "cfdon", "deepcpf1"}
+    bad = set(names) - {"azimuth", "rs3", "plmcrispr", "cfdon", "deepcpf1"}
     if bad:
         raise ValueError(f"unknown scorer(s): {sorted(bad)}")
     _SKIP.clear()
@@ -447,12 +578,17 @@ def skip_scorers(*names: str) -> None:
 
 
 def _scoring_guides_cas9(guides_list: List[Guide], cas_system: int, scoring_envs, threads: int, verbosity: int, debug: bool) -> List[Guide]:
-    """scoring.py:749-792: azimuth, rs3, (plm-crispr), cfdon, (crispron, sgdesigner) - in that order; cfdon_score
-    returns the guides in group order (scoring.py:383), so the list order changes there exactly as in the reference."""
+    """scoring.py:749-792: azimuth, rs3, plm-crispr, cfdon, (crispron, sgdesigner) - in that order; cfdon_score
+    returns the guides in group order (scoring.py:383), so the list order changes there exactly as in the reference.
+    PLM-CRISPR is the one place where this dispatcher is more lenient than the reference: it runs when a model is loaded
+    for the Cas system (scoring.set_plmcrispr_model); without one its slot stays "NA" and nothing raises, where the reference
+    fails on its missing checkpoint."""
     if "azimuth" not in _SKIP:
         guides_list = azimuth_score(guides_list, threads, verbosity, debug)
     if "rs3" not in _SKIP:
         guides_list = rs3_score(guides_list, threads, verbosity, debug)
+    if "plmcrispr" not in _SKIP and cas_system in _PLM:
+        guides_list = plmcrispr_score(guides_list, cas_system, threads, verbosity, debug)
     if "cfdon" not in _SKIP:
         guides_list = cfdon_score(guides_list, verbosity, debug)
     return guides_list
@@ -466,7 +602,7 @@ def _scoring_guides_cpf1(guides_list: List[Guide], threads: int, verbosity: int,
 
 
 def scoring_guides(guides: Dict, pam: PAM, scoring_envs, args) -> Dict:
-    """scoring.py:816-867: SpCas9 / xCas9 PAMs -> azimuth, rs3, cfdon; Cpf1 PAMs -> deepcpf1; any other PAM -> no score.
+    """scoring.py:816-867: SpCas9 / xCas9 PAMs -> azimuth, rs3, plm-crispr (when loaded), cfdon; Cpf1 PAMs -> deepcpf1; any other PAM -> no score.
     A scorer whose parameters were never supplied raises its own error class, as the reference's does when its model
     file is missing; Elevation-on (an external package with its own checkpoints) is refused rather than left at NA."""
     print_verbosity("Scoring guides", args.verbosity, VERBOSITYLVL[1])

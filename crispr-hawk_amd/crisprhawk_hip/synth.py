@@ -261,6 +261,42 @@ def deepcpf1_weights(seed: int = 2002) -> dict:
     )
 
 
+# sgrna_net().state_dict() of the reference's PLM-CRISPR (scores/plm_crispr/train_general.py:12-51), in its order
+PLMCRISPR_SHAPES = (
+    ("conv1.weight", (64, 5, 5)), ("conv1.bias", (64,)), ("conv2.weight", (64, 64, 5)), ("conv2.bias", (64,)),
+    ("conv3.weight", (64, 64, 5)), ("conv3.bias", (64,)), ("conv4.weight", (64, 5, 5)), ("conv4.bias", (64,)),
+    ("text_cnn.convs.0.weight", (128, 1280, 5)), ("text_cnn.convs.0.bias", (128,)),
+    ("text_cnn.convs.1.weight", (128, 1280, 9)), ("text_cnn.convs.1.bias", (128,)),
+    ("text_cnn.convs.2.weight", (128, 1280, 13)), ("text_cnn.convs.2.bias", (128,)),
+    ("lin1.weight", (2048, 7552)), ("lin1.bias", (2048,)), ("lin3.weight", (256, 2048)), ("lin3.bias", (256,)),
+    ("lin4.weight", (256, 384)), ("lin4.bias", (256,)), ("lin5.weight", (128, 256)), ("lin5.bias", (128,)),
+    ("lin6.weight", (1, 128)), ("lin6.bias", (1,)),
+    ("weight_net.0.weight", (128, 512)), ("weight_net.0.bias", (128,)),
+    ("weight_net.2.weight", (2, 128)), ("weight_net.2.bias", (2,)),
+)
+
+
+def plmcrispr_weights(seed: int = 2003) -> dict:
+    """Seeded fp32 parameters of PLM-CRISPR in torch layout, keyed by state_dict name (PLMCRISPR_SHAPES): weights are
+    N(0, 1) x 3 / sqrt(fan_in) with fan_in the product of all but the first dimension, biases N(0, 0.1^2).  torch's default
+    initialisation squeezes every score into 0.461-0.469, where a structural mistake hides; this family spreads them."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, shape in PLMCRISPR_SHAPES:
+        if name.endswith(".bias"):
+            out[name] = rng.normal(0.0, 0.1, size=shape).astype(np.float32)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            out[name] = (rng.standard_normal(size=shape, dtype=np.float32) * np.float32(3.0 / np.sqrt(fan_in))).astype(np.float32)
+    return out
+
+
+def plmcrispr_protein(seed: int, L: int) -> np.ndarray:
+    """A stand-in for a per-residue ESM embedding: (L, 1280) N(0, 1), rounded through fp16 as the reference's loader does."""
+    rng = np.random.default_rng([seed, L])
+    return rng.standard_normal(size=(L, 1280), dtype=np.float32).astype(np.float16).astype(np.float32)
+
+
 # --- C4: a whole contig with a phased panel too large to hold as a dense matrix ------------------
 class BlockGenotypes:
     """The SURVEY §8(d) genotype recipe (every chromosome copy carries the alt independently with probability AF) as a

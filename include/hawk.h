@@ -784,6 +784,41 @@ int hawk_host_effects(const hawk_effects_columns* cols, int family, const double
 /* round(x, 4) as Python computes it (csrc/hawk_effects.h: fx_round4), element by element */
 int hawk_host_round4(const double* x, uint64_t n, double* out);
 
+/* ---- PLM-CRISPR (scores/plm_crispr/train_general.py, class sgrna_net, forward with train=False; wrapper
+ * scores/plm_crispr/plm_crispr.py:136-258): n guide+PAM 23-mers -> n fp32 scores, all arithmetic in fp32 (lin1 and lin3 on the
+ * f32-input MFMA).  The 83 MB of parameters and the protein branch's result live in HBM behind a handle.
+ *
+ * hawk_plm_create: `params` is ONE packed fp32 block (host) in the order of sgrna_net().state_dict(), every tensor row-major in
+ * its torch shape:
+ *   conv1.weight[64][5][5] conv1.bias[64]  conv2.weight[64][64][5] conv2.bias[64]  conv3.weight[64][64][5] conv3.bias[64]
+ *   conv4.weight[64][5][5] conv4.bias[64]
+ *   text_cnn.convs.0.weight[128][1280][5] .bias[128]  text_cnn.convs.1.weight[128][1280][9] .bias[128]
+ *   text_cnn.convs.2.weight[128][1280][13] .bias[128]
+ *   lin1.weight[2048][7552] lin1.bias[2048]  lin3.weight[256][2048] lin3.bias[256]  lin4.weight[256][384] lin4.bias[256]
+ *   lin5.weight[128][256] lin5.bias[128]  lin6.weight[1][128] lin6.bias[1]
+ *   weight_net.0.weight[128][512] weight_net.0.bias[128]  weight_net.2.weight[2][128] weight_net.2.bias[2]
+ * (HAWK_PLM_NPARAMS floats; offsets in crispr-hawk_amd/csrc/hawk_plm.h).  `protein` is the per-residue ESM embedding, L x 1280
+ * fp32 (host); it is rounded through fp16 HERE (round to nearest even, as the reference's .to(torch.float16), plm_crispr.py:133),
+ * so a caller that has rounded already loses nothing.  L < 13 (the widest text_cnn kernel) -> HAWK_E_INVALID.  The call runs the
+ * protein branch once - text_cnn, lin4, relu, sigmoid - and keeps its 256 values; hawk_plm_protein copies them out.
+ *
+ * hawk_plm_score: `seqs` = n x len bytes (host, contiguous; A C G T N in either case), len must be 23 (HAWK_E_INVALID otherwise:
+ * the reference's ValueError); the 36-nt scaffold is appended on the device.  Any other character -> HAWK_E_IUPAC (the
+ * reference's KeyError), first writer wins, `out` is then unspecified.  Guides are processed `batch` at a time (0: 8192; at most
+ * HAWK_PLM_MAX_BATCH) with a workspace of batch x (7552 + 2048 + 256) floats from the caching allocator; a guide's score does
+ * not depend on batch, n or its place in `seqs`, bit for bit.  n = 0 is HAWK_OK.
+ * hawk_plm_timing: ms4 (may be NULL) receives the device times {front, lin1, lin3, tail} summed over the batches of the last
+ * hawk_plm_score that ran with timing enabled; `enable` switches it for the following calls (a timed call waits per batch). */
+#define HAWK_PLM_NPARAMS (2 * (1600 + 64) + 2 * (20480 + 64) + 128 * 1280 * (5 + 9 + 13) + 3 * 128 + 2048 * 7552 + 2048 + \
+                          256 * 2048 + 256 + 256 * 384 + 256 + 128 * 256 + 128 + 128 + 1 + 128 * 512 + 128 + 2 * 128 + 2)
+#define HAWK_PLM_MAX_BATCH 65536u
+typedef struct hawk_plm hawk_plm;
+int hawk_plm_create(hawk_ctx* ctx, const float* params, const float* protein, uint32_t L, hawk_plm** out);
+int hawk_plm_protein(hawk_plm* p, float out256[256]);
+int hawk_plm_score(hawk_plm* p, const char* seqs, uint32_t len, uint64_t n, uint32_t batch, float* out);
+int hawk_plm_timing(hawk_plm* p, int enable, float ms4[4]);
+void hawk_plm_free(hawk_plm* p);
+
 #ifdef __cplusplus
 }
 #endif
