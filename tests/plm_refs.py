@@ -34,7 +34,8 @@ def _conv_same(x, w, b):
     return out.reshape(n, p, -1).transpose(0, 2, 1)
 
 
-def _protein(params, protein, dt):
+def _pooled(params, protein, dt):
+    """the 384 max-pooled relu'd text_cnn outputs, [kernel 5 | kernel 9 | kernel 13] x 128 channels"""
     emb = np.asarray(protein, dtype=np.float32).astype(np.float16).astype(dt)  # plm_crispr.py:133
     feats = []
     for i, ks in enumerate((5, 9, 13)):
@@ -43,38 +44,90 @@ def _protein(params, protein, dt):
         win = sliding_window_view(emb, ks, axis=0)  # (P, 1280, ks)
         y = win.reshape(win.shape[0], -1) @ w.reshape(128, -1).T + b
         feats.append(np.maximum(y, 0).max(axis=0))
-    f = np.concatenate(feats)
-    y = params["lin4.weight"].astype(dt) @ f + params["lin4.bias"].astype(dt)
+    return np.concatenate(feats)
+
+
+def protein_head(pooled, params, dt):
+    """sigmoid(relu(lin4(pooled)))"""
+    y = params["lin4.weight"].astype(dt) @ pooled + params["lin4.bias"].astype(dt)
     return _sigmoid(np.maximum(y, 0)).astype(dt)
 
 
-def _forward(seqs, params, protein, dt, chunk=256):
-    P = {k: np.asarray(v).astype(dt) for k, v in params.items() if not k.startswith("text_cnn")}
-    prot = _protein(params, protein, dt)
+def _protein(params, protein, dt):
+    return protein_head(_pooled(params, protein, dt), params, dt)
+
+
+def _cast(params, dt):
+    return {k: np.asarray(v).astype(dt) for k, v in params.items() if not k.startswith("text_cnn")}
+
+
+def _features(cd, P, dt):
+    n = len(cd)
+    onehot = np.zeros((n, 59, 5), dtype=dt)
+    onehot[np.arange(n)[:, None], np.arange(59)[None, :], cd] = 1
+    x = onehot.reshape(n, 5, 59)  # .view(-1, 5, 59): a reshape, NOT a transpose (train_general.py:75)
+    be = _conv_same(x, P["conv4.weight"], P["conv4.bias"])
+    y = _sigmoid(_conv_same(x, P["conv1.weight"], P["conv1.bias"]))
+    y = _sigmoid(_conv_same(y, P["conv2.weight"], P["conv2.bias"]))
+    y = _sigmoid(_conv_same(y, P["conv3.weight"], P["conv3.bias"]))
+    return np.concatenate([y.reshape(n, -1), be.reshape(n, -1)], axis=1)  # each branch channel-major
+
+
+def _lin1(feat, P):
+    return _sigmoid(feat @ P["lin1.weight"].T + P["lin1.bias"])
+
+
+def _lin3(h1, P):
+    return h1 @ P["lin3.weight"].T + P["lin3.bias"]
+
+
+def _tail(sg, prot, P):
+    n = len(sg)
+    comb = np.concatenate([sg, np.broadcast_to(prot, (n, 256))], axis=1)
+    hid = np.maximum(comb @ P["weight_net.0.weight"].T + P["weight_net.0.bias"], 0)
+    lg = hid @ P["weight_net.2.weight"].T + P["weight_net.2.bias"]
+    e = np.exp(lg - lg.max(axis=1, keepdims=True))
+    wts = e / e.sum(axis=1, keepdims=True)
+    mix = wts[:, :1] * sg + wts[:, 1:] * prot
+    z = _sigmoid(mix @ P["lin5.weight"].T + P["lin5.bias"])
+    return _sigmoid(z @ P["lin6.weight"].T + P["lin6.bias"])[:, 0]
+
+
+def plm_layers(seqs, params, protein, dt, chunk=256):
+    """Every layer of the forward pass: feat (n, 7552), h1 (n, 2048) = sigmoid(lin1), sg (n, 256) = out_sgrna, prot (256) =
+    out_protein, pooled (384) = the text_cnn maxima, score (n).  The guides are evaluated `chunk` at a time."""
+    P = _cast(params, dt)
+    pooled = _pooled(params, protein, dt)
+    prot = protein_head(pooled, params, dt)
     codes = encode(seqs)
-    out = np.empty(len(codes), dtype=dt)
-    for lo in range(0, len(codes), chunk):
-        cd = codes[lo:lo + chunk]
-        n = len(cd)
-        onehot = np.zeros((n, 59, 5), dtype=dt)
-        onehot[np.arange(n)[:, None], np.arange(59)[None, :], cd] = 1
-        x = onehot.reshape(n, 5, 59)  # .view(-1, 5, 59): a reshape, NOT a transpose (train_general.py:75)
-        be = _conv_same(x, P["conv4.weight"], P["conv4.bias"])
-        y = _sigmoid(_conv_same(x, P["conv1.weight"], P["conv1.bias"]))
-        y = _sigmoid(_conv_same(y, P["conv2.weight"], P["conv2.bias"]))
-        y = _sigmoid(_conv_same(y, P["conv3.weight"], P["conv3.bias"]))
-        feat = np.concatenate([y.reshape(n, -1), be.reshape(n, -1)], axis=1)  # each branch channel-major
-        h = _sigmoid(feat @ P["lin1.weight"].T + P["lin1.bias"])
-        sg = h @ P["lin3.weight"].T + P["lin3.bias"]
-        comb = np.concatenate([sg, np.broadcast_to(prot, (n, 256))], axis=1)
-        hid = np.maximum(comb @ P["weight_net.0.weight"].T + P["weight_net.0.bias"], 0)
-        lg = hid @ P["weight_net.2.weight"].T + P["weight_net.2.bias"]
-        e = np.exp(lg - lg.max(axis=1, keepdims=True))
-        wts = e / e.sum(axis=1, keepdims=True)
-        mix = wts[:, :1] * sg + wts[:, 1:] * prot
-        z = _sigmoid(mix @ P["lin5.weight"].T + P["lin5.bias"])
-        out[lo:lo + n] = _sigmoid(z @ P["lin6.weight"].T + P["lin6.bias"])[:, 0]
+    n = len(codes)
+    out = {"feat": np.empty((n, 7552), dtype=dt), "h1": np.empty((n, 2048), dtype=dt), "sg": np.empty((n, 256), dtype=dt),
+           "prot": prot, "pooled": pooled, "score": np.empty(n, dtype=dt)}
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        out["feat"][lo:hi] = feat = _features(codes[lo:hi], P, dt)
+        out["h1"][lo:hi] = h1 = _lin1(feat, P)
+        out["sg"][lo:hi] = sg = _lin3(h1, P)
+        out["score"][lo:hi] = _tail(sg, prot, P)
     return out
+
+
+def plm_resume(layer, value, params, prot, dt=np.float64):
+    """the scores that follow from `value` standing for the intermediate `layer` ("feat", "h1" or "sg"): what a mistake in that
+    layer does to the score.  prot is out_protein (plm_layers(...)["prot"])."""
+    P = _cast(params, dt)
+    value = np.asarray(value, dtype=dt)
+    if layer == "feat":
+        value, layer = _lin1(value, P), "h1"
+    if layer == "h1":
+        value, layer = _lin3(value, P), "sg"
+    if layer != "sg":
+        raise ValueError(layer)
+    return _tail(value, np.asarray(prot, dtype=dt), P)
+
+
+def _forward(seqs, params, protein, dt, chunk=256):
+    return plm_layers(seqs, params, protein, dt, chunk)["score"]
 
 
 def plm_f64(seqs, params, protein):
