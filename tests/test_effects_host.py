@@ -78,22 +78,7 @@ def _round4(x):
 
 
 def test_round4_is_pythons_round_bit_for_bit():
-    vals = []
-    for name in refs.FIXTURES:  # the fixtures' distinct unrounded scores
-        _, G, _, _ = refs.host_report(name)
-        vals += np.unique(G.cfdon[~np.isnan(G.cfdon)]).tolist()
-    # (the issue speaks of 4x10^3 distinct scores; the three reports hold 5731 rows but only these few hundred distinct unrounded
-    # CFDon values - all of them are used, and the ties, their neighbours and the random values below carry the coverage)
-    assert len(set(vals)) >= 400
-    ties = [0.03125, 0.09375, 0.15625, -0.03125, -0.09375]                   # k / 2^n with five decimals: exact ties
-    ties += [(2 * k + 1) / 32.0 for k in range(0, 160)]                      # x.xxxx5 exactly when representable (odd / 32 has 5 decimals)
-    ties += [k / 2.0 ** n for n in (5, 6, 7, 8) for k in range(1, 2 ** n, 2)]
-    near = [f(t, d) for t in ties for f, d in ((math.nextafter, math.inf), (math.nextafter, -math.inf))]
-    rng = np.random.default_rng(14)
-    rand = rng.random(20000).tolist() + (rng.random(2000) * 200 - 100).tolist() + (rng.integers(0, 10 ** 6, 5000) / 1e5).tolist()
-    decimal_ties = [(2 * k + 1) / 20000.0 for k in range(0, 3000)]           # nearest doubles to x.xxxx5: never exact, either side
-    special = [0.0, -0.0, 1.0, -1.0, 1e-5, -1e-5, 5e-5, -5e-5, 4.9999e-5, 1e-300, 123456.78905, 0.99995, 0.00005, 2.5e-5]
-    x = np.array(vals + ties + near + rand + decimal_ties + special, dtype=np.float64)
+    x = np.array(refs.round4_values(), dtype=np.float64)   # (the list is shared with the device's round panel)
     got = _round4(x)
     want = np.array([round(v, 4) for v in x.tolist()], dtype=np.float64)
     bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
@@ -215,3 +200,51 @@ def test_seam_panels_on_the_host():
     assert len(set(r.pos_worst[r.chosen].tolist())) == 1
     fr = r.pos_first_rank[r.chosen].tolist()
     assert fr == sorted(r.pos_first_rank[r.position == np.arange(p.n_groups)].tolist())[:25]
+
+
+# ---- the plain reference (effects_refs.plain_effects: Python floats, sets and sorted(), nothing of the library) against the host
+# twin: the independent check of the shared rule header, on the seam panels of tests/test_gpu_effects_seams.py and the older ones
+def _host_equals_plain(p, order, calls):
+    st = gr.GroupEffects(p, p.hap_samples, p.is_ref_hap, order, engine="host")
+    assert st.perm is None  # the panels are built in collapse order: group numbers mean the same to both
+    for family, score, cands, K in calls:
+        refs.results_equal(st.rank(family, score, cands, K), refs.plain_effects(p, order, family, score, cands, K))
+
+
+def test_plain_reference_restates_the_products_constants():
+    assert refs.PlainResult.ARRAYS == gr.EffectsResult.ARRAYS
+    assert (refs.FX_NONE, refs.FX_TYPE_UNKNOWN, refs.SIGNED, refs.ABSOLUTE, refs.FX_MAX_K) == (gr.FX_NONE, gr.FX_TYPE_UNKNOWN, gr.SIGNED, gr.ABSOLUTE, 64)
+    src = open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", "hawk_effects.hip")).read()
+    hdr = open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", "hawk_effects.h")).read()
+    dev = open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", "hawk_device.h")).read()
+    assert f"#define FX_BLOCK {refs.FX_BLOCK}\n" in src and f"G < {refs.FX_LONG_WAVES} ? G : {refs.FX_LONG_WAVES}" in src
+    assert f"#define FX_MAX_K {refs.FX_MAX_K} " in hdr and f"#define FX_SHORT_LIST {refs.FX_SHORT_LIST}u" in hdr
+    assert f"#define FX_TOPK_MAX_BLOCKS {refs.FX_TOPK_MAX_BLOCKS}u" in dev
+
+
+@pytest.mark.parametrize("name", refs.SEAM_CASES)
+def test_seam_panels_are_on_their_seams_and_the_host_twin_equals_the_plain_reference(name):
+    p, order, calls, n_long = refs.seam_case(name)
+    refs.check_required(p)
+    _host_equals_plain(p, order, calls)
+
+
+def test_older_panels_host_twin_equals_the_plain_reference():
+    p = refs.rules_panel()
+    nan_scores = np.array([0.5, np.nan, 0.9, 0.1, 0.5, 0.6, 0.3, np.nan, 0.2])
+    for order in (np.arange(p.n_groups), np.arange(p.n_groups)[::-1].copy()):
+        _host_equals_plain(p, order, [(gr.SIGNED, None, (), 25), (gr.ABSOLUTE, nan_scores, (), 25), (gr.SIGNED, None, ((100, 1), (200, 0)), 2)])
+    pr = refs.right_panel()
+    _host_equals_plain(pr, np.arange(3), [(gr.SIGNED, None, (), 1), (gr.ABSOLUTE, None, (), 25)])
+    p, sizes = refs.positions_panel()
+    n = p.n_groups
+    rng = np.random.default_rng(10)
+    az = np.round(rng.random(n), 4)
+    az[rng.random(n) < 0.1] = np.nan
+    for order in (np.arange(n), np.arange(n)[::-1].copy(), np.random.default_rng(9).permutation(n)):
+        _host_equals_plain(p, order, [(gr.SIGNED, None, (), K) for K in (1, 25, 64)] + [(gr.ABSOLUTE, az, (), K) for K in (1, 25, 64)]
+                           + [(gr.ABSOLUTE, az, ((int(p.start[0]), int(p.strand[0])), (1, 0)), 64)])
+    p, want = refs.samples_panel()
+    _host_equals_plain(p, np.arange(p.n_groups), [(gr.SIGNED, None, (), 25)])
+    p, order = refs.tie_panel()
+    _host_equals_plain(p, order, [(gr.SIGNED, None, (), 25), (gr.ABSOLUTE, None, (), 64)])
