@@ -36,6 +36,7 @@ EXPORTS = [
     "hawk_comm_destroy", "hawk_comm_last_error", "hawk_comm_allgather_u64", "hawk_comm_gatherv", "hawk_table_gather", "hawk_host_ragged_join", "hawk_host_tsv_write", "hawk_host_vcf_index", "hawk_host_polish_rows", "hawk_host_variant_window", "hawk_host_polish_windows", "hawk_host_group_join", "hawk_host_group_samples", "hawk_gbt_predict", "hawk_gt_from_codes",
     "hawk_annot_create", "hawk_annot_query", "hawk_annot_download", "hawk_annot_free", "hawk_xplan_text",
     "hawk_offtarget_text", "hawk_offtarget_text_download", "hawk_host_offtarget_text",
+    "hawk_offtarget_bulge_summary", "hawk_host_offtarget_bulge_summary",
     "hawk_gnomad_scan", "hawk_gnomad_records", "hawk_gnomad_text", "hawk_gnomad_text_download", "hawk_gnomad_destroy",
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
     "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",

@@ -491,15 +491,27 @@ class GenomeIndex:
                                     decode_window(int(h["code"][i]), int(h["nmask"][i]), self.L)))
         return out
 
-    def summary(self, guides: Sequence[str], pam, right: bool, max_mm: int, cfd_tables=None, comm=None) -> dict:
-        """The scan's per-guide aggregates without its hits (hawk_offtarget_summary; mismatch-only): dict(hist = uint32
-        [n_guides, max_mm + 1] hits per guide and mismatch count - the on-target site included -, cfd_e4 = int64[n_guides]
-        the sum of round(CFD(guide, site), 4) over the guide's hits in units of 1e-4 (None without `cfd_tables` = (mm[20,4,4],
-        pam[16])), n_hits, n_unscorable = hits with a non-ACGT base under a CFD lookup, which count in hist and add nothing
-        to cfd_e4).  Every hit is consumed inside the match kernel: no capacity, no retry, nothing sized by the hits.
-        Duplicate guides get equal rows; an index without rows on this rank returns zeros.  The arrays are integers, so
-        shards add up exactly: with a communicator every rank's arrays are gathered to rank 0, which returns their sum
-        (other ranks return their own shard's)."""
+    BULGE_KINDS = ((True, 1), (True, 2), (False, 1), (False, 2))  # the order of `bulge_hist`: DNA 1, DNA 2, RNA 1, RNA 2
+
+    def summary(self, guides: Sequence[str], pam, right: bool, max_mm: int, cfd_tables=None, comm=None, bdna: int = 0, brna: int = 0) -> dict:
+        """The scan's per-guide aggregates without its hits (hawk_offtarget_summary, and with `bdna` / `brna` above zero one
+        hawk_offtarget_bulge_summary per (type, size)): dict(hist = uint32[n_guides, max_mm + 1] un-bulged hits per guide and
+        mismatch count - the on-target site included -, cfd_e4 = int64[n_guides] the sum of round(CFD, 4) over the guide's rows
+        in units of 1e-4 (None without `cfd_tables` = (mm[20,4,4], pam[16])), n_hits, n_unscorable = rows with a non-ACGT
+        base under a CFD lookup, which count in the histograms and add nothing to cfd_e4).  With bulges the dict also holds
+        bulge_hist = uint32[n_guides, 4, max_mm + 1], the bulged rows per guide, (type, size) in the order DNA 1, DNA 2, RNA 1,
+        RNA 2 (what was not asked for stays zero) and mismatch count; cfd_e4, n_hits and n_unscorable then cover ALL rows, a
+        bulged row's CFD being the one the off-targets table prints for it (rows_text).  `hist` stays the un-bulged histogram;
+        with both zero the dict is the mismatch-only one, key for key.  last_bulge_timing: the timing block of every (type,
+        size) call, as offtarget_arrays fills it.  Every row is consumed inside the kernel that finds it: no capacity, no
+        retry, nothing sized by the rows.  Duplicate guides get equal rows; an index without rows on this rank returns zeros.
+        The arrays are integers, so shards add up exactly: with a communicator every rank's arrays are gathered to rank 0,
+        which returns their sum (other ranks return their own shard's)."""
+        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
+            raise ValueError("bulges of 0..2 bases are enumerated")
+        if bdna > self.max_bulge:
+            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        bulged = bool(bdna or brna)
         n, stride = len(guides), int(max_mm) + 1
         g2 = encode_guides(guides)
         hist = np.zeros((n, stride), dtype=np.uint32)
@@ -507,11 +519,11 @@ class GenomeIndex:
         nh, nu = C.c_uint64(0), C.c_uint64(0)
         self._set_window(self.guidelen)
         timing = dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+        mm = pt = None
+        if cfd_tables is not None:
+            mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
+            pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
         if self.ds is not None:
-            mm = pt = None
-            if cfd_tables is not None:
-                mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
-                pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
             par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), self.guidelen, int(bool(right)), int(max_mm))
             tm = _lib.OtTiming()
             rc = self.ds._L.hawk_offtarget_summary(self.ds._h, C.byref(par), _p(g2), n, None if mm is None else _p(mm),
@@ -521,16 +533,57 @@ class GenomeIndex:
             timing = {k: getattr(tm, k) for k, _ in tm._fields_}
         self.last_timing = timing
         out = dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value))
+        if bulged:
+            out["bulge_hist"] = np.zeros((n, 4, stride), dtype=np.uint32)
+            self.last_bulge_timing = []
+            try:
+                for k, (dna, b) in enumerate(self.BULGE_KINDS):
+                    if b <= (bdna if dna else brna):
+                        part, tm = self._bulge_summary(g2, pam, right, int(max_mm), b, dna, mm, pt)
+                        self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
+                        out["bulge_hist"][:, k, :] = part["hist"]
+                        if cfd is not None:
+                            out["cfd_e4"] += part["cfd_e4"]
+                        out["n_hits"] += part["n_hits"]
+                        out["n_unscorable"] += part["n_unscorable"]
+            finally:
+                self._set_window(self.guidelen)
         if comm is not None and comm.world > 1:
             tail = np.array([out["n_hits"], out["n_unscorable"]], dtype=np.int64)
-            flat = np.concatenate([hist.reshape(-1).astype(np.int64), cfd if cfd is not None else np.zeros(0, np.int64), tail])
+            bh = out["bulge_hist"].reshape(-1).astype(np.int64) if bulged else np.zeros(0, np.int64)
+            flat = np.concatenate([hist.reshape(-1).astype(np.int64), cfd if cfd is not None else np.zeros(0, np.int64), bh, tail])
             parts = comm.gatherv_bytes(flat, 0)
             if comm.rank == 0:
                 tot = np.sum(np.stack(parts), axis=0, dtype=np.int64)
+                o1 = n * stride + (n if cfd is not None else 0)
                 out = dict(hist=tot[:n * stride].astype(np.uint32).reshape(n, stride),
                            cfd_e4=tot[n * stride:n * stride + n].copy() if cfd is not None else None,
                            n_hits=int(tot[-2]), n_unscorable=int(tot[-1]))
+                if bulged:
+                    out["bulge_hist"] = tot[o1:o1 + 4 * n * stride].astype(np.uint32).reshape(n, 4, stride)
         return out
+
+    def _bulge_summary(self, g2, pam, right: bool, max_mm: int, b: int, dna: bool, mm, pt):
+        """One hawk_offtarget_bulge_summary over this rank's rows: (dict(hist uint32[n, max_mm + 1], cfd_e4 int64[n] or None,
+        n_hits, n_unscorable) of the bulged rows of one (type, size), timing).  The scan ranges are left set for the windows of
+        that (type, size), as bulge_arrays leaves them."""
+        G, n = self.guidelen, len(g2)
+        if G - b < 3:
+            raise ValueError(f"guides of {G} bases leave no interior base to pair beside a bulge of {b}")
+        self._set_window(G + b if dna else G - b)
+        hist = np.zeros((n, max_mm + 1), dtype=np.uint32)
+        cfd = np.zeros(n, dtype=np.int64) if mm is not None else None
+        nh, nu = C.c_uint64(0), C.c_uint64(0)
+        timing = dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+        if self.ds is not None and n:
+            par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), G, int(bool(right)), max_mm)
+            tm = _lib.OtTiming()
+            rc = self.ds._L.hawk_offtarget_bulge_summary(self.ds._h, C.byref(par), _p(g2), n, 1 if dna else 2, int(b), None if mm is None else _p(mm),
+                                                         None if pt is None else _p(pt), _p(hist), None if cfd is None else _p(cfd),
+                                                         C.byref(nh), C.byref(nu), C.byref(tm))
+            _lib.check(rc, "hawk_offtarget_bulge_summary")
+            timing = {k: getattr(tm, k) for k, _ in tm._fields_}
+        return dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value)), timing
 
     def scan(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20, comm=None) -> List[OffTargetHit]:
         """All windows within ``max_mm`` mismatches of any guide, both strands, sorted by

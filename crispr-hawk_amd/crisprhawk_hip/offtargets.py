@@ -3,9 +3,10 @@
 (offtargets.py:328-363) computed in one GPU batch.  The scan's hits are rendered as
 CRISPRitz-format report lines so that ``Offtarget`` parsing, the per-guide counts and the global
 CFD ``100 / (100 + sum(cfd))`` (offtargets.py:561-627) keep the reference's semantics.
-When only the guide report's two columns are wanted (``pipeline.search_files(offtargets_table=False)``),
-``specificity_by_spacer`` takes them from ``GenomeIndex.summary``: the match kernels sum, per guide, the hits
-and their CFD rounded to 4 decimals as integers, and no site is listed, rendered, parsed or scored on the host.
+When only the guide report's two columns are wanted (``pipeline.search_files(offtargets_table=False)``, or
+``offtargets_summary=True`` at any ``bdna`` / ``brna``), ``specificity_by_spacer`` takes them from ``GenomeIndex.summary``: the
+match kernels and the bulge kernel sum, per guide, the rows and their CFD rounded to 4 decimals as integers, and no site is
+listed, rendered, parsed or scored on the host.
 With `annotations` the off-targets table gets one column per BED file (offtargets.py:407-483), joined on the device
 (bedannot.AnnotTable: one handle per file and contig of the table).  Elevation is out of scope.
 ``estimate_offtargets_spacers`` - the stage as ``pipeline.search_files`` runs it - keeps the hits as columns from the scan to the
@@ -218,11 +219,14 @@ def offtargets_by_spacer(offtargets: List[Offtarget], spacers) -> Dict[str, tupl
     return {sp: (len(r), str(round_score(_calculate_global_cfd(r)))) for sp, r in rows.items()}
 
 
-def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen: int, right: bool, debug: bool) -> Dict[str, tuple]:
+def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen: int, right: bool, debug: bool, bdna: int = 0,
+                          brna: int = 0) -> Dict[str, tuple]:
     """{SPACER: (count, global CFD text)} - offtargets_by_spacer's result without the per-site route: one
-    GenomeIndex.summary over the unique spacers (mismatch-only).  `count` is the guide's hits at 0..mm mismatches, the
-    on-target site included (the reference's len(rows)); the global CFD is 100 / (100 + sum of the sites' CFD rounded to 4
-    decimals), the sum kept as an integer number of 1e-4 units on the device.  PAMs outside SpCas9 / xCas9 get no CFD
+    GenomeIndex.summary over the unique spacers, with the sites of DNA / RNA bulges of up to `bdna` / `brna` bases (0..2) when
+    asked for.  `count` is the guide's rows at 0..mm mismatches, the on-target site and the bulged rows included (the
+    reference's len(rows)); the global CFD is 100 / (100 + sum of the rows' CFD rounded to 4 decimals), the sum kept as an
+    integer number of 1e-4 units on the device.  An index made here is built with max_bulge = bdna; bulge sizes outside 0..2
+    are a CrisprHawkOffTargetsError, as on the table route.  PAMs outside SpCas9 / xCas9 get no CFD
     ("1.0", what the table route's NA -> 0 gives).  The CFD tables are scoring.set_cfd_tables'; a hit with a non-ACGT base
     under a lookup raises CrisprHawkCfdScoreError as compute_cfd_batch does."""
     from .crisprhawk_error import CrisprHawkCfdScoreError
@@ -234,13 +238,18 @@ def specificity_by_spacer(spacers, pam: PAM, crispritz_index, mm: int, guidelen:
     if pam.cas_system in (SPCAS9, XCAS9):
         from .scoring import _tables
         tables = _tables(debug)
+    if bdna < 0 or brna < 0 or bdna > 2 or brna > 2:
+        exception_handler(CrisprHawkOffTargetsError, f"DNA / RNA bulges of 0..2 bases are enumerated (got {bdna} / {brna})", os.EX_DATAERR, debug)
     try:
-        res = _genome_index(crispritz_index, guidelen, len(pam)).summary(uniq, pam, right, mm, cfd_tables=tables)
+        res = _genome_index(crispritz_index, guidelen, len(pam), bdna).summary(uniq, pam, right, mm, cfd_tables=tables, bdna=bdna, brna=brna)
     except ValueError as e:
         exception_handler(CrisprHawkOffTargetsError, f"Off-targets search failed: {e}", os.EX_DATAERR, debug, e)
     if res["n_unscorable"] > 0:
         exception_handler(CrisprHawkCfdScoreError, "CFDon score calculation failed", os.EX_DATAERR, debug)
-    counts = res["hist"].sum(axis=1, dtype=np.int64).tolist()
+    counts = res["hist"].sum(axis=1, dtype=np.int64)
+    if "bulge_hist" in res:
+        counts = counts + res["bulge_hist"].sum(axis=(1, 2), dtype=np.int64)
+    counts = counts.tolist()
     sums = res["cfd_e4"].tolist() if res["cfd_e4"] is not None else [0] * len(uniq)
     return {sp: (int(c), str(round_score(100 / (100 + e4 / 1e4)))) for sp, c, e4 in zip(uniq, counts, sums)}
 

@@ -100,7 +100,7 @@ def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir
     """--estimate-offtargets for one region: {SPACER: (count, global CFD)} + offtargets_{contig}_{start}_{stop}.tsv."""
     from .offtargets import estimate_offtargets_spacers, specificity_by_spacer
     if not ot.get("table", True):  # the report's two columns alone: summed per guide on the device, no site listed
-        return specificity_by_spacer(spacers, pam, ot["genome"], ot["mm"], guidelen, right, debug)
+        return specificity_by_spacer(spacers, pam, ot["genome"], ot["mm"], guidelen, right, debug, ot["bdna"], ot["brna"])
     ann = ot.get("ann")
     return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug,
                                        ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None,
@@ -175,7 +175,8 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
                  device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
-                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, graphical_reports: bool = False,
+                 timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, offtargets_summary: bool = False,
+                 graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
@@ -194,6 +195,9 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     `bdna`, `brna` as on the reference's command line (bulges of up to 2 bases).  The per-site CFD needs `cfd_tables`.
     `offtargets_table=False` fills the two columns from the device's per-guide summary (offtargets.specificity_by_spacer)
     and writes no offtargets_*.tsv; it is mismatch-only, so asking for it with `bdna` or `brna` is a ValueError.
+    `offtargets_summary=True` takes the same summary route at the given `bdna` / `brna` - the bulged rows are counted and their
+    CFD summed inside the bulge kernel (GenomeIndex.summary(bdna=, brna=)) - and writes no offtargets_*.tsv either;
+    `offtargets_table` is then not consulted.
     `annotations` / `gene_annotations` (the reference's --annotation / --gene-annotation BED files, plain, gzip or BGZF, no .tbi
     needed) add one column per file to every guide report - the 4th BED column, or feature:gene_name, of the features a guide
     overlaps - named by `annotation_colnames` / `gene_annotation_colnames` or annotation_{i} / gene_annotation_{i}; the
@@ -221,8 +225,9 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
             now = _time.perf_counter()
             timings[stage] = timings.get(stage, 0.0) + now - _t[0]
             _t[0] = now
-    if not offtargets_table and (bdna or brna):
-        raise ValueError("offtargets_table=False is the mismatch-only summary: bulged sites (bdna / brna) need the off-targets table")
+    if not offtargets_summary and not offtargets_table and (bdna or brna):
+        raise ValueError("offtargets_table=False is the mismatch-only summary: bulged sites (bdna / brna) need the off-targets table, "
+                         "or offtargets_summary=True for the two report columns alone")
     ot = None
     if estimate_offtargets is not None:
         from .genome import GenomeIndex, read_fasta
@@ -231,7 +236,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
             genome = read_fasta(str(genome))
         if isinstance(genome, dict):
             genome = GenomeIndex(genome, guidelen, len(pam_seq), device=device, max_bulge=bdna)  # once for all regions
-        ot = dict(genome=genome, mm=mm, bdna=bdna, brna=brna, table=bool(offtargets_table))
+        ot = dict(genome=genome, mm=mm, bdna=bdna, brna=brna, table=bool(offtargets_table) and not offtargets_summary)
         if cfd_tables is not None:
             scoring.set_cfd_tables(*cfd_tables)
     if azimuth_model is not None:

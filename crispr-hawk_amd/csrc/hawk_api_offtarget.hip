@@ -159,6 +159,53 @@ static void ot_timing(hawk_hapset* hs, uint64_t nsites, hawk_ot_timing* timing, 
   timing->scanned_positions = pos;
 }
 
+// The summaries' block in hs->otsum, sized by the guides alone: counters[2] | cfd_e4[n_guides] | CFD tables[336] |
+// hist[n_guides][stride].  otsum_begin reserves it, zeroes it and uploads the tables (both or neither) on the stream; otsum_end
+// downloads it once, synchronises and fills the caller's outputs.
+struct OtSumBlock {
+  char* base;
+  size_t off_tab, off_hist, bytes;
+  uint32_t n_guides, stride;
+  bool tables;
+  unsigned long long* counters() const { return reinterpret_cast<unsigned long long*>(base); }
+  unsigned long long* cfd_e4() const { return reinterpret_cast<unsigned long long*>(base + 16); }
+  const double* tab() const { return tables ? reinterpret_cast<const double*>(base + off_tab) : nullptr; }
+  uint32_t* hist() const { return reinterpret_cast<uint32_t*>(base + off_hist); }
+};
+static int otsum_begin(hawk_hapset* hs, uint32_t n_guides, uint32_t stride, const double* cfd_mm, const double* cfd_pam, OtSumBlock* b) {
+  hipStream_t st = hs->ctx->stream;
+  b->n_guides = n_guides; b->stride = stride; b->tables = cfd_mm != nullptr;
+  b->off_tab = 16 + (size_t)n_guides * 8;
+  b->off_hist = b->off_tab + 336 * 8;
+  b->bytes = b->off_hist + (size_t)n_guides * stride * 4;
+  int rc;
+  if ((rc = hs->otsum.reserve(b->bytes))) return rc;
+  b->base = hs->otsum.as<char>();
+  HIPCHK(hipMemsetAsync(b->base, 0, b->bytes, st));
+  if (cfd_mm) {
+    HIPCHK(hipMemcpyAsync(b->base + b->off_tab, cfd_mm, 320 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->base + b->off_tab + 320 * 8, cfd_pam, 16 * 8, hipMemcpyHostToDevice, st));
+  }
+  return HAWK_OK;
+}
+static int otsum_end(hawk_hapset* hs, const OtSumBlock& b, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable) {
+  hipStream_t st = hs->ctx->stream;
+  // one download: everything but the tables would do, the block is small either way
+  std::vector<char> host(b.bytes);
+  HIPCHK(hipMemcpyAsync(host.data(), b.base, b.bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  uint64_t cnt[2];
+  memcpy(cnt, host.data(), 16);
+  *n_hits = cnt[0];
+  *n_unscorable = cnt[1];
+  if (b.n_guides) {
+    memcpy(out_hist, host.data() + b.off_hist, (size_t)b.n_guides * b.stride * 4);
+    if (out_cfd_e4 && b.tables) memcpy(out_cfd_e4, host.data() + 16, (size_t)b.n_guides * 8);
+    else if (out_cfd_e4) memset(out_cfd_e4, 0, (size_t)b.n_guides * 8);
+  }
+  return HAWK_OK;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------- K7 off-targets
@@ -292,23 +339,15 @@ int hawk_offtarget_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint6
   hawk_ctx* ctx = f.ctx;
   // One block, sized by the guides alone: counters[2] | cfd_e4[n_guides] | CFD tables[336] | hist[n_guides][max_mm + 1].
   // No hits / othit buffer is reserved on this path: a hit ends in these sums inside the match kernel.
-  const uint32_t stride = p->max_mm + 1;
-  const size_t off_tab = 16 + (size_t)n_guides * 8, off_hist = off_tab + 336 * 8;
-  const size_t bytes = off_hist + (size_t)n_guides * stride * 4;
-  if ((rc = hs->otsum.reserve(bytes))) return rc;
-  char* base = hs->otsum.as<char>();
-  HIPCHK(hipMemsetAsync(base, 0, bytes, ctx->stream));
-  if (cfd_mm) {
-    HIPCHK(hipMemcpyAsync(base + off_tab, cfd_mm, 320 * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(base + off_tab + 320 * 8, cfd_pam, 16 * 8, hipMemcpyHostToDevice, ctx->stream));
-  }
+  OtSumBlock blk;
+  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk))) return rc;
   OtSummary sm;
   sm.sites = hs->sites.as<OtSite>();
-  sm.tab = cfd_mm ? reinterpret_cast<const double*>(base + off_tab) : nullptr;
-  sm.hist = reinterpret_cast<uint32_t*>(base + off_hist);
-  sm.cfd_e4 = reinterpret_cast<unsigned long long*>(base + 16);
-  sm.counters = reinterpret_cast<unsigned long long*>(base);
-  sm.stride = stride;
+  sm.tab = blk.tab();
+  sm.hist = blk.hist();
+  sm.cfd_e4 = blk.cfd_e4();
+  sm.counters = blk.counters();
+  sm.stride = blk.stride;
   sm.sp0 = f.sp0;
   sm.pam2 = (p->right ? 0 : f.G) + (int)p->pamlen - 2;
   sm.ncmp = std::min(f.G, 20);
@@ -324,19 +363,50 @@ int hawk_offtarget_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint6
   }
   HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
   HIPCHK(hipGetLastError());
-  // one download: everything but the tables would do, the block is small either way
-  std::vector<char> host(bytes);
-  HIPCHK(hipMemcpyAsync(host.data(), base, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  uint64_t cnt[2];
-  memcpy(cnt, host.data(), 16);
-  *n_hits = cnt[0];
-  *n_unscorable = cnt[1];
-  if (n_guides) {
-    memcpy(out_hist, host.data() + off_hist, (size_t)n_guides * stride * 4);
-    if (out_cfd_e4 && cfd_mm) memcpy(out_cfd_e4, host.data() + 16, (size_t)n_guides * 8);
-    else if (out_cfd_e4) memset(out_cfd_e4, 0, (size_t)n_guides * 8);
-  }
+  if ((rc = otsum_end(hs, blk, out_hist, out_cfd_e4, n_hits, n_unscorable))) return rc;
+  ot_timing(hs, f.nsites, timing, 5);
+  return HAWK_OK;
+}
+
+int hawk_offtarget_bulge_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, uint32_t bulge_type,
+                                 uint32_t bulge_size, const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
+                                 uint64_t* n_hits, uint64_t* n_unscorable, hawk_ot_timing* timing) {
+  // the argument rules of hawk_offtarget_summary ...
+  if (!hs || !p || !n_hits || !n_unscorable || (n_guides && !out_hist) || !cfd_mm != !cfd_pam || (cfd_mm && n_guides && !out_cfd_e4))
+    return HAWK_E_INVALID;
+  if (bulge_type < 1 || bulge_type > 2 || bulge_size < 1 || bulge_size > 2) return HAWK_E_INVALID;
+  if ((cfd_mm && p->pamlen < 2) || p->max_mm > 32) return HAWK_E_UNSUPPORTED;
+  // ... and the front half of hawk_offtarget_bulges: p->guidelen is the GUIDE's, the window scan is about the site's spacer
+  const bool dna = bulge_type == 1;
+  const uint32_t G = p->guidelen;
+  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;
+  hawk_ot_params ps = *p;
+  const uint32_t Gs = ps.guidelen = dna ? G + bulge_size : G - bulge_size;
+  if (Gs + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
+  if (!hs->has_meta || hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
+  for (uint32_t h = 0; h < hs->n_hap; ++h)
+    if (hs->scan_stop[h] > hs->scan_start[h] && (int64_t)hs->scan_stop[h] - 1 + Gs + p->pamlen > (int64_t)hs->hap_len[h]) return HAWK_E_INVALID;
+  OtFront f;
+  int rc = ot_front(hs, &ps, guides2, n_guides, &f, false);
+  if (rc) return rc;
+  hawk_ctx* ctx = f.ctx;
+  // No hits / othit buffer and no cap on this path: a row ends in the block's sums inside k_ot_bulge.
+  OtSumBlock blk;
+  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk))) return rc;
+  OtBulgeSummary sm;
+  sm.tab = blk.tab();
+  sm.hist = blk.hist();
+  sm.cfd_e4 = blk.cfd_e4();
+  sm.counters = blk.counters();
+  sm.stride = blk.stride;
+  sm.pamlen = (int32_t)p->pamlen;
+  sm.right = p->right ? 1 : 0;
+  HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));  // the zeroing and the table upload are not the kernel's time
+  hawk_launch_ot_bulge_sum(ctx->stream, hs->sites.as<OtSite>(), f.nsites, hs->guides.as<uint64_t>(), n_guides, (int)G, f.sp0, (int)p->max_mm,
+                           dna ? 1 : 0, (int)bulge_size, sm);
+  HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
+  HIPCHK(hipGetLastError());
+  if ((rc = otsum_end(hs, blk, out_hist, out_cfd_e4, n_hits, n_unscorable))) return rc;
   ot_timing(hs, f.nsites, timing, 5);
   return HAWK_OK;
 }

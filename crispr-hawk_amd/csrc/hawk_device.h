@@ -255,6 +255,17 @@ struct OtBulgeHit { uint64_t site; uint32_t guide, mm, gaps, pad; };
 void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
                           int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_ot_bulge_gather(hipStream_t st, const OtSite* sites, const OtBulgeHit* hits, uint64_t n_hits, OtSite* out);
+// k_ot_bulge with the summary's sink (hawk_otbulge.hip: OtbSumSink): where a bulged row goes instead of hits[].
+struct OtBulgeSummary {
+  const double* tab;             // CFD tables mm[20][4][4] + pam[16]; nullptr: counts only
+  uint32_t* hist;                // [n_guides][stride], zeroed
+  unsigned long long* cfd_e4;    // [n_guides], zeroed: per-guide sum of the rows' CFD in units of 1e-4
+  unsigned long long* counters;  // [0] rows, [1] rows with an ambiguous base under a CFD lookup; zeroed
+  uint32_t stride;               // max_mm + 1
+  int32_t pamlen, right;
+};
+void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
+                              int sp0, int max_mm, int dna, int bsize, const OtBulgeSummary& sm);
 // The match kernels with the summary's hit sink (hawk_offtarget.hip: OtSumSink): where a hit goes instead of hits[].
 struct OtSummary {
   const OtSite* sites;

@@ -13,6 +13,7 @@
 
 #include "../../include/hawk.h"
 #include "hawk_ottext.h"
+#include "hawk_otbulge.h"
 #include "hawk_gnomad.h"
 #include "hawk_effects.h"
 
@@ -721,6 +722,43 @@ int hawk_host_offtarget_text(uint64_t n, const uint32_t* guide, const uint32_t* 
     w.w = blob + off[i];
     (void)emit(i, w);
   }
+  return HAWK_OK;
+}
+
+// ---- the bulged off-target summary on the host ----------------------------------------------------------------------------------
+// hawk_offtarget_bulge_summary without a device: the site windows are given (code / nmask as a site record holds them), every
+// (site, guide) pair goes through otb_pair (hawk_otbulge.h) - the function the kernel's summing sink runs - in a plain loop, and
+// the rows are summed as the kernel sums them.
+int hawk_host_offtarget_bulge_summary(const uint64_t* code, const uint32_t* nmask, uint64_t n_sites, const uint64_t* guides2, uint32_t n_guides,
+                                      const hawk_ot_params* p, uint32_t bulge_type, uint32_t bulge_size, const double* cfd_mm,
+                                      const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable) {
+  if (!p || !n_hits || !n_unscorable || (n_guides && (!guides2 || !out_hist)) || (n_sites && (!code || !nmask)) || !cfd_mm != !cfd_pam ||
+      (cfd_mm && n_guides && !out_cfd_e4))
+    return HAWK_E_INVALID;
+  if (bulge_type < 1 || bulge_type > 2 || bulge_size < 1 || bulge_size > 2) return HAWK_E_INVALID;
+  if ((cfd_mm && p->pamlen < 2) || p->max_mm > 32) return HAWK_E_UNSUPPORTED;
+  const bool dna = bulge_type == 1;
+  const uint32_t G = p->guidelen;
+  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;
+  if ((dna ? G + bulge_size : G - bulge_size) + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
+  double tab[336];
+  if (cfd_mm) { memcpy(tab, cfd_mm, 320 * sizeof(double)); memcpy(tab + 320, cfd_pam, 16 * sizeof(double)); }
+  const uint32_t stride = p->max_mm + 1;
+  uint64_t hits = 0, uns = 0;
+  if (n_guides) memset(out_hist, 0, (size_t)n_guides * stride * 4);
+  if (n_guides && out_cfd_e4) memset(out_cfd_e4, 0, (size_t)n_guides * 8);
+  for (uint64_t i = 0; i < n_sites; ++i)
+    for (uint32_t g = 0; g < n_guides; ++g) {
+      const OtbPair r = otb_pair(code[i], nmask[i], guides2[g], (int)G, (int)p->pamlen, p->right ? 1 : 0, (int)bulge_size, dna, (int)p->max_mm,
+                                 cfd_mm ? tab : nullptr);
+      if (r.mm > (int)p->max_mm) continue;
+      ++hits;
+      ++out_hist[(size_t)g * stride + (uint32_t)r.mm];
+      if (r.units == OT_TEXT_UNSCORABLE) ++uns;
+      else if (r.units > 0) out_cfd_e4[g] += r.units;
+    }
+  *n_hits = hits;
+  *n_unscorable = uns;
   return HAWK_OK;
 }
 

@@ -1,5 +1,7 @@
-// hawk_otbulge.h - the placement selection of a bulged (site, guide) pair, shared by k_ot_bulge (hawk_otbulge.hip) and by the host
-// program that checks it against a plain walk over the placements (otbulge_check_main.cpp; plain C++: no device types).
+// hawk_otbulge.h - a bulged (site, guide) pair stated once: its shift vectors, the placement selection and (otb_pair) the row the
+// pair makes - mismatches, gaps and the CFD of the off-targets table's row.  Shared by k_ot_bulge (hawk_otbulge.hip), by the host
+// twin of the bulged summary (hawk_host_offtarget_bulge_summary, hawk_hostutil.hip) and by the host programs that check it against
+// plain restatements (otbulge_check_main.cpp, otbsum_check_main.cpp).  Plain C++: no device types.
 //
 // A bulge of b bases aligns a LONGER sequence of span = n + b positions (DNA bulge: the site spacer; RNA bulge: the guide) with a
 // SHORTER one of n positions (DNA: the guide; RNA: the site spacer); b interior positions 1 .. span - 2 of the longer one - the
@@ -14,8 +16,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "hawk_ottext.h"
+
 #ifdef __HIPCC__
-#define OTB_HD __host__ __device__ __forceinline__
+#define OTB_HD __host__ __device__ inline __attribute__((always_inline))  // __forceinline__, spelt out: hawk_hostutil.hip includes no HIP header
 #else
 #define OTB_HD inline
 #endif
@@ -64,4 +68,65 @@ OTB_HD OtbBest otb_best(const uint64_t* m, int b, int span, uint32_t forbid, int
     }
   }
   return r;
+}
+
+// spread the 32 bits of x to the even bit positions of a 64-bit word
+OTB_HD uint64_t otb_spread(uint32_t x) {
+  uint64_t v = x;
+  v = (v | (v << 16)) & 0x0000ffff0000ffffull;
+  v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
+  v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
+  v = (v | (v << 2)) & 0x3333333333333333ull;
+  v = (v | (v << 1)) & 0x5555555555555555ull;
+  return v;
+}
+
+// The shift vectors of one pair.  code / nmsp: the site's spacer (Gs bases from bit 0, nothing above), g: the guide (G bases).
+// even = the even bits of the n = min(G, Gs) positions of the shorter sequence.
+template <int B, bool DNA>
+OTB_HD void otb_vectors(uint64_t code, uint32_t nmsp, uint64_t g, uint64_t even, uint64_t (&m)[B + 1]) {
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int k = 0; k <= B; ++k) {
+    const uint64_t x = DNA ? (g ^ (code >> (2 * k))) : (code ^ (g >> (2 * k)));
+    m[k] = ((x | (x >> 1)) | otb_spread(DNA ? (nmsp >> k) : nmsp)) & even;
+  }
+}
+
+// The row of one pair, from the site's WINDOW as a site record holds it (wcode / wnmask: Gs + P bases in guide orientation,
+// Gs = G + B for a DNA bulge, G - B for an RNA bulge; the PAM in front when `right`) and the guide's code: the placement otb_best
+// selects and, when it is within max_mm, the CFD of the row the off-targets table prints for it - ot_text_row (hawk_ottext.h) on
+// the record the pair makes, its text discarded, so the units are the table's by construction.  mm > max_mm: no row (gaps and
+// units mean nothing).  units: OT_TEXT_NA without tables, OT_TEXT_UNSCORABLE as ot_text_row has it.
+// Needs B + 3 <= G <= 32 and Gs + P <= 32 (hawk_offtarget_bulges' refusals).
+struct OtbPair { int mm; uint32_t gaps; long long units; };
+
+template <int B, bool DNA>
+OTB_HD OtbPair otb_pair_t(uint64_t wcode, uint32_t wnmask, uint64_t g, int G, int P, int right, int max_mm, const double* tab) {
+  const int Gs = DNA ? G + B : G - B, n = DNA ? G : Gs, span = n + B, sp0 = right ? P : 0;
+  const uint64_t even = (n >= 32 ? ~0ull : otb_low(n)) & OTB_EVEN;
+  const uint64_t code = (wcode >> (2 * sp0)) & (Gs >= 32 ? ~0ull : otb_low(Gs));
+  const uint32_t nmsp = (wnmask >> sp0) & (Gs >= 32 ? 0xffffffffu : ((1u << Gs) - 1u));
+  uint64_t m[B + 1];
+  otb_vectors<B, DNA>(code, nmsp, g, even, m);
+  const OtbBest r = otb_best(m, B, span, DNA ? nmsp : 0u, max_mm);
+  OtbPair out;
+  out.mm = r.mm; out.gaps = r.gaps; out.units = OT_TEXT_NA;
+  if (r.mm > max_mm) return out;
+  OtTextRec rec;
+  rec.guide = 0; rec.row = 0; rec.q = 0; rec.nmask = wnmask; rec.code = wcode; rec.gaps = r.gaps;
+  rec.strand = 0; rec.mm = (uint8_t)r.mm; rec.kind = DNA ? 1 : 2; rec.size = (uint8_t)B;
+  OtTextFmt f;
+  f.G = (uint32_t)G; f.P = (uint32_t)P; f.right = right ? 1u : 0u;
+  for (int k = 0; k < 32; ++k) f.pam[k] = 'N';  // the nominal PAM is text only
+  OtTextDiscard sink;
+  out.units = ot_text_row(rec, g, nullptr, 0, 0, f, tab, sink);
+  return out;
+}
+
+// the same with the bulge as arguments: b 1..2
+OTB_HD OtbPair otb_pair(uint64_t wcode, uint32_t wnmask, uint64_t g, int G, int P, int right, int b, bool dna, int max_mm, const double* tab) {
+  if (dna) return b == 1 ? otb_pair_t<1, true>(wcode, wnmask, g, G, P, right, max_mm, tab) : otb_pair_t<2, true>(wcode, wnmask, g, G, P, right, max_mm, tab);
+  return b == 1 ? otb_pair_t<1, false>(wcode, wnmask, g, G, P, right, max_mm, tab) : otb_pair_t<2, false>(wcode, wnmask, g, G, P, right, max_mm, tab);
 }

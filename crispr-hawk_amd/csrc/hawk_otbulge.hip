@@ -9,41 +9,66 @@
 //           holds 64 entries the wave verifies them one per lane: the placement loop then runs with every lane busy instead of
 //           one lane walking it while 63 wait.  What is left at the end of a guide chunk is verified before the chunk is replaced;
 //   verify  otb_best: fewest mismatches, ties to the smallest gap tuple, no ambiguous site base bulged out;
-//   sink    rows within max_mm go to hits[] behind an atomic counter that keeps counting past `cap` (the caller retries).
-// Integer / bitwise throughout, wave64, no MFMA shape.
+//   sink    what becomes of a row within max_mm is the kernel's Sink (a template parameter, as in hawk_offtarget.hip): OtbListSink
+//           appends it to hits[] behind an atomic counter that keeps counting past `cap` (the caller retries); OtbSumSink adds it
+//           to the per-guide histogram and CFD sum of hawk_offtarget_bulge_summary, which holds nothing sized by the hits.
+// Integer / bitwise throughout (the summary's CFD product is fp64), wave64, no MFMA shape.
 #include "hawk_bits.h"
 #include "hawk_otbulge.h"
 
 #define OT_GCHUNK 1024  // as hawk_offtarget.hip
 #define OTB_NW (HAWK_BLOCK / WAVE)
 
-// spread the 32 bits of x to the even bit positions of a 64-bit word
-__device__ __forceinline__ uint64_t otb_spread(uint32_t x) {
-  uint64_t v = x;
-  v = (v | (v << 16)) & 0x0000ffff0000ffffull;
-  v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
-  v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
-  v = (v | (v << 2)) & 0x3333333333333333ull;
-  v = (v | (v << 1)) & 0x5555555555555555ull;
-  return v;
-}
-
-// The shift vectors of one pair.  code / nmsp: the site's spacer (Gs bases from bit 0, nothing above), g: the guide (G bases).
-// even = the even bits of the n = min(G, Gs) positions of the shorter sequence.
-template <int B, bool DNA>
-__device__ __forceinline__ void otb_vectors(uint64_t code, uint32_t nmsp, uint64_t g, uint64_t even, uint64_t (&m)[B + 1]) {
-#pragma unroll
-  for (int k = 0; k <= B; ++k) {
-    const uint64_t x = DNA ? (g ^ (code >> (2 * k))) : (code ^ (g >> (2 * k)));
-    m[k] = ((x | (x >> 1)) | otb_spread(DNA ? (nmsp >> k) : nmsp)) & even;
+// ---- pair sinks.  pair<B, DNA>(sites, site index, guide index, the guide's code, the site's spacer code / ambiguity bits as the
+// wave holds them in LDS, even, G, span, max_mm): verify one queued pair and do with its row what the call is for.
+// The list: the row goes to hits[] (hawk_offtarget_bulges).
+struct OtbListSink {
+  OtBulgeHit* __restrict__ hits;
+  uint64_t cap;
+  unsigned long long* __restrict__ n_hits;
+  template <int B, bool DNA>
+  __device__ __forceinline__ void pair(const OtSite* __restrict__, uint64_t site, uint32_t guide, uint64_t g, uint64_t code, uint32_t nm,
+                                       uint64_t even, int, int span, int max_mm) const {
+    uint64_t m[B + 1];
+    otb_vectors<B, DNA>(code, nm, g, even, m);
+    const OtbBest r = otb_best(m, B, span, DNA ? nm : 0u, max_mm);
+    if (r.mm <= max_mm) {
+      const unsigned long long o = atomicAdd(n_hits, 1ull);
+      if (o < cap) {
+        OtBulgeHit hh;
+        hh.site = site; hh.guide = guide; hh.mm = (uint32_t)r.mm; hh.gaps = r.gaps; hh.pad = 0;
+        hits[o] = hh;
+      }
+    }
   }
-}
+};
 
-template <int B, bool DNA>
+// The summary (hawk_offtarget_bulge_summary): the row is consumed where it is found, as OtSumSink (hawk_offtarget.hip) consumes a
+// mismatch-only hit - hist[guide][mm] += 1 and, with tables, cfd_e4[guide] += the row's CFD in units of 1e-4.  The site record is
+// read back (it is in L2 from the wave's own first read) and otb_pair (hawk_otbulge.h) states the pair from the record's window:
+// the function the host twin runs, the units ot_text_row gives the table's row.  An unscorable row counts in hist and in
+// counters[1] and adds nothing.  Integer sums: no order of the atomics, no sharding changes them.  Nothing here is sized by the hits.
+// The spacer code, ambiguity bits, `even` and `span` the wave holds are NOT used here (unnamed parameters): otb_pair cuts the spacer
+// out of the record's window and forms the vectors itself, so that kernel and host twin run one statement of a pair; the second
+// otb_vectors + otb_best per queued pair is the price (10.4 ms against the list's 9.8 ms on the r05 panel).
+struct OtbSumSink : OtBulgeSummary {  // hawk_device.h: tab, hist, cfd_e4, counters, stride, pamlen, right
+  template <int B, bool DNA>
+  __device__ __forceinline__ void pair(const OtSite* __restrict__ sites, uint64_t site, uint32_t guide, uint64_t g, uint64_t, uint32_t,
+                                       uint64_t, int G, int, int max_mm) const {
+    const OtSite st = sites[site];
+    const OtbPair r = otb_pair_t<B, DNA>(st.code, st.nmask, g, G, pamlen, right, max_mm, tab);
+    if (r.mm > max_mm) return;
+    atomicAdd(counters, 1ull);
+    atomicAdd(hist + (size_t)guide * stride + (uint32_t)r.mm, 1u);
+    if (r.units == OT_TEXT_UNSCORABLE) atomicAdd(counters + 1, 1ull);
+    else if (r.units > 0) atomicAdd(cfd_e4 + guide, (unsigned long long)r.units);
+  }
+};
+
+template <int B, bool DNA, class Sink>
 __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_bulge(const OtSite* __restrict__ sites, uint64_t n_sites,
                                                           const uint64_t* __restrict__ guides, uint32_t n_guides, int G, int sp0,
-                                                          int max_mm, OtBulgeHit* __restrict__ hits, uint64_t cap,
-                                                          unsigned long long* __restrict__ n_hits) {
+                                                          int max_mm, Sink sink) {
   __shared__ uint64_t s_g[OT_GCHUNK];
   __shared__ uint64_t s_code[OTB_NW][WAVE];
   __shared__ uint32_t s_nm[OTB_NW][WAVE];
@@ -82,18 +107,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_bulge(const OtSite* __restric
   // entry e of the queue, verified by this lane
   auto verify = [&](uint32_t e, uint32_t g0) {
     const uint32_t l = e & (WAVE - 1), t = e >> 6;
-    uint64_t m[B + 1];
-    const uint32_t nm = s_nm[wv][l];
-    otb_vectors<B, DNA>(s_code[wv][l], nm, s_g[t], even, m);
-    const OtbBest r = otb_best(m, B, span, DNA ? nm : 0u, max_mm);
-    if (r.mm <= max_mm) {
-      const unsigned long long o = atomicAdd(n_hits, 1ull);
-      if (o < cap) {
-        OtBulgeHit hh;
-        hh.site = i0 + l; hh.guide = g0 + t; hh.mm = (uint32_t)r.mm; hh.gaps = r.gaps; hh.pad = 0;
-        hits[o] = hh;
-      }
-    }
+    sink.template pair<B, DNA>(sites, i0 + l, g0 + t, s_g[t], s_code[wv][l], s_nm[wv][l], even, G, span, max_mm);
   };
 
   for (uint32_t g0 = 0; g0 < n_guides; g0 += OT_GCHUNK) {
@@ -136,12 +150,26 @@ void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites,
                           int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits) {
   if (!n_sites || !n_guides) return;
   const dim3 grid((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), block(HAWK_BLOCK);
-#define OTB_LAUNCH(B, D) \
-  hipLaunchKernelGGL((k_ot_bulge<B, D>), grid, block, 0, st, sites, n_sites, guides, n_guides, guidelen, sp0, max_mm, hits, cap, n_hits)
+  const OtbListSink sink{hits, cap, n_hits};
+#define OTB_LAUNCH(B, D, S) \
+  hipLaunchKernelGGL((k_ot_bulge<B, D, S>), grid, block, 0, st, sites, n_sites, guides, n_guides, guidelen, sp0, max_mm, sink)
   if (dna) {
-    if (bsize == 1) OTB_LAUNCH(1, true); else OTB_LAUNCH(2, true);
+    if (bsize == 1) OTB_LAUNCH(1, true, OtbListSink); else OTB_LAUNCH(2, true, OtbListSink);
   } else {
-    if (bsize == 1) OTB_LAUNCH(1, false); else OTB_LAUNCH(2, false);
+    if (bsize == 1) OTB_LAUNCH(1, false, OtbListSink); else OTB_LAUNCH(2, false, OtbListSink);
+  }
+}
+
+// The same kernel with the summary's sink (hawk_offtarget_bulge_summary).
+void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
+                              int sp0, int max_mm, int dna, int bsize, const OtBulgeSummary& sm) {
+  if (!n_sites || !n_guides) return;
+  const dim3 grid((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), block(HAWK_BLOCK);
+  const OtbSumSink sink{sm};
+  if (dna) {
+    if (bsize == 1) OTB_LAUNCH(1, true, OtbSumSink); else OTB_LAUNCH(2, true, OtbSumSink);
+  } else {
+    if (bsize == 1) OTB_LAUNCH(1, false, OtbSumSink); else OTB_LAUNCH(2, false, OtbSumSink);
   }
 #undef OTB_LAUNCH
 }

@@ -11,7 +11,8 @@
 // Gs = G + size (DNA bulge), G - size (RNA bulge) or G; its PAM stands in front when `right` is set.
 //
 // The emitter writes through a sink (put(byte)): with OtTextCount it gives the row's length, with OtTextBytes the row - the
-// length pass and the fill pass are the same function and cannot drift apart.  No device code here: the header compiles as
+// length pass and the fill pass are the same function and cannot drift apart; with OtTextDiscard what is left is the row's CFD,
+// which is how the bulged summary (otb_pair, hawk_otbulge.h) gets the table's units without restating them.  No device code here: the header compiles as
 // plain C++ too (the host-only sanitizer builds of hawk_hostutil.hip).
 #pragma once
 #include <stdint.h>
@@ -57,6 +58,9 @@ struct OtTextCount {
 struct OtTextBytes {
   uint8_t* w;
   HAWK_HD void put(uint8_t c) { *w++ = c; }
+};
+struct OtTextDiscard {  // the row's CFD alone (otb_pair, hawk_otbulge.h): the text goes nowhere
+  HAWK_HD void put(uint8_t) {}
 };
 
 // the site's spacer length; 0 for a record no row can be made of

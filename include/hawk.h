@@ -497,6 +497,30 @@ int hawk_offtarget_bulges(hawk_hapset* rows, const hawk_ot_params* p, const uint
 int hawk_offtarget_summary(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
                            const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
                            uint64_t* n_hits, uint64_t* n_unscorable, hawk_ot_timing* timing);
+/* The summary of the bulged sites of one (type, size): hawk_offtarget_bulges' rows consumed inside k_ot_bulge instead of listed - no
+ * hit list, no cap, no retry; device memory is sized by n_guides and max_mm alone.  All pairs, as hawk_offtarget_bulges.
+ *   out_hist[g][m]  (row stride max_mm + 1) rows of guide g whose selected placement has m mismatches
+ *   out_cfd_e4[g]   sum over guide g's rows of the CFD the off-targets table prints for the row, in units of 1e-4: the value
+ *                   hawk_offtarget_text computes for the record (site window, guide, mm, gaps, kind, size) - the alignment column as
+ *                   the table's position index, columns beside a '-' skipped, the last two characters of the spacer field as the
+ *                   PAM key - through the same function (csrc/hawk_ottext.h: ot_text_row; csrc/hawk_otbulge.h: otb_pair)
+ * p->guidelen is the GUIDE's length; bulge_type / bulge_size, the scan ranges and their refusals as hawk_offtarget_bulges (type or
+ * size out of range, a plan view, scan ranges set for a shorter window: HAWK_E_INVALID; G - bulge_size < 3, G > 32, Gs + pamlen >
+ * 32: HAWK_E_UNSUPPORTED); cfd_mm / cfd_pam, *n_hits, *n_unscorable and the remaining rules as hawk_offtarget_summary (both tables
+ * or neither; HAWK_E_UNSUPPORTED for tables with pamlen < 2 and for max_mm > 32).  An unscorable row counts in out_hist and in
+ * *n_unscorable and adds nothing.  Nothing is written to the outputs of a refused call. */
+int hawk_offtarget_bulge_summary(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
+                                 uint32_t bulge_type, uint32_t bulge_size, const double* cfd_mm, const double* cfd_pam,
+                                 uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable,
+                                 hawk_ot_timing* timing);
+/* The same sums on the host, no device: the site windows are given - code[i] / nmask[i] of the Gs + pamlen bases of site i in guide
+ * orientation, as hawk_offtarget_bulges returns them (every one is taken to bear the PAM; p->pam_fwd / pam_rev are not read) - and
+ * every (site, guide) pair goes through the function the kernel's summing sink runs, in a plain loop.  Same parameters, tables,
+ * outputs and argument refusals. */
+int hawk_host_offtarget_bulge_summary(const uint64_t* code, const uint32_t* nmask, uint64_t n_sites, const uint64_t* guides2,
+                                      uint32_t n_guides, const hawk_ot_params* p, uint32_t bulge_type, uint32_t bulge_size,
+                                      const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
+                                      uint64_t* n_hits, uint64_t* n_unscorable);
 
 /* The hits of hawk_offtarget_scan / hawk_offtarget_bulges as the rows of offtargets_{contig}_{start}_{stop}.tsv (offtargets.py:
  * 41-53, 530-544), written on the device: per row the eleven fields chrom, position, strand, grna, spacer, pam, mm, bulge_size,
