@@ -41,6 +41,7 @@ EXPORTS = [
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
     "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
     "hawk_host_effects", "hawk_host_round4",
+    "hawk_table_resolve_unphased", "hawk_resolve_download", "hawk_resolve_free", "hawk_host_resolve_unphased",
     "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
 ]
 
@@ -124,6 +125,41 @@ class EffectsTiming(C.Structure):
                 ("n_groups", C.c_uint64), ("n_positions", C.c_uint64), ("n_long", C.c_uint64)]
 
 
+class ResolveAlleles(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("key", C.c_void_p), ("off", C.c_void_p), ("ref", C.c_void_p)]
+
+
+class ResolveColumns(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("win_stride", C.c_uint64), ("hap", C.c_void_p), ("pos", C.c_void_p), ("strand", C.c_void_p),
+                ("start", C.c_void_p), ("flags", C.c_void_p), ("win", C.c_void_p), ("hap_len", C.c_void_p), ("hap_is_ref", C.c_void_p),
+                ("pam_fwd", C.c_uint64), ("pam_rev", C.c_uint64), ("n_hap", C.c_uint32), ("guidelen", C.c_uint32), ("pamlen", C.c_uint32),
+                ("right", C.c_uint32)]
+
+
+class ResolveDecline(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("reserved", C.c_int32), ("row", C.c_int64)]
+
+
+class ResolveTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("refsort_ms", C.c_float), ("count_ms", C.c_float), ("scan_ms", C.c_float), ("fill_ms", C.c_float),
+                ("total_ms", C.c_float), ("n_batches", C.c_uint32), ("reserved", C.c_uint32), ("n_rows", C.c_uint64), ("n_resolved", C.c_uint64),
+                ("n_kept", C.c_uint64)]
+
+
+RESOLVE_REASONS = {1: "an ambiguous position without allele entries", 2: "more than one haplotype flagged REF",
+                   3: "a REF row with more than one combination", 4: "a row of more than 2^32 - 1 combinations",
+                   5: "a row whose kept guides do not fit the batch budget"}
+
+
+class HawkResolveDeclined(HawkStatusError):
+    """hawk_table_resolve_unphased / hawk_host_resolve_unphased declined (include/hawk.h: HAWK_RESOLVE_*): the caller takes the
+    host route, which raises what the reference raises."""
+
+    def __init__(self, status: int, where: str, reason: int, row: int):
+        self.reason, self.row = reason, row
+        super().__init__(status, where, f"{RESOLVE_REASONS.get(reason, reason)} (row {row})")
+
+
 class OtTiming(C.Structure):
     _fields_ = [("scan_ms", C.c_float), ("sites_ms", C.c_float), ("match_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_sites", C.c_uint64), ("scanned_positions", C.c_uint64)]
@@ -158,6 +194,7 @@ def lib() -> C.CDLL:
         L.hawk_annot_free.restype = None
         L.hawk_gnomad_destroy.restype = None
         L.hawk_effects_free.restype = None
+        L.hawk_resolve_free.restype = None
         L.hawk_plm_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:

@@ -351,6 +351,77 @@ def decode_windows(win: np.ndarray, W: int) -> List[str]:
     return [raw[i * W:(i + 1) * W].decode("ascii") for i in range(n)]
 
 
+class ResolvedColumns:
+    """The guides an unphased table resolves to, as columns: `src_row[k]` the table row guide k comes from (ascending; inside a
+    row the guides are in itertools.product order), `win[5, k]` its window slices, and per TABLE row `n_resolved` (combinations
+    whose PAM still matches) and `n_kept` (those the REF-redundancy rule leaves)."""
+
+    __slots__ = ("src_row", "win", "n_resolved", "n_kept", "timing", "engine", "window_len")
+
+    def windows(self) -> List[str]:
+        return decode_windows(self.win, self.window_len)
+
+    def reference_order(self, tab: "GuideTable") -> np.ndarray:
+        """Permutation of the kept guides giving the list order of the reference's search(): remove_redundant_guides walks a
+        dict keyed by (start, strand) in first-seen order over the guides BEFORE its filter - a key's rank is the smallest
+        emission index among its rows with n_resolved > 0 - each key in emission order, a row's guides in combination order.
+        `tab`: the downloaded table the columns were resolved from.  Row-level arrays only."""
+        n = tab.n_rows
+        if n == 0 or len(self.src_row) == 0:
+            return np.zeros(0, dtype=np.int64)
+        emit = tab.emission_order()
+        rank = np.empty(n, np.int64)
+        rank[emit] = np.arange(n)
+        key = tab.start.astype(np.int64) * 2 + tab.strand
+        _, inv = np.unique(key, return_inverse=True)
+        first = np.full(inv.max() + 1, n, dtype=np.int64)
+        seen = self.n_resolved > 0
+        np.minimum.at(first, inv[seen], rank[seen])
+        rows = np.flatnonzero(self.n_kept > 0)
+        rows = rows[np.lexsort((rank[rows], first[inv[rows]]))]
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(self.n_kept, out=off[1:])
+        cnt = self.n_kept[rows].astype(np.int64)
+        base = np.repeat(off[rows], cnt)
+        within = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        return base + within
+
+
+def resolve_columns_host(hap, pos, strand, start, flags, win, hap_len, is_ref, alleles, pam_bits: int, pam_bitsrc: int, guidelen: int,
+                         pamlen: int, right: bool, n_resolved: Optional[np.ndarray] = None, n_kept: Optional[np.ndarray] = None,
+                         batch_bytes: Optional[int] = None):
+    """hawk_host_resolve_unphased on host columns -> (src_row, win[5, n_kept]); the per-row counts go into n_resolved / n_kept
+    when given.  No device.  Raises _lib.HawkResolveDeclined where the call declines."""
+    import os
+    L = _lib.lib()
+    n = len(hap)
+    key, off, ref = (np.ascontiguousarray(a, dt) for a, dt in zip(alleles, (np.uint64, np.uint32, np.uint8)))
+    al = _lib.ResolveAlleles(len(key), key.ctypes.data, off.ctypes.data, ref.ctypes.data if len(ref) else None)
+    cols = _lib.ResolveColumns()
+    keep = [np.ascontiguousarray(hap, np.uint32), np.ascontiguousarray(pos, np.uint32), np.ascontiguousarray(strand, np.uint8),
+            np.ascontiguousarray(start, np.int64), np.ascontiguousarray(flags, np.uint8), np.ascontiguousarray(win, np.uint64).reshape(5, -1),
+            np.ascontiguousarray(hap_len, np.uint32), np.ascontiguousarray(is_ref, np.uint8)]
+    cols.n_rows, cols.win_stride = n, keep[5].shape[1]
+    cols.hap, cols.pos, cols.strand, cols.start, cols.flags, cols.win, cols.hap_len, cols.hap_is_ref = (a.ctypes.data for a in keep)
+    cols.pam_fwd, cols.pam_rev, cols.n_hap, cols.guidelen, cols.pamlen, cols.right = pam_bits, pam_bitsrc, len(keep[6]), guidelen, pamlen, int(bool(right))
+    if batch_bytes is None:
+        batch_bytes = int(os.environ.get("HAWK_RESOLVE_BATCH_BYTES", 0) or (256 << 20))
+    n_resolved = np.zeros(n, np.uint32) if n_resolved is None else n_resolved
+    n_kept = np.zeros(n, np.uint32) if n_kept is None else n_kept
+    dec, no, nr = _lib.ResolveDecline(), C.c_uint64(), C.c_uint64()
+
+    def call(src, w, cap):
+        rc = L.hawk_host_resolve_unphased(C.byref(cols), C.byref(al), C.c_uint64(batch_bytes), _p(n_resolved), _p(n_kept), _p(src), _p(w),
+                                          C.c_uint64(cap), C.byref(no), C.byref(nr), C.byref(dec))
+        if rc != _lib.HAWK_OK and dec.reason:
+            raise _lib.HawkResolveDeclined(rc, "hawk_host_resolve_unphased", dec.reason, dec.row)
+        _lib.check(rc, "hawk_host_resolve_unphased")
+    call(None, None, 0)  # the counts: how large the outputs are
+    src, w = np.empty(no.value, np.uint32), np.empty((5, no.value), np.uint64)
+    call(src, w, no.value)
+    return src, w
+
+
 class GuideTable:
     """Columnar guide table of one fused search (rows in (haplotype, tile, strand, position) order)."""
 
@@ -436,6 +507,56 @@ class GuideTable:
         g.export_ms = ms.value
         g.n_candidates, g.n_hits = self.n_candidates, self.n_hits
         return g
+
+    def resolve_unphased(self, haplotypes, pam, engine: str = "device") -> "ResolvedColumns":
+        """The rows' IUPAC windows resolved into their allele combinations (search_guides.py:163-257, 473-480) with the PAM
+        re-check and the REF-redundancy rule (340-369) applied - on the table in HBM (`engine="device"`:
+        hawk_table_resolve_unphased) or by the same header on the host (`"host"`: hawk_host_resolve_unphased on the downloaded
+        columns).  Call it before download().  `haplotypes`: the Haplotype list the set was made from, or the allele table
+        search_guides.flatten_variant_alleles made of it; `pam`: a PAM, or (bits, bitsrc).  Raises _lib.HawkResolveDeclined
+        where the call declines (include/hawk.h)."""
+        if self._t is None:
+            raise RuntimeError("resolve_unphased() needs the device-resident table: call it before download()")
+        if engine not in ("device", "host"):
+            raise ValueError(f"engine {engine!r}: 'device' or 'host'")
+        if isinstance(haplotypes, tuple):
+            key, off, ref = haplotypes
+        else:
+            from .search_guides import flatten_variant_alleles
+            key, off, ref = flatten_variant_alleles(haplotypes)
+        key = np.ascontiguousarray(key, np.uint64); off = np.ascontiguousarray(off, np.uint32); ref = np.ascontiguousarray(ref, np.uint8)
+        al = _lib.ResolveAlleles(len(key), key.ctypes.data, off.ctypes.data, ref.ctypes.data if len(ref) else None)
+        bits, bitsrc = pam if isinstance(pam, tuple) else (pam.bits, pam.bitsrc)
+        L, n = self._hs._L, self.n_rows
+        dec, nk, nr = _lib.ResolveDecline(), C.c_uint64(), C.c_uint64()
+        out = ResolvedColumns()
+        out.engine, out.window_len = engine, self.window_len
+        out.n_resolved = np.zeros(n, np.uint32); out.n_kept = np.zeros(n, np.uint32)
+        if engine == "device":
+            h, tm = C.c_void_p(), _lib.ResolveTiming()
+            rc = L.hawk_table_resolve_unphased(self._t, C.byref(al), C.c_uint64(bits), C.c_uint64(bitsrc), C.byref(h), C.byref(nk), C.byref(nr),
+                                               C.byref(dec), C.byref(tm))
+            if rc != _lib.HAWK_OK and dec.reason:
+                raise _lib.HawkResolveDeclined(rc, "hawk_table_resolve_unphased", dec.reason, dec.row)
+            _lib.check(rc, "hawk_table_resolve_unphased")
+            try:  # the batches are copied straight into these arrays (page-locked once they are large)
+                dev = getattr(self._hs, "device", None)
+                out.src_row = _lib.pinned_empty(nk.value, np.uint32, dev)
+                out.win = _lib.pinned_empty(5 * nk.value, np.uint64, dev).reshape(5, nk.value)
+                _lib.check(L.hawk_resolve_download(h, _p(out.src_row), _p(out.win), _p(out.n_resolved), _p(out.n_kept), C.byref(tm)),
+                           "hawk_resolve_download")
+            finally:
+                L.hawk_resolve_free(h)
+            out.timing = {k: getattr(tm, k) for k, _ in tm._fields_ if k != "reserved"}
+        else:
+            hap = np.empty(n, np.uint32); pos = np.empty(n, np.uint32); strand = np.empty(n, np.uint8); start = np.empty(n, np.int64)
+            flags = np.empty(n, np.uint8); win = np.empty((5, n), np.uint64)
+            _lib.check(L.hawk_table_download(self._t, _p(hap), _p(pos), _p(strand), _p(start), None, _p(flags), None, _p(win)), "hawk_table_download")
+            hap_len = np.ascontiguousarray(self._hs.hap_len, np.uint32); is_ref = np.ascontiguousarray(self._hs.is_ref, np.uint8)
+            out.src_row, out.win = resolve_columns_host(hap, pos, strand, start, flags, win, hap_len, is_ref, (key, off, ref), bits, bitsrc,
+                                                        self.guidelen, self.pamlen, self.right, out.n_resolved, out.n_kept)
+            out.timing = {}
+        return out
 
     def download(self) -> "GuideTable":
         if self._downloaded:

@@ -119,10 +119,10 @@ def _plan_row_variants(info, vt) -> List[bytes]:
 
 
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
-                       ot=None, ann=None, lap=None, tables=None) -> str:
+                       ot=None, ann=None, lap=None, tables=None, unphased_engine=None) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
-    (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows,
-    resolve_guide on the host, search_guides.py:163-257) and the fallback for phased records the device expansion
+    (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows; their
+    windows resolved on the device table, search_guides.search's `unphased_engine`) and the fallback for phased records the device expansion
     declines (a chromosome copy carrying overlapping records, multi-base deletion alts).  The search itself still runs
     on the device; then the reference's order of business: annotate -> reverse_guides -> CFDon -> report."""
     from . import haplotypes as hap_mod
@@ -143,7 +143,7 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, [h.id for h in haps],
                                                       [h.variants for h in haps], [h.samples for h in haps],
                                                       sequences=[h.sequence.sequence for h in haps])
-    guides = search(pam, region, haps, None, guidelen, right, bool(records), phased, 0, debug)
+    guides = search(pam, region, haps, None, guidelen, right, bool(records), phased, 0, debug, unphased_engine=unphased_engine)
     cfd = None
     if mm is not None:
         scoring.set_cfd_tables(mm, pt)

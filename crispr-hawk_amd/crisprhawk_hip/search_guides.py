@@ -6,9 +6,12 @@ scan / filter / coordinate / redundancy work done by the HIP kernels through the
 ``haplotypes_bits`` argument is accepted for signature compatibility; the planes are the
 encoded form and are built once per call for all haplotypes together.
 With an unphased VCF the candidates come from the same device pass (the PAM match is a set
-intersection, so IUPAC-encoded haplotypes need no special casing) and are then expanded on the
-host through ``resolve_guide`` exactly as search_guides.py:163-257, 473-480 does: that step is a
-Cartesian product over a handful of ambiguous positions per window, string work by nature."""
+intersection, so IUPAC-encoded haplotypes need no special casing).  Resolving their windows into allele
+combinations (search_guides.py:163-257, 473-480) is a mixed-radix enumeration over the 5-bit codes of the
+window slices: the device does it on the table in HBM (hawk_table_resolve_unphased: count, offsets,
+fill, with the PAM re-check and remove_redundant_guides' compare against REF's row) and hands back
+columns; ``resolve_guide`` stays as the host route (``unphased_engine="host"``), which is also where a
+call goes that the device route declines - it raises what the reference raises."""
 import os
 from collections import defaultdict
 from typing import DefaultDict, Dict, List, Optional, Tuple, Union
@@ -20,6 +23,7 @@ from itertools import product
 from .crisprhawk_error import CrisprHawkCfdScoreError, CrisprHawkIupacTableError
 from .exception_handlers import exception_handler
 from .guide import GUIDESEQPAD, Guide
+from ._lib import HawkStatusError
 from .hapset import DeviceHapSet, GuideTable, HostHaplotype, PosSegments
 from .haplotype import Haplotype
 from .pam import PAM
@@ -193,18 +197,86 @@ def guides_from_table(tab: GuideTable, haplotypes: List[Haplotype], debug: bool,
     return guides
 
 
+def flatten_variant_alleles(haplotypes: List[Haplotype]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``Haplotype.variant_alleles`` of a haplotype list as the allele table of hawk_table_resolve_unphased: sorted keys
+    (haplotype index << 32 | relative position), CSR offsets of each key's entries, and one byte per entry - the index
+    of its ref in "ACGT", or 255 when the ref is no single upper-case base (_decode_iupac compares the upper-case base
+    with the ref string, so such an entry makes every option lower case)."""
+    keys, counts, refs = [], [], []
+    for hi, h in enumerate(haplotypes):
+        va = h.variant_alleles
+        for rel in sorted(va):
+            if not 0 <= rel < (1 << 32):
+                continue
+            keys.append((hi << 32) | int(rel))
+            counts.append(len(va[rel]))
+            refs.extend("ACGT".find(a[0]) if len(a[0]) == 1 and a[0] in "ACGT" else 255 for a in va[rel])
+    off = np.zeros(len(keys) + 1, np.uint32)
+    if keys:
+        np.cumsum(np.asarray(counts, np.int64), out=off[1:])
+    return np.asarray(keys, np.uint64), off, np.asarray(refs, np.int64).astype(np.uint8)
+
+
+UNPHASED_ENGINES = (None, "device", "host")
+last_resolve_timing: Dict[str, float] = {}  # hawk_resolve_timing of the last search() that resolved on the device (tools/time_resolve_unphased.py)
+
+
 def search(pam: PAM, region: Region, haplotypes: List[Haplotype], haplotypes_bits, guidelen: int, right: bool,
-           variants_present: bool, phased: bool, verbosity: int, debug: bool, cfd_tables=None) -> List[Guide]:
+           variants_present: bool, phased: bool, verbosity: int, debug: bool, cfd_tables=None,
+           unphased_engine: Optional[str] = None) -> List[Guide]:
     """search_guides.py:510-548.  ``cfd_tables=(mm, pam)`` additionally scores CFDon in the same
-    device pass (kept on each Guide for scoring.cfdon_score)."""
+    device pass (kept on each Guide for scoring.cfdon_score).  ``unphased_engine`` (unphased VCFs only): "device"
+    resolves the IUPAC windows on the table in HBM, "host" through resolve_guide; None takes HAWK_UNPHASED_ENGINE, else
+    the device route.  A call the device route declines or refuses (include/hawk.h; any status but a HIP failure) takes the host
+    route, under either setting."""
+    if unphased_engine not in UNPHASED_ENGINES:
+        raise ValueError(f"unphased_engine {unphased_engine!r}: None, 'device' or 'host'")
     print_verbosity(f"Searching guide candidates in {region.coordinates}", verbosity, VERBOSITYLVL[3])
     ds = _device_set(region, haplotypes, len(pam))
     mm, pt = cfd_tables if cfd_tables is not None else (None, None)
     if variants_present and not phased:
-        tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right)
+        engine = unphased_engine or os.environ.get("HAWK_UNPHASED_ENGINE") or "device"
+        if engine not in ("device", "host"):
+            raise ValueError(f"HAWK_UNPHASED_ENGINE={engine!r}: 'device' or 'host'")
+        tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right, download=False)
+        if engine == "device":
+            try:
+                res = tab.resolve_unphased(haplotypes, pam, "device")
+            except HawkStatusError as e:  # a decline (HawkResolveDeclined) or a refusal, e.g. a geometry the kernels do not take
+                print_verbosity(f"Unphased windows resolved on the host: {e}", verbosity, VERBOSITYLVL[3])
+            else:
+                last_resolve_timing.clear()
+                last_resolve_timing.update(res.timing)
+                return _guides_from_resolved(tab, res, haplotypes, debug)
         return _resolve_unphased(tab, haplotypes, pam, guidelen, right, debug)
     tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right, mm, pt)
     return guides_from_table(tab, haplotypes, debug)
+
+
+def _guides_from_resolved(tab: GuideTable, res, haplotypes: List[Haplotype], debug: bool) -> List[Guide]:
+    """The Guide list of the device route: one Guide per kept column entry, with the constructor arguments
+    _resolve_unphased gives it, in the reference's list order (ResolvedColumns.reference_order)."""
+    tab.download()
+    order = res.reference_order(tab)
+    seqs = res.windows()
+    ras = tab.right_as_stored()
+    guidelen, pamlen = tab.guidelen, tab.pamlen
+    L = guidelen + pamlen
+    guides: List[Guide] = []
+    for k in order:
+        i = int(res.src_row[k])
+        h = haplotypes[int(tab.hap[i])]
+        r, pos = bool(ras[i]), int(tab.pos[i])
+        pivot = pos if r else pos - guidelen
+
+        def _pm(seg=h.segments, pivot=pivot):
+            g = seg.lookup(np.arange(pivot, pivot + L))
+            return {k: int(g[k]) for k in range(L)}
+        g = Guide(int(tab.start[i]), int(tab.stop[i]), seqs[k], guidelen, pamlen, int(tab.strand[i]), h.samples, h.variants,
+                  h.afs, _pm, debug, r, h.id)
+        g._hip_pos, g._hip_hap = pos, int(tab.hap[i])
+        guides.append(g)
+    return guides
 
 
 def _resolve_unphased(tab: GuideTable, haplotypes: List[Haplotype], pam: PAM, guidelen: int, right: bool, debug: bool) -> List[Guide]:

@@ -455,6 +455,27 @@ struct FxDev {
   uint64_t* alt_off;    // [K + 1]
   uint32_t* alt_group;
 };
+// ---- unphased IUPAC windows resolved on the table (hawk_resolve.hip; the rules themselves: hawk_resolve.h)
+#include "hawk_resolve.h"
+struct UrDev {
+  GuideCols c;              // either layout
+  uint64_t n;               // rows
+  const uint32_t* hap_len;  // [n_hap]
+  const uint8_t* is_ref;    // [n_hap]
+  uint32_t n_hap;
+  UrGeom g;
+  UrAlleles al;             // device pointers
+  const uint64_t* ref_key;  // [n] sorted start * 2 + strand of REF's rows, UR_SAT behind them
+  const uint32_t* ref_row;  // [n] the row of each key
+};
+size_t hawk_ur_temp_bytes(uint64_t n);
+int hawk_launch_ur_refsort(hipStream_t st, const UrDev& d, void* temp, size_t temp_bytes, uint64_t* keys /* [2][n] */, uint32_t* vals /* [2][n] */);
+void hawk_launch_ur_count(hipStream_t st, const UrDev& d, uint32_t* n_resolved, uint32_t* n_kept, unsigned long long* decline /* ~0 */,
+                          unsigned long long* totals /* [2], zeroed */);
+int hawk_launch_ur_offsets(hipStream_t st, const uint32_t* n_kept /* [n + 1], last 0 */, uint64_t n, void* temp, size_t temp_bytes, uint64_t* offsets);
+void hawk_launch_ur_fill(hipStream_t st, const UrDev& d, const uint32_t* n_resolved, const uint32_t* n_kept, const uint64_t* offsets, uint64_t r0,
+                         uint64_t r1, uint64_t o0, uint64_t n_out, uint32_t* out_src, uint64_t* out_win, uint64_t out_stride);
+
 #define FX_TOPK_MAX_BLOCKS 1024u
 void hawk_launch_fx_isref_gather(hipStream_t st, const uint8_t* hap_is_ref, const uint32_t* member_hap, const uint64_t* member_off, uint64_t n_groups, uint8_t* out);
 void hawk_launch_fx_groups(hipStream_t st, const FxDev& F);

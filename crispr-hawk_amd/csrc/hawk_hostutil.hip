@@ -16,6 +16,7 @@
 #include "hawk_otbulge.h"
 #include "hawk_gnomad.h"
 #include "hawk_effects.h"
+#include "hawk_resolve.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -1104,6 +1105,100 @@ int hawk_host_effects(const hawk_effects_columns* cols, int family, const double
     }
   }
   if (out->alt_off) out->alt_off[chosen.size()] = at;
+  return HAWK_OK;
+}
+
+// ---- unphased IUPAC windows (hawk_resolve.h): the host twin of hawk_table_resolve_unphased
+static UrRow ur_host_row(const hawk_resolve_columns* c, uint64_t i) {
+  UrRow r;
+  r.hap = c->hap[i]; r.pos = c->pos[i]; r.strand = c->strand[i]; r.flags = c->flags[i];
+  r.hap_len = r.hap < c->n_hap ? c->hap_len[r.hap] : 0u;
+  for (int pl = 0; pl < UR_PLANES; ++pl) r.win[pl] = c->win[(uint64_t)pl * c->win_stride + i];
+  return r;
+}
+
+int hawk_host_resolve_unphased(const hawk_resolve_columns* cols, const hawk_resolve_alleles* alleles, uint64_t batch_bytes,
+                               uint32_t* row_resolved, uint32_t* row_kept, uint32_t* src_row, uint64_t* win, uint64_t out_cap,
+                               uint64_t* n_out, uint64_t* n_resolved, hawk_resolve_decline* decline) {
+  if (decline) { decline->reason = 0; decline->reserved = 0; decline->row = -1; }
+  if (!cols || !alleles || !n_out) return HAWK_E_INVALID;
+  *n_out = 0;
+  if (n_resolved) *n_resolved = 0;
+  const uint64_t n = cols->n_rows;
+  UrGeom g;
+  g.pam_fwd = cols->pam_fwd; g.pam_rev = cols->pam_rev; g.guidelen = (int32_t)cols->guidelen; g.pamlen = (int32_t)cols->pamlen;
+  g.right = cols->right ? 1 : 0; g.W = g.guidelen + g.pamlen + 2 * UR_PAD;
+  if (cols->guidelen > 64 || cols->pamlen > 64) return HAWK_E_INVALID;
+  const int bad = ur_check_geom(g);
+  if (bad) return bad == 2 ? HAWK_E_UNSUPPORTED : HAWK_E_INVALID;
+  if (n && (!cols->hap || !cols->pos || !cols->strand || !cols->start || !cols->flags || !cols->win || !cols->hap_len || !cols->hap_is_ref ||
+            cols->win_stride < n || n > 0xffffffffull))
+    return HAWK_E_INVALID;
+  UrAlleles al;
+  al.key = alleles->key; al.off = alleles->off; al.ref = alleles->ref; al.n_keys = alleles->n_keys;
+  if (!ur_check_alleles(al)) return HAWK_E_INVALID;
+  for (uint64_t i = 0; i < n; ++i)
+    if (cols->hap[i] >= cols->n_hap || cols->strand[i] > 1) return HAWK_E_INVALID;
+  auto declined = [&](int reason, int64_t row) {
+    if (decline) { decline->reason = reason; decline->row = row; }
+    return (reason == UR_DECL_ROW_SIZE || reason == UR_DECL_BATCH) ? HAWK_E_CAPACITY : HAWK_E_UNSUPPORTED;
+  };
+  uint32_t n_ref = 0;
+  for (uint32_t h = 0; h < cols->n_hap; ++h) n_ref += cols->hap_is_ref[h] ? 1u : 0u;
+  if (n && n_ref > 1) return declined(UR_DECL_MULTI_REF, -1);
+  std::vector<std::pair<uint64_t, uint32_t>> ref;  // (start * 2 + strand, row) of REF's rows, sorted
+  for (uint64_t i = 0; i < n; ++i)
+    if (cols->hap_is_ref[cols->hap[i]]) ref.emplace_back((uint64_t)cols->start[i] * 2u + cols->strand[i], (uint32_t)i);
+  std::sort(ref.begin(), ref.end());
+  auto partner = [&](uint64_t i, const UrRow& row, uint64_t* refwin) {
+    if (!(row.flags & 1u) || cols->hap_is_ref[row.hap]) return false;
+    const uint64_t want = (uint64_t)cols->start[i] * 2u + row.strand;
+    auto it = std::lower_bound(ref.begin(), ref.end(), std::make_pair(want, (uint32_t)0));
+    if (it == ref.end() || it->first != want) return false;
+    const UrRow pr = ur_host_row(cols, it->second);
+    UrCounts pc;
+    if (ur_counts(pr, g, al, pr.win, false, &pc) != UR_DECL_NONE || pc.total == 0) return false;
+    for (int pl = 0; pl < 4; ++pl) refwin[pl] = pr.win[pl];
+    return true;
+  };
+  std::vector<uint32_t> res(n), kept(n);
+  uint64_t total = 0, total_res = 0;
+  const uint64_t bcap = batch_bytes / UR_OUT_BYTES;
+  for (uint64_t i = 0; i < n; ++i) {
+    const UrRow row = ur_host_row(cols, i);
+    uint64_t refwin[4] = {0, 0, 0, 0};
+    const bool has = partner(i, row, refwin);
+    UrCounts c;
+    int why = ur_counts(row, g, al, refwin, has, &c);
+    if (!why && cols->hap_is_ref[row.hap] && c.total > 1) why = UR_DECL_REF_AMBIG;
+    if (!why && c.total > UR_MAX_ROW) why = UR_DECL_ROW_SIZE;
+    if (why) return declined(why, (int64_t)i);
+    res[i] = (uint32_t)c.total; kept[i] = (uint32_t)(c.total - c.drop);
+    total += kept[i]; total_res += res[i];
+  }
+  if (batch_bytes)
+    for (uint64_t i = 0; i < n; ++i)
+      if (kept[i] > bcap) return declined(UR_DECL_BATCH, (int64_t)i);
+  *n_out = total;
+  if (n_resolved) *n_resolved = total_res;
+  if (row_resolved) std::copy(res.begin(), res.end(), row_resolved);
+  if (row_kept) std::copy(kept.begin(), kept.end(), row_kept);
+  if (!src_row && !win) return HAWK_OK;
+  if (out_cap < total) return HAWK_E_CAPACITY;
+  uint64_t o = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (!kept[i]) continue;
+    const UrRow row = ur_host_row(cols, i);
+    uint64_t refwin[4] = {0, 0, 0, 0}, w[UR_PLANES];
+    const bool has = partner(i, row, refwin);
+    for (uint32_t jk = 0; jk < kept[i]; ++jk, ++o) {
+      ur_unrank(row, g, al, refwin, has, res[i], res[i] - kept[i], jk, w);
+      if (has && ur_core_equal(w, refwin, g)) return HAWK_E_INVALID;  // the rule itself, on the words: a kept guide is never REF's core
+      if (src_row) src_row[o] = (uint32_t)i;
+      if (win)
+        for (int pl = 0; pl < UR_PLANES; ++pl) win[(uint64_t)pl * out_cap + o] = w[pl];
+    }
+  }
   return HAWK_OK;
 }
 

@@ -808,6 +808,83 @@ int hawk_host_effects(const hawk_effects_columns* cols, int family, const double
 /* round(x, 4) as Python computes it (csrc/hawk_effects.h: fx_round4), element by element */
 int hawk_host_round4(const double* x, uint64_t n, double* out);
 
+/* ---- unphased IUPAC windows resolved on the table: retrieve_guides' unphased branch and remove_redundant_guides
+ * (search_guides.py:163-257, 340-369, 463-480) on the rows in HBM.  The rules are stated once, in csrc/hawk_resolve.h, for the
+ * kernels (k_ur_count, k_ur_fill) and for hawk_host_resolve_unphased: a row's validity (is_pamhit_valid, strict on the right), the
+ * options of a window position (its set bases in A, C, G, T order, once per allele entry of (haplotype, position), upper case where
+ * the base is the entry's ref), the PAM re-check on the resolved PAM slice, itertools.product order (leftmost position slowest),
+ * and the redundancy rule: a combination of a non-REF row is dropped when a REF guide shares its (start, strand) and its upper-cased
+ * core (window offsets [10, W - 10)) is REF's.  W = guidelen + pamlen + 20 <= 64.
+ *
+ * The allele table: `key` = sorted (haplotype row << 32 | position in the haplotype) of every position with entries, `off` the CSR
+ * offsets of its entries, `ref` one byte per entry (the entry's ref base 0-3 for A C G T, 255 when its ref is not one base).
+ *
+ * hawk_table_resolve_unphased runs on a table whose set carries its metadata (hawk_hapset_set_meta), before hawk_table_download;
+ * the table stays as it is.  It uploads the allele table, lists REF's rows by (start, strand), counts (k_ur_count), scans and reads
+ * the offsets back: *n_kept says how much room the result needs.  hawk_resolve_download then runs the fill pass (k_ur_fill) in
+ * batches of whole rows of at most HAWK_RESOLVE_BATCH_BYTES (environment, read by hawk_table_resolve_unphased, default 256 MiB; 44
+ * bytes per kept guide) of device memory and copies every batch straight into what is not NULL of src_row[n_kept] and
+ * win[5][n_kept] (plane stride n_kept; host - page-locked for copies at link speed - or device); row_resolved / row_kept[n_rows]:
+ * per table row the combinations after the PAM re-check and after the redundancy rule.  Kept guides come in table-row order,
+ * inside a row in enumeration order.  The handle reads the set's row buffers: it must be downloaded before the next search on the
+ * set (HAWK_E_INVALID afterwards) and freed before the set is destroyed.  `timing`: the first call fills all but fill_ms and
+ * n_batches, the download returns the same with them (total_ms: both calls' device intervals).
+ *
+ * A call DECLINES - nothing is computed, *out stays NULL, `decline` (optional) names the reason and the first offending row - with
+ *   HAWK_E_UNSUPPORTED  HAWK_RESOLVE_NO_ENTRY   an ambiguous position without allele entries (the reference's KeyError)
+ *                       HAWK_RESOLVE_MULTI_REF  more than one haplotype flagged REF (row = -1)
+ *                       HAWK_RESOLVE_REF_AMBIG  a REF row with more than one combination
+ *   HAWK_E_CAPACITY     HAWK_RESOLVE_ROW_SIZE   a row of more than 2^32 - 1 combinations (counts are 64-bit and saturate)
+ *                       HAWK_RESOLVE_BATCH      a row whose kept guides do not fit the batch budget
+ * HAWK_E_INVALID: a stale or merged table, a malformed allele table (unsorted keys, offsets that do not ascend, a ref byte that is
+ * neither 0-3 nor 255).  hawk_host_resolve_unphased: the same from host arrays by the same header, single-threaded, no device;
+ * src_row[out_cap] and win[5][out_cap] (plane stride out_cap) are written when either is not NULL: HAWK_E_CAPACITY with
+ * decline->reason == 0 and the need in *n_out when out_cap is too small (the per-row counts are written); with both NULL the call
+ * only counts.  batch_bytes: the budget a row's kept guides must fit (0: none). */
+#define HAWK_RESOLVE_NO_ENTRY 1
+#define HAWK_RESOLVE_MULTI_REF 2
+#define HAWK_RESOLVE_REF_AMBIG 3
+#define HAWK_RESOLVE_ROW_SIZE 4
+#define HAWK_RESOLVE_BATCH 5
+typedef struct hawk_resolve hawk_resolve;
+typedef struct {
+  uint64_t n_keys;
+  const uint64_t* key;
+  const uint32_t* off;  /* [n_keys + 1] */
+  const uint8_t* ref;   /* [off[n_keys]] */
+} hawk_resolve_alleles;
+typedef struct {
+  uint64_t n_rows, win_stride;
+  const uint32_t* hap;
+  const uint32_t* pos;
+  const uint8_t* strand;
+  const int64_t* start;
+  const uint8_t* flags;
+  const uint64_t* win;        /* [5][win_stride] */
+  const uint32_t* hap_len;    /* [n_hap] */
+  const uint8_t* hap_is_ref;  /* [n_hap] */
+  uint64_t pam_fwd, pam_rev;
+  uint32_t n_hap, guidelen, pamlen, right;
+} hawk_resolve_columns;
+typedef struct {
+  int32_t reason;  /* HAWK_RESOLVE_*, 0: none */
+  int32_t reserved;
+  int64_t row;     /* table row, -1: none */
+} hawk_resolve_decline;
+typedef struct {
+  float upload_ms, refsort_ms, count_ms, scan_ms, fill_ms, total_ms; /* HIP events; fill_ms: kernels and copies of all batches (hawk_resolve_download) */
+  uint32_t n_batches, reserved;
+  uint64_t n_rows, n_resolved, n_kept;
+} hawk_resolve_timing;
+int hawk_table_resolve_unphased(hawk_table* t, const hawk_resolve_alleles* alleles, uint64_t pam_fwd, uint64_t pam_rev, hawk_resolve** out,
+                                uint64_t* n_kept, uint64_t* n_resolved, hawk_resolve_decline* decline, hawk_resolve_timing* timing);
+int hawk_resolve_download(hawk_resolve* r, uint32_t* src_row, uint64_t* win, uint32_t* row_resolved, uint32_t* row_kept,
+                          hawk_resolve_timing* timing);
+void hawk_resolve_free(hawk_resolve* r);
+int hawk_host_resolve_unphased(const hawk_resolve_columns* cols, const hawk_resolve_alleles* alleles, uint64_t batch_bytes,
+                               uint32_t* row_resolved, uint32_t* row_kept, uint32_t* src_row, uint64_t* win, uint64_t out_cap,
+                               uint64_t* n_out, uint64_t* n_resolved, hawk_resolve_decline* decline);
+
 /* ---- PLM-CRISPR (scores/plm_crispr/train_general.py, class sgrna_net, forward with train=False; wrapper
  * scores/plm_crispr/plm_crispr.py:136-258): n guide+PAM 23-mers -> n fp32 scores, all arithmetic in fp32 (lin1 and lin3 on the
  * f32-input MFMA).  The 83 MB of parameters and the protein branch's result live in HBM behind a handle.
