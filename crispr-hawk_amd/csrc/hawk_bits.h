@@ -43,6 +43,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v), WAVE - 1);
 }
+// the same for 64-bit values, exact modulo 2^64: three limbs of 22 / 22 / 20 bits, so that no limb's sum over 64 lanes leaves 32
+// bits (64 x 2^22 = 2^28) and no carry is lost.  (Summing the two 32-bit halves with wave_sum drops the carries out of the low
+// half as soon as the low halves add up to 2^32.)
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+  const unsigned long long s0 = wave_sum((uint32_t)v & 0x3fffffu), s1 = wave_sum((uint32_t)(v >> 22) & 0x3fffffu),
+                           s2 = wave_sum((uint32_t)(v >> 44));
+  return s0 + (s1 << 22) + (s2 << 44);
+}
 // exclusive scan over a workgroup of NW wavefronts; *total gets the workgroup sum.
 // s_w: NW words of LDS.  Contains two barriers: every thread of the workgroup must call it.
 template <int NW>

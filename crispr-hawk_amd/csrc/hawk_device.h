@@ -336,6 +336,8 @@ void hawk_launch_gt_fill(hipStream_t st, uint32_t n_cols, const int32_t* var_r0,
                          const unsigned long long* ballots, const uint64_t* col_off, uint32_t* hv_idx, int32_t* hv_o, int64_t* col_delta,
                          const uint64_t* indel_off, uint32_t* indel_entry);
 #define HAWK_LIST_CAP 512  // entries per tile in the count pass -> emit pass hand-over list (hawk_search.hip LIST_CAP)
+enum { HAWK_MSCAN_ONE = 0, HAWK_MSCAN_M1_M23 = 1, HAWK_MSCAN_WIDE = 2, HAWK_MSCAN_M1_M2_M3 = 3 };  // k_mscan_one / k_mscan1 + k_mscan23 / k_mscan1w + k_mscan23w / k_mscan1, 2, 3
+int hawk_mscan_route(uint64_t n, bool shards, bool aligned);
 void hawk_launch_mscan(hipStream_t st, const uint32_t* counts, uint64_t n, unsigned long long* partial,
                        const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals);
 void hawk_launch_cfd(hipStream_t st, const char* wt, const char* sg, uint32_t len, const char* pam2, uint64_t n,

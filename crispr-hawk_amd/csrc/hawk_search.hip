@@ -613,6 +613,9 @@ void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const Sca
 // ---------------------------------------------------------------------------------------
 // multi-workgroup exclusive scan of u32 counts -> u64 offsets (3 small launches)
 // ---------------------------------------------------------------------------------------
+// Domain: offsets, partials and totals are 64-bit and exact (the wave reductions are wave_sum64); what stays 32-bit is the scan
+// INSIDE one workgroup tile (block_excl_scan), so a tile's counts must add up to less than 2^32: counts <= 2^22 on the routes of
+// 1024 entries per workgroup, <= 2^20 on the wide one (4096).  The product's counts are <= 65 536 (a tile's rows).
 #define MS_TILE 1024  // entries per workgroup (4 per thread)
 
 __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1(const uint32_t* __restrict__ counts, uint64_t n,
@@ -624,7 +627,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1(const uint32_t* __restric
   unsigned long long s = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) if (i0 + k < n) s += counts[i0 + k];
-  s = (unsigned long long)wave_sum((uint32_t)s) + ((unsigned long long)wave_sum((uint32_t)(s >> 32)) << 32);
+  s = wave_sum64(s);
   if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&s_sum, s);
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = s_sum;
@@ -697,7 +700,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan23(const uint32_t* __restri
   __syncthreads();
   unsigned long long pre = 0;
   for (uint32_t j = threadIdx.x; j < blockIdx.x; j += HAWK_BLOCK) pre += partial[j];
-  pre = (unsigned long long)wave_sum((uint32_t)pre) + ((unsigned long long)wave_sum((uint32_t)(pre >> 32)) << 32);
+  pre = wave_sum64(pre);
   if ((threadIdx.x & (WAVE - 1)) == 0 && pre) atomicAdd(&s_sum[0], pre);
   if (blockIdx.x == 0 && shards) {  // 256 (candidates, hits) partial sums of the count pass
     atomicAdd(&s_sum[1], shards[2 * threadIdx.x]);
@@ -767,7 +770,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1w(const uint32_t* __restri
   } else {
     for (int k = 0; k < MSW_IPT; ++k) if (i0 + k < n) s += counts[i0 + k];
   }
-  s = (unsigned long long)wave_sum((uint32_t)s) + ((unsigned long long)wave_sum((uint32_t)(s >> 32)) << 32);
+  s = wave_sum64(s);
   if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&s_sum, s);
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = s_sum;
@@ -781,7 +784,7 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan23w(const uint32_t* __restr
   __syncthreads();
   unsigned long long pre = 0;
   for (uint32_t j = threadIdx.x; j < blockIdx.x; j += HAWK_BLOCK) pre += partial[j];
-  pre = (unsigned long long)wave_sum((uint32_t)pre) + ((unsigned long long)wave_sum((uint32_t)(pre >> 32)) << 32);
+  pre = wave_sum64(pre);
   if ((threadIdx.x & (WAVE - 1)) == 0 && pre) atomicAdd(&s_sum[0], pre);
   if (blockIdx.x == 0 && shards) {
     atomicAdd(&s_sum[1], shards[2 * threadIdx.x]);
@@ -825,25 +828,41 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan23w(const uint32_t* __restr
   }
 }
 
+// Which kernels scan n counts: the one place that knows the thresholds (hawk_launch_mscan switches on it, the tests ask it).
+// aligned: counts AND offsets are 16-byte aligned - the wide pair loads four counts and stores two offsets at a time.
+int hawk_mscan_route(uint64_t n, bool shards, bool aligned) {
+  if (n <= 2048 && shards) return HAWK_MSCAN_ONE;
+  const uint64_t nb = (n + MS_TILE - 1) / MS_TILE, nbw = (n + MSW_TILE - 1) / MSW_TILE;
+  if (nb > 4096 && nbw <= 4096 && shards && aligned) return HAWK_MSCAN_WIDE;
+  return nb <= 4096 && shards ? HAWK_MSCAN_M1_M23 : HAWK_MSCAN_M1_M2_M3;
+}
+
+// n >= 1.  Every caller has at least one count: the plane search, the raw PAM scan and the off-target site scan pass their set's
+// tiles (hawk_hapset_create refuses a set without rows, and a row has at least one tile), the cluster search adds its instance
+// groups to those, and the collapse by templates calls only when there are distinct clusters.  With n == 0 and no shard sums the
+// grids below would have 0 workgroups, which is not a launch.
 void hawk_launch_mscan(hipStream_t st, const uint32_t* counts, uint64_t n, unsigned long long* partial,
                        const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals) {
-  if (n <= 2048 && shards) {
-    const uint32_t ipt = (uint32_t)((n + 1023) / 1024);
-    hipLaunchKernelGGL(k_mscan_one, dim3(1), dim3(1024), 0, st, counts, (uint32_t)n, ipt ? ipt : 1u, shards, offsets, totals);
-    return;
-  }
+  const bool aligned = (reinterpret_cast<uintptr_t>(counts) & 15) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 15) == 0;
   const uint32_t nb = (uint32_t)((n + MS_TILE - 1) / MS_TILE);
   const uint32_t nbw = (uint32_t)((n + MSW_TILE - 1) / MSW_TILE);
-  if (nb > 4096 && nbw <= 4096 && shards && (reinterpret_cast<uintptr_t>(counts) & 15) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 15) == 0) {
-    hipLaunchKernelGGL(k_mscan1w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
-    hipLaunchKernelGGL(k_mscan23w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nbw, shards, offsets, totals);
-    return;
+  switch (hawk_mscan_route(n, shards != nullptr, aligned)) {
+    case HAWK_MSCAN_ONE: {
+      const uint32_t ipt = (uint32_t)((n + 1023) / 1024);
+      hipLaunchKernelGGL(k_mscan_one, dim3(1), dim3(1024), 0, st, counts, (uint32_t)n, ipt ? ipt : 1u, shards, offsets, totals);
+      return;
+    }
+    case HAWK_MSCAN_WIDE:
+      hipLaunchKernelGGL(k_mscan1w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan23w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nbw, shards, offsets, totals);
+      return;
+    case HAWK_MSCAN_M1_M23:
+      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan23, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nb, shards, offsets, totals);
+      return;
+    default:  // HAWK_MSCAN_M1_M2_M3
+      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan2, dim3(1), dim3(1024), 0, st, partial, (uint64_t)nb, shards, totals);
+      hipLaunchKernelGGL(k_mscan3, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, offsets);
   }
-  hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
-  if (nb <= 4096 && shards) {
-    hipLaunchKernelGGL(k_mscan23, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nb, shards, offsets, totals);
-    return;
-  }
-  hipLaunchKernelGGL(k_mscan2, dim3(1), dim3(1024), 0, st, partial, (uint64_t)nb, shards, totals);
-  hipLaunchKernelGGL(k_mscan3, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, offsets);
 }

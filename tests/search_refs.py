@@ -22,6 +22,7 @@ BLOCK = 256         # HAWK_BLOCK: survivors one pass of phase C takes
 NSEG = 64           # position-map segments staged per tile
 TAIL = 64           # tile_end = tile + TILE + TAIL
 MS_TILE = 1024      # counts per workgroup of k_mscan1 / k_mscan23 / k_mscan3
+MSW_TILE = 4096     # ... of the wide pair k_mscan1w / k_mscan23w (16 per thread)
 PAD = 10            # GUIDESEQPAD
 STARTP = 100_001    # genomic position of REF's first base
 
@@ -42,13 +43,33 @@ def segment_starts(pm) -> np.ndarray:
     return np.concatenate(([0], np.flatnonzero(np.diff(pm) != 1) + 1)).astype(np.int64)
 
 
-def scan_kernel(n: int, shards: bool = True) -> str:
-    """hawk_launch_mscan's choice for n counts (the wide pair needs more than 4096 partials: not reachable at test size)"""
+def scan_route(n: int, shards: bool = True, aligned: bool = True) -> dict:
+    """hawk_mscan_route restated, with the figures the kernels of the route derive from n: route (ONE / M1_M23 / WIDE / M1_M2_M3),
+    tile (counts per workgroup), partials (workgroups), chunks (trips of k_mscan2's loop over 1024 partials), last_chunk (partials
+    in its last trip), trips (of the prefix loop of k_mscan23 / k_mscan23w in the last workgroup), tail (counts in the last
+    workgroup).  aligned: counts and offsets both on a 16-byte boundary."""
+    assert n >= 1
     if n <= 2048 and shards:
-        return f"k_mscan_one ipt={max(1, (n + 1023) // 1024)}"
-    nb = (n + MS_TILE - 1) // MS_TILE
-    assert nb <= 4096
-    return f"k_mscan1+k_mscan23 {nb} partials" if shards else f"k_mscan1/2/3 {nb} partials"
+        return dict(route="ONE", tile=0, partials=0, chunks=0, last_chunk=0, trips=0, tail=n, ipt=max(1, (n + 1023) // 1024))
+    nb, nbw = (n + MS_TILE - 1) // MS_TILE, (n + MSW_TILE - 1) // MSW_TILE
+    if nb > 4096 and nbw <= 4096 and shards and aligned:
+        return dict(route="WIDE", tile=MSW_TILE, partials=nbw, chunks=0, last_chunk=0, trips=(nbw - 1 + BLOCK - 1) // BLOCK,
+                    tail=n - (nbw - 1) * MSW_TILE)
+    if nb <= 4096 and shards:
+        return dict(route="M1_M23", tile=MS_TILE, partials=nb, chunks=0, last_chunk=0, trips=(nb - 1 + BLOCK - 1) // BLOCK,
+                    tail=n - (nb - 1) * MS_TILE)
+    chunks = (nb + 1023) // 1024
+    return dict(route="M1_M2_M3", tile=MS_TILE, partials=nb, chunks=chunks, last_chunk=nb - (chunks - 1) * 1024, trips=0,
+                tail=n - (nb - 1) * MS_TILE)
+
+
+def scan_kernel(n: int, shards: bool = True, aligned: bool = True) -> str:
+    """hawk_launch_mscan's choice for n counts, in words"""
+    r = scan_route(n, shards, aligned)
+    if r["route"] == "ONE":
+        return f"k_mscan_one ipt={r['ipt']}"
+    name = {"M1_M23": "k_mscan1+k_mscan23", "WIDE": "k_mscan1w+k_mscan23w", "M1_M2_M3": "k_mscan1/2/3"}[r["route"]]
+    return f"{name} {r['partials']} partials"
 
 
 def emit_path(valid: int, is_ref: bool, survivors: int) -> str:

@@ -97,3 +97,30 @@ def test_the_oracle_refuses_a_scan_range_that_reads_past_the_row(filler):
         with pytest.raises(ora.OracleError) as e:
             ora.search(ora.HapSet([prev, row], [pm0, pm], [True, False], [(0, 198), (0, stop)]), "NGG", 20, False)
         assert e.value.code == -8
+
+
+def test_the_scan_routes_change_where_the_launcher_says():
+    """hawk_mscan_route (hawk_search.hip) restated by sr.scan_route: both sides of every threshold, for every combination of shard
+    sums and alignment."""
+    route = lambda n, shards=True, aligned=True: sr.scan_route(n, shards, aligned)["route"]
+    # one workgroup up to 2048 counts, with shard sums only
+    assert [route(n) for n in (1, 2048, 2049)] == ["ONE", "ONE", "M1_M23"]
+    assert [route(n, shards=False) for n in (1, 2048, 2049)] == ["M1_M2_M3"] * 3
+    assert route(2048, aligned=False) == "ONE"
+    # the fused second kernel up to 4096 partials of 1024, whatever the alignment
+    assert [route(n) for n in (4096 * 1024, 4096 * 1024 + 1)] == ["M1_M23", "WIDE"]
+    assert [route(n, aligned=False) for n in (4096 * 1024, 4096 * 1024 + 1)] == ["M1_M23", "M1_M2_M3"]
+    # the wide pair up to 4096 partials of 4096, aligned and with shard sums only
+    assert [route(n) for n in (4096 * 4096, 4096 * 4096 + 1)] == ["WIDE", "M1_M2_M3"]
+    assert all(route(n, shards=False, aligned=a) == "M1_M2_M3" for n in (4096 * 1024, 4096 * 1024 + 1, 4096 * 4096) for a in (True, False))
+    # the figures behind the route
+    assert sr.scan_route(262_144)["partials"] == 256 and sr.scan_route(262_144)["trips"] == 1 and sr.scan_route(262_145)["trips"] == 1
+    assert sr.scan_route(262_145)["partials"] == 257 and sr.scan_route(263_169)["trips"] == 2 and sr.scan_route(4096 * 1024)["trips"] == 16
+    w = sr.scan_route(4_194_305)
+    assert (w["partials"], w["tail"], w["trips"]) == (1025, 1, 4) and sr.scan_route(4096 * 4096)["partials"] == 4096
+    u = sr.scan_route(4_194_305, aligned=False)
+    assert (u["partials"], u["chunks"], u["last_chunk"], u["tail"]) == (4097, 5, 1, 1)
+    m = sr.scan_route(1_048_577, shards=False)
+    assert (m["partials"], m["chunks"], m["last_chunk"]) == (1025, 2, 1) and sr.scan_route(1_048_576, shards=False)["chunks"] == 1
+    assert sr.scan_kernel(4_194_305) == "k_mscan1w+k_mscan23w 1025 partials"
+    assert sr.scan_kernel(4_194_305, aligned=False) == "k_mscan1/2/3 4097 partials"
