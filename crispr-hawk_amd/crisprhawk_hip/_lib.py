@@ -22,6 +22,7 @@ HAWK_E_UNSUPPORTED = -7
 HAWK_E_COMM = -8
 HAWK_E_OVERLAP = -9
 HAWK_E_CLAMP = -10
+HAWK_E_OOM = -11
 
 EXPORTS = [
     "hawk_device_count", "hawk_init", "hawk_destroy", "hawk_strerror", "hawk_last_hip_error", "hawk_stream",
@@ -42,6 +43,7 @@ EXPORTS = [
     "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
     "hawk_host_effects", "hawk_host_round4",
     "hawk_table_resolve_unphased", "hawk_resolve_download", "hawk_resolve_free", "hawk_host_resolve_unphased",
+    "hawk_resolve_groups", "hawk_ugroups_download", "hawk_ugroups_free", "hawk_host_unphased_groups",
     "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
 ]
 
@@ -146,6 +148,12 @@ class ResolveTiming(C.Structure):
                 ("n_kept", C.c_uint64)]
 
 
+class UgroupsTiming(C.Structure):
+    _fields_ = [("fill_ms", C.c_float), ("keys_ms", C.c_float), ("sort_ms", C.c_float), ("heads_ms", C.c_float), ("emit_ms", C.c_float),
+                ("total_ms", C.c_float), ("n_batches", C.c_uint32), ("reserved", C.c_uint32), ("n_kept", C.c_uint64), ("n_groups", C.c_uint64),
+                ("n_members", C.c_uint64)]
+
+
 RESOLVE_REASONS = {1: "an ambiguous position without allele entries", 2: "more than one haplotype flagged REF",
                    3: "a REF row with more than one combination", 4: "a row of more than 2^32 - 1 combinations",
                    5: "a row whose kept guides do not fit the batch budget"}
@@ -195,6 +203,7 @@ def lib() -> C.CDLL:
         L.hawk_gnomad_destroy.restype = None
         L.hawk_effects_free.restype = None
         L.hawk_resolve_free.restype = None
+        L.hawk_ugroups_free.restype = None
         L.hawk_plm_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:

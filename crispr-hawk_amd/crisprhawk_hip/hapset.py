@@ -422,6 +422,75 @@ def resolve_columns_host(hap, pos, strand, start, flags, win, hap_len, is_ref, a
     return src, w
 
 
+class UnphasedGroups:
+    """Report groups of an unphased table (hawk_resolve_groups / hawk_host_unphased_groups): one representative kept guide per
+    group as columns + CSR member haplotypes (each haplotype once, ascending; the first is the representative's) - the fields
+    reports.ReportGroups has, plus `rep_src_row` (the table row of the representative), `hap`, `is_ref` (the group's origin),
+    `timing` (hawk_ugroups_timing; empty on the host engine) and `resolve_timing`.  Groups ascend by (start, strand, origin, stop,
+    core planes): csrc/hawk_ugroups.h."""
+
+    def __init__(self, guidelen: int, pamlen: int, right: bool, n_groups: int, n_members: int, device: Optional[int] = None):
+        self.guidelen, self.pamlen, self.right, self.n_groups, self.n_members = guidelen, pamlen, bool(right), n_groups, n_members
+        ng = n_groups
+
+        def pe(n, dt):  # page-locked from 1 MB on, as GroupTable
+            return _lib.pinned_empty(n, dt, device)
+        self.rep_src_row = pe(ng, np.uint32); self.hap = pe(ng, np.uint32); self.pos = pe(ng, np.uint32); self.strand = pe(ng, np.uint8)
+        self.start = pe(ng, np.int64); self.stop = pe(ng, np.int64); self.is_ref = pe(ng, np.uint8); self.cfdon = pe(ng, np.float64)
+        self.win = pe(5 * ng, np.uint64).reshape(5, ng)
+        self.gc_num = pe(ng, np.uint8); self.gc_den = pe(ng, np.uint8)
+        self.member_off = pe(ng + 1, np.uint64); self.member_hap = pe(n_members, np.uint32)
+        self.member_off[-1:] = 0
+        self.timing, self.resolve_timing, self.engine, self.n_kept = {}, {}, "device", 0
+
+    @property
+    def window_len(self) -> int:
+        return self.guidelen + self.pamlen + 2 * GUIDESEQPAD
+
+    def windows(self, rows: Optional[np.ndarray] = None) -> List[str]:
+        return decode_windows(self.win if rows is None else self.win[:, rows], self.window_len)
+
+    def _args(self):
+        return (_p(self.rep_src_row), _p(self.hap), _p(self.pos), _p(self.strand), _p(self.start), _p(self.stop), _p(self.is_ref),
+                _p(self.cfdon), _p(self.win), _p(self.gc_num), _p(self.gc_den), _p(self.member_off), _p(self.member_hap))
+
+
+def _cfd_arrays(cfd_tables):
+    if cfd_tables is None:
+        return None, None
+    return (np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(320), np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16))
+
+
+def unphased_groups_host(hap, pos, strand, start, stop, flags, win, hap_len, is_ref, src_row, kwin, pam_bits: int, pam_bitsrc: int,
+                         guidelen: int, pamlen: int, right: bool, cfd_tables=None, flank: Tuple[int, int] = (0, 0)) -> "UnphasedGroups":
+    """hawk_host_unphased_groups on host columns (the table's rows + the kept guides `src_row`, `kwin[5, n_kept]` of
+    resolve_columns_host) -> UnphasedGroups.  No device."""
+    L = _lib.lib()
+    cols = _lib.ResolveColumns()
+    keep = [np.ascontiguousarray(hap, np.uint32), np.ascontiguousarray(pos, np.uint32), np.ascontiguousarray(strand, np.uint8),
+            np.ascontiguousarray(start, np.int64), np.ascontiguousarray(flags, np.uint8), np.ascontiguousarray(win, np.uint64).reshape(5, -1),
+            np.ascontiguousarray(hap_len, np.uint32), np.ascontiguousarray(is_ref, np.uint8)]
+    cols.n_rows, cols.win_stride = len(keep[0]), keep[5].shape[1]
+    cols.hap, cols.pos, cols.strand, cols.start, cols.flags, cols.win, cols.hap_len, cols.hap_is_ref = (a.ctypes.data for a in keep)
+    cols.pam_fwd, cols.pam_rev, cols.n_hap, cols.guidelen, cols.pamlen, cols.right = pam_bits, pam_bitsrc, len(keep[6]), guidelen, pamlen, int(bool(right))
+    stop = np.ascontiguousarray(stop, np.int64)
+    src = np.ascontiguousarray(src_row, np.uint32)
+    kw = np.ascontiguousarray(kwin, np.uint64).reshape(5, -1)
+    mm, pt = _cfd_arrays(cfd_tables)
+    ng, nm = C.c_uint64(), C.c_uint64()
+
+    def call(g, gcap, mcap):
+        outs = g._args() if g is not None else (None,) * 13
+        _lib.check(L.hawk_host_unphased_groups(C.byref(cols), _p(stop), _p(src), _p(kw), C.c_uint64(len(src)), C.c_uint64(kw.shape[1]), _p(mm), _p(pt),
+                                               C.c_uint32(int(flank[0])), C.c_uint32(int(flank[1])), C.c_uint64(gcap), C.c_uint64(mcap), *outs,
+                                               C.byref(ng), C.byref(nm)), "hawk_host_unphased_groups")
+    call(None, 0, 0)  # the counts: how large the outputs are
+    g = UnphasedGroups(guidelen, pamlen, right, ng.value, nm.value)
+    call(g, ng.value, nm.value)
+    g.engine, g.n_kept = "host", len(src)
+    return g
+
+
 class GuideTable:
     """Columnar guide table of one fused search (rows in (haplotype, tile, strand, position) order)."""
 
@@ -557,6 +626,60 @@ class GuideTable:
                                                         self.guidelen, self.pamlen, self.right, out.n_resolved, out.n_kept)
             out.timing = {}
         return out
+
+    def resolve_unphased_groups(self, haplotypes, pam, cfd_tables=None, flank: Tuple[int, int] = (0, 0), engine: str = "device") -> "UnphasedGroups":
+        """The report groups of the rows' resolved IUPAC windows (resolve_unphased, then what reports.report_from_guides and
+        scoring.cfdon_score do with the guides) without a Guide object: the kept guides stay in HBM, are keyed as the report
+        merges them - `flank` = (4, 3) keeps guides apart that differ in the bases the model scorers read - scored with CFDon
+        against the REF guide at the same (start, strand) when `cfd_tables = (mm, pam)` is given (NaN otherwise and without a
+        partner), and come back as one representative per group + CSR member haplotypes (`engine="device"`:
+        hawk_table_resolve_unphased + hawk_resolve_groups; `"host"`: the twins on the downloaded columns).  Call it before
+        download().  Raises _lib.HawkResolveDeclined where the resolution declines, _lib.HawkStatusError on any other status."""
+        if self._t is None:
+            raise RuntimeError("resolve_unphased_groups() needs the device-resident table: call it before download()")
+        if engine not in ("device", "host"):
+            raise ValueError(f"engine {engine!r}: 'device' or 'host'")
+        if isinstance(haplotypes, tuple):
+            key, off, ref = haplotypes
+        else:
+            from .search_guides import flatten_variant_alleles
+            key, off, ref = flatten_variant_alleles(haplotypes)
+        key = np.ascontiguousarray(key, np.uint64); off = np.ascontiguousarray(off, np.uint32); ref = np.ascontiguousarray(ref, np.uint8)
+        bits, bitsrc = pam if isinstance(pam, tuple) else (pam.bits, pam.bitsrc)
+        L, n = self._hs._L, self.n_rows
+        if engine == "host":
+            hap = np.empty(n, np.uint32); pos = np.empty(n, np.uint32); strand = np.empty(n, np.uint8); start = np.empty(n, np.int64)
+            stop = np.empty(n, np.int64); flags = np.empty(n, np.uint8); win = np.empty((5, n), np.uint64)
+            _lib.check(L.hawk_table_download(self._t, _p(hap), _p(pos), _p(strand), _p(start), _p(stop), _p(flags), None, _p(win)), "hawk_table_download")
+            hap_len = np.ascontiguousarray(self._hs.hap_len, np.uint32); is_ref = np.ascontiguousarray(self._hs.is_ref, np.uint8)
+            src, kw = resolve_columns_host(hap, pos, strand, start, flags, win, hap_len, is_ref, (key, off, ref), bits, bitsrc, self.guidelen,
+                                           self.pamlen, self.right)
+            return unphased_groups_host(hap, pos, strand, start, stop, flags, win, hap_len, is_ref, src, kw, bits, bitsrc, self.guidelen,
+                                        self.pamlen, self.right, cfd_tables, flank)
+        al = _lib.ResolveAlleles(len(key), key.ctypes.data, off.ctypes.data, ref.ctypes.data if len(ref) else None)
+        dec, nk, nr = _lib.ResolveDecline(), C.c_uint64(), C.c_uint64()
+        h, rtm = C.c_void_p(), _lib.ResolveTiming()
+        rc = L.hawk_table_resolve_unphased(self._t, C.byref(al), C.c_uint64(bits), C.c_uint64(bitsrc), C.byref(h), C.byref(nk), C.byref(nr),
+                                           C.byref(dec), C.byref(rtm))
+        if rc != _lib.HAWK_OK and dec.reason:
+            raise _lib.HawkResolveDeclined(rc, "hawk_table_resolve_unphased", dec.reason, dec.row)
+        _lib.check(rc, "hawk_table_resolve_unphased")
+        mm, pt = _cfd_arrays(cfd_tables)
+        gh, ng, nm, tm = C.c_void_p(), C.c_uint64(), C.c_uint64(), _lib.UgroupsTiming()
+        try:
+            _lib.check(L.hawk_resolve_groups(h, _p(mm), _p(pt), C.c_uint32(int(flank[0])), C.c_uint32(int(flank[1])), C.byref(gh), C.byref(ng),
+                                             C.byref(nm), C.byref(tm)), "hawk_resolve_groups")
+        finally:
+            L.hawk_resolve_free(h)
+        try:
+            g = UnphasedGroups(self.guidelen, self.pamlen, self.right, ng.value, nm.value, getattr(self._hs, "device", None))
+            _lib.check(L.hawk_ugroups_download(gh, *g._args()), "hawk_ugroups_download")
+        finally:
+            L.hawk_ugroups_free(gh)
+        g.n_kept = nk.value
+        g.timing = {k: getattr(tm, k) for k, _ in tm._fields_ if k != "reserved"}
+        g.resolve_timing = {k: getattr(rtm, k) for k, _ in rtm._fields_ if k != "reserved"}
+        return g
 
     def download(self) -> "GuideTable":
         if self._downloaded:

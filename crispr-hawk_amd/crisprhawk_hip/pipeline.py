@@ -21,6 +21,7 @@ from . import reports
 from . import scoring
 from .pam import CPF1, PAM, SPCAS9, XCAS9
 from .readers import VCF, Bed, Fasta
+from .utils import VERBOSITYLVL, print_verbosity
 from .expand import HaplotypeBuildError
 from .workload import HapInfo, RowLabel, expand_from_vcf, hap_labels
 
@@ -118,13 +119,33 @@ def _plan_row_variants(info, vt) -> List[bytes]:
     return out
 
 
+UNPHASED_REPORTS = (None, "groups", "objects")
+
+
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
-                       ot=None, ann=None, lap=None, tables=None, unphased_engine=None) -> str:
+                       ot=None, ann=None, lap=None, tables=None, unphased_engine=None, unphased_report=None, azimuth_model=None,
+                       deepcpf1_weights=None, plm_on=False) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows; their
     windows resolved on the device table, search_guides.search's `unphased_engine`) and the fallback for phased records the device expansion
     declines (a chromosome copy carrying overlapping records, multi-base deletion alts).  The search itself still runs
-    on the device; then the reference's order of business: annotate -> reverse_guides -> CFDon -> report."""
+    on the device.
+
+    An unphased interval with records then takes `unphased_report` (None: HAWK_UNPHASED_REPORT, else "groups"):
+      "groups"   the kept guides stay in HBM and become report groups there (GuideTable.resolve_unphased_groups: CFDon against
+                 the REF guide, the report's key - widened to the scorers' k-mer when Azimuth or DeepCpf1 is on - one
+                 representative and the member haplotypes per group); from the groups on it is the phased route's own code
+                 (_group_report_columns: model scorers on the representatives, the annotation join, the off-target callback,
+                 reports.group_columns, write_report_tsv).  No Guide object is built, and the report carries the model scores the
+                 caller switched on.  Falls back to "objects" - with a line at verbosity level 3 that carries the status - when the
+                 resolution declines, when any status other than a HIP failure comes back, or when `unphased_engine` (or
+                 HAWK_UNPHASED_ENGINE) asks for the host.
+      "objects"  the reference's order of business on Guide objects: annotate -> reverse_guides -> CFDon -> report
+                 (reports.report_from_guides; the model-score columns say NA).  The phased fallback always takes it.
+    Either way there is no collapsed table in HBM for the variant-effect stage: `graphical_reports` / `candidate_guides` on such
+    an interval stay a ValueError (_search_intervals)."""
+    if unphased_report not in UNPHASED_REPORTS:
+        raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
     from . import haplotypes as hap_mod
     from .annotation import reverse_guides
     from .haplotype import Haplotype
@@ -143,6 +164,18 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, [h.id for h in haps],
                                                       [h.variants for h in haps], [h.samples for h in haps],
                                                       sequences=[h.sequence.sequence for h in haps])
+    if records and not phased:
+        mode = unphased_report or os.environ.get("HAWK_UNPHASED_REPORT") or "groups"
+        if mode not in ("groups", "objects"):
+            raise ValueError(f"HAWK_UNPHASED_REPORT={mode!r}: 'groups' or 'objects'")
+        engine = unphased_engine or os.environ.get("HAWK_UNPHASED_ENGINE") or "device"
+        if mode == "groups" and engine == "host":
+            print_verbosity("Unphased report from Guide objects: the host engine was asked for", 0, VERBOSITYLVL[3])
+        elif mode == "groups":
+            path = _unphased_groups_report(coord, region, haps, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, azimuth_model,
+                                           deepcpf1_weights, plm_on)
+            if path is not None:
+                return path
     guides = search(pam, region, haps, None, guidelen, right, bool(records), phased, 0, debug, unphased_engine=unphased_engine)
     cfd = None
     if mm is not None:
@@ -170,14 +203,81 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
     return path
 
 
+def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool, ot, ann, lap,
+                            azimuth_model, deepcpf1_weights, plm_on) -> Optional[str]:
+    """_search_host_built's "groups" route from the built haplotypes to the report file; None: the device declined or refused
+    and the caller takes the object route."""
+    from ._lib import HawkStatusError
+    from .search_guides import _device_set
+    lap = lap or (lambda stage: None)
+    lap("host-built route: unphased haplotypes built on the host")
+    ds = _device_set(region, haps, len(pam))
+    try:
+        tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right, download=False)
+        azimuth_on = pam.cas_system in (SPCAS9, XCAS9) and azimuth_model is not None
+        deepcpf1_on = pam.cas_system == CPF1 and deepcpf1_weights is not None
+        try:
+            groups = tab.resolve_unphased_groups(haps, pam, (mm, pt) if mm is not None else None,
+                                                 (4, 3) if (azimuth_on or deepcpf1_on) else (0, 0), "device")
+        except HawkStatusError as e:  # a decline (HawkResolveDeclined) or a refusal; a HIP failure is a HawkDeviceError and is raised
+            print_verbosity(f"Unphased report from Guide objects: {e}", 0, VERBOSITYLVL[3])
+            return None
+        finally:
+            tab.close()
+        is_ref_hap = np.asarray(ds.is_ref, dtype=bool)
+    finally:
+        ds.close()
+    lap("host-built route: planes, search, resolution and report groups on the device")
+    bed_start, bed_stop = coord.start + PADDING, coord.stop - PADDING
+    cols, order, plain, _ = _group_report_columns(coord, groups, reports.HapLabels.from_objects(haps), is_ref_hap, pam, guidelen, right, outdir,
+                                                  mm is not None, debug, ot, ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
+    return _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_start, bed_stop, lap)
+
+
+def _group_report_columns(coord, groups, labels, is_ref_hap, pam, guidelen, right, outdir, score, debug, ot, ann, azimuth_on, deepcpf1_on, plm_on,
+                          bed_start, bed_stop, lap):
+    """Report groups (hapset.GroupTable of a collapsed table, hapset.UnphasedGroups) -> the report as columns: model scorers on the
+    representatives, the annotation join, the off-target callback, reports.group_columns.  -> (cols, order, plain, scores)"""
+    # model-based scorers run once per report row, on the group representatives (scoring.py:749-813), when the
+    # caller has supplied their parameters
+    scores = {}
+    if groups.n_groups and (azimuth_on or deepcpf1_on or plm_on):
+        kmers = reports.group_kmers(groups)
+        if azimuth_on:
+            scores["score_azimuth"] = np.asarray(scoring.azimuth(kmers, debug), dtype=np.float64)
+        if deepcpf1_on:
+            scores["score_deepcpf1"] = np.asarray(scoring.deepcpf1(kmers, debug), dtype=np.float64)
+        if plm_on:  # guide + PAM of the 4 + 23 + 3 k-mer (left-PAM systems only reach here)
+            scores["score_plmcrispr"] = np.asarray(scoring.plmcrispr([k[4:27] for k in kmers], pam.cas_system, debug), dtype=np.float64)
+    anncols = None
+    if ann:  # one join per file over the groups' (start, stop), while the table is closed and before the report's own threads start
+        anncols = ann.columns(coord.contig)(np.asarray(groups.start, dtype=np.int64), np.asarray(groups.stop, dtype=np.int64))
+        lap(ANN_STAGE)
+    otcb = None if ot is None else (lambda spacers: _offtargets(spacers, pam, ot, coord, guidelen, right, outdir, debug))
+    # the report as columns (no Python string per row: the carriers' columns of a 2504-sample panel are 0.6 GB of text), written
+    # by the library's TSV writer
+    cols, order, plain = reports.group_columns(groups, labels, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", scores, score,
+                                               is_ref_hap=is_ref_hap, offtargets=otcb, annotations=anncols)
+    lap("report assembly")
+    return cols, order, plain, scores
+
+
+def _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_start, bed_stop, lap) -> str:
+    path = os.path.join(outdir, reports.report_filename(coord.contig, bed_start, bed_stop, pam, guidelen))
+    reports.write_report_tsv(path, cols, order, plain)
+    lap("TSV text + write")
+    return path
+
+
 # Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
-# candidate_guides and figures sit before `annotations`), and only the order of the last three parameters is held fixed.
+# candidate_guides, figures, unphased_report and unphased_engine sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
                  device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
                  timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, offtargets_summary: bool = False,
                  graphical_reports: bool = False,
-                 candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None, annotations: Optional[List[str]] = None,
+                 candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
+                 unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
                  tables: Optional[Dict[str, str]] = None) -> Dict[str, str]:
@@ -214,8 +314,15 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     --candidate-guides) are forced into the delta tables and each gets its sub-report
     crisprhawk_candidate_guides__{contig}_{position}_{pam}_{guidelen}.tsv (candidate_guides.subset_reports).  Pass a dict as
     `figures` and it is filled with {str(coordinate): [paths]}.  Intervals whose haplotypes are built on the host (unphased
-    VCFs, records the device expansion declines) have no device table: asking for the stage there is a ValueError.  (Everything
-    from `timings` on is meant to be passed by keyword.)"""
+    VCFs, records the device expansion declines) have no device table: asking for the stage there is a ValueError.
+    `unphased_report` (unphased VCFs; None reads HAWK_UNPHASED_REPORT, else "groups"): "groups" turns the resolved guides into
+    report groups on the device and writes the report through the phased route's column writer - no Guide object, and the
+    model-score columns (`azimuth_model`, `deepcpf1_weights`, `plmcrispr_model`) are filled as in a phased report; "objects" is
+    the route over Guide objects and pandas, whose model-score columns say NA (_search_host_built).  `unphased_engine` as
+    search_guides.search takes it; "host" implies the object route.  (Everything from `timings` on is meant to be passed by
+    keyword.)"""
+    if unphased_report not in UNPHASED_REPORTS:
+        raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
     import time as _time
     check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
@@ -282,14 +389,14 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                   figures=figures if figures is not None else {})
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
-                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on)
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on, unphased_report, unphased_engine)
     finally:
         if ann is not None:
             ann.close()
 
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
-                      deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False) -> Dict[str, str]:
+                      deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False, unphased_report=None, unphased_engine=None) -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
     def no_table():
         if fx is not None and (fx["on"] or fx["cgs"]):
@@ -301,7 +408,8 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
         if v is not None and not v.phased:
             no_table()
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
-                                                   pt if score else None, debug, ot, ann, lap, tables)
+                                                   pt if score else None, debug, ot, ann, lap, tables, unphased_engine, unphased_report,
+                                                   azimuth_model, deepcpf1_weights, plm_on)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])
@@ -348,27 +456,8 @@ def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, 
     """One interval from its exported groups to its files: scorers, annotation join, report, the optional tables.  `tab`: the
     collapsed table, still in HBM, when the variant-effect stage is on (the caller closes it whatever happens here)."""
     if True:
-        # model-based scorers run once per report row, on the group representatives (scoring.py:749-813), when the
-        # caller has supplied their parameters
-        scores = {}
-        if groups.n_groups and (azimuth_on or deepcpf1_on or plm_on):
-            kmers = reports.group_kmers(groups)
-            if azimuth_on:
-                scores["score_azimuth"] = np.asarray(scoring.azimuth(kmers, debug), dtype=np.float64)
-            if deepcpf1_on:
-                scores["score_deepcpf1"] = np.asarray(scoring.deepcpf1(kmers, debug), dtype=np.float64)
-            if plm_on:  # guide + PAM of the 4 + 23 + 3 k-mer (left-PAM systems only reach here)
-                scores["score_plmcrispr"] = np.asarray(scoring.plmcrispr([k[4:27] for k in kmers], pam.cas_system, debug), dtype=np.float64)
-        anncols = None
-        if ann:  # one join per file over the groups' (start, stop), while the table is closed and before the report's own threads start
-            anncols = ann.columns(coord.contig)(np.asarray(groups.start, dtype=np.int64), np.asarray(groups.stop, dtype=np.int64))
-            lap(ANN_STAGE)
-        otcb = None if ot is None else (lambda spacers: _offtargets(spacers, pam, ot, coord, guidelen, right, outdir, debug))
-        # the report as columns (no Python string per row: the carriers' columns of a 2504-sample panel are 0.6 GB of text), written
-        # by the library's TSV writer
-        cols, order, plain = reports.group_columns(groups, labels, pam, coord.contig, f"{coord.contig}:{bed_start}-{bed_stop}", scores, score,
-                                                   is_ref_hap=np.asarray(ds.is_ref, dtype=bool), offtargets=otcb, annotations=anncols)
-        lap("report assembly")
+        cols, order, plain, scores = _group_report_columns(coord, groups, labels, np.asarray(ds.is_ref, dtype=bool), pam, guidelen, right, outdir, score,
+                                                           debug, ot, ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
         if fx is not None:  # the table is still collapsed in HBM: the effects stage ranks its groups there, by the report's row order
             from . import candidate_guides as cg_mod, graphical_reports as gr_mod
             made = []
@@ -395,7 +484,4 @@ def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, 
             plan.close()
         ds.close()
         lap("report assembly")
-        path = os.path.join(outdir, reports.report_filename(coord.contig, bed_start, bed_stop, pam, guidelen))
-        reports.write_report_tsv(path, cols, order, plain)
-        paths[str(coord)] = path
-        lap("TSV text + write")
+        paths[str(coord)] = _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_start, bed_stop, lap)

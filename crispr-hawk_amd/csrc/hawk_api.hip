@@ -111,6 +111,7 @@ const char* hawk_strerror(int s) {
     case HAWK_E_COMM: return "RCCL failure";
     case HAWK_E_OVERLAP: return "a chromosome copy carries overlapping variants";
     case HAWK_E_CLAMP: return "variant beyond the original region length";
+    case HAWK_E_OOM: return "out of device memory";
     default: return "unknown status";
   }
 }

@@ -11,31 +11,10 @@
 
 #include "hawk_host.h"
 
-struct hawk_resolve {
-  hawk_ctx* ctx;
-  hawk_hapset* hs;        // whose columns the table's rows lie in ...
-  uint64_t gen = 0;       // ... as long as no later search has overwritten them
-  GuideCols cols;
-  UrGeom g;
-  uint64_t n_rows = 0, n_kept = 0, n_resolved = 0, bcap = 0, n_keys = 0;
-  DevBuf key, aoff, ref, rkeys, rvals, res, kept, off;  // the allele table, REF's sorted keys, per-row counts and offsets
-  std::vector<uint64_t> h_off;                           // [n_rows + 1]
-  std::vector<uint32_t> h_cnt;                           // row_resolved[n_rows], row_kept[n_rows]
-  hawk_resolve_timing tm;
-};
-
+// (struct hawk_resolve, ur_dev: hawk_host.h - hawk_api_ugroups.hip reads the handle too)
 static void ur_release(hawk_resolve* r) {
   for (DevBuf* b : {&r->key, &r->aoff, &r->ref, &r->rkeys, &r->rvals, &r->res, &r->kept, &r->off}) b->release();
   delete r;
-}
-
-static UrDev ur_dev(const hawk_resolve* r) {
-  UrDev d;
-  memset(&d, 0, sizeof(d));
-  d.c = r->cols; d.n = r->n_rows; d.hap_len = r->hs->d_hap_len; d.is_ref = r->hs->d_is_ref; d.n_hap = r->hs->n_hap; d.g = r->g;
-  d.al.key = r->key.as<uint64_t>(); d.al.off = r->aoff.as<uint32_t>(); d.al.ref = r->ref.as<uint8_t>(); d.al.n_keys = r->n_keys;
-  d.ref_key = r->rkeys.as<uint64_t>() + r->n_rows; d.ref_row = r->rvals.as<uint32_t>() + r->n_rows;
-  return d;
 }
 
 extern "C" {
@@ -190,6 +169,7 @@ int hawk_resolve_download(hawk_resolve* r, uint32_t* src_row, uint64_t* win, uin
     }
     (void)hipEventElapsedTime(&tm.fill_ms, ctx->ev[0], ctx->ev[1]);
     tm.total_ms += tm.fill_ms;
+    r->downloaded = true;  // (hawk_resolve_groups takes a handle once, in place of this call)
   }
   if (timing) *timing = tm;
   return HAWK_OK;

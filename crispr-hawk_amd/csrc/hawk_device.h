@@ -478,6 +478,48 @@ int hawk_launch_ur_offsets(hipStream_t st, const uint32_t* n_kept /* [n + 1], la
 void hawk_launch_ur_fill(hipStream_t st, const UrDev& d, const uint32_t* n_resolved, const uint32_t* n_kept, const uint64_t* offsets, uint64_t r0,
                          uint64_t r1, uint64_t o0, uint64_t n_out, uint32_t* out_src, uint64_t* out_win, uint64_t out_stride);
 
+// ---- report groups of the kept guides (hawk_ugroups.hip; the rules themselves: hawk_ugroups.h)
+#include "hawk_ugroups.h"
+struct UgDev {
+  GuideCols c;               // the table, either layout
+  const uint8_t* is_ref;     // [n_hap]
+  uint32_t n_hap;
+  uint64_t n_rows;
+  const uint64_t* ref_key;   // [n_rows] sorted start * 2 + strand of REF's rows, UR_SAT behind them
+  const uint32_t* ref_row;   // [n_rows] the row of each key
+  const uint32_t* row_kept;  // [n_rows] kept guides per table row
+  const uint64_t* row_off;   // [n_rows + 1] first kept guide of a row
+  uint64_t n;                // kept guides
+  const uint32_t* src_row;   // [n]
+  const uint64_t* win;       // [5][n]
+  const double* cfd;         // [UG_CFD_MM + UG_CFD_PAM], or null: every CFDon is NaN
+  UgGeom g;
+};
+struct UgWork {          // per kept guide, [n] each
+  uint64_t* keyw;        // [UG_KEY_WORDS][n]
+  uint64_t* hp;          // hap << 32 | pos
+  double* cfdon;
+  uint16_t* gc;          // num | den << 8
+};
+struct UgOut {           // the groups, in HBM
+  uint32_t *rep_src_row, *hap, *pos;
+  uint8_t *strand, *is_ref, *gc_num, *gc_den;
+  int64_t *start, *stop;
+  double* cfdon;
+  uint64_t *win, *member_off;  // [5][n_groups], [n_groups + 1]
+  uint32_t* member_hap;
+  uint64_t n_groups, n_members;
+};
+size_t hawk_ug_temp_bytes(uint64_t n);
+void hawk_launch_ug_keys(hipStream_t st, const UgDev& u, const UgWork& w, uint32_t* idx /* [n]: 0 .. n - 1 */, int* status);
+// the LSD passes: (hap << 32 | pos) first, then the key words from the least significant; returns the sorted order (vals_a or vals_b), null on failure
+const uint32_t* hawk_launch_ug_sort(hipStream_t st, const UgDev& u, const UgWork& w, void* temp, size_t temp_bytes, uint64_t* keys_a, uint64_t* keys_b,
+                                    uint32_t* vals_a /* 0 .. n - 1 */, uint32_t* vals_b);
+void hawk_launch_ug_heads(hipStream_t st, const UgWork& w, uint64_t n, const uint32_t* order, uint32_t* gflag /* [n + 1], last 0 */,
+                          uint32_t* mflag /* [n + 1], last 0 */);
+void hawk_launch_ug_emit(hipStream_t st, const UgDev& u, const UgWork& w, const uint32_t* order, const uint32_t* gflag, const uint32_t* mflag,
+                         const uint64_t* gidx /* [n + 1] */, const uint64_t* midx /* [n + 1] */, const UgOut& o);
+
 #define FX_TOPK_MAX_BLOCKS 1024u
 void hawk_launch_fx_isref_gather(hipStream_t st, const uint8_t* hap_is_ref, const uint32_t* member_hap, const uint64_t* member_off, uint64_t n_groups, uint8_t* out);
 void hawk_launch_fx_groups(hipStream_t st, const FxDev& F);

@@ -227,6 +227,28 @@ struct hawk_table {
 // HAWK_E_INVALID when a later hawk_search on the same set has overwritten the table's columns
 inline bool hawk_table_stale(const hawk_table* t) { return t->hs && t->gen != t->hs->cols_gen; }
 
+// hawk_table_resolve_unphased's handle (hawk_api_resolve.hip); hawk_resolve_groups (hawk_api_ugroups.hip) reads it as well
+struct hawk_resolve {
+  hawk_ctx* ctx;
+  hawk_hapset* hs;        // whose columns the table's rows lie in ...
+  uint64_t gen = 0;       // ... as long as no later search has overwritten them
+  GuideCols cols;
+  UrGeom g;
+  uint64_t n_rows = 0, n_kept = 0, n_resolved = 0, bcap = 0, n_keys = 0;
+  DevBuf key, aoff, ref, rkeys, rvals, res, kept, off;  // the allele table, REF's sorted keys, per-row counts and offsets
+  std::vector<uint64_t> h_off;                           // [n_rows + 1]
+  std::vector<uint32_t> h_cnt;                           // row_resolved[n_rows], row_kept[n_rows]
+  hawk_resolve_timing tm;
+  bool downloaded = false;  // the fill pass has run: by hawk_resolve_download, or by hawk_resolve_groups in its place
+};
+inline UrDev ur_dev(const hawk_resolve* r) {
+  UrDev d = {};
+  d.c = r->cols; d.n = r->n_rows; d.hap_len = r->hs->d_hap_len; d.is_ref = r->hs->d_is_ref; d.n_hap = r->hs->n_hap; d.g = r->g;
+  d.al.key = r->key.as<uint64_t>(); d.al.off = r->aoff.as<uint32_t>(); d.al.ref = r->ref.as<uint8_t>(); d.al.n_keys = r->n_keys;
+  d.ref_key = r->rkeys.as<uint64_t>() + r->n_rows; d.ref_row = r->rvals.as<uint32_t>() + r->n_rows;
+  return d;
+}
+
 int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c);
 
 // shared by the C-ABI translation units (hawk_api_*.hip)

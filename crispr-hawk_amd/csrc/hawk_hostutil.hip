@@ -17,6 +17,7 @@
 #include "hawk_gnomad.h"
 #include "hawk_effects.h"
 #include "hawk_resolve.h"
+#include "hawk_ugroups.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -1199,6 +1200,106 @@ int hawk_host_resolve_unphased(const hawk_resolve_columns* cols, const hawk_reso
         for (int pl = 0; pl < UR_PLANES; ++pl) win[(uint64_t)pl * out_cap + o] = w[pl];
     }
   }
+  return HAWK_OK;
+}
+
+// ---- report groups of the kept guides (hawk_ugroups.h): the host twin of hawk_resolve_groups
+int hawk_host_unphased_groups(const hawk_resolve_columns* cols, const int64_t* stop, const uint32_t* src_row, const uint64_t* win,
+                              uint64_t n_kept, uint64_t win_stride, const double* cfd_mm, const double* cfd_pam, uint32_t flank_up,
+                              uint32_t flank_down, uint64_t group_cap, uint64_t member_cap, uint32_t* rep_src_row, uint32_t* hap,
+                              uint32_t* pos, uint8_t* strand, int64_t* start, int64_t* out_stop, uint8_t* is_ref, double* cfdon,
+                              uint64_t* out_win, uint8_t* gc_num, uint8_t* gc_den, uint64_t* member_off, uint32_t* member_hap,
+                              uint64_t* n_groups, uint64_t* n_members) {
+  if (n_groups) *n_groups = 0;
+  if (n_members) *n_members = 0;
+  if (!cols || !n_groups || !n_members || (cfd_mm && !cfd_pam)) return HAWK_E_INVALID;
+  if (cols->guidelen > 64 || cols->pamlen > 64) return HAWK_E_INVALID;
+  UgGeom g;
+  g.guidelen = (int32_t)cols->guidelen; g.pamlen = (int32_t)cols->pamlen; g.right = cols->right ? 1 : 0;
+  g.L = g.guidelen + g.pamlen; g.W = g.L + 2 * UG_PAD; g.up = (int32_t)flank_up; g.down = (int32_t)flank_down;
+  const int bad = ug_check_geom(g, flank_up, flank_down);
+  if (bad) return bad == 2 ? HAWK_E_UNSUPPORTED : HAWK_E_INVALID;
+  const uint64_t n = n_kept, nr = cols->n_rows;
+  if (n > 0xffffffffull) return HAWK_E_UNSUPPORTED;
+  if (n && (!src_row || !win || !stop || win_stride < n || !cols->hap || !cols->pos || !cols->strand || !cols->start || !cols->hap_is_ref ||
+            nr > 0xffffffffull))
+    return HAWK_E_INVALID;
+  for (uint64_t k = 0; k < n; ++k)
+    if (src_row[k] >= nr || cols->hap[src_row[k]] >= cols->n_hap || cols->strand[src_row[k]] > 1 || (k && src_row[k] < src_row[k - 1])) return HAWK_E_INVALID;
+  // REF's kept guides by (start, strand): hawk_table_resolve_unphased declines a REF row of more than one
+  std::vector<std::pair<uint64_t, uint64_t>> ref;
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint64_t i = src_row[k];
+    if (cols->hap_is_ref[cols->hap[i]]) ref.emplace_back((uint64_t)cols->start[i] * 2u + cols->strand[i], k);
+  }
+  std::sort(ref.begin(), ref.end());
+  struct Item { uint64_t key[UG_KEY_WORDS], hp, k; };
+  std::vector<Item> items(n);
+  std::vector<double> score(n, std::nan(""));
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint64_t i = src_row[k];
+    uint64_t w[UG_PLANES];
+    for (int pl = 0; pl < UG_PLANES; ++pl) w[pl] = win[(uint64_t)pl * win_stride + k];
+    Item& it = items[k];
+    ug_key(g, cols->start[i], stop[i], cols->strand[i], cols->hap_is_ref[cols->hap[i]] != 0, w, it.key);
+    it.hp = ((uint64_t)cols->hap[i] << 32) | cols->pos[i];
+    it.k = k;
+    if (!cfd_mm) continue;
+    const uint64_t want = (uint64_t)cols->start[i] * 2u + cols->strand[i];
+    auto p = std::lower_bound(ref.begin(), ref.end(), std::make_pair(want, (uint64_t)0));
+    if (p == ref.end() || p->first != want) continue;
+    uint64_t core[4], rcore[4];
+    for (int pl = 0; pl < 4; ++pl) { core[pl] = ug_core(w[pl], g); rcore[pl] = ug_core(win[(uint64_t)pl * win_stride + p->second], g); }
+    bool err;
+    score[k] = ug_cfdon(core, rcore, cols->strand[i], g, cfd_mm, cfd_pam, &err);
+    if (err) return HAWK_E_CFD;
+  }
+  std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
+    for (int q = 0; q < UG_KEY_WORDS; ++q)
+      if (a.key[q] != b.key[q]) return a.key[q] < b.key[q];
+    return a.hp != b.hp ? a.hp < b.hp : a.k < b.k;
+  });
+  uint64_t ng = 0, nm = 0;
+  for (uint64_t j = 0; j < n; ++j) {
+    const bool hg = !j || memcmp(items[j].key, items[j - 1].key, sizeof(items[j].key)) != 0;
+    ng += hg ? 1 : 0;
+    nm += (hg || (items[j].hp >> 32) != (items[j - 1].hp >> 32)) ? 1 : 0;
+  }
+  *n_groups = ng; *n_members = nm;
+  const bool any = rep_src_row || hap || pos || strand || start || out_stop || is_ref || cfdon || out_win || gc_num || gc_den || member_off || member_hap;
+  if (!any) return HAWK_OK;
+  if (group_cap < ng || member_cap < nm) return HAWK_E_CAPACITY;
+  uint64_t gi = 0, mi = 0;
+  for (uint64_t j = 0; j < n; ++j) {
+    const Item& it = items[j];
+    const bool hg = !j || memcmp(it.key, items[j - 1].key, sizeof(it.key)) != 0;
+    const bool hm = hg || (it.hp >> 32) != (items[j - 1].hp >> 32);
+    if (hg) {
+      const uint64_t k = it.k, i = src_row[k];
+      uint64_t w[UG_PLANES];
+      for (int pl = 0; pl < UG_PLANES; ++pl) w[pl] = win[(uint64_t)pl * win_stride + k];
+      const uint32_t gc = ug_gc(w, cols->strand[i], g);
+      if (rep_src_row) rep_src_row[gi] = (uint32_t)i;
+      if (hap) hap[gi] = (uint32_t)(it.hp >> 32);
+      if (pos) pos[gi] = (uint32_t)it.hp;
+      if (strand) strand[gi] = (uint8_t)(it.key[1] >> 1);
+      if (is_ref) is_ref[gi] = (uint8_t)(it.key[1] & 1u);
+      if (start) start[gi] = ug_unbias(it.key[0]);
+      if (out_stop) out_stop[gi] = ug_unbias(it.key[2]);
+      if (cfdon) cfdon[gi] = score[k];
+      if (out_win)
+        for (int pl = 0; pl < UG_PLANES; ++pl) out_win[(uint64_t)pl * group_cap + gi] = w[pl];
+      if (gc_num) gc_num[gi] = (uint8_t)(gc & 0xffu);
+      if (gc_den) gc_den[gi] = (uint8_t)(gc >> 8);
+      if (member_off) member_off[gi] = mi;
+      ++gi;
+    }
+    if (hm) {
+      if (member_hap) member_hap[mi] = (uint32_t)(it.hp >> 32);
+      ++mi;
+    }
+  }
+  if (member_off) member_off[ng] = nm;
   return HAWK_OK;
 }
 

@@ -38,7 +38,8 @@ typedef enum {
   HAWK_E_UNSUPPORTED = -7, /* parameter outside the kernel's range (e.g. guidelen+pamlen > 44) */
   HAWK_E_COMM = -8,        /* RCCL failure or librccl.so missing (hawk_comm_last_error() has the text) */
   HAWK_E_OVERLAP = -9,     /* a chromosome copy carries overlapping variants (haplotype.py:214-252 raises on them) */
-  HAWK_E_CLAMP = -10       /* an indel reaches past the region's original length (the reference's clamp, haplotype.py:199-201) */
+  HAWK_E_CLAMP = -10,      /* an indel reaches past the region's original length (the reference's clamp, haplotype.py:199-201) */
+  HAWK_E_OOM = -11         /* device memory the allocator cannot give (hawk_resolve_groups) */
 } hawk_status;
 
 typedef struct hawk_ctx hawk_ctx;
@@ -884,6 +885,53 @@ void hawk_resolve_free(hawk_resolve* r);
 int hawk_host_resolve_unphased(const hawk_resolve_columns* cols, const hawk_resolve_alleles* alleles, uint64_t batch_bytes,
                                uint32_t* row_resolved, uint32_t* row_kept, uint32_t* src_row, uint64_t* win, uint64_t out_cap,
                                uint64_t* n_out, uint64_t* n_resolved, hawk_resolve_decline* decline);
+
+/* ---- report groups of an unphased resolution: the kept guides of a hawk_resolve handle grouped as the guide report merges them
+ * (reports.report_from_guides), with CFDon against the REF guide at the same (start, strand) (scoring.cfdon_score), in HBM.  The
+ * rules are stated once, in csrc/hawk_ugroups.h, for the kernels (k_ug_keys, k_ug_heads, k_ug_emit) and for
+ * hawk_host_unphased_groups.
+ *
+ * The key of a kept guide, compared in this order: start, strand, origin (its row's haplotype is REF), stop, then the five
+ * planes (A, C, G, T, case) of its core at window offsets [10 - up, W - 10 + down), flank_up / flank_down (<= 10) in guide
+ * orientation as hawk_table_collapse_ex takes them ((0, 0): the plain report, (4, 3): the scorers' k-mer).  Two guides share a
+ * group iff their keys are equal (decided on the words, by an LSD sequence of radix sorts - no hash); groups come out ascending
+ * by the key.  Inside a group the guides are ordered by (haplotype row, pos, kept index): the first is the representative, whose
+ * src_row, hap, pos, strand, start, stop, is_ref, cfdon, win[5] and G/C counts (of its spacer, as hawk_table_collapse counts) are
+ * the group's; member_hap[member_off[g] .. member_off[g + 1]) holds each haplotype row of the group once, ascending.
+ * CFDon: the guide's REF partner is the one kept guide of a REF row at the same (start, strand) - a REF row that is invalid or
+ * whose PAM fails the re-check kept nothing and is no partner; without a partner, or with cfd_mm NULL, the value is NaN; else the
+ * left-to-right fp64 product of hawk_search's CFDon (cfd_mm[20][4][4], cfd_pam[16]); a base under a lookup that is not one of
+ * A C G T is HAWK_E_CFD.
+ *
+ * hawk_resolve_groups is called on the handle IN PLACE OF hawk_resolve_download, before the next search on the set; it runs the
+ * fill pass into device memory (44 bytes per kept guide, batched under HAWK_RESOLVE_BATCH_BYTES as the download) and after it
+ * the handle counts as downloaded.  *out is a valid, empty result for zero kept guides.  HAWK_E_INVALID: a handle that was
+ * already downloaded or grouped, or whose table a later search has overwritten; cfd_mm without cfd_pam.  HAWK_E_UNSUPPORTED: a
+ * flank above 10, more than 2^32 - 1 kept guides.  HAWK_E_OOM: device memory the allocator cannot give.  On every status but
+ * HAWK_OK *out stays NULL and nothing is left allocated.  hawk_ugroups_download copies what is not NULL (host or device
+ * destinations; win[5][n_groups], member_off[n_groups + 1]).  The result owns its memory: it outlives the handle and the set, not
+ * the context.  hawk_host_unphased_groups: the same from host arrays (the table's columns + `stop`, and src_row[n_kept] /
+ * win[5][win_stride] of the kept guides, src_row ascending as hawk_resolve_download gives it) by the same header,
+ * single-threaded, no device; outputs of group_cap / member_cap entries (win[5][group_cap]) are written when the counts fit,
+ * else HAWK_E_CAPACITY with the need in *n_groups / *n_members (every output pointer may be NULL; all NULL: the call counts). */
+typedef struct hawk_ugroups hawk_ugroups;
+typedef struct {
+  float fill_ms, keys_ms, sort_ms, heads_ms, emit_ms, total_ms; /* HIP events; heads_ms: the head flags and both scans */
+  uint32_t n_batches, reserved;                                  /* batches of the fill pass */
+  uint64_t n_kept, n_groups, n_members;
+} hawk_ugroups_timing;
+int hawk_resolve_groups(hawk_resolve* r, const double* cfd_mm, const double* cfd_pam, uint32_t flank_up, uint32_t flank_down,
+                        hawk_ugroups** out, uint64_t* n_groups, uint64_t* n_members, hawk_ugroups_timing* timing);
+int hawk_ugroups_download(hawk_ugroups* g, uint32_t* rep_src_row, uint32_t* hap, uint32_t* pos, uint8_t* strand, int64_t* start,
+                          int64_t* stop, uint8_t* is_ref, double* cfdon, uint64_t* win, uint8_t* gc_num, uint8_t* gc_den,
+                          uint64_t* member_off, uint32_t* member_hap);
+void hawk_ugroups_free(hawk_ugroups* g);
+int hawk_host_unphased_groups(const hawk_resolve_columns* cols, const int64_t* stop, const uint32_t* src_row, const uint64_t* win,
+                              uint64_t n_kept, uint64_t win_stride, const double* cfd_mm, const double* cfd_pam, uint32_t flank_up,
+                              uint32_t flank_down, uint64_t group_cap, uint64_t member_cap, uint32_t* rep_src_row, uint32_t* hap,
+                              uint32_t* pos, uint8_t* strand, int64_t* start, int64_t* out_stop, uint8_t* is_ref, double* cfdon,
+                              uint64_t* out_win, uint8_t* gc_num, uint8_t* gc_den, uint64_t* member_off, uint32_t* member_hap,
+                              uint64_t* n_groups, uint64_t* n_members);
 
 /* ---- PLM-CRISPR (scores/plm_crispr/train_general.py, class sgrna_net, forward with train=False; wrapper
  * scores/plm_crispr/plm_crispr.py:136-258): n guide+PAM 23-mers -> n fp32 scores, all arithmetic in fp32 (lin1 and lin3 on the
