@@ -188,7 +188,7 @@ static int search_view_args(SearchRun* r) {
   const size_t n_uniq = std::max<uint32_t>(cl.n_uniq, 1), n_inst = std::max<uint32_t>(cl.n_inst, 1);
   int rc;
   if ((rc = hs->cs_res.reserve(n_uniq * 32)) || (rc = hs->cs_tbase.reserve(n_uniq * 4)) || (rc = hs->cs_trows.reserve((size_t)r->tcap * hawk_cs_row_bytes())) ||
-      (rc = hs->cs_itb.reserve(n_inst * 4)) || (rc = hs->cs_icnt.reserve(n_inst * 4)))
+      (rc = hs->cs_inst.reserve(n_inst * 16)))
     return rc;
   return HAWK_OK;
 }
@@ -220,8 +220,8 @@ static int search_count(SearchRun* r) {
     hawk_launch_cs_templates(st, r->d, r->va, r->cd, r->sp, r->gp, r->ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, &blk->template_rows,
                              r->tcap, &blk->status);
     (void)hipEventRecord(ev[EV_TEMPLATES_DONE], st);
-    hawk_launch_cs_count(st, r->d, r->va, r->cd, r->sp, hs->cs_res.p, &blk->template_rows, r->tcap, counts + r->plane_tiles, hs->cs_icnt.as<uint32_t>(),
-                         hs->cs_itb.as<uint32_t>(), r->shards);
+    hawk_launch_cs_count(st, r->d, r->va, r->cd, r->sp, hs->cs_res.p, &blk->template_rows, r->tcap, counts + r->plane_tiles, hs->cs_inst.p,
+                         r->shards);
   } else if (r->vx) {
     hawk_launch_vsearch(st, 0, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, hs->vcnt0.as<uint32_t>(), r->shards, nullptr, GuideCols{}, &blk->status,
                         r->plane_tiles, r->v_tiles);
@@ -266,7 +266,7 @@ static int search_emit(SearchRun* r, const GuideCols& cols, const GuideCols& pac
   if (launch) {
     const hipStream_t ref_st = r->by_cluster ? r->side : st;
     if (r->by_cluster) {  // the main stream's kernel first, then the fork (nothing is queued on the side stream yet)
-      hawk_launch_cs_emit_rows(st, r->cd, hs->cs_icnt.as<uint32_t>(), hs->cs_itb.as<uint32_t>(), hs->cs_trows.p, offsets + r->plane_tiles, &blk->template_rows,
+      hawk_launch_cs_emit_rows(st, r->cd.n_inst, hs->cs_inst.p, hs->cs_trows.p, offsets + r->plane_tiles, &blk->template_rows,
                                r->tcap, packed.rows, packed.cap, &blk->status);
       HIPCHK(hipStreamWaitEvent(r->side, ev[r->emit_begin], 0));
     }

@@ -882,27 +882,45 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
   if (leader) { res[2 * u] = make_uint4(n0, n1, hits, cand); res[2 * u + 1] = make_uint4((uint32_t)tb, h_front, h_behind, 0u); tbase[u] = (uint32_t)tb; }
 }
 
+// 16 bytes to a 16-byte-aligned address, past the caches' allocation (`nt`): the table is written once and read by a later kernel.
+// The four dword stores to consecutive addresses are merged into one global_store_dwordx4 ... nt by the compiler.
+__device__ __forceinline__ void nt_store4(uint32_t* q, const uint4& v) {
+  __builtin_nontemporal_store(v.x, q); __builtin_nontemporal_store(v.y, q + 1);
+  __builtin_nontemporal_store(v.z, q + 2); __builtin_nontemporal_store(v.w, q + 3);
+}
+// an instance's hand-over record, k_cs_count -> k_cs_emit_rows: a plain store (the next kernel but one reads it: written `nt` the
+// emit pass took 0.397 ms for 0.375 on C3, profiles/emit_cold.md), read once: one global_load_dwordx4 ... nt
+__device__ __forceinline__ void cs_inst_store(uint4* q, const uint4& v) { *q = v; }
+__device__ __forceinline__ uint4 cs_inst_load(const uint4* q) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(q));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
 // every instance: rows = those of its cluster; the job's totals get the cluster's own hits and those of the clean run in front of it -
 // REF's hits before this cluster minus REF's hits behind the cluster in front (second half of the two entries, the neighbour's through the lane
-// below): two 16-byte gathers per instance.  CS_CNT_U instances per thread, loads issued level by level.
+// below): two 16-byte gathers per instance.  CS_CNT_U instances per thread, loads issued level by level: the instance's four dictionary
+// words (cluster, run in front, haplotype row, position) are read-once streams and go out together, the gathers follow.
+// What the emit pass needs of an instance leaves here as ONE 16-byte record {rows, first template row, haplotype row <<
+// HAWK_ROW_HAP_SHIFT, position}: the emit pass then reads one stream this kernel has just written and nothing of the dictionary,
+// whose arrays k_cl_fill wrote several hundred MB of traffic earlier in a step that rebuilds it (profiles/emit_cold.md).
 #define CS_CNT_U 4
 __global__ __launch_bounds__(256) void k_cs_count(HapSetDev hs, VcArgs va, ClDict cd, ScanParams p, const uint4* __restrict__ res,
                                                   const unsigned long long* __restrict__ t_count, uint64_t t_cap,
-                                                  uint32_t* __restrict__ group_counts, uint32_t* __restrict__ counts, uint32_t* __restrict__ inst_tb,
-                                                  unsigned long long* __restrict__ shards) {
+                                                  uint32_t* __restrict__ group_counts, uint4* __restrict__ inst, unsigned long long* __restrict__ shards) {
   __shared__ uint32_t s_red[256 / WAVE][2];
   const uint32_t i0 = blockIdx.x * (256 * CS_CNT_U) + threadIdx.x;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const bool ovf = *t_count > t_cap;  // the template rows outgrew their reservation: no table (the host reruns the search)
-  uint32_t uid[CS_CNT_U], below[CS_CNT_U];
-  int32_t paf[CS_CNT_U];
+  uint32_t uid[CS_CNT_U], below[CS_CNT_U], row[CS_CNT_U];
+  int32_t paf[CS_CNT_U], o[CS_CNT_U];
   bool in[CS_CNT_U];
 #pragma unroll
   for (int u = 0; u < CS_CNT_U; ++u) {
     const uint32_t i = i0 + u * 256;
     in[u] = i < cd.n_inst;
     const uint32_t ic = in[u] ? i : 0u;
-    uid[u] = cd.inst_uid[ic]; paf[u] = cd.inst_pa[ic];
+    uid[u] = __builtin_nontemporal_load(cd.inst_uid + ic); paf[u] = __builtin_nontemporal_load(cd.inst_pa + ic);
+    row[u] = __builtin_nontemporal_load(cd.inst_row + ic); o[u] = __builtin_nontemporal_load(cd.inst_o + ic);
     below[u] = CL_NONE;
     if (lane == 0 && in[u] && i > 0) below[u] = cd.inst_uid[i - 1];  // (the other lanes' neighbour is the lane below)
   }
@@ -931,16 +949,16 @@ __global__ __launch_bounds__(256) void k_cs_count(HapSetDev hs, VcArgs va, ClDic
         const uint32_t hc = r2[u].y - behind;
         hits += hc; cand += hc;
       } else {
-        const int32_t pa = paf[u], pb = cd.inst_o[i] - (p.L - 1);
+        const int32_t pa = paf[u], pb = o[u] - (p.L - 1);
         if (pb > pa) {
-          const VcRanges rg = cs_ranges(hs, p, cd.inst_row[i]);
+          const VcRanges rg = cs_ranges(hs, p, row[u]);
           vc_count_run(va, rg, pa, pb, cd.inst_rb[i], cand, hits);
         }
       }
       hits += r[u].z; cand += r[u].w;
       rows_i = ovf ? 0u : r[u].x + r[u].y;
-      counts[i] = rows_i;
-      inst_tb[i] = r2[u].x;  // the instance's first template row: the emit pass reads it next to the count instead of going through the cluster
+      // the hand-over record (r2.x: the instance's first template row, so the emit pass does not go through the cluster number)
+      cs_inst_store(inst + i, make_uint4(rows_i, r2[u].x, row[u] << HAWK_ROW_HAP_SHIFT, (uint32_t)o[u]));
     }
     // what the offset scan runs over: the rows of 64 consecutive instances (one wave here, one wave's contiguous stretch of the table in
     // the emit pass) - 1.4 x 10^5 entries on C3 instead of 8.8 x 10^6
@@ -962,12 +980,6 @@ __global__ __launch_bounds__(256) void k_cs_count(HapSetDev hs, VcArgs va, ClDic
   }
 }
 
-// 16 bytes to a 16-byte-aligned address, past the caches' allocation (`nt`): the table is written once and read by a later kernel.
-// The four dword stores to consecutive addresses are merged into one global_store_dwordx4 ... nt by the compiler.
-__device__ __forceinline__ void nt_store4(uint32_t* q, const uint4& v) {
-  __builtin_nontemporal_store(v.x, q); __builtin_nontemporal_store(v.y, q + 1);
-  __builtin_nontemporal_store(v.z, q + 2); __builtin_nontemporal_store(v.w, q + 3);
-}
 // ---- packed rows (round 4): the guide table of a cluster search as ONE array of 64-byte rows -----------------------------
 // A template row (CsRow, hawk_rows.h: the field order is written down there) with two words patched: pos and the haplotype row.  A wave's rows are contiguous, four lanes move one row (16 bytes each), so every store
 // instruction writes 1 KB of consecutive addresses and the whole table is a single linear write stream - twelve column
@@ -977,8 +989,7 @@ __device__ __forceinline__ void nt_store4(uint32_t* q, const uint4& v) {
 // 160 MB read set cache-resident and 0.53 with it in HBM): so a wave asks for all its instance data at once, up front, and
 // keeps the template loads of the next 128 rows in flight while it stores the current 128.
 template <int NI, int CE_CH>
-__global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uint32_t* __restrict__ inst_row, const int32_t* __restrict__ inst_o,
-                                                      const uint32_t* __restrict__ counts, const uint32_t* __restrict__ inst_tb,
+__global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uint4* __restrict__ inst,
                                                       const CsRow* __restrict__ trows, const uint64_t* __restrict__ offsets,
                                                       const unsigned long long* __restrict__ t_count, uint64_t t_cap, uint4* __restrict__ rows,
                                                       uint64_t cap, int* status) {
@@ -994,17 +1005,17 @@ __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uin
   const uint32_t wv = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
   const uint32_t i0 = (blockIdx.x * 4 + wv) * NE;  // the wave's first instance
   if (i0 >= n_inst) return;
-  // per instance: four independent streaming loads (k_cs_count left the row count and the first template row of each instance, so
-  // nothing here waits for a gather through the cluster number); lane l takes instances i0 + 64 c + l
+  // per instance: ONE 16-byte streaming load of the record k_cs_count has just left {rows, first template row, haplotype row
+  // shifted, position} - nothing here waits for a gather through the cluster number or reads the dictionary's arrays; lane l takes
+  // instances i0 + 64 c + l (lanes past the last instance are clamped onto it and count no rows)
   uint32_t cnt[NI], tb[NI], h[NI];
   int32_t dq[NI];
 #pragma unroll
   for (int c = 0; c < NI; ++c) {
     const uint32_t i = i0 + c * WAVE + lane;
     const bool in = i < n_inst;
-    const uint32_t ii = in ? i : n_inst - 1;
-    cnt[c] = counts[ii]; tb[c] = inst_tb[ii]; h[c] = inst_row[ii]; dq[c] = inst_o[ii];
-    if (!in) cnt[c] = 0;
+    const uint4 rec = cs_inst_load(inst + (in ? i : n_inst - 1));
+    cnt[c] = in ? rec.x : 0u; tb[c] = rec.y; h[c] = rec.z; dq[c] = (int32_t)rec.w;
   }
   // the wave's first row
   const uint64_t o0 = offsets[i0 / WAVE];  // one offset per 64 instances (k_cs_count's groups); wave-uniform: a scalar load
@@ -1013,7 +1024,7 @@ __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uin
   for (int c = 0; c < NI; ++c) {
     const uint32_t inc = wave_incl_scan(cnt[c]);
     s_ex[wv][c * WAVE + lane] = Wt + inc - cnt[c];
-    s_tb[wv][c * WAVE + lane] = tb[c]; s_h[wv][c * WAVE + lane] = h[c] << HAWK_ROW_HAP_SHIFT; s_dq[wv][c * WAVE + lane] = dq[c];
+    s_tb[wv][c * WAVE + lane] = tb[c]; s_h[wv][c * WAVE + lane] = h[c]; s_dq[wv][c * WAVE + lane] = dq[c];
     Wt += (uint32_t)__builtin_amdgcn_readlane((int)inc, WAVE - 1);
   }
   if (Wt == 0) return;  // wave-uniform
@@ -1071,15 +1082,25 @@ __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uin
     }
   }
 }
-void hawk_launch_cs_emit_rows(hipStream_t st, const ClDict& cd, const uint32_t* counts, const uint32_t* inst_tb, const void* trows, const uint64_t* offsets,
+// the ONE instantiation of the emit pass: 64-instance groups per wave, rows per chunk (the sweeps are below)
+constexpr int CS_EMIT_NI = 4, CS_EMIT_CH = 256;
+void hawk_cs_emit_geometry(uint32_t* inst_per_wave, uint32_t* rows_per_chunk) { *inst_per_wave = CS_EMIT_NI * WAVE; *rows_per_chunk = CS_EMIT_CH; }
+void hawk_launch_cs_emit_rows(hipStream_t st, uint32_t n_inst, const void* inst, const void* trows, const uint64_t* offsets,
                               const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status) {
-  if (!cd.n_inst) return;
+  if (!n_inst) return;
   // 256 instances per wave, 256 rows in flight per wave (184 VGPRs: two waves per SIMD).  Measured on C3 (profiles/r04_emit_rows.md):
   // 64 / 128 / 256 rows in flight at 8 / 4 / 2 waves per SIMD: 0.53 / 0.47 / 0.45 ms before the offset scan went to one entry per
-  // 64 instances, 0.39 (128 rows, 128 instances) / 0.38 after - few waves with long contiguous bursts write best
-  constexpr int NI = 4, CH = 256;
-  hipLaunchKernelGGL((k_cs_emit_rows<NI, CH>), dim3((cd.n_inst + 256 * NI - 1) / (256 * NI)), dim3(256), 0, st, cd.n_inst, cd.inst_row, cd.inst_o, counts,
-                     inst_tb, static_cast<const CsRow*>(trows), offsets, t_count, t_cap, static_cast<uint4*>(rows), cap, status);
+  // 64 instances, 0.39 (128 rows, 128 instances) / 0.38 after - few waves with long contiguous bursts write best.
+  // Those figures are searches of a resident dictionary.  Behind a dictionary build (every step of bench.py) the pass took 0.45 - 0.48
+  // while it read inst_row / inst_o / counts / inst_tb itself, and 0.37 - 0.38 in either regime since it reads k_cs_count's records.
+  // Swept again behind the build, on the records (profiles/emit_cold.md; instances per wave x rows per chunk: VGPRs, waves per SIMD,
+  // ms rebuilt / resident): 128 x 128: 103, 4, 0.377 / 0.374; 128 x 256: 184, 2, 0.378 / 0.367; 256 x 128: 104, 4, 0.376 / 0.373;
+  // 256 x 256: 185, 2, 0.374 - 0.380 / 0.371 - 0.374; 512 x 128: 105, 3 (LDS), 0.382 / 0.377; 512 x 256: 186, 2, 0.378 / 0.371 -
+  // all inside one another's spread (0.01), so the instantiation stays.  On the four arrays 512 instances per wave gained 0.03
+  // behind the build (0.434 for 0.467) and the records made that gain moot.
+  constexpr int NI = CS_EMIT_NI, CH = CS_EMIT_CH;
+  hipLaunchKernelGGL((k_cs_emit_rows<NI, CH>), dim3((n_inst + 256 * NI - 1) / (256 * NI)), dim3(256), 0, st, n_inst, static_cast<const uint4*>(inst),
+                     static_cast<const CsRow*>(trows), offsets, t_count, t_cap, static_cast<uint4*>(rows), cap, status);
 }
 
 void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const GuideParams& gp,
@@ -1090,11 +1111,10 @@ void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs&
                      t_count, t_cap, status);
 }
 void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const void* res,
-                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, uint32_t* counts, uint32_t* inst_tb,
-                          unsigned long long* shards) {
+                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, void* inst, unsigned long long* shards) {
   if (!cd.n_inst) return;
   hipLaunchKernelGGL(k_cs_count, dim3((cd.n_inst + 256 * CS_CNT_U - 1) / (256 * CS_CNT_U)), dim3(256), 0, st, hs, va, cd, p, static_cast<const uint4*>(res), t_count, t_cap,
-                     group_counts, counts, inst_tb, shards);
+                     group_counts, static_cast<uint4*>(inst), shards);
 }
 
 // columns -> packed rows (REF's rows, which the plane kernels write as columns; a columnar table before an exchange) and back:

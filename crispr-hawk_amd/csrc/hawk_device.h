@@ -184,10 +184,11 @@ void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs&
                               const struct RefInfo& ri, void* res /* 32 B per distinct cluster */, uint32_t* tbase, void* trows,
                               unsigned long long* t_count, uint64_t t_cap, int* status);
 void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const void* res,
-                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, uint32_t* counts, uint32_t* inst_tb,
+                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, void* inst /* 16 B per instance */,
                           unsigned long long* shards);
-void hawk_launch_cs_emit_rows(hipStream_t st, const ClDict& cd, const uint32_t* counts, const uint32_t* inst_tb, const void* trows, const uint64_t* offsets,
+void hawk_launch_cs_emit_rows(hipStream_t st, uint32_t n_inst, const void* inst, const void* trows, const uint64_t* offsets,
                               const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status);
+void hawk_cs_emit_geometry(uint32_t* inst_per_wave, uint32_t* rows_per_chunk);  // of the instantiation hawk_launch_cs_emit_rows launches
 // hawk_meta.hip: the rows' metadata of an expansion plan, built on the device
 void hawk_launch_list_check(hipStream_t st, const uint64_t* row_off, uint32_t n_rows, const uint32_t* hv_idx, const int32_t* hv_o,
                             const int32_t* v_r0, const int32_t* v_span, const int32_t* v_chain, uint32_t n_var, uint32_t ref_len,
