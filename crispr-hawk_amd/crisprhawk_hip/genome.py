@@ -54,6 +54,11 @@ def encode_guides(guides: Sequence[str]) -> np.ndarray:
     return (codes.astype(np.uint64) << (2 * np.arange(L, dtype=np.uint64))).sum(axis=1, dtype=np.uint64)
 
 
+def _no_timing() -> dict:
+    """The timing block (hawk_ot_timing) of a call that had nothing to run."""
+    return dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+
+
 def decode_window(code: int, nmask: int, length: int) -> str:
     return "".join("N" if (nmask >> i) & 1 else "ACGT"[(code >> (2 * i)) & 3] for i in range(length))
 
@@ -205,30 +210,53 @@ class GenomeIndex:
         mismatch-only scans of derived guides that are shorter or longer than the guides themselves (scan_bulges)."""
         guidelen = self.guidelen if guidelen is None else int(guidelen)
         self._set_window(guidelen)
-        empty = dict(guide=np.zeros(0, np.uint32), row=np.zeros(0, np.uint32), q=np.zeros(0, np.uint32), strand=np.zeros(0, np.uint8),
-                     mm=np.zeros(0, np.uint8), code=np.zeros(0, np.uint64), nmask=np.zeros(0, np.uint32))
         if self.ds is None:
-            return empty, dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
-        L = self.ds._L
+            return {k: np.zeros(0, t) for k, t in self.OT_COLUMNS[:7]}, _no_timing()
         g2 = encode_guides(guides)
         par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), guidelen, int(bool(right)), max_mm)
+        return self._collect("hawk_offtarget_scan", (self.ds._h, C.byref(par), _p(g2), len(g2)), 7, cap)
+
+    OT_COLUMNS = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
+                  ("nmask", np.uint32), ("gaps", np.uint64), ("kind", np.uint8), ("size", np.uint8))
+
+    def _collect(self, fn: str, head: tuple, n_cols: int, cap: int):
+        """One listing call `fn`(*head, the first n_cols OT_COLUMNS as outputs of `cap` rows, cap, &n, &timing), again with room for
+        n + 1024 rows for as long as it answers HAWK_E_CAPACITY: (the columns trimmed to the n rows, row made global; timing)."""
+        cols = self.OT_COLUMNS[:n_cols]
         while True:
-            og = np.empty(cap, np.uint32); orow = np.empty(cap, np.uint32); oq = np.empty(cap, np.uint32)
-            ost = np.empty(cap, np.uint8); omm = np.empty(cap, np.uint8); oc = np.empty(cap, np.uint64); onm = np.empty(cap, np.uint32)
-            n = C.c_uint64(0)
-            tm = _lib.OtTiming()
-            rc = L.hawk_offtarget_scan(self.ds._h, C.byref(par), _p(g2), len(g2), _p(og), _p(orow), _p(oq), _p(ost), _p(omm),
-                                       _p(oc), _p(onm), C.c_uint64(cap), C.byref(n), C.byref(tm))
-            if rc == _lib.HAWK_E_CAPACITY:
-                cap = int(n.value) + 1024
-                continue
-            _lib.check(rc, "hawk_offtarget_scan")
-            break
+            o = {k: np.empty(cap, t) for k, t in cols}
+            n, tm = C.c_uint64(0), _lib.OtTiming()
+            rc = getattr(self.ds._L, fn)(*head, *[_p(o[k]) for k, _t in cols], C.c_uint64(cap), C.byref(n), C.byref(tm))
+            if rc != _lib.HAWK_E_CAPACITY:
+                break
+            cap = int(n.value) + 1024
+        _lib.check(rc, fn)
         self.last_timing = {k: getattr(tm, k) for k, _ in tm._fields_}
-        k = int(n.value)
-        hits = dict(guide=og[:k].copy(), row=(orow[:k] + np.uint32(self.row_lo)), q=oq[:k].copy(), strand=ost[:k].copy(), mm=omm[:k].copy(),
-                    code=oc[:k].copy(), nmask=onm[:k].copy())
+        hits = {k: o[k][:int(n.value)].copy() for k, _t in cols}
+        hits["row"] = hits["row"] + np.uint32(self.row_lo)
         return hits, self.last_timing
+
+    def _check_bulges(self, bdna: int, brna: int) -> None:
+        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
+            raise ValueError("bulges of 0..2 bases are enumerated")
+        if bdna > self.max_bulge:
+            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+
+    BULGE_KINDS = ((True, 1), (True, 2), (False, 1), (False, 2))  # the order of `bulge_hist`: DNA 1, DNA 2, RNA 1, RNA 2
+
+    def _each_bulge(self, bdna: int, brna: int, run) -> list:
+        """`run(b, dna)` -> (result, timing) for every (type, size) asked for, in BULGE_KINDS order: [(slot in BULGE_KINDS, dna, b,
+        result)], the timing blocks in last_bulge_timing.  The index's own window is put back, also when a call raises."""
+        self.last_bulge_timing, out = [], []
+        try:
+            for k, (dna, b) in enumerate(self.BULGE_KINDS):
+                if b <= (bdna if dna else brna):
+                    res, tm = run(b, dna)
+                    self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
+                    out.append((k, dna, b, res))
+        finally:
+            self._set_window(self.guidelen)
+        return out
 
     # ---- bulged sites (the -bDNA / -bRNA arguments of the reference's CRISPRitz call, offtargets.py:264-268) -------------
     def scan_bulges(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int, brna: int, cap: int = 1 << 20,
@@ -247,19 +275,17 @@ class GenomeIndex:
         the same rows in the same order."""
         if engine not in ("derived", "device"):
             raise ValueError(f"engine {engine!r}: 'derived' or 'device'")
-        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
-            raise ValueError("bulges of 0..2 bases are enumerated")
-        if bdna > self.max_bulge:
-            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        self._check_bulges(bdna, brna)
         G = self.guidelen
         guides = [g.upper() for g in guides]
+        order = lambda r: (r.guide, r.bulge_type, r.bulge_size, self._contig_rank(r.contig), r.position, r.strand == "-")
+        if engine == "device":  # last_bulge_timing: the timing block of every (type, size) call
+            parts = self._each_bulge(bdna, brna, lambda b, dna: self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap))
+            return sorted((r for _k, dna, b, h in parts for r in self._bulge_rows_device(h, guides, right, b, dna)), key=order)
         out: List[BulgeHit] = []
-        self.last_bulge_timing = []  # engine="device": the timing block of every (type, size) call
+        self.last_bulge_timing = []
         for dna, bmax in ((True, bdna), (False, brna)):
             for b in range(1, bmax + 1):
-                if engine == "device":
-                    out += self._bulge_rows_device(guides, pam, right, max_mm, b, dna, cap)
-                    continue
                 step = max(1, int(max_derived) // max(1, derived_per_guide(G, b, dna)))
                 Gs = G + b if dna else G - b
                 for g0 in range(0, len(guides), step):
@@ -269,7 +295,7 @@ class GenomeIndex:
                     h, _tm = self.scan_arrays(derived, pam, right, max_mm, cap, guidelen=Gs)
                     out += self._bulge_rows(h, guides, np.asarray(owner) + g0, np.asarray(gaps, dtype=np.uint64), Gs, b, dna, right, max_mm)
         self._set_window(self.guidelen)
-        out.sort(key=lambda r: (r.guide, r.bulge_type, r.bulge_size, self._contig_rank(r.contig), r.position, r.strand == "-"))
+        out.sort(key=order)
         return out
 
     def _contig_rank(self, name: str) -> int:
@@ -366,31 +392,13 @@ class GenomeIndex:
         g2 = encode_guides(guides)
         if len(g2) and len(guides[0]) != G:
             raise ValueError(f"guides of {len(guides[0])} bases on an index built for {G}")
-        cols = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
-                ("nmask", np.uint32), ("gaps", np.uint64))
         if self.ds is None or len(g2) == 0:
-            return {k: np.zeros(0, t) for k, t in cols}, dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
+            return {k: np.zeros(0, t) for k, t in self.OT_COLUMNS[:8]}, _no_timing()
         par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), G, int(bool(right)), max_mm)
-        while True:
-            o = {k: np.empty(cap, t) for k, t in cols}
-            n = C.c_uint64(0)
-            tm = _lib.OtTiming()
-            rc = self.ds._L.hawk_offtarget_bulges(self.ds._h, C.byref(par), _p(g2), len(g2), 1 if dna else 2, int(b), *[_p(o[k]) for k, _t in cols],
-                                                  C.c_uint64(cap), C.byref(n), C.byref(tm))
-            if rc == _lib.HAWK_E_CAPACITY:
-                cap = int(n.value) + 1024
-                continue
-            _lib.check(rc, "hawk_offtarget_bulges")
-            break
-        self.last_timing = {k: getattr(tm, k) for k, _ in tm._fields_}
-        k = int(n.value)
-        hits = {name: o[name][:k].copy() for name, _t in cols}
-        hits["row"] = hits["row"] + np.uint32(self.row_lo)
-        return hits, self.last_timing
+        return self._collect("hawk_offtarget_bulges", (self.ds._h, C.byref(par), _p(g2), len(g2), 1 if dna else 2, int(b)), 8, cap)
 
-    def _bulge_rows_device(self, guides, pam, right: bool, max_mm: int, b: int, dna: bool, cap: int) -> List["BulgeHit"]:
-        h, tm = self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)
-        self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
+    def _bulge_rows_device(self, h, guides, right: bool, b: int, dna: bool) -> List["BulgeHit"]:
+        """The columns of one bulge_arrays as BulgeHits, in their order."""
         if len(h["guide"]) == 0:
             return []
         Gs = self.guidelen + b if dna else self.guidelen - b
@@ -399,33 +407,19 @@ class GenomeIndex:
                 for i in range(len(h["guide"]))]
 
     # ---- the off-targets table without an object per site (hawk_offtarget_text) ------------------------------------------
-    OT_COLUMNS = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
-                  ("nmask", np.uint32), ("gaps", np.uint64), ("kind", np.uint8), ("size", np.uint8))
-
     def offtarget_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int = 0, brna: int = 0, cap: int = 1 << 20):
         """Every hit of `guides` as columns - one scan_arrays, one bulge_arrays per (type, size), concatenated with `kind`
         (0 = X, 1 = DNA, 2 = RNA) and `size` columns (gaps = 0 for un-bulged hits) - in the order the product's file has: the
         un-bulged hits in scan()'s order, then the bulged ones in scan_bulges()' order (guide, type, size, contig, position,
         strand), by one lexsort of integer keys.  No OffTargetHit / BulgeHit is built.  The index's own window is put back."""
-        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
-            raise ValueError("bulges of 0..2 bases are enumerated")
-        if bdna > self.max_bulge:
-            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        self._check_bulges(bdna, brna)
         guides = [g.upper() for g in guides]
-        parts = []
         h, _tm = self.scan_arrays(guides, pam, right, max_mm, cap)
         n0 = len(h["guide"])
-        parts.append(dict(h, gaps=np.zeros(n0, np.uint64), kind=np.zeros(n0, np.uint8), size=np.zeros(n0, np.uint8)))
-        self.last_bulge_timing = []
-        try:
-            for dna, bmax in ((True, bdna), (False, brna)):
-                for b in range(1, bmax + 1):
-                    hb, tm = self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)
-                    self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
-                    nb = len(hb["guide"])
-                    parts.append(dict(hb, kind=np.full(nb, 1 if dna else 2, np.uint8), size=np.full(nb, b, np.uint8)))
-        finally:
-            self._set_window(self.guidelen)
+        parts = [dict(h, gaps=np.zeros(n0, np.uint64), kind=np.zeros(n0, np.uint8), size=np.zeros(n0, np.uint8))]
+        for _k, dna, b, hb in self._each_bulge(bdna, brna, lambda b, dna: self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)):
+            nb = len(hb["guide"])
+            parts.append(dict(hb, kind=np.full(nb, 1 if dna else 2, np.uint8), size=np.full(nb, b, np.uint8)))
         cols = {k: np.concatenate([pt[k] for pt in parts]).astype(t, copy=False) for k, t in self.OT_COLUMNS}
         # rows of a contig ascend with their offsets and own disjoint starts: (row, q) orders as (contig, position) does
         order = np.lexsort((cols["strand"], cols["q"], cols["row"], cols["size"], cols["kind"], cols["guide"], cols["kind"] != 0))
@@ -460,10 +454,7 @@ class GenomeIndex:
         od = None if order is None else np.ascontiguousarray(order, dtype=np.uint64)
         if od is not None and len(od) != n:
             raise ValueError("rows_text: `order` must name every row once")
-        mm = pt = None
-        if cfd_tables is not None:
-            mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
-            pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
+        mm, pt = self._cfd_tables(cfd_tables)
         device = self.ds.device if self.ds is not None else None
         L, ctx = _lib.lib(), _lib.context(device)
         par = _lib.OtParams(0, 0, len(pam), self.guidelen, int(bool(right)), 0)
@@ -491,8 +482,6 @@ class GenomeIndex:
                                     decode_window(int(h["code"][i]), int(h["nmask"][i]), self.L)))
         return out
 
-    BULGE_KINDS = ((True, 1), (True, 2), (False, 1), (False, 2))  # the order of `bulge_hist`: DNA 1, DNA 2, RNA 1, RNA 2
-
     def summary(self, guides: Sequence[str], pam, right: bool, max_mm: int, cfd_tables=None, comm=None, bdna: int = 0, brna: int = 0) -> dict:
         """The scan's per-guide aggregates without its hits (hawk_offtarget_summary, and with `bdna` / `brna` above zero one
         hawk_offtarget_bulge_summary per (type, size)): dict(hist = uint32[n_guides, max_mm + 1] un-bulged hits per guide and
@@ -507,47 +496,22 @@ class GenomeIndex:
         retry, nothing sized by the rows.  Duplicate guides get equal rows; an index without rows on this rank returns zeros.
         The arrays are integers, so shards add up exactly: with a communicator every rank's arrays are gathered to rank 0,
         which returns their sum (other ranks return their own shard's)."""
-        if not (0 <= bdna <= 2 and 0 <= brna <= 2):
-            raise ValueError("bulges of 0..2 bases are enumerated")
-        if bdna > self.max_bulge:
-            raise ValueError(f"the index was built for DNA bulges of up to {self.max_bulge} bases (GenomeIndex(max_bulge=...))")
+        self._check_bulges(bdna, brna)
         bulged = bool(bdna or brna)
         n, stride = len(guides), int(max_mm) + 1
         g2 = encode_guides(guides)
-        hist = np.zeros((n, stride), dtype=np.uint32)
-        cfd = np.zeros(n, dtype=np.int64) if cfd_tables is not None else None
-        nh, nu = C.c_uint64(0), C.c_uint64(0)
         self._set_window(self.guidelen)
-        timing = dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
-        mm = pt = None
-        if cfd_tables is not None:
-            mm = np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4)
-            pt = np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16)
-        if self.ds is not None:
-            par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), self.guidelen, int(bool(right)), int(max_mm))
-            tm = _lib.OtTiming()
-            rc = self.ds._L.hawk_offtarget_summary(self.ds._h, C.byref(par), _p(g2), n, None if mm is None else _p(mm),
-                                                   None if pt is None else _p(pt), _p(hist), None if cfd is None else _p(cfd),
-                                                   C.byref(nh), C.byref(nu), C.byref(tm))
-            _lib.check(rc, "hawk_offtarget_summary")
-            timing = {k: getattr(tm, k) for k, _ in tm._fields_}
-        self.last_timing = timing
-        out = dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value))
+        mm, pt = self._cfd_tables(cfd_tables)
+        out, self.last_timing = self._summary_call("hawk_offtarget_summary", g2, pam, right, int(max_mm), mm, pt)
+        hist, cfd = out["hist"], out["cfd_e4"]
         if bulged:
             out["bulge_hist"] = np.zeros((n, 4, stride), dtype=np.uint32)
-            self.last_bulge_timing = []
-            try:
-                for k, (dna, b) in enumerate(self.BULGE_KINDS):
-                    if b <= (bdna if dna else brna):
-                        part, tm = self._bulge_summary(g2, pam, right, int(max_mm), b, dna, mm, pt)
-                        self.last_bulge_timing.append(dict(tm, bulge_type="DNA" if dna else "RNA", bulge_size=b))
-                        out["bulge_hist"][:, k, :] = part["hist"]
-                        if cfd is not None:
-                            out["cfd_e4"] += part["cfd_e4"]
-                        out["n_hits"] += part["n_hits"]
-                        out["n_unscorable"] += part["n_unscorable"]
-            finally:
-                self._set_window(self.guidelen)
+            for k, _dna, _b, part in self._each_bulge(bdna, brna, lambda b, dna: self._bulge_summary(g2, pam, right, int(max_mm), b, dna, mm, pt)):
+                out["bulge_hist"][:, k, :] = part["hist"]
+                if cfd is not None:
+                    out["cfd_e4"] += part["cfd_e4"]
+                out["n_hits"] += part["n_hits"]
+                out["n_unscorable"] += part["n_unscorable"]
         if comm is not None and comm.world > 1:
             tail = np.array([out["n_hits"], out["n_unscorable"]], dtype=np.int64)
             bh = out["bulge_hist"].reshape(-1).astype(np.int64) if bulged else np.zeros(0, np.int64)
@@ -571,17 +535,30 @@ class GenomeIndex:
         if G - b < 3:
             raise ValueError(f"guides of {G} bases leave no interior base to pair beside a bulge of {b}")
         self._set_window(G + b if dna else G - b)
+        return self._summary_call("hawk_offtarget_bulge_summary", g2, pam, right, max_mm, mm, pt, 1 if dna else 2, int(b), run=n > 0)
+
+    @staticmethod
+    def _cfd_tables(cfd_tables):
+        """(mm[20,4,4], pam[16]) as the contiguous float64 arrays the library reads, or (None, None)"""
+        if cfd_tables is None:
+            return None, None
+        return (np.ascontiguousarray(cfd_tables[0], dtype=np.float64).reshape(20, 4, 4),
+                np.ascontiguousarray(cfd_tables[1], dtype=np.float64).reshape(16))
+
+    def _summary_call(self, fn: str, g2, pam, right: bool, max_mm: int, mm, pt, *kind, run: bool = True):
+        """One summary call `fn` over this rank's rows, `kind` = (bulge type, size) for the bulged one: (dict(hist uint32[n,
+        max_mm + 1], cfd_e4 int64[n] or None without tables, n_hits, n_unscorable), timing) - zeros without rows or with `run` false."""
+        n = len(g2)
         hist = np.zeros((n, max_mm + 1), dtype=np.uint32)
         cfd = np.zeros(n, dtype=np.int64) if mm is not None else None
         nh, nu = C.c_uint64(0), C.c_uint64(0)
-        timing = dict(scan_ms=0.0, sites_ms=0.0, match_ms=0.0, total_ms=0.0, n_sites=0, scanned_positions=0)
-        if self.ds is not None and n:
-            par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), G, int(bool(right)), max_mm)
+        timing = _no_timing()
+        if self.ds is not None and run:
+            par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), self.guidelen, int(bool(right)), max_mm)
             tm = _lib.OtTiming()
-            rc = self.ds._L.hawk_offtarget_bulge_summary(self.ds._h, C.byref(par), _p(g2), n, 1 if dna else 2, int(b), None if mm is None else _p(mm),
-                                                         None if pt is None else _p(pt), _p(hist), None if cfd is None else _p(cfd),
-                                                         C.byref(nh), C.byref(nu), C.byref(tm))
-            _lib.check(rc, "hawk_offtarget_bulge_summary")
+            rc = getattr(self.ds._L, fn)(self.ds._h, C.byref(par), _p(g2), n, *kind, _p(mm), _p(pt), _p(hist), _p(cfd),
+                                         C.byref(nh), C.byref(nu), C.byref(tm))
+            _lib.check(rc, fn)
             timing = {k: getattr(tm, k) for k, _ in tm._fields_}
         return dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value)), timing
 

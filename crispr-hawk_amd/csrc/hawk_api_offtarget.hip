@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -59,17 +60,14 @@ static int ot_seed_tables(hawk_hapset* hs, const uint64_t* guides2, uint32_t n_g
   return HAWK_OK;
 }
 
-// The front half hawk_offtarget_scan and hawk_offtarget_summary share: argument checks, the choice of the match kernel and its
-// bucketed guide tables, PAM scan -> site records (events 0..3 recorded), guides uploaded, the first 64 bytes of `misc` zeroed.
+// The front half the four entry points share: argument checks, the choice of the match kernel and its bucketed guide tables, PAM
+// scan -> site records (events 0..3 recorded), guides uploaded, the first 64 bytes of `misc` zeroed.  `m` names the kernel chosen
+// and everything it reads: a caller hands it to a match launcher (hawk_device.h) with its sink, or its sites and guides to k_ot_bulge.
 struct OtFront {
   hawk_ctx* ctx;
-  uint64_t nsites;
-  int G, sp0;
-  bool seeded, pairs;
-  OtSeeds sd;
-  OtPairSeeds ps;
+  OtMatchPlan m;
 };
-// `want_seeds` false: all pairs whatever the guide count, no bucketed tables (hawk_offtarget_bulges, whose p->guidelen is the SITE's spacer).
+// `want_seeds` false: all pairs whatever the guide count, no bucketed tables (ot_bulge_front, whose p->guidelen is the SITE's spacer).
 static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, OtFront* f, bool want_seeds = true) {
   if (!hs || !p || !hs->has_meta || (n_guides && !guides2)) return HAWK_E_INVALID;
   if (hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
@@ -96,14 +94,15 @@ static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* gu
   // blocks, k_ot_match_seeded).  All pairs otherwise; HAWK_OT_ALLPAIRS=1 (read per call) forces them, the reference the parity
   // tests compare the seeded kernels against.
   const char* e_all = getenv("HAWK_OT_ALLPAIRS");
-  const int G = f->G = (int)p->guidelen, nb = (int)p->max_mm + 1;
-  f->sp0 = p->right ? (int)p->pamlen : 0;
-  const bool seeded = f->seeded = want_seeds && !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
-  const bool pairs = f->pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
-  OtSeeds& sd = f->sd;
-  OtPairSeeds& ps = f->ps;
-  memset(&sd, 0, sizeof(sd));
-  memset(&ps, 0, sizeof(ps));
+  const int G = (int)p->guidelen, nb = (int)p->max_mm + 1;
+  const bool seeded = want_seeds && !(e_all && e_all[0] == '1') && n_guides >= 64 && nb <= OT_MAX_BLOCKS && nb * 2 <= G;
+  const bool pairs = seeded && nb + 1 <= OT_MAX_BLOCKS;  // (max_mm + 2 <= G follows from 2 (max_mm + 1) <= G)
+  OtMatchPlan& m = f->m;
+  memset(&m, 0, sizeof(m));
+  m.kind = pairs ? OT_MATCH_PAIRS : seeded ? OT_MATCH_SEEDED : OT_MATCH_ALL;
+  m.n_guides = n_guides; m.guidelen = G; m.sp0 = p->right ? (int)p->pamlen : 0; m.max_mm = (int)p->max_mm;
+  OtSeeds& sd = m.sd;
+  OtPairSeeds& ps = m.ps;
   if (pairs) {
     ps.nb = nb + 1;
     ot_blocks(G, ps.nb, 4, ps.start, ps.klen, ps.pmask2);
@@ -136,12 +135,14 @@ static int ot_front(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* gu
   ScanTotals tot;
   HIPCHK(hipMemcpyAsync(&tot, hs->totals.p, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint64_t nsites = f->nsites = tot.n_keep;
+  const uint64_t nsites = m.n_sites = tot.n_keep;
   if ((rc = hs->sites.reserve(std::max<uint64_t>(nsites, 1) * sizeof(OtSite)))) return rc;
   HIPCHK(hipEventRecord(ev[2], ctx->stream));
   if (nsites) hawk_launch_ot_sites(ctx->stream, d, sp, hs->keepF.as<uint32_t>(), hs->keepR.as<uint32_t>(),
                                    hs->offsets.as<uint64_t>(), hs->sites.as<OtSite>());
   HIPCHK(hipEventRecord(ev[3], ctx->stream));
+  m.sites = hs->sites.as<OtSite>(); m.guides = hs->guides.as<uint64_t>();
+  m.goff = hs->otoff.as<uint32_t>(); m.gcode = hs->otcode.as<uint64_t>(); m.gid = hs->otid.as<uint32_t>();
   return HAWK_OK;
 }
 // events 0..4 -> hawk_ot_timing; the match kernel ran between events m0 and 4
@@ -160,19 +161,25 @@ static void ot_timing(hawk_hapset* hs, uint64_t nsites, hawk_ot_timing* timing, 
 }
 
 // The summaries' block in hs->otsum, sized by the guides alone: counters[2] | cfd_e4[n_guides] | CFD tables[336] |
-// hist[n_guides][stride].  otsum_begin reserves it, zeroes it and uploads the tables (both or neither) on the stream; otsum_end
-// downloads it once, synchronises and fills the caller's outputs.
+// hist[n_guides][stride].  No hits / othit buffer and no cap on this path: a hit ends in these sums inside the kernel that finds
+// it.  otsum_begin reserves the block, zeroes it, uploads the tables (both or neither) on the stream, points the sink's shared
+// fields (OtSumOut) into it and records event 5: the zeroing and the upload are not the kernel's time.  otsum_end, after the
+// kernel: event 4, one download, synchronise, the caller's outputs and the timing.
 struct OtSumBlock {
   char* base;
   size_t off_tab, off_hist, bytes;
   uint32_t n_guides, stride;
   bool tables;
-  unsigned long long* counters() const { return reinterpret_cast<unsigned long long*>(base); }
-  unsigned long long* cfd_e4() const { return reinterpret_cast<unsigned long long*>(base + 16); }
-  const double* tab() const { return tables ? reinterpret_cast<const double*>(base + off_tab) : nullptr; }
-  uint32_t* hist() const { return reinterpret_cast<uint32_t*>(base + off_hist); }
 };
-static int otsum_begin(hawk_hapset* hs, uint32_t n_guides, uint32_t stride, const double* cfd_mm, const double* cfd_pam, OtSumBlock* b) {
+// The summaries' argument rules.
+static int ot_sum_args(const hawk_ot_params* p, uint32_t n_guides, const double* cfd_mm, const double* cfd_pam, const uint32_t* out_hist,
+                       const int64_t* out_cfd_e4, const uint64_t* n_hits, const uint64_t* n_unscorable) {
+  if (!n_hits || !n_unscorable || (n_guides && !out_hist) || !cfd_mm != !cfd_pam || (cfd_mm && n_guides && !out_cfd_e4)) return HAWK_E_INVALID;
+  if (p && ((cfd_mm && p->pamlen < 2) || p->max_mm > 32)) return HAWK_E_UNSUPPORTED;  // the PAM table is keyed by PAM[-2:]; a window has <= 32 bases
+  return HAWK_OK;
+}
+static int otsum_begin(hawk_hapset* hs, uint32_t n_guides, uint32_t stride, const double* cfd_mm, const double* cfd_pam, OtSumBlock* b,
+                       OtSumOut* sm) {
   hipStream_t st = hs->ctx->stream;
   b->n_guides = n_guides; b->stride = stride; b->tables = cfd_mm != nullptr;
   b->off_tab = 16 + (size_t)n_guides * 8;
@@ -186,10 +193,19 @@ static int otsum_begin(hawk_hapset* hs, uint32_t n_guides, uint32_t stride, cons
     HIPCHK(hipMemcpyAsync(b->base + b->off_tab, cfd_mm, 320 * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->base + b->off_tab + 320 * 8, cfd_pam, 16 * 8, hipMemcpyHostToDevice, st));
   }
+  sm->counters = reinterpret_cast<unsigned long long*>(b->base);
+  sm->cfd_e4 = reinterpret_cast<unsigned long long*>(b->base + 16);
+  sm->tab = cfd_mm ? reinterpret_cast<const double*>(b->base + b->off_tab) : nullptr;
+  sm->hist = reinterpret_cast<uint32_t*>(b->base + b->off_hist);
+  sm->stride = stride;
+  HIPCHK(hipEventRecord(hs->ctx->ev[5], st));
   return HAWK_OK;
 }
-static int otsum_end(hawk_hapset* hs, const OtSumBlock& b, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable) {
+static int otsum_end(hawk_hapset* hs, const OtFront& f, const OtSumBlock& b, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits,
+                     uint64_t* n_unscorable, hawk_ot_timing* timing) {
   hipStream_t st = hs->ctx->stream;
+  HIPCHK(hipEventRecord(hs->ctx->ev[4], st));
+  HIPCHK(hipGetLastError());
   // one download: everything but the tables would do, the block is small either way
   std::vector<char> host(b.bytes);
   HIPCHK(hipMemcpyAsync(host.data(), b.base, b.bytes, hipMemcpyDeviceToHost, st));
@@ -202,6 +218,74 @@ static int otsum_end(hawk_hapset* hs, const OtSumBlock& b, uint32_t* out_hist, i
     memcpy(out_hist, host.data() + b.off_hist, (size_t)b.n_guides * b.stride * 4);
     if (out_cfd_e4 && b.tables) memcpy(out_cfd_e4, host.data() + 16, (size_t)b.n_guides * 8);
     else if (out_cfd_e4) memset(out_cfd_e4, 0, (size_t)b.n_guides * 8);
+  }
+  ot_timing(hs, f.m.n_sites, timing, 5);
+  return HAWK_OK;
+}
+
+// The front of the two bulged entry points: p->guidelen is the GUIDE's, the window scan is about the site's spacer.  Refusals in
+// this order: type / size (INVALID), lengths (UNSUPPORTED), then metadata, view, scan ranges and what ot_front refuses.
+static bool otb_kind_ok(uint32_t bulge_type, uint32_t bulge_size) { return bulge_type >= 1 && bulge_type <= 2 && bulge_size >= 1 && bulge_size <= 2; }
+static int ot_bulge_front(hawk_hapset* hs, const hawk_ot_params* p, uint32_t bulge_type, uint32_t bulge_size, const uint64_t* guides2,
+                          uint32_t n_guides, OtFront* f, int* G_out, int* dna_out) {
+  if (!hs || !p || !otb_kind_ok(bulge_type, bulge_size)) return HAWK_E_INVALID;
+  const bool dna = bulge_type == 1;
+  const uint32_t G = p->guidelen;
+  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;  // a guide code is 2 bits x 32; two end bases and one interior base stay paired
+  hawk_ot_params ps = *p;
+  const uint32_t Gs = ps.guidelen = dna ? G + bulge_size : G - bulge_size;  // the site's spacer: what the window scan is about
+  if (Gs + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
+  // the rows' scan ranges must be those of windows of Gs + pamlen bases (hawk_hapset_set_meta): a window that starts inside a
+  // range set for a shorter window would reach past its row
+  if (!hs->has_meta || hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
+  for (uint32_t h = 0; h < hs->n_hap; ++h)
+    if (hs->scan_stop[h] > hs->scan_start[h] && (int64_t)hs->scan_stop[h] - 1 + Gs + p->pamlen > (int64_t)hs->hap_len[h]) return HAWK_E_INVALID;
+  *G_out = (int)G;
+  *dna_out = dna ? 1 : 0;
+  return ot_front(hs, &ps, guides2, n_guides, f, false);
+}
+
+// What follows a list sink's kernel, Hit = OtHit or OtBulgeHit: event 4, the count read back (*n_out; HAWK_E_CAPACITY past `cap`),
+// the timing, then the hits and their sites - gathered into a compact array on the device - in two downloads behind one
+// synchronise, scattered into the columns asked for (each may be null; `gaps` exists for bulged hits only).
+struct OtCols {
+  uint32_t *guide, *row, *q;
+  uint8_t *strand, *mm;
+  uint64_t* code;
+  uint32_t* nmask;
+  uint64_t* gaps;
+};
+template <class Hit>
+static int ot_download(hawk_hapset* hs, const OtFront& f, const OtCols& o, uint64_t cap, uint64_t* n_out, hawk_ot_timing* timing) {
+  hipStream_t st = f.ctx->stream;
+  HIPCHK(hipEventRecord(f.ctx->ev[4], st));
+  HIPCHK(hipGetLastError());
+  unsigned long long nh = 0;
+  HIPCHK(hipMemcpyAsync(&nh, hs->misc.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  *n_out = nh;
+  ot_timing(hs, f.m.n_sites, timing);
+  if (nh > cap) return HAWK_E_CAPACITY;
+  if (!nh) return HAWK_OK;
+  std::vector<Hit> hh(nh);
+  std::vector<OtSite> ss(nh);
+  int rc;
+  if ((rc = hs->othit.reserve(nh * sizeof(OtSite)))) return rc;
+  hawk_launch_ot_gather(st, f.m.sites, hs->hits.as<Hit>(), nh, hs->othit.as<OtSite>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hh.data(), hs->hits.p, nh * sizeof(Hit), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(ss.data(), hs->othit.p, nh * sizeof(OtSite), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nh; ++i) {
+    if (o.guide) o.guide[i] = hh[i].guide;
+    if (o.row) o.row[i] = ss[i].row;
+    if (o.q) o.q[i] = ss[i].q & 0x7fffffffu;
+    if (o.strand) o.strand[i] = (uint8_t)(ss[i].q >> 31);
+    if (o.mm) o.mm[i] = (uint8_t)hh[i].mm;
+    if (o.code) o.code[i] = ss[i].code;
+    if (o.nmask) o.nmask[i] = ss[i].nmask;
+    if constexpr (std::is_same<Hit, OtBulgeHit>::value)
+      if (o.gaps) o.gaps[i] = hh[i].gaps;
   }
   return HAWK_OK;
 }
@@ -225,190 +309,62 @@ int hawk_offtarget_scan(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t
   OtFront f;
   int rc = ot_front(hs, p, guides2, n_guides, &f);
   if (rc) return rc;
-  hawk_ctx* ctx = f.ctx;
-  hipEvent_t* ev = ctx->ev;
-  const uint64_t nsites = f.nsites;
   if ((rc = hs->hits.reserve(std::max<uint64_t>(cap, 1) * sizeof(OtHit)))) return rc;
-  unsigned long long* d_nhits = hs->misc.as<unsigned long long>();
-  if (f.pairs) {
-    hawk_launch_ot_match_pairs(ctx->stream, hs->sites.as<OtSite>(), nsites, f.ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                               hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
-  } else if (f.seeded) {
-    hawk_launch_ot_match_seeded(ctx->stream, hs->sites.as<OtSite>(), nsites, f.sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                                hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
-  } else {
-    hawk_launch_ot_match(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, f.G, f.sp0,
-                         (int)p->max_mm, hs->hits.as<OtHit>(), cap, d_nhits);
-  }
-  HIPCHK(hipEventRecord(ev[4], ctx->stream));
-  HIPCHK(hipGetLastError());
-  unsigned long long nh = 0;
-  HIPCHK(hipMemcpyAsync(&nh, d_nhits, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *n_out = nh;
-  ot_timing(hs, nsites, timing);
-  if (nh > cap) return HAWK_E_CAPACITY;
-  if (!nh) return HAWK_OK;
-  std::vector<OtHit> hh(nh);
-  HIPCHK(hipMemcpy(hh.data(), hs->hits.p, nh * sizeof(OtHit), hipMemcpyDeviceToHost));
-  // the sites of the hits: gathered into a compact array on the device, one download
-  std::vector<OtSite> ss(nh);
-  if ((rc = hs->othit.reserve(nh * sizeof(OtSite)))) return rc;
-  hawk_launch_ot_gather(ctx->stream, hs->sites.as<OtSite>(), hs->hits.as<OtHit>(), nh, hs->othit.as<OtSite>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(ss.data(), hs->othit.p, nh * sizeof(OtSite), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (uint64_t i = 0; i < nh; ++i) {
-    if (out_guide) out_guide[i] = hh[i].guide;
-    if (out_row) out_row[i] = ss[i].row;
-    if (out_q) out_q[i] = ss[i].q & 0x7fffffffu;
-    if (out_strand) out_strand[i] = (uint8_t)(ss[i].q >> 31);
-    if (out_mm) out_mm[i] = (uint8_t)hh[i].mm;
-    if (out_code) out_code[i] = ss[i].code;
-    if (out_nmask) out_nmask[i] = ss[i].nmask;
-  }
-  return HAWK_OK;
+  hawk_launch_ot_match(f.ctx->stream, f.m, hs->hits.as<OtHit>(), cap, hs->misc.as<unsigned long long>());
+  return ot_download<OtHit>(hs, f, {out_guide, out_row, out_q, out_strand, out_mm, out_code, out_nmask, nullptr}, cap, n_out, timing);
 }
 
 int hawk_offtarget_bulges(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, uint32_t bulge_type,
                           uint32_t bulge_size, uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand,
                           uint8_t* out_mm, uint64_t* out_code, uint32_t* out_nmask, uint64_t* out_gaps, uint64_t cap, uint64_t* n_out,
                           hawk_ot_timing* timing) {
-  if (!n_out || !p || !hs) return HAWK_E_INVALID;
-  if (bulge_type < 1 || bulge_type > 2 || bulge_size < 1 || bulge_size > 2) return HAWK_E_INVALID;
-  const bool dna = bulge_type == 1;
-  const uint32_t G = p->guidelen;
-  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;  // a guide code is 2 bits x 32; two end bases and one interior base stay paired
-  hawk_ot_params ps = *p;
-  const uint32_t Gs = ps.guidelen = dna ? G + bulge_size : G - bulge_size;  // the site's spacer: what the window scan is about
-  if (Gs + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
-  // the rows' scan ranges must be those of windows of Gs + pamlen bases (hawk_hapset_set_meta): a window that starts inside a
-  // range set for a shorter window would reach past its row
-  if (!hs->has_meta) return HAWK_E_INVALID;
-  for (uint32_t h = 0; h < hs->n_hap; ++h)
-    if (hs->scan_stop[h] > hs->scan_start[h] && (int64_t)hs->scan_stop[h] - 1 + Gs + p->pamlen > (int64_t)hs->hap_len[h]) return HAWK_E_INVALID;
+  if (!n_out) return HAWK_E_INVALID;
   OtFront f;
-  int rc = ot_front(hs, &ps, guides2, n_guides, &f, false);
+  int G, dna;
+  int rc = ot_bulge_front(hs, p, bulge_type, bulge_size, guides2, n_guides, &f, &G, &dna);
   if (rc) return rc;
-  hawk_ctx* ctx = f.ctx;
-  hipEvent_t* ev = ctx->ev;
-  const uint64_t nsites = f.nsites;
   // sized by the rows asked for and (ot_front) by the guides: nothing here grows with the placements
   if ((rc = hs->hits.reserve(std::max<uint64_t>(cap, 1) * sizeof(OtBulgeHit)))) return rc;
-  unsigned long long* d_nhits = hs->misc.as<unsigned long long>();
-  hawk_launch_ot_bulge(ctx->stream, hs->sites.as<OtSite>(), nsites, hs->guides.as<uint64_t>(), n_guides, (int)G, f.sp0, (int)p->max_mm,
-                       dna ? 1 : 0, (int)bulge_size, hs->hits.as<OtBulgeHit>(), cap, d_nhits);
-  HIPCHK(hipEventRecord(ev[4], ctx->stream));
-  HIPCHK(hipGetLastError());
-  unsigned long long nh = 0;
-  HIPCHK(hipMemcpyAsync(&nh, d_nhits, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *n_out = nh;
-  ot_timing(hs, nsites, timing);
-  if (nh > cap) return HAWK_E_CAPACITY;
-  if (!nh) return HAWK_OK;
-  std::vector<OtBulgeHit> hh(nh);
-  std::vector<OtSite> ss(nh);
-  if ((rc = hs->othit.reserve(nh * sizeof(OtSite)))) return rc;
-  hawk_launch_ot_bulge_gather(ctx->stream, hs->sites.as<OtSite>(), hs->hits.as<OtBulgeHit>(), nh, hs->othit.as<OtSite>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(hh.data(), hs->hits.p, nh * sizeof(OtBulgeHit), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ss.data(), hs->othit.p, nh * sizeof(OtSite), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (uint64_t i = 0; i < nh; ++i) {
-    if (out_guide) out_guide[i] = hh[i].guide;
-    if (out_row) out_row[i] = ss[i].row;
-    if (out_q) out_q[i] = ss[i].q & 0x7fffffffu;
-    if (out_strand) out_strand[i] = (uint8_t)(ss[i].q >> 31);
-    if (out_mm) out_mm[i] = (uint8_t)hh[i].mm;
-    if (out_code) out_code[i] = ss[i].code;
-    if (out_nmask) out_nmask[i] = ss[i].nmask;
-    if (out_gaps) out_gaps[i] = hh[i].gaps;
-  }
-  return HAWK_OK;
+  hawk_launch_ot_bulge(f.ctx->stream, f.m.sites, f.m.n_sites, f.m.guides, n_guides, G, f.m.sp0, f.m.max_mm, dna, (int)bulge_size,
+                       hs->hits.as<OtBulgeHit>(), cap, hs->misc.as<unsigned long long>());
+  return ot_download<OtBulgeHit>(hs, f, {out_guide, out_row, out_q, out_strand, out_mm, out_code, out_nmask, out_gaps}, cap, n_out, timing);
 }
 
 int hawk_offtarget_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, const double* cfd_mm,
                            const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4, uint64_t* n_hits, uint64_t* n_unscorable,
                            hawk_ot_timing* timing) {
-  if (!n_hits || !n_unscorable || (n_guides && !out_hist) || !cfd_mm != !cfd_pam || (cfd_mm && n_guides && !out_cfd_e4)) return HAWK_E_INVALID;
-  if (p && ((cfd_mm && p->pamlen < 2) || p->max_mm > 32)) return HAWK_E_UNSUPPORTED;  // the PAM table is keyed by PAM[-2:]; a window has <= 32 bases
-  OtFront f;
-  int rc = ot_front(hs, p, guides2, n_guides, &f);
+  int rc = ot_sum_args(p, n_guides, cfd_mm, cfd_pam, out_hist, out_cfd_e4, n_hits, n_unscorable);
   if (rc) return rc;
-  hawk_ctx* ctx = f.ctx;
-  // One block, sized by the guides alone: counters[2] | cfd_e4[n_guides] | CFD tables[336] | hist[n_guides][max_mm + 1].
-  // No hits / othit buffer is reserved on this path: a hit ends in these sums inside the match kernel.
+  OtFront f;
+  if ((rc = ot_front(hs, p, guides2, n_guides, &f))) return rc;
   OtSumBlock blk;
-  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk))) return rc;
   OtSummary sm;
-  sm.sites = hs->sites.as<OtSite>();
-  sm.tab = blk.tab();
-  sm.hist = blk.hist();
-  sm.cfd_e4 = blk.cfd_e4();
-  sm.counters = blk.counters();
-  sm.stride = blk.stride;
-  sm.sp0 = f.sp0;
-  sm.pam2 = (p->right ? 0 : f.G) + (int)p->pamlen - 2;
-  sm.ncmp = std::min(f.G, 20);
-  HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));  // the zeroing and the table upload are not the match kernel's time
-  if (f.pairs) {
-    hawk_launch_ot_match_pairs_sum(ctx->stream, sm.sites, f.nsites, f.ps, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                                   hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
-  } else if (f.seeded) {
-    hawk_launch_ot_match_seeded_sum(ctx->stream, sm.sites, f.nsites, f.sd, hs->otoff.as<uint32_t>(), hs->otcode.as<uint64_t>(),
-                                    hs->otid.as<uint32_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
-  } else {
-    hawk_launch_ot_match_sum(ctx->stream, sm.sites, f.nsites, hs->guides.as<uint64_t>(), n_guides, f.G, f.sp0, (int)p->max_mm, sm);
-  }
-  HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
-  HIPCHK(hipGetLastError());
-  if ((rc = otsum_end(hs, blk, out_hist, out_cfd_e4, n_hits, n_unscorable))) return rc;
-  ot_timing(hs, f.nsites, timing, 5);
-  return HAWK_OK;
+  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk, &sm))) return rc;
+  sm.sites = f.m.sites;
+  sm.sp0 = f.m.sp0;
+  sm.pam2 = (p->right ? 0 : f.m.guidelen) + (int)p->pamlen - 2;
+  sm.ncmp = std::min(f.m.guidelen, 20);
+  hawk_launch_ot_match_sum(f.ctx->stream, f.m, sm);
+  return otsum_end(hs, f, blk, out_hist, out_cfd_e4, n_hits, n_unscorable, timing);
 }
 
 int hawk_offtarget_bulge_summary(hawk_hapset* hs, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides, uint32_t bulge_type,
                                  uint32_t bulge_size, const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
                                  uint64_t* n_hits, uint64_t* n_unscorable, hawk_ot_timing* timing) {
-  // the argument rules of hawk_offtarget_summary ...
-  if (!hs || !p || !n_hits || !n_unscorable || (n_guides && !out_hist) || !cfd_mm != !cfd_pam || (cfd_mm && n_guides && !out_cfd_e4))
-    return HAWK_E_INVALID;
-  if (bulge_type < 1 || bulge_type > 2 || bulge_size < 1 || bulge_size > 2) return HAWK_E_INVALID;
-  if ((cfd_mm && p->pamlen < 2) || p->max_mm > 32) return HAWK_E_UNSUPPORTED;
-  // ... and the front half of hawk_offtarget_bulges: p->guidelen is the GUIDE's, the window scan is about the site's spacer
-  const bool dna = bulge_type == 1;
-  const uint32_t G = p->guidelen;
-  if (G > 32 || G < bulge_size + 3) return HAWK_E_UNSUPPORTED;
-  hawk_ot_params ps = *p;
-  const uint32_t Gs = ps.guidelen = dna ? G + bulge_size : G - bulge_size;
-  if (Gs + p->pamlen > 32) return HAWK_E_UNSUPPORTED;
-  if (!hs->has_meta || hs->vplan) return HAWK_E_INVALID;  // a plan view holds no planes
-  for (uint32_t h = 0; h < hs->n_hap; ++h)
-    if (hs->scan_stop[h] > hs->scan_start[h] && (int64_t)hs->scan_stop[h] - 1 + Gs + p->pamlen > (int64_t)hs->hap_len[h]) return HAWK_E_INVALID;
-  OtFront f;
-  int rc = ot_front(hs, &ps, guides2, n_guides, &f, false);
+  // a missing handle and a bulge that is none are refused before the summaries' UNSUPPORTED
+  if (!hs || !p || !otb_kind_ok(bulge_type, bulge_size)) return HAWK_E_INVALID;
+  int rc = ot_sum_args(p, n_guides, cfd_mm, cfd_pam, out_hist, out_cfd_e4, n_hits, n_unscorable);
   if (rc) return rc;
-  hawk_ctx* ctx = f.ctx;
-  // No hits / othit buffer and no cap on this path: a row ends in the block's sums inside k_ot_bulge.
+  OtFront f;
+  int G, dna;
+  if ((rc = ot_bulge_front(hs, p, bulge_type, bulge_size, guides2, n_guides, &f, &G, &dna))) return rc;
   OtSumBlock blk;
-  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk))) return rc;
   OtBulgeSummary sm;
-  sm.tab = blk.tab();
-  sm.hist = blk.hist();
-  sm.cfd_e4 = blk.cfd_e4();
-  sm.counters = blk.counters();
-  sm.stride = blk.stride;
+  if ((rc = otsum_begin(hs, n_guides, p->max_mm + 1, cfd_mm, cfd_pam, &blk, &sm))) return rc;
   sm.pamlen = (int32_t)p->pamlen;
   sm.right = p->right ? 1 : 0;
-  HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));  // the zeroing and the table upload are not the kernel's time
-  hawk_launch_ot_bulge_sum(ctx->stream, hs->sites.as<OtSite>(), f.nsites, hs->guides.as<uint64_t>(), n_guides, (int)G, f.sp0, (int)p->max_mm,
-                           dna ? 1 : 0, (int)bulge_size, sm);
-  HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
-  HIPCHK(hipGetLastError());
-  if ((rc = otsum_end(hs, blk, out_hist, out_cfd_e4, n_hits, n_unscorable))) return rc;
-  ot_timing(hs, f.nsites, timing, 5);
-  return HAWK_OK;
+  hawk_launch_ot_bulge_sum(f.ctx->stream, f.m.sites, f.m.n_sites, f.m.guides, n_guides, G, f.m.sp0, f.m.max_mm, dna, (int)bulge_size, sm);
+  return otsum_end(hs, f, blk, out_hist, out_cfd_e4, n_hits, n_unscorable, timing);
 }
 
 // ---------------------------------------------------------------------------- the off-targets table as text (hawk_ottext.hip)

@@ -234,57 +234,60 @@ struct OtPairSeeds {
   uint8_t pi[OT_MAX_PAIRS], pj[OT_MAX_PAIRS];
   uint32_t off_base[OT_MAX_PAIRS];
 };
-void hawk_launch_ot_match_pairs(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
-                                const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                OtHit* hits, uint64_t cap, unsigned long long* n_hits);
-
-// launch wrappers
-void hawk_launch_ot_onehot(hipStream_t st, uint32_t* const* plane, uint64_t nwords);
-void hawk_launch_ot_sites(hipStream_t st, const HapSetDev& hs, const ScanParams& p, const uint32_t* keepF, const uint32_t* keepR,
-                          const uint64_t* offsets, OtSite* sites);
-void hawk_launch_ot_match(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
-                          int guidelen, int sp0, int max_mm, OtHit* hits, uint64_t cap, unsigned long long* n_hits);
-void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
-                                 const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                 OtHit* hits, uint64_t cap, unsigned long long* n_hits);
-void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const OtHit* hits, uint64_t n_hits, OtSite* out);
-// Bulged sites (hawk_otbulge.hip: k_ot_bulge).  `sites`: the records of a scan whose window is Gs + pamlen bases, Gs = guidelen +
-// bsize (dna) or guidelen - bsize (RNA bulge); one launch per (type, size).  A row per (site, guide) whose best placement of the
-// bsize gaps has <= max_mm mismatches; gaps: bit i = position i (of the site spacer for DNA bulges, of the guide for RNA bulges)
-// faces nothing.  *n_hits (zeroed) counts past cap.
-struct OtBulgeHit { uint64_t site; uint32_t guide, mm, gaps, pad; };
-void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
-                          int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits);
-void hawk_launch_ot_bulge_gather(hipStream_t st, const OtSite* sites, const OtBulgeHit* hits, uint64_t n_hits, OtSite* out);
-// k_ot_bulge with the summary's sink (hawk_otbulge.hip: OtbSumSink): where a bulged row goes instead of hits[].
-struct OtBulgeSummary {
-  const double* tab;             // CFD tables mm[20][4][4] + pam[16]; nullptr: counts only
-  uint32_t* hist;                // [n_guides][stride], zeroed
-  unsigned long long* cfd_e4;    // [n_guides], zeroed: per-guide sum of the rows' CFD in units of 1e-4
-  unsigned long long* counters;  // [0] rows, [1] rows with an ambiguous base under a CFD lookup; zeroed
-  uint32_t stride;               // max_mm + 1
-  int32_t pamlen, right;
-};
-void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
-                              int sp0, int max_mm, int dna, int bsize, const OtBulgeSummary& sm);
-// The match kernels with the summary's hit sink (hawk_offtarget.hip: OtSumSink): where a hit goes instead of hits[].
-struct OtSummary {
+// Which match kernel a call runs and what it reads (chosen by ot_front, hawk_api_offtarget.hip): all pairs (k_ot_match: `guides`),
+// single-block seeds (k_ot_match_seeded: sd + the bucketed tables goff / gcode / gid) or pair seeds (k_ot_match_pairs: ps + the
+// tables).  The bulge kernels read the same sites and guides; their guidelen is the GUIDE's, this one the window scan's spacer.
+enum OtMatchKind { OT_MATCH_ALL, OT_MATCH_SEEDED, OT_MATCH_PAIRS };
+struct OtMatchPlan {
+  OtMatchKind kind;
+  OtSeeds sd;
+  OtPairSeeds ps;
   const OtSite* sites;
+  uint64_t n_sites;
+  const uint64_t* guides;
+  uint32_t n_guides;
+  const uint32_t* goff;
+  const uint64_t* gcode;
+  const uint32_t* gid;
+  int guidelen, sp0, max_mm;
+};
+// What the summaries' sinks share (OtSumSink, hawk_offtarget.hip; OtbSumSink, hawk_otbulge.hip): where a hit goes instead of hits[].
+struct OtSumOut {
   const double* tab;             // CFD tables mm[20][4][4] + pam[16]; nullptr: counts only
   uint32_t* hist;                // [n_guides][stride], zeroed
   unsigned long long* cfd_e4;    // [n_guides], zeroed: per-guide sum of round(CFD, 4) in units of 1e-4 (two's complement)
   unsigned long long* counters;  // [0] hits, [1] hits with an ambiguous base under a CFD lookup; zeroed
   uint32_t stride;               // max_mm + 1
-  int32_t sp0, pam2, ncmp;       // window positions of spacer base 0 and of PAM[-2]; min(guidelen, 20)
+  OtSumOut() {}  // user-provided for the layout alone: the ABI then starts a derived struct's fields right behind `stride`
 };
-void hawk_launch_ot_match_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
-                              int guidelen, int sp0, int max_mm, const OtSummary& sm);
-void hawk_launch_ot_match_seeded_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
-                                     const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                     const OtSummary& sm);
-void hawk_launch_ot_match_pairs_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
-                                    const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                    const OtSummary& sm);
+struct OtSumSites { const OtSite* sites; };
+struct OtSummary : OtSumSites, OtSumOut {  // sites, then OtSumOut's fields
+  int32_t sp0, pam2, ncmp;                 // window positions of spacer base 0 and of PAM[-2]; min(guidelen, 20)
+};
+struct OtBulgeSummary : OtSumOut {
+  int32_t pamlen, right;
+};
+static_assert(sizeof(OtSummary) == 56 && sizeof(OtBulgeSummary) == 48, "kernel arguments: the layouts the sinks were compiled for");
+// Bulged sites (hawk_otbulge.hip: k_ot_bulge).  `sites`: the records of a scan whose window is Gs + pamlen bases, Gs = guidelen +
+// bsize (dna) or guidelen - bsize (RNA bulge); one launch per (type, size).  A row per (site, guide) whose best placement of the
+// bsize gaps has <= max_mm mismatches; gaps: bit i = position i (of the site spacer for DNA bulges, of the guide for RNA bulges)
+// faces nothing.  *n_hits (zeroed) counts past cap.
+struct OtBulgeHit { uint64_t site; uint32_t guide, mm, gaps, pad; };
+
+// launch wrappers
+void hawk_launch_ot_onehot(hipStream_t st, uint32_t* const* plane, uint64_t nwords);
+void hawk_launch_ot_sites(hipStream_t st, const HapSetDev& hs, const ScanParams& p, const uint32_t* keepF, const uint32_t* keepR,
+                          const uint64_t* offsets, OtSite* sites);
+// the plan's match kernel with the list sink (hits[] behind a counter that keeps counting past cap) / the summary's sink
+void hawk_launch_ot_match(hipStream_t st, const OtMatchPlan& m, OtHit* hits, uint64_t cap, unsigned long long* n_hits);
+void hawk_launch_ot_match_sum(hipStream_t st, const OtMatchPlan& m, const OtSummary& sm);
+// the sites of the hits as a compact array; Hit = OtHit or OtBulgeHit (both begin with the site's index)
+template <class Hit>
+void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const Hit* hits, uint64_t n_hits, OtSite* out);
+void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
+                          int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits);
+void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
+                              int sp0, int max_mm, int dna, int bsize, const OtBulgeSummary& sm);
 void hawk_launch_pack(hipStream_t st, const uint8_t* ascii, const uint64_t* seq_off, uint32_t hap0, uint32_t n_hap_batch,
                       uint64_t batch_base, const uint32_t* hap_len, uint32_t S, uint32_t* const* plane,
                       unsigned long long* bad_index);

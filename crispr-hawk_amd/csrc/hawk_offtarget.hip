@@ -189,12 +189,6 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match(const OtSite* __restric
     }
   }
 }
-void hawk_launch_ot_match(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
-                          int guidelen, int sp0, int max_mm, OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
-                     n_sites, guides, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
-}
 
 // Seeded match.  Each thread owns one site and visits, per block, the bucket of guides whose key bases equal the
 // site's (a gather from the L2-resident bucketed guide table).  A pair that agrees in the key bases of several
@@ -230,13 +224,6 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_seeded(const OtSite* __
       sink(i, gi[t], gc[t], mm);
     }
   }
-}
-void hawk_launch_ot_match_seeded(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
-                                 const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                 OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_seeded<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st,
-                     sites, n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
 }
 
 // Pair seeds, candidates dealt evenly.  A wave takes 64 sites.  Per pair of blocks every lane looks its site's bucket up (two
@@ -320,41 +307,40 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_ot_match_pairs(const OtSite* __r
     }
   }
 }
-void hawk_launch_ot_match_pairs(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
-                                const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_pairs<OtListSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
-                     n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtListSink{hits, cap, n_hits});
-}
 
-// The same three kernels with the summary's sink (hawk_offtarget_summary).
-void hawk_launch_ot_match_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides,
-                              int guidelen, int sp0, int max_mm, const OtSummary& sm) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
-                     n_sites, guides, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
+// The plan's match kernel with a sink: one thread per site whichever the kernel.
+template <class Sink>
+static void ot_match_launch(hipStream_t st, const OtMatchPlan& m, const Sink& sink) {
+  if (!m.n_sites || !m.n_guides) return;
+  const dim3 grid((uint32_t)((m.n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), block(HAWK_BLOCK);
+  switch (m.kind) {
+    case OT_MATCH_PAIRS:
+      hipLaunchKernelGGL(k_ot_match_pairs<Sink>, grid, block, 0, st, m.sites, m.n_sites, m.ps, m.goff, m.gcode, m.gid, m.n_guides,
+                         m.guidelen, m.sp0, m.max_mm, sink);
+      break;
+    case OT_MATCH_SEEDED:
+      hipLaunchKernelGGL(k_ot_match_seeded<Sink>, grid, block, 0, st, m.sites, m.n_sites, m.sd, m.goff, m.gcode, m.gid, m.n_guides,
+                         m.guidelen, m.sp0, m.max_mm, sink);
+      break;
+    case OT_MATCH_ALL:
+      hipLaunchKernelGGL(k_ot_match<Sink>, grid, block, 0, st, m.sites, m.n_sites, m.guides, m.n_guides, m.guidelen, m.sp0, m.max_mm, sink);
+      break;
+  }
 }
-void hawk_launch_ot_match_seeded_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtSeeds& sd, const uint32_t* goff,
-                                     const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                     const OtSummary& sm) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_seeded<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st,
-                     sites, n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
+void hawk_launch_ot_match(hipStream_t st, const OtMatchPlan& m, OtHit* hits, uint64_t cap, unsigned long long* n_hits) {
+  ot_match_launch(st, m, OtListSink{hits, cap, n_hits});
 }
-void hawk_launch_ot_match_pairs_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const OtPairSeeds& sd, const uint32_t* goff,
-                                    const uint64_t* gcode, const uint32_t* gid, uint32_t n_guides, int guidelen, int sp0, int max_mm,
-                                    const OtSummary& sm) {
-  if (!n_sites || !n_guides) return;
-  hipLaunchKernelGGL(k_ot_match_pairs<OtSumSink>, dim3((uint32_t)((n_sites + HAWK_BLOCK - 1) / HAWK_BLOCK)), dim3(HAWK_BLOCK), 0, st, sites,
-                     n_sites, sd, goff, gcode, gid, n_guides, guidelen, sp0, max_mm, OtSumSink{sm});
-}
+void hawk_launch_ot_match_sum(hipStream_t st, const OtMatchPlan& m, const OtSummary& sm) { ot_match_launch(st, m, OtSumSink{sm}); }
 
-__global__ __launch_bounds__(256) void k_ot_gather(const OtSite* __restrict__ sites, const OtHit* __restrict__ hits, uint64_t n_hits,
+template <class Hit>
+__global__ __launch_bounds__(256) void k_ot_gather(const OtSite* __restrict__ sites, const Hit* __restrict__ hits, uint64_t n_hits,
                                                    OtSite* __restrict__ out) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n_hits) out[i] = sites[hits[i].site];
 }
-void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const OtHit* hits, uint64_t n_hits, OtSite* out) {
-  if (n_hits) hipLaunchKernelGGL(k_ot_gather, dim3((uint32_t)((n_hits + 255) / 256)), dim3(256), 0, st, sites, hits, n_hits, out);
+template <class Hit>
+void hawk_launch_ot_gather(hipStream_t st, const OtSite* sites, const Hit* hits, uint64_t n_hits, OtSite* out) {
+  if (n_hits) hipLaunchKernelGGL(k_ot_gather<Hit>, dim3((uint32_t)((n_hits + 255) / 256)), dim3(256), 0, st, sites, hits, n_hits, out);
 }
+template void hawk_launch_ot_gather<OtHit>(hipStream_t, const OtSite*, const OtHit*, uint64_t, OtSite*);
+template void hawk_launch_ot_gather<OtBulgeHit>(hipStream_t, const OtSite*, const OtBulgeHit*, uint64_t, OtSite*);

@@ -173,12 +173,3 @@ void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_si
   }
 #undef OTB_LAUNCH
 }
-
-__global__ __launch_bounds__(256) void k_ot_bulge_gather(const OtSite* __restrict__ sites, const OtBulgeHit* __restrict__ hits, uint64_t n_hits,
-                                                         OtSite* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n_hits) out[i] = sites[hits[i].site];
-}
-void hawk_launch_ot_bulge_gather(hipStream_t st, const OtSite* sites, const OtBulgeHit* hits, uint64_t n_hits, OtSite* out) {
-  if (n_hits) hipLaunchKernelGGL(k_ot_bulge_gather, dim3((uint32_t)((n_hits + 255) / 256)), dim3(256), 0, st, sites, hits, n_hits, out);
-}

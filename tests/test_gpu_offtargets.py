@@ -615,3 +615,74 @@ def test_bulged_offtargets_at_scale():
                   key=lambda t: (t[0], t[1], t[2], ci[t[3]], t[4], t[5] == "-"))
     chosen = set(sample)
     assert [t[:8] for t in full if t[0] in chosen] == want and len(want) >= 12
+
+
+# ---- hawk_offtarget_scan at its capacity seam, once per match kernel ------------------------------------------------------------
+def _raw_scan(idx, guides, pam, right, max_mm, cap, columns=True):
+    """hawk_offtarget_scan as the ABI has it: (status, *n_out, the rows written as sorted tuples); `columns` false: every optional
+    output column is null"""
+    import ctypes as C
+
+    from crisprhawk_hip import _lib
+    from crisprhawk_hip.genome import encode_guides
+    from crisprhawk_hip.hapset import _p
+    g2 = encode_guides(guides)
+    par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), idx.guidelen, int(bool(right)), max_mm)
+    o = {k: np.zeros(max(cap, 1), t) for k, t in GenomeIndex.OT_COLUMNS[:7]}  # guide row q strand mm code nmask
+    n = C.c_uint64(0)
+    rc = idx.ds._L.hawk_offtarget_scan(idx.ds._h, C.byref(par), _p(g2), len(g2), *[_p(a) if columns else None for a in o.values()],
+                                       C.c_uint64(cap), C.byref(n), None)
+    k = min(int(n.value), cap) if rc == _lib.HAWK_OK else 0
+    return rc, int(n.value), sorted(zip(*[a[:k].tolist() for a in o.values()]))
+
+
+_CAP_CACHE = {}
+
+
+def _cap_case():
+    """5 001 random bases in two contigs cut into rows of 2 048, near-copies of the first guides planted; 64 guides of 20 bases"""
+    if not _CAP_CACHE:
+        rng = np.random.default_rng(5309)
+        guides = [synth.random_sequence(rng, 20) for _ in range(64)]
+        contigs = {}
+        for name, n in (("c1", 3500), ("c2", 1501)):
+            g = list(synth.random_sequence(rng, n, iupac_frac=0.001))
+            for gd in guides[:4]:
+                _plant(rng, g, gd, "TGG", False, 3, 3)
+            contigs[name] = "".join(g)
+        _CAP_CACHE["case"] = (guides, contigs, GenomeIndex(contigs, 20, 3, piece=2048))
+    return _CAP_CACHE["case"]
+
+
+@pytest.mark.parametrize("kernel,n_guides,max_mm", [("all_pairs", 8, 3), ("pair_seeds", 64, 3), ("single_block", 64, 7)])
+def test_scan_capacity_contract(kernel, n_guides, max_mm, monkeypatch):
+    """hawk_offtarget_scan raw, one call per match kernel (8 guides: all pairs; 64 guides at max_mm 3: pair seeds; at max_mm 7 the
+    max_mm + 2 blocks of pair seeds exceed OT_MAX_BLOCKS: single-block seeds).  The rows of a run with ample room are the
+    oracle's; cap one below the need and cap = 0: HAWK_E_CAPACITY with the exact need; cap = need: the same rows; every optional
+    column null: OK with the same count."""
+    from crisprhawk_hip import _lib
+    from crisprhawk_hip.genome import decode_window
+    monkeypatch.delenv("HAWK_OT_ALLPAIRS", raising=False)
+    guides, contigs, idx = _cap_case()
+    guides = guides[:n_guides]
+    pam = PAM("NGG", False, True)
+    pam.encode(0)
+    want = sorted((int(r["guide"]), name, int(r["pos"]), int(r["strand"]), int(r["mm"]))
+                  for name, seq in contigs.items() for r in ora.offtargets(seq, guides, "NGG", False, max_mm))
+    need = len(want)
+    assert need >= 2 and len(set(want)) == need
+    rc, n, ample = _raw_scan(idx, guides, pam, False, max_mm, 4096)
+    assert rc == _lib.HAWK_OK and n == need == len(ample)
+    assert sorted((g, idx.rows[row][0], idx.rows[row][1] + q, strand, mm) for g, row, q, strand, mm, _code, _nmask in ample) == want
+    for g, row, q, strand, _mm, code, nmask in ample:  # the window as the genome has it, in guide orientation
+        name, off, _own = idx.rows[row]
+        w = contigs[name][off + q:off + q + 23].upper()
+        w = ora.revcomp(w) if strand else w
+        assert decode_window(code, nmask, 23) == "".join(c if c in "ACGT" else "N" for c in w)
+    for cap in (need - 1, 0):
+        rc, n, none = _raw_scan(idx, guides, pam, False, max_mm, cap)
+        assert (rc, n, none) == (_lib.HAWK_E_CAPACITY, need, [])
+    rc, n, rows = _raw_scan(idx, guides, pam, False, max_mm, need)
+    assert rc == _lib.HAWK_OK and n == need and set(rows) == set(ample) and len(rows) == need
+    rc, n, _rows = _raw_scan(idx, guides, pam, False, max_mm, need, columns=False)
+    assert rc == _lib.HAWK_OK and n == need
