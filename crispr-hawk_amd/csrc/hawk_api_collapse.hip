@@ -2,164 +2,186 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <new>
-#include <unordered_map>
-#include <vector>
 
 #include "hawk_host.h"
 
 extern "C" {
 
-static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms);
-static int collapse_by_templates(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms);
-int hawk_table_collapse_ex(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
-  if (!t || !n_groups || !t->hs || hawk_table_stale(t)) return HAWK_E_INVALID;
-  if (flank_up > HAWK_PAD || flank_down > HAWK_PAD) return HAWK_E_UNSUPPORTED;
-  // A table the cluster search wrote is grouped on its template rows
-  if (t->by_cluster && t->n_rows) return collapse_by_templates(t, flank_up, flank_down, n_groups, kernel_ms);
-  return collapse_rows(t, flank_up, flank_down, n_groups, kernel_ms);
-}
-static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
-  hawk_hapset* hs = t->hs;
-  hawk_ctx* ctx = hs->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint64_t n = t->n_rows;
-  t->collapsed = false;
-  *n_groups = 0;
-  if (kernel_ms) *kernel_ms = 0.f;
-  hs->collapse_gen = t->gen;
-  if (n == 0) { t->n_groups = 0; t->collapsed = true; return HAWK_OK; }
-  if (n > 0xffffffffull || hs->max_gen - hs->min_gen > 0xffffffffll) return HAWK_E_UNSUPPORTED;
-  unsigned end_bit = 32;
-  while (end_bit < 64 && ((uint64_t)(hs->max_gen - hs->min_gen) >> (end_bit - 32)) != 0) ++end_bit;
-  // low hash bits the sort leaves out: start bits + strand + hash fill whole 8-bit passes, at least 24 hash bits stay
-  const unsigned pos_bits = end_bit - 31;  // start - base, strand
-  const unsigned hash_bits = std::min(31u, (pos_bits + 24 + 7) / 8 * 8 - pos_bits);
-  const unsigned begin_bit = 31 - hash_bits;
-  const size_t temp_bytes = hawk_collapse_temp_bytes(n, begin_bit, end_bit);
-  int rc;
-  if ((rc = hs->ckeys.reserve(2 * n * 8)) || (rc = hs->cvals.reserve(2 * n * 4)) || (rc = hs->cflags.reserve(n * 4)) ||
-      (rc = hs->cgidx.reserve(n * 4)) || (rc = hs->ctemp.reserve(temp_bytes + 16)) || (rc = hs->cgoff.reserve((n + 1) * 8)) ||
-      (rc = hs->cgc.reserve(2 * n)) || (rc = hs->ccnt.reserve(32)))
-    return rc;
-  // Rows are grouped on (start, strand, 63 hash bits of the rest) and the grouping is then VERIFIED: every member against
-  // its group's first member on the full key (k_collapse_verify).  A mismatch - two different rows under one hash, never
-  // seen - sends the call through the exact path (full 64-byte keys compared neighbour by neighbour), which
-  // HAWK_COLLAPSE_EXACT=1 forces from the start.  The verification cannot be switched off in the product library.
-  const char* ex = getenv("HAWK_COLLAPSE_EXACT");
+// HAWK_COLLAPSE_EXACT=1 groups on the full keys from the start, HAWK_COLLAPSE_MODE=sort / hash overrides the choice between the
+// sort and the hash table; read once per call.
+struct CollapsePolicy {
+  bool exact, force_hash, force_sort;
+  bool verify, weak;  // the product library can neither skip the verification nor weaken the hash
+  static CollapsePolicy read() {
+    const char *ex = getenv("HAWK_COLLAPSE_EXACT"), *md = getenv("HAWK_COLLAPSE_MODE");
+    CollapsePolicy p = {ex && ex[0] == '1', md && md[0] == 'h', md && md[0] == 's', true, false};
 #ifdef HAWK_TEST_HOOKS  // libhawk_hip_hooks.so only (tests/hooks_collapse_check.py): a 4-bit hash so that the verify pass HAS collisions
-  const char* vf = getenv("HAWK_COLLAPSE_VERIFY");  // to catch, and a way to look at the grouping without it
-  const char* wk = getenv("HAWK_COLLAPSE_WEAK_HASH");
-  const bool verify = !(vf && vf[0] == '0'), weak = wk && wk[0] == '1';
-#else
-  const bool verify = true, weak = false;
+    const char* vf = getenv("HAWK_COLLAPSE_VERIFY");  // to catch, and a way to look at the grouping without it
+    const char* wk = getenv("HAWK_COLLAPSE_WEAK_HASH");
+    p.verify = !(vf && vf[0] == '0');
+    p.weak = wk && wk[0] == '1';
 #endif
-  bool exact = ex && ex[0] == '1';
-  for (int round = 0; round < 2; ++round, exact = true) {
-  if (exact && (rc = hs->cfull.reserve(hawk_collapse_full_bytes(n)))) return rc;
-  // ---- grouping through a hash table (hawk_collapse.hip) when groups are expected to be far fewer than rows: the sort
-  // below then only orders (group number, row).  HAWK_COLLAPSE_MODE=sort / hash overrides the choice; a table that turns
-  // out too small, or an unlucky seed twice, falls through to the sort.
-  bool verified_bad = false;
-  {
-    const char* md = getenv("HAWK_COLLAPSE_MODE");
-    const bool force_hash = md && md[0] == 'h', force_sort = md && md[0] == 's';
-    const uint64_t g_est = hs->last_groups ? hs->last_groups + hs->last_groups / 4 : n / 16;
-    uint64_t C = 1024;
-    while (C < 2 * g_est) C <<= 1;  // at most half full (with the 25 % head room of g_est)
-    const bool fits = C <= (1ull << 26) && hs->max_gen - hs->min_gen < 0xffffffffll;
-    const bool want = !exact && !weak && !force_sort && fits && (force_hash || (n >= (1u << 20) && (hs->last_groups == 0 || hs->last_groups * 8 <= n)));
-    if (want) {
-      const size_t tb = hawk_collapse_hash_temp_bytes(n, (uint32_t)C);
-      if ((rc = hs->ctable.reserve(C * 16)) || (rc = hs->cocc.reserve(C * 4)) || (rc = hs->cdense.reserve(C * 4)) ||
-          (rc = hs->cgkey.reserve(2 * C * 8)) || (rc = hs->cgslot.reserve(2 * C * 4)) || (rc = hs->ctemp.reserve(std::max(tb, temp_bytes) + 16)) ||
-          (rc = hs->ccnt.reserve(32)))
-        return rc;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        unsigned long long hc[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemsetAsync(hs->ccnt.p, 0, 32, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-        if (hawk_launch_collapse_hash1(ctx->stream, t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)flank_up, (int)flank_down,
-                                       hs->min_gen, 0x9e3779b97f4a7c15ull * (uint64_t)(attempt + 1), hs->ctemp.p, tb, hs->ctable.p, (uint32_t)C,
-                                       hs->cocc.as<uint32_t>(), hs->cdense.as<uint32_t>(), hs->cgkey.as<uint64_t>(), hs->cgslot.as<uint32_t>(),
-                                       hs->cflags.as<uint32_t>(), hs->ccnt.as<unsigned long long>()))
-          return HAWK_E_HIP;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, hs->ccnt.p, 24, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (hc[1]) { hs->last_groups = n; if (hs->plan_groups) *hs->plan_groups = n; break; }   // no room: sort now, a larger table (or the sort) next time
-        if (hc[0]) continue;                         // two identities under one key: another seed
-        const uint64_t ng = hc[2];
-        if (hawk_launch_collapse_hash2(ctx->stream, t->cols, n, (uint32_t)ng, (int)t->guidelen, (int)t->pamlen, (int)t->right, end_bit, hs->ctemp.p, tb,
-                                       hs->cgkey.as<uint64_t>(), hs->cgslot.as<uint32_t>(), (uint32_t)C, hs->cocc.as<uint32_t>(),
-                                       hs->cflags.as<uint32_t>(), hs->ckeys.as<uint32_t>(), hs->cvals.as<uint32_t>(), hs->cgoff.as<uint64_t>(),
-                                       hs->cgc.as<uint8_t>(), hs->cgc.as<uint8_t>() + n))
-          return HAWK_E_HIP;
-        if (verify) {  // slot_of_row = cflags, slot -> group number = cocc (hawk_launch_collapse_hash2's arguments above)
-          if ((rc = hs->cfull.reserve(ng * 64 + 64))) return rc;
-          hawk_launch_collapse_verify_rows(ctx->stream, t->cols, hs->d_is_ref, n, (uint32_t)ng, (int)t->guidelen, (int)t->pamlen, (int)flank_up,
-                                           (int)flank_down, hs->cvals.as<uint32_t>() + n, hs->cflags.as<uint32_t>(), hs->cocc.as<uint32_t>(),
-                                           hs->cgoff.as<uint64_t>(), hs->cfull.p, hs->ccnt.as<unsigned long long>() + 3);
-        }
-        HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hs->cgoff.as<uint64_t>() + ng, &n, 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(&hc[3], hs->ccnt.as<unsigned long long>() + 3, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (kernel_ms) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); *kernel_ms += ms; }
-        if (hc[3]) { verified_bad = true; break; }  // two different rows under one group: the exact path decides
-        hs->last_groups = ng;
-        if (hs->plan_groups) *hs->plan_groups = ng;
-        t->n_groups = ng; t->collapsed = true;
-        *n_groups = ng;
-        return HAWK_OK;
-      }
-    }
+    return p;
   }
-  if (verified_bad) continue;
+};
+
+// one collapse of the rows of a table: what every path of it is handed
+struct CollapseJob {
+  hawk_table* t; CollapseKey key; CollapsePolicy pol;
+  unsigned begin_bit, end_bit;  // the sort key's bits in use
+  size_t temp_bytes;            // rocprim's temporary storage for the sort path
+  uint64_t* n_groups; float* kernel_ms;
+};
+enum CollapseNext { COLLAPSE_DONE, COLLAPSE_TO_SORT, COLLAPSE_TO_EXACT };
+
+static uint64_t seed_of(int attempt) { return 0x9e3779b97f4a7c15ull * (uint64_t)(attempt + 1); }
+
+// the interval between events ev[first] and ev[first + 1], both recorded and waited for, onto *kernel_ms
+static void add_interval(hawk_ctx* ctx, int first, float* kernel_ms) {
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, ctx->ev[first], ctx->ev[first + 1]);
+  if (kernel_ms) *kernel_ms += ms;
+}
+
+// The end of every path: group_off's closing entry and the wait for it, then what the call leaves behind.  `refuted` (hash-table
+// path): the verification's counter comes back in the same wait, and a grouping it refutes leaves nothing behind.
+static int finish(hawk_table* t, uint64_t ng, uint64_t* n_groups, bool* refuted = nullptr) {
+  hawk_hapset* hs = t->hs;
+  hipStream_t st = hs->ctx->stream;
+  const uint64_t n = t->n_rows;
+  unsigned long long mismatches = 0;
+  HIPCHK(hipMemcpyAsync(hs->cws.group_off() + ng, &n, 8, hipMemcpyHostToDevice, st));
+  if (refuted) HIPCHK(hipMemcpyAsync(&mismatches, hs->cws.counters() + 3, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (refuted && (*refuted = mismatches != 0)) return HAWK_OK;
+  hs->cws.gen = t->gen;
+  hs->cws.last_groups = ng;
+  if (hs->plan_groups) *hs->plan_groups = ng;
+  t->n_groups = ng; t->collapsed = true;
+  *n_groups = ng;
+  return HAWK_OK;
+}
+
+// Slots of the hash table to group through, 0 for the sort: the table when groups are expected to be far fewer than rows - the
+// sort then only orders (group number, row).
+static uint64_t table_slots(const hawk_hapset* hs, uint64_t n, const CollapsePolicy& pol) {
+  const uint64_t last = hs->cws.last_groups;
+  const uint64_t g_est = last ? last + last / 4 : n / 16;
+  uint64_t C = 1024;
+  while (C < 2 * g_est) C <<= 1;  // at most half full (with the 25 % head room of g_est)
+  const bool fits = C <= (1ull << 26) && hs->max_gen - hs->min_gen < 0xffffffffll;
+  const bool want = !pol.weak && !pol.force_sort && fits && (pol.force_hash || (n >= (1u << 20) && (last == 0 || last * 8 <= n)));
+  return want ? C : 0;
+}
+
+// Grouping through a hash table of C slots (hawk_collapse.hip).  A table that turns out too small, or an unlucky seed twice, falls
+// through to the sort.
+static int group_by_table(const CollapseJob& j, uint64_t C, CollapseNext* next) {
+  hawk_hapset* hs = j.t->hs;
+  hawk_ctx* ctx = hs->ctx;
+  CollapseWs& ws = hs->cws;
+  const uint64_t n = j.key.n;
+  const size_t tb = hawk_collapse_hash_temp_bytes(n, (uint32_t)C);
+  int rc;
+  if ((rc = ws.reserve_table(C, std::max(tb, j.temp_bytes)))) return rc;
+  CollapseHashView v = ws.hash_view(tb, n, C);
+  *next = COLLAPSE_TO_SORT;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    unsigned long long hc[3] = {0, 0, 0};
+    HIPCHK(hipMemsetAsync(ws.cnt.p, 0, 32, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (hawk_launch_collapse_hash1(ctx->stream, j.key, v, seed_of(attempt))) return HAWK_E_HIP;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hc, ws.cnt.p, 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (hc[1]) {  // no room: sort now, a larger table (or the sort) next time
+      ws.last_groups = n;
+      if (hs->plan_groups) *hs->plan_groups = n;
+      return HAWK_OK;
+    }
+    if (hc[0]) continue;  // two identities under one key: another seed
+    const uint64_t ng = hc[2];
+    if (hawk_launch_collapse_hash2(ctx->stream, j.key, v, (uint32_t)ng, j.end_bit)) return HAWK_E_HIP;
+    if (j.pol.verify) {
+      if ((rc = ws.full.reserve(ng * 64 + 64))) return rc;
+      v.full = ws.full.p;
+      hawk_launch_collapse_verify_rows(ctx->stream, j.key, v, (uint32_t)ng);
+    }
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIPCHK(hipGetLastError());
+    bool refuted = false;
+    if ((rc = finish(j.t, ng, j.n_groups, &refuted))) return rc;
+    add_interval(ctx, 0, j.kernel_ms);
+    *next = refuted ? COLLAPSE_TO_EXACT : COLLAPSE_DONE;  // two different rows under one group: the exact path decides
+    return HAWK_OK;
+  }
+  return HAWK_OK;
+}
+
+// Grouping by a sort of all rows on (start, strand, hash bits); `exact`: on all 31 hash bits, identities compared on the full keys.
+static int group_by_sort(const CollapseJob& j, bool exact, CollapseNext* next) {
+  hawk_hapset* hs = j.t->hs;
+  hawk_ctx* ctx = hs->ctx;
+  CollapseWs& ws = hs->cws;
+  const uint64_t n = j.key.n;
+  int rc;
+  if (exact && (rc = ws.full.reserve(hawk_collapse_full_bytes(n)))) return rc;
+  const CollapseSortView v = ws.sort_view(j.temp_bytes, n);
   unsigned long long cnt[3] = {0, 0, 0};
   // A new seed whenever two different rows of one (start, strand) collide: in the hash bits of the key (24 to 31) on the usual
   // path, which needs them apart to keep equal rows contiguous - thousands of different rows under one start (k of them collide
   // with probability ~ k^2 / 2^(bits + 1) per seed) can use up all four seeds, and the call goes to the exact path; there only in
   // all 63 hash bits, because its rows are sorted by identity below the key (hawk_launch_collapse).
   for (int attempt = 0; attempt < 4; ++attempt) {
-    HIPCHK(hipMemsetAsync(hs->ccnt.p, 0, 32, ctx->stream));
+    HIPCHK(hipMemsetAsync(ws.cnt.p, 0, 32, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if (hawk_launch_collapse(ctx->stream, t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)t->right, (int)flank_up,
-                             (int)flank_down, hs->min_gen, exact ? 0u : begin_bit, end_bit, 0x9e3779b97f4a7c15ull * (uint64_t)(attempt + 1), hs->ctemp.p,
-                             temp_bytes, hs->ckeys.as<uint64_t>(), hs->cvals.as<uint32_t>(), hs->cflags.as<uint32_t>(),
-                             hs->cgidx.as<uint32_t>(), hs->ccnt.as<unsigned long long>(), hs->cgoff.as<uint64_t>(), hs->cgc.as<uint8_t>(),
-                             hs->cgc.as<uint8_t>() + n, hs->cgidx.as<uint32_t>(), exact ? hs->cfull.p : nullptr, weak && !exact))
+    if (hawk_launch_collapse(ctx->stream, j.key, v, exact ? 0u : j.begin_bit, j.end_bit, seed_of(attempt), exact, j.pol.weak && !exact))
       return HAWK_E_HIP;
-    if (verify && !exact)  // group of sorted position j: exclusive scan of the head flags + its own flag - 1
-      hawk_launch_collapse_verify(ctx->stream, t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)flank_up, (int)flank_down,
-                                  hs->cvals.as<uint32_t>() + n, hs->cgidx.as<uint32_t>(), hs->cflags.as<uint32_t>(), hs->cgoff.as<uint64_t>(),
-                                  hs->ccnt.as<unsigned long long>() + 2);
+    if (j.pol.verify && !exact) hawk_launch_collapse_verify(ctx->stream, j.key, v);
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cnt, hs->ccnt.p, 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cnt, ws.cnt.p, 24, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); *kernel_ms += ms; }
+    add_interval(ctx, 0, j.kernel_ms);
     if (cnt[0] == cnt[1]) break;
   }
-  if (cnt[0] != cnt[1]) { if (!exact) continue; return HAWK_E_UNSUPPORTED; }
-  if (cnt[2]) continue;  // the verify pass found a group holding two different rows: once more, exactly
-  const uint64_t ng = cnt[1];
-  HIPCHK(hipMemcpyAsync(hs->cgoff.as<uint64_t>() + ng, &n, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hs->last_groups = ng;
-  if (hs->plan_groups) *hs->plan_groups = ng;
-  t->n_groups = ng; t->collapsed = true;
-  *n_groups = ng;
-  return HAWK_OK;
-  }
-  return HAWK_E_UNSUPPORTED;
+  // every seed used up, or the verify pass found a group holding two different rows: once more, exactly
+  if (cnt[0] != cnt[1] || cnt[2]) { *next = COLLAPSE_TO_EXACT; return exact ? HAWK_E_UNSUPPORTED : HAWK_OK; }
+  *next = COLLAPSE_DONE;
+  return finish(j.t, cnt[1], j.n_groups);
+}
+
+static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
+  hawk_hapset* hs = t->hs;
+  HIPCHK(hipSetDevice(hs->ctx->device));
+  const uint64_t n = t->n_rows;
+  t->collapsed = false;
+  *n_groups = 0;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (n == 0) { hs->cws.gen = t->gen; t->n_groups = 0; t->collapsed = true; return HAWK_OK; }
+  if (n > 0xffffffffull || hs->max_gen - hs->min_gen > 0xffffffffll) return HAWK_E_UNSUPPORTED;
+  CollapseJob j = {t, {t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)t->right, (int)flank_up, (int)flank_down, hs->min_gen},
+                   CollapsePolicy::read(), 0, 32, 0, n_groups, kernel_ms};
+  while (j.end_bit < 64 && ((uint64_t)(hs->max_gen - hs->min_gen) >> (j.end_bit - 32)) != 0) ++j.end_bit;
+  // low hash bits the sort leaves out: start bits + strand + hash fill whole 8-bit passes, at least 24 hash bits stay
+  const unsigned pos_bits = j.end_bit - 31;  // start - base, strand
+  const unsigned hash_bits = std::min(31u, (pos_bits + 24 + 7) / 8 * 8 - pos_bits);
+  j.begin_bit = 31 - hash_bits;
+  j.temp_bytes = hawk_collapse_temp_bytes(n, j.begin_bit, j.end_bit);
+  int rc;
+  if ((rc = hs->cws.reserve_rows(n, j.temp_bytes))) return rc;
+  // Rows are grouped on (start, strand, 63 hash bits of the rest) and the grouping is then VERIFIED: every member against
+  // its group's first member on the full key (k_collapse_verify).  A mismatch - two different rows under one hash, never
+  // seen - sends the call through the exact path (full 64-byte keys compared neighbour by neighbour), which
+  // HAWK_COLLAPSE_EXACT=1 forces from the start.  The verification cannot be switched off in the product library.
+  CollapseNext next = j.pol.exact ? COLLAPSE_TO_EXACT : COLLAPSE_TO_SORT;
+  const uint64_t C = j.pol.exact ? 0 : table_slots(hs, n, j.pol);
+  if (C && (rc = group_by_table(j, C, &next))) return rc;
+  if (next == COLLAPSE_TO_SORT && (rc = group_by_sort(j, false, &next))) return rc;
+  if (next == COLLAPSE_TO_EXACT && (rc = group_by_sort(j, true, &next))) return rc;
+  return next == COLLAPSE_DONE ? HAWK_OK : HAWK_E_UNSUPPORTED;
 }
 
 // The collapse of a table the cluster search wrote.  Every non-REF row is a copy of one of the search's template rows in all the
@@ -170,6 +192,7 @@ static int collapse_rows(hawk_table* t, uint32_t flank_up, uint32_t flank_down, 
 static int collapse_by_templates(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
   hawk_hapset* hs = t->hs;
   hawk_ctx* ctx = hs->ctx;
+  CollapseWs& ws = hs->cws;
   HIPCHK(hipSetDevice(ctx->device));
   const hawk_xplan* vx = hs->vplan;
   if (!vx || !vx->cl.usable) return HAWK_E_INVALID;
@@ -206,82 +229,67 @@ static int collapse_by_templates(hawk_table* t, uint32_t flank_up, uint32_t flan
   HIPCHK(hipGetLastError());
   const uint64_t t_live = tot.n_keep;
   const uint64_t nm = r0 + t_live;
-  if (r0 > n || nm == 0 || nm > 0xffffffffull || r0 + 0 > n) return HAWK_E_INVALID;
+  if (r0 > n || nm == 0 || nm > 0xffffffffull) return HAWK_E_INVALID;
   int rc;
   GuideCols mini;
-  if ((rc = hawk_reserve_cols(hs->cmini, nm, &mini)) || (rc = hs->cm_gid.reserve(nm * 4))) return rc;
-  float ms_a = 0.f, ms_b = 0.f, ms_c = 0.f;
+  if ((rc = hawk_reserve_cols(ws.mini, nm, &mini)) || (rc = ws.m_gid.reserve(nm * 4))) return rc;
   HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
   hawk_launch_cc_mini(ctx->stream, t->cols, r0, hs->cs_trows.p, t_live, d_moff, hs->cs_tbase.as<uint32_t>(), nu, hs->ref_startp, mini);
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
   HIPCHK(hipGetLastError());
-  // everything the rest of this call reserves in the set's collapse workspace is reserved HERE, for the full table, before the
-  // mini collapse fills it: a reservation after k_cc_gidm has been queued could hand the buffers it reads back to the pool
-  {
-    const size_t tb_full = hawk_collapse_expand_temp_bytes(n);
-    if ((rc = hs->ckeys.reserve(std::max<size_t>(2 * nm * 8, 2 * n * 4))) || (rc = hs->cvals.reserve(2 * n * 4)) ||
-        (rc = hs->cgoff.reserve((nm + 1) * 8)) || (rc = hs->cgc.reserve(2 * n)) || (rc = hs->ctemp.reserve(tb_full + 16)) ||
-        (rc = hs->cflags.reserve(n * 4)))
-      return rc;
-  }
+  // everything the rest of this call needs in the set's collapse workspace is reserved HERE, for the full table, before the
+  // mini collapse fills it: a reservation after k_cc_gidm has been queued could hand the buffers it reads back to the pool.
+  // (keys: the mini table's 64-bit sort keys, then the table's (group number, row) ping-pong; group_off: G <= nm groups)
+  const size_t tb = hawk_collapse_expand_temp_bytes(n);
+  if ((rc = ws.keys.reserve(std::max<size_t>(2 * nm * 8, 2 * n * 4))) || (rc = ws.vals.reserve(2 * n * 4)) || (rc = ws.goff.reserve((nm + 1) * 8)) ||
+      (rc = ws.gc.reserve(2 * n)) || (rc = ws.temp.reserve(tb + 16)) || (rc = ws.flags.reserve(n * 4)))
+    return rc;
   hawk_table tm;  // the mini table borrows the set's collapse workspace like any table of the set
   tm.hs = hs; tm.ctx = ctx; tm.n_rows = nm; tm.n_cand = tm.n_hits = 0; tm.cap = mini.cap; tm.cols = mini;
   tm.guidelen = t->guidelen; tm.pamlen = t->pamlen; tm.right = t->right; tm.n_groups = 0; tm.collapsed = false; tm.gen = t->gen;
   uint64_t G = 0;
-  if ((rc = collapse_rows(&tm, flank_up, flank_down, &G, &ms_b))) return rc;
+  if ((rc = collapse_rows(&tm, flank_up, flank_down, &G, kernel_ms))) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  (void)hipEventElapsedTime(&ms_a, ctx->ev[8], ctx->ev[9]);
+  add_interval(ctx, 8, kernel_ms);
   // every mini row's group number, then every table row's; the table's rows sorted by (group, row)
-  unsigned gbits = 1;
-  while (gbits < 32 && (G >> gbits) != 0) ++gbits;
-  const size_t tb = hawk_collapse_expand_temp_bytes(n);
   HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
-  hawk_launch_cc_gidm(ctx->stream, hs->cvals.as<uint32_t>() + nm, hs->cgoff.as<uint64_t>(), nm, G, hs->cm_gid.as<uint32_t>());
-  if ((rc = hs->ckeys.reserve(2 * n * 4)) || (rc = hs->cvals.reserve(2 * n * 4)) || (rc = hs->cgoff.reserve((std::max<uint64_t>(G, nm) + 1) * 8)) ||
-      (rc = hs->cgc.reserve(2 * n)) || (rc = hs->ctemp.reserve(tb + 16)) || (rc = hs->cflags.reserve(n * 4)))
-    return rc;
+  hawk_launch_cc_gidm(ctx->stream, ws.perm(nm), ws.group_off(), nm, G, ws.m_gid.as<uint32_t>());
   ClDict cd;
   memset(&cd, 0, sizeof(cd));
   cd.n_inst = vx->cl.n_inst; cd.n_uniq = vx->cl.n_uniq; cd.inst_uid = vx->cl.inst_uid.as<uint32_t>();
-  hawk_launch_cs_gid(ctx->stream, cd, hs->cs_res.p, d_moff, hs->offsets.as<uint64_t>() + t->plane_tiles, r0, n,
-                     hs->cm_gid.as<uint32_t>(), hs->ckeys.as<uint32_t>(), hs->cvals.as<uint32_t>());
-  if (hawk_launch_collapse_expand(ctx->stream, t->cols, n, gbits, (int)t->guidelen, (int)t->pamlen, (int)t->right, hs->ctemp.p, tb, hs->ckeys.as<uint32_t>(),
-                                  hs->cvals.as<uint32_t>(), hs->cgoff.as<uint64_t>(), hs->cgc.as<uint8_t>(), hs->cgc.as<uint8_t>() + n))
-    return HAWK_E_HIP;
-  HIPCHK(hipMemcpyAsync(hs->cgoff.as<uint64_t>() + G, &n, 8, hipMemcpyHostToDevice, ctx->stream));
+  const CollapseKey key = {t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)t->right, (int)flank_up, (int)flank_down, hs->min_gen};
+  const CollapseHashView v = ws.hash_view(tb, n, 0);  // no table: the rows' group numbers come from their template rows
+  hawk_launch_cs_gid(ctx->stream, cd, hs->cs_res.p, d_moff, hs->offsets.as<uint64_t>() + t->plane_tiles, r0, n, ws.m_gid.as<uint32_t>(), v.gid, v.vals);
+  if (hawk_launch_collapse_expand(ctx->stream, key, v, G)) return HAWK_E_HIP;
   HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  (void)hipEventElapsedTime(&ms_c, ctx->ev[8], ctx->ev[9]);
-  if (kernel_ms) *kernel_ms = ms_a + ms_b + ms_c;
-  hs->collapse_gen = t->gen;
-  hs->last_groups = G;
-  if (hs->plan_groups) *hs->plan_groups = G;
-  t->n_groups = G; t->collapsed = true;
-  *n_groups = G;
+  if ((rc = finish(t, G, n_groups))) return rc;
+  add_interval(ctx, 8, kernel_ms);
   return HAWK_OK;
 }
 
+int hawk_table_collapse_ex(hawk_table* t, uint32_t flank_up, uint32_t flank_down, uint64_t* n_groups, float* kernel_ms) {
+  if (!t || !n_groups || !t->hs || hawk_table_stale(t)) return HAWK_E_INVALID;
+  if (flank_up > HAWK_PAD || flank_down > HAWK_PAD) return HAWK_E_UNSUPPORTED;
+  // A table the cluster search wrote is grouped on its template rows
+  if (t->by_cluster && t->n_rows) return collapse_by_templates(t, flank_up, flank_down, n_groups, kernel_ms);
+  return collapse_rows(t, flank_up, flank_down, n_groups, kernel_ms);
+}
 int hawk_table_collapse(hawk_table* t, uint64_t* n_groups, float* kernel_ms) {
   return hawk_table_collapse_ex(t, 0, 0, n_groups, kernel_ms);
 }
 
-// the collapse results live in the set's workspace: valid for the table that was collapsed last, until the next search
-static bool collapse_valid(const hawk_table* t) {
-  return t && t->collapsed && t->hs && !hawk_table_stale(t) && t->hs->collapse_gen == t->gen;
-}
-
 int hawk_table_collapse_download(hawk_table* t, uint32_t* perm, uint64_t* group_off, uint8_t* gc_num, uint8_t* gc_den) {
   if (!collapse_valid(t)) return HAWK_E_INVALID;
-  hawk_hapset* hs = t->hs;
-  hawk_ctx* ctx = hs->ctx;
+  const CollapseWs& ws = t->hs->cws;
+  hawk_ctx* ctx = t->hs->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   const uint64_t n = t->n_rows, ng = t->n_groups;
   if (n == 0) { if (group_off) group_off[0] = 0; return HAWK_OK; }
-  if (perm) HIPCHK(hipMemcpyAsync(perm, hs->cvals.as<uint32_t>() + n, n * 4, hipMemcpyDefault, ctx->stream));
-  if (group_off) HIPCHK(hipMemcpyAsync(group_off, hs->cgoff.p, (ng + 1) * 8, hipMemcpyDefault, ctx->stream));
-  if (gc_num) HIPCHK(hipMemcpyAsync(gc_num, hs->cgc.p, ng, hipMemcpyDefault, ctx->stream));
-  if (gc_den) HIPCHK(hipMemcpyAsync(gc_den, hs->cgc.as<uint8_t>() + n, ng, hipMemcpyDefault, ctx->stream));
+  if (perm) HIPCHK(hipMemcpyAsync(perm, ws.perm(n), n * 4, hipMemcpyDefault, ctx->stream));
+  if (group_off) HIPCHK(hipMemcpyAsync(group_off, ws.group_off(), (ng + 1) * 8, hipMemcpyDefault, ctx->stream));
+  if (gc_num) HIPCHK(hipMemcpyAsync(gc_num, ws.gc_num(), ng, hipMemcpyDefault, ctx->stream));
+  if (gc_den) HIPCHK(hipMemcpyAsync(gc_den, ws.gc_den(n), ng, hipMemcpyDefault, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return HAWK_OK;
 }
@@ -295,14 +303,12 @@ int hawk_table_collapse_export(hawk_table* t, uint32_t* rep_row, uint32_t* pos, 
   const uint64_t n = t->n_rows, ng = t->n_groups;
   if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return HAWK_OK;
-  // the representatives' columns and the member list reuse collapse workspace that is dead by now:
-  // ckeys (2n u64: the sort's key ping-pong) holds the rep columns when they fit, cflags (n u32) the members
   GuideCols rep;
-  int rc = hawk_reserve_cols(hs->crep, ng, &rep);
+  int rc = hawk_reserve_cols(hs->cws.rep, ng, &rep);
   if (rc) return rc;
-  uint32_t* d_mem = hs->cflags.as<uint32_t>();
+  uint32_t* d_mem = hs->cws.members();
   HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-  hawk_launch_collapse_export(ctx->stream, t->cols, n, ng, hs->cvals.as<uint32_t>() + n, hs->cgoff.as<uint64_t>(), rep, d_mem);
+  hawk_launch_collapse_export(ctx->stream, t->cols, n, ng, hs->cws.perm(n), hs->cws.group_off(), rep, d_mem);
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   HIPCHK(hipGetLastError());
   hipStream_t st = ctx->stream;
@@ -318,9 +324,8 @@ int hawk_table_collapse_export(hawk_table* t, uint32_t* rep_row, uint32_t* pos, 
       HIPCHK(hipMemcpyAsync(win + (size_t)p * ng, rep.win + (size_t)p * rep.cap, ng * 8, hipMemcpyDefault, st));
   if (member_hap) HIPCHK(hipMemcpyAsync(member_hap, d_mem, n * 4, hipMemcpyDefault, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[0], ctx->ev[1]);
+  add_interval(ctx, 0, kernel_ms);
   return HAWK_OK;
 }
-
 
 }  // extern "C"

@@ -137,7 +137,7 @@ int hawk_effects_create_columns(hawk_ctx* ctx, const hawk_effects_columns* cols,
 
 int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap_off, const uint32_t* sample_id, uint32_t n_hap,
                         uint32_t n_sample_ids, hawk_effects** out, hawk_effects_timing* timing) {
-  if (!t || !out || !t->collapsed || !t->hs || hawk_table_stale(t) || t->hs->collapse_gen != t->gen) return HAWK_E_INVALID;
+  if (!out || !collapse_valid(t)) return HAWK_E_INVALID;
   hawk_hapset* hs = t->hs;
   hawk_ctx* ctx = hs->ctx;
   const uint64_t n = t->n_rows, G = n ? t->n_groups : 0;
@@ -161,12 +161,12 @@ int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap
   memset(&rep, 0, sizeof(rep));
   if ((rc = f->start.reserve(G * 8 + 8)) || (rc = f->strand.reserve(G + 1)) || (rc = f->rank.reserve(G * 4 + 4)) || (rc = f->cfdon.reserve(G * 8 + 8)) ||
       (rc = tmp.alloc((void**)&d_hoff, ((uint64_t)n_hap + 1) * 8)) || (rc = tmp.alloc((void**)&d_sid, NS * 4 + 4)) ||
-      (G && (rc = hawk_reserve_cols(hs->crep, G, &rep))))
+      (G && (rc = hawk_reserve_cols(hs->cws.rep, G, &rep))))
     return fail(rc);
   hipError_t e = hipEventRecord(ctx->ev[0], st);
-  uint32_t* d_mem = hs->cflags.as<uint32_t>();  // the group export, as hawk_table_collapse_export runs it: representatives + members
+  uint32_t* d_mem = hs->cws.members();  // the group export, as hawk_table_collapse_export runs it: representatives + members
   if (e == hipSuccess && G) {
-    hawk_launch_collapse_export(st, t->cols, n, G, hs->cvals.as<uint32_t>() + n, hs->cgoff.as<uint64_t>(), rep, d_mem);
+    hawk_launch_collapse_export(st, t->cols, n, G, hs->cws.perm(n), hs->cws.group_off(), rep, d_mem);
     e = hipGetLastError();
   }
   auto cp = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
@@ -181,7 +181,7 @@ int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap
   }
   FxCols d;
   memset(&d, 0, sizeof(d));
-  d.n_groups = G; d.win_stride = rep.cap; d.stop = rep.stop; d.win = rep.win; d.member_off = hs->cgoff.as<uint64_t>(); d.member_hap = d_mem;
+  d.n_groups = G; d.win_stride = rep.cap; d.stop = rep.stop; d.win = rep.win; d.member_off = hs->cws.group_off(); d.member_hap = d_mem;
   d.hap_off = d_hoff; d.sample_id = d_sid; d.n_hap = n_hap; d.n_sample_ids = n_sample_ids; d.guidelen = t->guidelen; d.pamlen = t->pamlen; d.right = t->right;
   if ((rc = fx_build(f, d, hs->d_is_ref, timing, ctx->ev[0]))) return fail(rc);
   *out = f;

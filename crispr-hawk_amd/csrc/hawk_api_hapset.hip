@@ -71,13 +71,11 @@ void hawk_hapset_destroy(hawk_hapset* hs) {
   hawk_pool_free(hs->d_scan_stop); hawk_pool_free(hs->d_seg_off);
   hawk_pool_free(hs->d_seg_rel); hawk_pool_free(hs->d_seg_gen); hawk_pool_free(hs->d_tile_meta);
   DevBuf* bufs[] = {&hs->keepF, &hs->keepR, &hs->counts, &hs->offsets, &hs->totals, &hs->misc, &hs->cfd, &hs->partial,
-                    &hs->sites, &hs->hits, &hs->guides, &hs->lists, &hs->ckeys, &hs->cvals, &hs->cflags, &hs->cgidx,
-                    &hs->ctemp, &hs->cgoff, &hs->cgc, &hs->ccnt, &hs->cfull, &hs->ctable, &hs->cocc, &hs->cdense, &hs->cgkey, &hs->cgslot, &hs->otoff, &hs->otcode, &hs->otid, &hs->othit, &hs->otsum, &hs->refbits,
-                    &hs->big, &hs->refhp, &hs->vcnt0, &hs->cs_res, &hs->cs_tbase, &hs->cs_trows, &hs->cs_inst, &hs->rowsA, &hs->cm_gid};
-  for (auto& b : hs->cmini) b.release();
+                    &hs->sites, &hs->hits, &hs->guides, &hs->lists, &hs->otoff, &hs->otcode, &hs->otid, &hs->othit, &hs->otsum, &hs->refbits,
+                    &hs->big, &hs->refhp, &hs->vcnt0, &hs->cs_res, &hs->cs_tbase, &hs->cs_trows, &hs->cs_inst, &hs->rowsA};
+  hs->cws.release();
   for (auto* b : bufs) b->release();
   for (auto& b : hs->colsA) b.release();
-  for (auto& b : hs->crep) b.release();
   delete hs;
 }
 

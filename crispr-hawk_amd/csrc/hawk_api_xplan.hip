@@ -147,7 +147,7 @@ static int xplan_install(const hawk_xplan* x, hawk_hapset* hs) {
   hs->ref_startp = x->ref_startp; hs->min_gen = x->min_gen; hs->max_gen = x->max_gen;
   hs->scan_start = x->scan_start; hs->scan_stop = x->scan_stop;
   hs->ref_index = x->ref_index; hs->has_meta = true; hs->n_ref_rows = x->n_ref_rows;
-  hs->plan_groups = x->groups; hs->last_groups = *x->groups;
+  hs->plan_groups = x->groups; hs->cws.last_groups = *x->groups;
   hs->has_partner = x->has_partner; hs->partner_start = x->partner_start; hs->partner_stop = x->partner_stop;
   hs->refbits_valid = false;
   ++hs->cols_gen;

@@ -63,6 +63,40 @@ __device__ __forceinline__ bool same_row(const RowKey& a, const RowKey& b) {
   for (int pl = 0; pl < HAWK_PLANES; ++pl) s = s && a.core[pl] == b.core[pl];
   return s;
 }
+// The 64-bit hash of a row's identity below (start, strand).  Its top 31 bits fill the sort key behind start - base and the strand
+// (`hash_mask` drops the low ones the sort leaves out; the hash table keys on all 31), its low 32 are the rows' second word id2.
+__device__ __forceinline__ uint64_t row_hash(const RowKey& k, uint64_t seed) {
+  uint64_t h = seed;
+#pragma unroll
+  for (int pl = 0; pl < HAWK_PLANES; ++pl) h = mix64(h ^ k.core[pl]);
+  return mix64(h ^ (uint64_t)k.stop ^ ((uint64_t)(k.sr >> 1) << 63));
+}
+__device__ __forceinline__ uint64_t sort_key(const RowKey& k, int64_t base, uint64_t h, uint32_t hash_mask) {
+  return ((uint64_t)(k.start - base) << 32) | ((uint64_t)(k.sr & 1u) << 31) | ((h >> 33) & hash_mask);
+}
+// The full key as one 64-byte record: a pass that compares rows scattered over the table reads one line per row instead of nine
+// (one per column).
+struct KeyRecord { ulonglong4 a, b; };
+__device__ __forceinline__ KeyRecord key_record(const RowKey& k) {
+  return {make_ulonglong4((unsigned long long)k.start, (unsigned long long)k.stop, (unsigned long long)k.sr, k.core[0]),
+          make_ulonglong4(k.core[1], k.core[2], k.core[3], k.core[4])};
+}
+__device__ __forceinline__ bool same4(const ulonglong4& a, const ulonglong4& b) {
+  return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
+}
+__device__ __forceinline__ bool same_record(const KeyRecord& x, const KeyRecord& y) { return same4(x.a, y.a) && same4(x.b, y.b); }
+// (G/C bases, unambiguous bases) of row r's spacer inside the stored (+ strand) core: behind the PAM when the PAM comes first
+// (right ^ strand)
+__device__ __forceinline__ uchar2 spacer_gc(const GuideCols& c, uint64_t r, int guidelen, int pamlen, int right) {
+  const bool pamfirst = (right != 0) != (gc_strand(c, r) != 0);
+  const int sh = HAWK_PAD + (pamfirst ? pamlen : 0);
+  const uint64_t m = guidelen >= 64 ? ~0ull : ((1ull << guidelen) - 1ull);
+  const uint64_t A = (gc_win(c, 0, r) >> sh) & m, C = (gc_win(c, 1, r) >> sh) & m, G = (gc_win(c, 2, r) >> sh) & m,
+                 T = (gc_win(c, 3, r) >> sh) & m;
+  const uint64_t gc = (C | G) & ~(A | T);  // C, G, S
+  const uint64_t at = (A | T) & ~(C | G);  // A, T, W
+  return make_uchar2((uint8_t)__popcll(gc), (uint8_t)__popcll(gc | at));
+}
 
 __global__ __launch_bounds__(256) void k_collapse_keys(GuideCols c, const uint8_t* __restrict__ is_ref, uint64_t n, int L, int up, int down,
                                                        int64_t base, uint64_t seed, uint32_t hash_mask, uint32_t id_mask,
@@ -71,17 +105,9 @@ __global__ __launch_bounds__(256) void k_collapse_keys(GuideCols c, const uint8_
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const RowKey k = row_key(c, is_ref, i, L, up, down);
-  // the full key as one 64-byte record: the head pass compares neighbours of the SORTED order, i.e. rows scattered
-  // over the table - one line per row here instead of nine (one per column) there
-  if (full) {
-    full[2 * i] = make_ulonglong4((unsigned long long)k.start, (unsigned long long)k.stop, (unsigned long long)k.sr, k.core[0]);
-    full[2 * i + 1] = make_ulonglong4(k.core[1], k.core[2], k.core[3], k.core[4]);
-  }
-  uint64_t h = seed;
-#pragma unroll
-  for (int pl = 0; pl < HAWK_PLANES; ++pl) h = mix64(h ^ k.core[pl]);
-  h = mix64(h ^ (uint64_t)k.stop ^ ((uint64_t)(k.sr >> 1) << 63));
-  keys[i] = ((uint64_t)(k.start - base) << 32) | ((uint64_t)(k.sr & 1u) << 31) | ((h >> 33) & hash_mask);
+  if (full) reinterpret_cast<KeyRecord*>(full)[i] = key_record(k);  // the head pass compares neighbours of the SORTED order
+  const uint64_t h = row_hash(k, seed);
+  keys[i] = sort_key(k, base, h, hash_mask);
   vals[i] = (uint32_t)i;
   id2[i] = (uint32_t)h & id_mask;  // id_mask / hash_mask = 0: the test that forces hash collisions (HAWK_COLLAPSE_WEAK_HASH)
 }
@@ -94,9 +120,6 @@ __global__ __launch_bounds__(256) void k_collapse_by_id(const uint64_t* __restri
   if (j < n) out[j] = keys[order[j]];
 }
 
-__device__ __forceinline__ bool same4(const ulonglong4& a, const ulonglong4& b) {
-  return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
-}
 __global__ __launch_bounds__(256) void k_collapse_heads(const ulonglong4* __restrict__ full, const uint32_t* __restrict__ id2, uint64_t n,
                                                         const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                         uint32_t* __restrict__ flags, unsigned long long* __restrict__ counters) {
@@ -114,7 +137,8 @@ __global__ __launch_bounds__(256) void k_collapse_heads(const ulonglong4* __rest
         const uint64_t a = vals[j], b = vals[j - 1];
         if (full) {  // exact: rows of one key lie sorted by identity (k_collapse_by_id), so the identity counts as key here
           hk = id2[a] != id2[b];
-          hf = hk || !(same4(full[2 * a], full[2 * b]) && same4(full[2 * a + 1], full[2 * b + 1]));
+          const KeyRecord* rec = reinterpret_cast<const KeyRecord*>(full);
+          hf = hk || !same_record(rec[a], rec[b]);
         } else {
           hf = id2[a] != id2[b];
         }
@@ -139,17 +163,9 @@ __global__ __launch_bounds__(256) void k_collapse_groups(GuideCols c, uint64_t n
   if (j >= n || !flags[j]) return;
   const uint32_t g = gidx[j];
   group_off[g] = j;
-  const uint64_t r = vals[j];
-  // the spacer inside the stored (+ strand) core: behind the PAM when the PAM comes first (right ^ strand)
-  const bool pamfirst = (right != 0) != (gc_strand(c, r) != 0);
-  const int sh = HAWK_PAD + (pamfirst ? pamlen : 0);
-  const uint64_t m = guidelen >= 64 ? ~0ull : ((1ull << guidelen) - 1ull);
-  const uint64_t A = (gc_win(c, 0, r) >> sh) & m, C = (gc_win(c, 1, r) >> sh) & m, G = (gc_win(c, 2, r) >> sh) & m,
-                 T = (gc_win(c, 3, r) >> sh) & m;
-  const uint64_t gc = (C | G) & ~(A | T);  // C, G, S
-  const uint64_t at = (A | T) & ~(C | G);  // A, T, W
-  gc_num[g] = (uint8_t)__popcll(gc);
-  gc_den[g] = (uint8_t)__popcll(gc | at);
+  const uchar2 gc = spacer_gc(c, vals[j], guidelen, pamlen, right);
+  gc_num[g] = gc.x;
+  gc_den[g] = gc.y;
 }
 
 // Every member of a group against the group's first member on the FULL key (start, stop, strand, origin, the five core
@@ -180,9 +196,7 @@ __global__ __launch_bounds__(256) void k_collapse_head_keys(GuideCols c, const u
                                                             ulonglong4* __restrict__ full) {
   const uint32_t g = blockIdx.x * 256 + threadIdx.x;
   if (g >= G) return;
-  const RowKey k = row_key(c, is_ref, perm[group_off[g]], L, up, down);
-  full[2 * (size_t)g] = make_ulonglong4((unsigned long long)k.start, (unsigned long long)k.stop, (unsigned long long)k.sr, k.core[0]);
-  full[2 * (size_t)g + 1] = make_ulonglong4(k.core[1], k.core[2], k.core[3], k.core[4]);
+  reinterpret_cast<KeyRecord*>(full)[g] = key_record(row_key(c, is_ref, perm[group_off[g]], L, up, down));
 }
 __global__ __launch_bounds__(256) void k_collapse_verify_rows(GuideCols c, const uint8_t* __restrict__ is_ref, uint64_t n, int L, int up, int down,
                                                               const uint32_t* __restrict__ slot_of_row, const uint32_t* __restrict__ slot2rank,
@@ -191,29 +205,25 @@ __global__ __launch_bounds__(256) void k_collapse_verify_rows(GuideCols c, const
   bool bad = false;
   if (i < n) {
     const RowKey k = row_key(c, is_ref, i, L, up, down);
-    const size_t g = slot2rank[slot_of_row[i]];
-    const ulonglong4 a = full[2 * g], b = full[2 * g + 1];
-    bad = !(a.x == (unsigned long long)k.start && a.y == (unsigned long long)k.stop && a.z == (unsigned long long)k.sr && a.w == k.core[0] &&
-            b.x == k.core[1] && b.y == k.core[2] && b.z == k.core[3] && b.w == k.core[4]);
+    const KeyRecord head = reinterpret_cast<const KeyRecord*>(full)[slot2rank[slot_of_row[i]]];  // both halves loaded before the compare
+    bad = !same_record(head, key_record(k));
   }
   const unsigned long long bl = __ballot(bad);
   if (bl && (threadIdx.x & 63) == 0) atomicAdd(mismatches, (unsigned long long)__popcll(bl));
 }
-void hawk_launch_collapse_verify_rows(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, uint32_t G, int guidelen, int pamlen,
-                                      int flank_up, int flank_down, const uint32_t* perm, const uint32_t* slot_of_row, const uint32_t* slot2rank,
-                                      const uint64_t* group_off, void* full /* 64 B per group */, unsigned long long* mismatches) {
-  if (!n || !G) return;
-  hipLaunchKernelGGL(k_collapse_head_keys, dim3((G + 255) / 256), dim3(256), 0, st, c, is_ref, G, guidelen + pamlen, flank_up, flank_down, perm,
-                     group_off, (ulonglong4*)full);
-  hipLaunchKernelGGL(k_collapse_verify_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, is_ref, n, guidelen + pamlen, flank_up,
-                     flank_down, slot_of_row, slot2rank, (const ulonglong4*)full, mismatches);
+void hawk_launch_collapse_verify_rows(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint32_t G) {
+  if (!k.n || !G) return;
+  const int L = k.guidelen + k.pamlen;
+  hipLaunchKernelGGL(k_collapse_head_keys, dim3((G + 255) / 256), dim3(256), 0, st, k.c, k.is_ref, G, L, k.flank_up, k.flank_down, v.vals + k.n,
+                     v.group_off, (ulonglong4*)v.full);
+  hipLaunchKernelGGL(k_collapse_verify_rows, dim3((unsigned)((k.n + 255) / 256)), dim3(256), 0, st, k.c, k.is_ref, k.n, L, k.flank_up, k.flank_down,
+                     v.slot_of_row, v.slot_rank, (const ulonglong4*)v.full, v.counters + 3);
 }
-void hawk_launch_collapse_verify(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int flank_up,
-                                 int flank_down, const uint32_t* perm, const uint32_t* grp_a, const uint32_t* grp_b, const uint64_t* group_off,
-                                 unsigned long long* mismatches) {
-  if (!n) return;
-  hipLaunchKernelGGL(k_collapse_verify, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, is_ref, n, guidelen + pamlen, flank_up,
-                     flank_down, perm, grp_a, grp_b, group_off, mismatches);
+// group of sorted position j: exclusive scan of the head flags + its own flag - 1
+void hawk_launch_collapse_verify(hipStream_t st, const CollapseKey& k, const CollapseSortView& v) {
+  if (!k.n) return;
+  hipLaunchKernelGGL(k_collapse_verify, dim3((unsigned)((k.n + 255) / 256)), dim3(256), 0, st, k.c, k.is_ref, k.n, k.guidelen + k.pamlen, k.flank_up,
+                     k.flank_down, v.vals + k.n, v.group_index, v.head_flags, v.group_off, v.counters + 2);
 }
 
 // whole rows of a set against each other, all five planes: the check behind collapsing haplotypes on their content hash
@@ -251,36 +261,34 @@ size_t hawk_collapse_temp_bytes(uint64_t n, unsigned begin_bit, unsigned end_bit
   return std::max(std::max(a, b), std::max(d, e));
 }
 
-// keys/vals: [2][n] ping-pong; flags, gidx: [n]; counters: [2], zeroed by the caller; group_off must hold
-// n + 1 entries (the number of groups is only known afterwards)
-int hawk_launch_collapse(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int right,
-                         int flank_up, int flank_down, int64_t base, unsigned begin_bit, unsigned end_bit, uint64_t seed, void* temp, size_t temp_bytes, uint64_t* keys, uint32_t* vals,
-                         uint32_t* flags, uint32_t* gidx, unsigned long long* counters, uint64_t* group_off, uint8_t* gc_num,
-                         uint8_t* gc_den, uint32_t* id2, void* full, int weak_hash) {
-  const int L = guidelen + pamlen;
+int hawk_launch_collapse(hipStream_t st, const CollapseKey& k, const CollapseSortView& v, unsigned begin_bit, unsigned end_bit, uint64_t seed,
+                         bool exact, bool weak_hash) {
+  const uint64_t n = k.n;
+  const int L = k.guidelen + k.pamlen;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_collapse_keys, grid, block, 0, st, c, is_ref, n, L, flank_up, flank_down, base, seed,
-                     weak_hash ? 0u : (~((1u << begin_bit) - 1u) & 0x7fffffffu), weak_hash ? 0u : 0xffffffffu, keys, vals, id2, (ulonglong4*)full);
-  size_t tb = temp_bytes;
-  if (full) {
-    // Exact path (begin_bit = 0 here): rows by identity first (`flags` takes the sorted identities, free until the head pass),
+  void* const full = exact ? v.full : nullptr;
+  hipLaunchKernelGGL(k_collapse_keys, grid, block, 0, st, k.c, k.is_ref, n, L, k.flank_up, k.flank_down, k.base, seed,
+                     weak_hash ? 0u : (~((1u << begin_bit) - 1u) & 0x7fffffffu), weak_hash ? 0u : 0xffffffffu, v.keys, v.vals, v.id2, (ulonglong4*)full);
+  size_t tb = v.temp_bytes;
+  if (exact) {
+    // Exact path (begin_bit = 0 here): rows by identity first (`head_flags` takes the sorted identities, free until the head pass),
     // then by key.  The head pass then needs no collision-free key: it opens a group where key, identity or full record change,
     // and counts a changed record under one key + identity (63 equal hash bits, never seen) for the host to answer with a seed.
-    if (rocprim::radix_sort_pairs(temp, tb, id2, flags, vals, vals + n, n, 0, 32, st) != hipSuccess) return -2;
-    hipLaunchKernelGGL(k_collapse_by_id, grid, block, 0, st, keys, vals + n, n, keys + n);
-    tb = temp_bytes;
-    if (rocprim::radix_sort_pairs(temp, tb, keys + n, keys, vals + n, vals, n, begin_bit, end_bit, st) != hipSuccess) return -2;
-    if (hipMemcpyAsync(keys + n, keys, n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(vals + n, vals, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if (rocprim::radix_sort_pairs(v.temp, tb, v.id2, v.head_flags, v.vals, v.vals + n, n, 0, 32, st) != hipSuccess) return -2;
+    hipLaunchKernelGGL(k_collapse_by_id, grid, block, 0, st, v.keys, v.vals + n, n, v.keys + n);
+    tb = v.temp_bytes;
+    if (rocprim::radix_sort_pairs(v.temp, tb, v.keys + n, v.keys, v.vals + n, v.vals, n, begin_bit, end_bit, st) != hipSuccess) return -2;
+    if (hipMemcpyAsync(v.keys + n, v.keys, n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(v.vals + n, v.vals, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return -2;
-  } else if (rocprim::radix_sort_pairs(temp, tb, keys, keys + n, vals, vals + n, n, begin_bit, end_bit, st) != hipSuccess) {
+  } else if (rocprim::radix_sort_pairs(v.temp, tb, v.keys, v.keys + n, v.vals, v.vals + n, n, begin_bit, end_bit, st) != hipSuccess) {
     return -2;
   }
-  hipLaunchKernelGGL(k_collapse_heads, grid, block, 0, st, (const ulonglong4*)full, id2, n, keys + n, vals + n, flags, counters);
-  tb = temp_bytes;
-  if (rocprim::exclusive_scan(temp, tb, flags, gidx, 0u, n, rocprim::plus<uint32_t>(), st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_collapse_groups, grid, block, 0, st, c, n, vals + n, flags, gidx, guidelen, pamlen, right, group_off, gc_num,
-                     gc_den);
+  hipLaunchKernelGGL(k_collapse_heads, grid, block, 0, st, (const ulonglong4*)full, v.id2, n, v.keys + n, v.vals + n, v.head_flags, v.counters);
+  tb = v.temp_bytes;
+  if (rocprim::exclusive_scan(v.temp, tb, v.head_flags, v.group_index, 0u, n, rocprim::plus<uint32_t>(), st) != hipSuccess) return -2;
+  hipLaunchKernelGGL(k_collapse_groups, grid, block, 0, st, k.c, n, v.vals + n, v.head_flags, v.group_index, k.guidelen, k.pamlen, k.right, v.group_off,
+                     v.gc_num, v.gc_den);
   return 0;
 }
 
@@ -332,11 +340,8 @@ __global__ __launch_bounds__(256) void k_cg_insert(GuideCols c, const uint8_t* _
   // the table has turned out too small (far more groups than expected): the call is going to the sort path anyway
   if (__hip_atomic_load(&counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 4096ull) return;
   const RowKey k = row_key(c, is_ref, i, L, up, down);
-  uint64_t h = seed;
-#pragma unroll
-  for (int pl = 0; pl < HAWK_PLANES; ++pl) h = mix64(h ^ k.core[pl]);
-  h = mix64(h ^ (uint64_t)k.stop ^ ((uint64_t)(k.sr >> 1) << 63));
-  const unsigned long long key = ((uint64_t)(k.start - base) << 32) | ((uint64_t)(k.sr & 1u) << 31) | (h >> 33);
+  const uint64_t h = row_hash(k, seed);
+  const unsigned long long key = sort_key(k, base, h, 0x7fffffffu);
   const unsigned long long idr = ((unsigned long long)(uint32_t)h << 32) | (uint32_t)i;
   uint32_t s = (uint32_t)mix64(key) & mask;
   for (int probe = 0; probe < CG_MAXPROBE; ++probe, s = (s + 1) & mask) {
@@ -391,15 +396,9 @@ __global__ __launch_bounds__(256) void k_cg_groups(GuideCols c, uint64_t n, cons
   const uint32_t g = gid[j];
   if (j && gid[j - 1] == g) return;
   group_off[g] = j;
-  const uint64_t r = vals[j];  // the group's first member in table order
-  const bool pamfirst = (right != 0) != (gc_strand(c, r) != 0);
-  const int sh = HAWK_PAD + (pamfirst ? pamlen : 0);
-  const uint64_t m = guidelen >= 64 ? ~0ull : ((1ull << guidelen) - 1ull);
-  const uint64_t A = (gc_win(c, 0, r) >> sh) & m, C = (gc_win(c, 1, r) >> sh) & m, G = (gc_win(c, 2, r) >> sh) & m,
-                 T = (gc_win(c, 3, r) >> sh) & m;
-  const uint64_t gc = (C | G) & ~(A | T), at = (A | T) & ~(C | G);
-  gc_num[g] = (uint8_t)__popcll(gc);
-  gc_den[g] = (uint8_t)__popcll(gc | at);
+  const uchar2 gc = spacer_gc(c, vals[j], guidelen, pamlen, right);  // of the group's first member in table order
+  gc_num[g] = gc.x;
+  gc_den[g] = gc.y;
 }
 
 size_t hawk_collapse_hash_temp_bytes(uint64_t n, uint32_t C) {
@@ -412,56 +411,47 @@ size_t hawk_collapse_hash_temp_bytes(uint64_t n, uint32_t C) {
   return std::max(a, std::max(b, d));
 }
 
-// stage 1: rows into the table, occupied slots packed; counters[0] = identity collisions, [1] = rows that found no
-// slot, [2] = groups - read by the host before stage 2.  table: C slots (a power of two), flags / dense: C words each,
-// gkey: 2 * C, gslot: 2 * C (sort ping-pong)
-int hawk_launch_collapse_hash1(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int flank_up,
-                               int flank_down, int64_t base, uint64_t seed, void* temp, size_t temp_bytes, void* table, uint32_t C,
-                               uint32_t* flags, uint32_t* dense, uint64_t* gkey, uint32_t* gslot, uint32_t* slot_of_row,
-                               unsigned long long* counters) {
-  const int L = guidelen + pamlen;
-  if (hipMemsetAsync(table, 0xff, (size_t)C * sizeof(CgSlot), st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_cg_insert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, is_ref, n, L, flank_up, flank_down, base, seed,
-                     (CgSlot*)table, C - 1, slot_of_row, counters);
+// stage 1: rows into the table, occupied slots packed; the host reads the counters before stage 2
+int hawk_launch_collapse_hash1(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint64_t seed) {
+  const uint32_t C = v.C;
+  if (hipMemsetAsync(v.table, 0xff, (size_t)C * sizeof(CgSlot), st) != hipSuccess) return -2;
+  hipLaunchKernelGGL(k_cg_insert, dim3((unsigned)((k.n + 255) / 256)), dim3(256), 0, st, k.c, k.is_ref, k.n, k.guidelen + k.pamlen, k.flank_up,
+                     k.flank_down, k.base, seed, (CgSlot*)v.table, C - 1, v.slot_of_row, v.counters);
   const dim3 cg((C + 255) / 256);
-  hipLaunchKernelGGL(k_cg_occ, cg, dim3(256), 0, st, (const CgSlot*)table, C, flags);
-  size_t tb = temp_bytes;
-  if (rocprim::exclusive_scan(temp, tb, flags, dense, 0u, (size_t)C, rocprim::plus<uint32_t>(), st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_cg_pack, cg, dim3(256), 0, st, (const CgSlot*)table, C, flags, dense, gkey, gslot, counters);
+  hipLaunchKernelGGL(k_cg_occ, cg, dim3(256), 0, st, (const CgSlot*)v.table, C, v.occ);
+  size_t tb = v.temp_bytes;
+  if (rocprim::exclusive_scan(v.temp, tb, v.occ, v.dense, 0u, (size_t)C, rocprim::plus<uint32_t>(), st) != hipSuccess) return -2;
+  hipLaunchKernelGGL(k_cg_pack, cg, dim3(256), 0, st, (const CgSlot*)v.table, C, v.occ, v.dense, v.gkey, v.gslot, v.counters);
   return 0;
 }
 
-// stage 2: groups in key order, rows by (group, row).  slot2rank: C words (may be `flags` of stage 1); gid: 2 * n, vals: 2 * n
-int hawk_launch_collapse_hash2(hipStream_t st, const GuideCols& c, uint64_t n, uint32_t G, int guidelen, int pamlen, int right, unsigned key_end_bit,
-                               void* temp, size_t temp_bytes, uint64_t* gkey, uint32_t* gslot, uint32_t C, uint32_t* slot2rank,
-                               const uint32_t* slot_of_row, uint32_t* gid, uint32_t* vals, uint64_t* group_off, uint8_t* gc_num,
-                               uint8_t* gc_den) {
-  size_t tb = temp_bytes;
-  if (rocprim::radix_sort_pairs(temp, tb, gkey, gkey + C, gslot, gslot + C, (size_t)G, 0, key_end_bit, st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_cg_rank, dim3((G + 255) / 256), dim3(256), 0, st, gslot + C, G, slot2rank);
-  const dim3 grid((unsigned)((n + 255) / 256));
-  hipLaunchKernelGGL(k_cg_rowgid, grid, dim3(256), 0, st, slot_of_row, slot2rank, n, gid, vals);
-  unsigned gbits = 1;
-  while (gbits < 32 && (G >> gbits) != 0) ++gbits;
-  tb = temp_bytes;
-  if (rocprim::radix_sort_pairs(temp, tb, gid, gid + n, vals, vals + n, (size_t)n, 0, gbits, st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_cg_groups, grid, dim3(256), 0, st, c, n, vals + n, gid + n, guidelen, pamlen, right, group_off, gc_num, gc_den);
-  return 0;
+// stage 2: groups in key order, every row's group number, then the tail below
+int hawk_launch_collapse_hash2(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint32_t G, unsigned key_end_bit) {
+  size_t tb = v.temp_bytes;
+  if (rocprim::radix_sort_pairs(v.temp, tb, v.gkey, v.gkey + v.C, v.gslot, v.gslot + v.C, (size_t)G, 0, key_end_bit, st) != hipSuccess) return -2;
+  hipLaunchKernelGGL(k_cg_rank, dim3((G + 255) / 256), dim3(256), 0, st, v.gslot + v.C, G, v.slot_rank);
+  hipLaunchKernelGGL(k_cg_rowgid, dim3((unsigned)((k.n + 255) / 256)), dim3(256), 0, st, v.slot_of_row, v.slot_rank, k.n, v.gid, v.vals);
+  return hawk_launch_collapse_expand(st, k, v, G);
 }
 
-// the tail of the grouping for a table whose rows already know their group number (collapse_by_templates): rows sorted by
-// (group, row), CSR offsets and G/C counts from each group's first member.  gid / vals: 2 * n words each (sort ping-pong)
+// The tail of the grouping for rows that know their group number (stage 2 above; a cluster-searched table, whose rows inherit
+// their template row's): rows sorted by (group, row) on the bits G groups need, CSR offsets and G/C counts from each group's first member.
 size_t hawk_collapse_expand_temp_bytes(uint64_t n) {
   size_t d = 0;
   (void)rocprim::radix_sort_pairs(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0, 32,
                                   (hipStream_t)0);
   return d;
 }
-int hawk_launch_collapse_expand(hipStream_t st, const GuideCols& c, uint64_t n, unsigned gbits, int guidelen, int pamlen, int right, void* temp,
-                                size_t temp_bytes, uint32_t* gid, uint32_t* vals, uint64_t* group_off, uint8_t* gc_num, uint8_t* gc_den) {
-  size_t tb = temp_bytes;
-  if (rocprim::radix_sort_pairs(temp, tb, gid, gid + n, vals, vals + n, (size_t)n, 0, gbits, st) != hipSuccess) return -2;
-  hipLaunchKernelGGL(k_cg_groups, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, n, vals + n, gid + n, guidelen, pamlen, right, group_off, gc_num,
-                     gc_den);
+static unsigned group_bits(uint64_t G) {
+  unsigned gbits = 1;
+  while (gbits < 32 && (G >> gbits) != 0) ++gbits;
+  return gbits;
+}
+int hawk_launch_collapse_expand(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint64_t G) {
+  const uint64_t n = k.n;
+  size_t tb = v.temp_bytes;
+  if (rocprim::radix_sort_pairs(v.temp, tb, v.gid, v.gid + n, v.vals, v.vals + n, (size_t)n, 0, group_bits(G), st) != hipSuccess) return -2;
+  hipLaunchKernelGGL(k_cg_groups, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, k.c, n, v.vals + n, v.gid + n, k.guidelen, k.pamlen, k.right,
+                     v.group_off, v.gc_num, v.gc_den);
   return 0;
 }

@@ -299,37 +299,57 @@ void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const Sca
                         const RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, unsigned long long* shards,
                         const uint64_t* offsets, GuideCols out, int* status, uint32_t* lists, uint32_t* big_count,
                         unsigned long long* big_list, hipEvent_t mid = nullptr, uint32_t n_tiles = 0xffffffffu);
+// ---- the collapse (hawk_collapse.hip).  These structs are host-side: the kernels keep their plain parameter lists.
+struct CollapseKey {  // the rows of one table and what two of them are compared on
+  GuideCols c; const uint8_t* is_ref; uint64_t n;
+  int guidelen, pamlen, right, flank_up, flank_down;
+  int64_t base;  // the set's smallest genomic position: the sort key holds start - base
+};
+// Plain device-pointer views of the set's collapse workspace (CollapseWs in hawk_host.h, which says who shares storage with whom),
+// one per path.  What both hold: rocprim's scratch, the row ids, the counters and the result.
+struct CollapseView {
+  void* temp; size_t temp_bytes;
+  uint32_t* vals;  // [2][n] sort ping-pong; the half every path's last sort writes is the result's permutation
+  void* full;      // 64-byte full-key records: one per row on the exact sort path, one per group on the hash path
+  // [4], zeroed by the caller.  Sort path: heads by key, heads by identity, verify mismatches.  Hash path: identity collisions,
+  // rows that found no slot, groups, verify mismatches.
+  unsigned long long* counters;
+  uint64_t* group_off;  // n + 1 entries: the number of groups is only known afterwards
+  uint8_t *gc_num, *gc_den;
+};
+struct CollapseSortView : CollapseView {
+  uint64_t* keys;         // [2][n] sort ping-pong
+  uint32_t* head_flags;   // [n]
+  uint32_t* group_index;  // [n] exclusive scan of the head flags
+  uint32_t* id2;          // [n] 32 further hash bits per row, read by the head pass: group_index's storage
+};
+struct CollapseHashView : CollapseView {
+  void* table; uint32_t C;  // C slots of 16 B, a power of two
+  uint32_t* occ;          // [C] stage 1: occupied slots
+  uint32_t* slot_rank;    // [C] stage 2: slot -> group number, in occ's storage
+  uint32_t* dense;        // [C]
+  uint64_t* gkey; uint32_t* gslot;  // [2][C] each: the (key, slot) sort's ping-pong
+  uint32_t* slot_of_row;  // [n]
+  uint32_t* gid;          // [2][n] every row's group number: with vals the (group number, row) sort's ping-pong
+};
 size_t hawk_collapse_temp_bytes(uint64_t n, unsigned begin_bit, unsigned end_bit);
-int hawk_launch_collapse(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int right,
-                         int flank_up, int flank_down, int64_t base, unsigned begin_bit, unsigned end_bit, uint64_t seed, void* temp, size_t temp_bytes, uint64_t* keys, uint32_t* vals,
-                         uint32_t* flags, uint32_t* gidx, unsigned long long* counters, uint64_t* group_off, uint8_t* gc_num,
-                         uint8_t* gc_den, uint32_t* id2 /* may alias gidx */, void* full /* null: identity by hash */, int weak_hash = 0);
-void hawk_launch_collapse_verify(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int flank_up,
-                                 int flank_down, const uint32_t* perm, const uint32_t* grp_a, const uint32_t* grp_b, const uint64_t* group_off,
-                                 unsigned long long* mismatches);
-void hawk_launch_collapse_verify_rows(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, uint32_t G, int guidelen, int pamlen,
-                                      int flank_up, int flank_down, const uint32_t* perm, const uint32_t* slot_of_row, const uint32_t* slot2rank,
-                                      const uint64_t* group_off, void* full /* 64 B per group */, unsigned long long* mismatches);
-void hawk_launch_rows_equal(hipStream_t st, const HapSetDev& hs, uint32_t n_pairs, const uint32_t* ra, const uint32_t* rb, uint8_t* equal);
 size_t hawk_collapse_full_bytes(uint64_t n);
+size_t hawk_collapse_hash_temp_bytes(uint64_t n, uint32_t C);
 size_t hawk_collapse_expand_temp_bytes(uint64_t n);
-int hawk_launch_collapse_expand(hipStream_t st, const GuideCols& c, uint64_t n, unsigned gbits, int guidelen, int pamlen, int right, void* temp,
-                                size_t temp_bytes, uint32_t* gid, uint32_t* vals, uint64_t* group_off, uint8_t* gc_num, uint8_t* gc_den);
+int hawk_launch_collapse(hipStream_t st, const CollapseKey& k, const CollapseSortView& v, unsigned begin_bit, unsigned end_bit, uint64_t seed,
+                         bool exact /* identity by full key, not by hash */, bool weak_hash = false);
+void hawk_launch_collapse_verify(hipStream_t st, const CollapseKey& k, const CollapseSortView& v);
+int hawk_launch_collapse_hash1(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint64_t seed);
+int hawk_launch_collapse_hash2(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint32_t G, unsigned key_end_bit);
+void hawk_launch_collapse_verify_rows(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint32_t G);
+int hawk_launch_collapse_expand(hipStream_t st, const CollapseKey& k, const CollapseHashView& v, uint64_t G);  // reads temp, gid, vals; writes the result
+void hawk_launch_rows_equal(hipStream_t st, const HapSetDev& hs, uint32_t n_pairs, const uint32_t* ra, const uint32_t* rb, uint8_t* equal);
 void hawk_launch_cc_ucnt(hipStream_t st, const void* res, uint32_t nu, uint32_t* cnt);
 void hawk_launch_cc_mini(hipStream_t st, const GuideCols& c, uint64_t r0, const void* trows, uint64_t t_rows, const uint64_t* moff, const uint32_t* tbase,
                          uint32_t nu, int64_t startp, GuideCols m);
 void hawk_launch_cc_gidm(hipStream_t st, const uint32_t* perm, const uint64_t* goff, uint64_t nm, uint64_t G, uint32_t* gidm);
 void hawk_launch_cs_gid(hipStream_t st, const ClDict& cd, const void* res, const uint64_t* moff, const uint64_t* offsets, uint64_t r0, uint64_t n,
                         const uint32_t* gidm, uint32_t* gid, uint32_t* vals);
-size_t hawk_collapse_hash_temp_bytes(uint64_t n, uint32_t C);
-int hawk_launch_collapse_hash1(hipStream_t st, const GuideCols& c, const uint8_t* is_ref, uint64_t n, int guidelen, int pamlen, int flank_up,
-                               int flank_down, int64_t base, uint64_t seed, void* temp, size_t temp_bytes, void* table, uint32_t C,
-                               uint32_t* flags, uint32_t* dense, uint64_t* gkey, uint32_t* gslot, uint32_t* slot_of_row,
-                               unsigned long long* counters);
-int hawk_launch_collapse_hash2(hipStream_t st, const GuideCols& c, uint64_t n, uint32_t G, int guidelen, int pamlen, int right, unsigned key_end_bit,
-                               void* temp, size_t temp_bytes, uint64_t* gkey, uint32_t* gslot, uint32_t C, uint32_t* slot2rank,
-                               const uint32_t* slot_of_row, uint32_t* gid, uint32_t* vals, uint64_t* group_off, uint8_t* gc_num,
-                               uint8_t* gc_den);
 void hawk_launch_collapse_export(hipStream_t st, const GuideCols& c, uint64_t n, uint64_t ng, const uint32_t* perm,
                                  const uint64_t* group_off, const GuideCols& rep, uint32_t* member_hap);
 void hawk_launch_gt_parse(hipStream_t st, const uint8_t* text, const uint64_t* line_off, const uint64_t* gt_off, uint64_t n_lines,

@@ -5,7 +5,9 @@
 
 #include <cstddef>
 #include <cstdio>
+#include <initializer_list>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "../../include/hawk.h"
@@ -103,6 +105,65 @@ struct DevBuf {
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The collapse workspace of a set (hawk_api_collapse.hip): the buffers, and in the accessors the roles they take in turn - every
+// `+ n` and every shared storage of the stage is stated here.  The results stay valid for the table that was collapsed last.
+struct CollapseWs {
+  DevBuf keys, vals, flags, gidx, temp, goff, gc, cnt, full;  // the sort path and the result
+  DevBuf table, occ, dense, gkey, gslot;                       // the hash-table path
+  DevBuf mini[8], m_gid;  // a cluster-searched table: REF's rows + the template rows as a table of their own, their group numbers
+  DevBuf rep[8];          // hawk_table_collapse_export: one representative row per group
+  uint64_t gen = 0;          // generation of the table whose results sit here
+  uint64_t last_groups = 0;  // groups of the last collapse on this set (sizes the hash table of the next one)
+  void release() {
+    for (DevBuf* b : {&keys, &vals, &flags, &gidx, &temp, &goff, &gc, &cnt, &full, &table, &occ, &dense, &gkey, &gslot, &m_gid}) b->release();
+    for (auto& b : mini) b.release();
+    for (auto& b : rep) b.release();
+  }
+  // ---- the result of a collapse of n rows
+  uint32_t* perm(uint64_t n) const { return vals.as<uint32_t>() + n; }  // the half of the row-id ping-pong every path's last sort writes
+  uint64_t* group_off() const { return goff.as<uint64_t>(); }
+  uint8_t* gc_num() const { return gc.as<uint8_t>(); }
+  uint8_t* gc_den(uint64_t n) const { return gc.as<uint8_t>() + n; }  // one byte per group behind the n bytes gc_num may take
+  // the export's member list: `flags` (head flags / slot_of_row), dead once the groups stand
+  uint32_t* members() const { return flags.as<uint32_t>(); }
+  unsigned long long* counters() const { return cnt.as<unsigned long long>(); }
+  // ---- reservations; `temp_bytes` as the hawk_collapse_*temp_bytes functions give them
+  static int reserve_each(std::initializer_list<std::pair<DevBuf*, size_t>> needs) {
+    for (const auto& need : needs)
+      if (int rc = need.first->reserve(need.second)) return rc;
+    return HAWK_OK;
+  }
+  int reserve_rows(uint64_t n, size_t temp_bytes) {
+    return reserve_each({{&keys, 2 * n * 8}, {&vals, 2 * n * 4}, {&flags, n * 4}, {&gidx, n * 4}, {&temp, temp_bytes + 16}, {&goff, (n + 1) * 8},
+                         {&gc, 2 * n}, {&cnt, 32}});
+  }
+  int reserve_table(uint64_t C, size_t temp_bytes) {
+    return reserve_each({{&table, C * 16}, {&occ, C * 4}, {&dense, C * 4}, {&gkey, 2 * C * 8}, {&gslot, 2 * C * 4}, {&temp, temp_bytes + 16}, {&cnt, 32}});
+  }
+  // ---- the views the launchers take (hawk_device.h)
+  void fill(CollapseView* v, size_t temp_bytes, uint64_t n) const {
+    v->temp = temp.p; v->temp_bytes = temp_bytes; v->vals = vals.as<uint32_t>(); v->full = full.p; v->counters = counters();
+    v->group_off = group_off(); v->gc_num = gc_num(); v->gc_den = gc_den(n);
+  }
+  CollapseSortView sort_view(size_t temp_bytes, uint64_t n) const {
+    CollapseSortView v = {};
+    fill(&v, temp_bytes, n);
+    v.keys = keys.as<uint64_t>(); v.head_flags = flags.as<uint32_t>();
+    // id2 is written by the key pass and last read by the head pass; the scan that writes group_index comes behind both
+    v.group_index = v.id2 = gidx.as<uint32_t>();
+    return v;
+  }
+  CollapseHashView hash_view(size_t temp_bytes, uint64_t n, uint64_t C) const {
+    CollapseHashView v = {};
+    fill(&v, temp_bytes, n);
+    v.table = table.p; v.C = (uint32_t)C; v.dense = dense.as<uint32_t>(); v.gkey = gkey.as<uint64_t>(); v.gslot = gslot.as<uint32_t>();
+    v.occ = v.slot_rank = occ.as<uint32_t>();  // the occupancy flags are dead once stage 1 has packed the occupied slots
+    v.slot_of_row = flags.as<uint32_t>();      // no head flags on this path
+    v.gid = keys.as<uint32_t>();               // 2 n words in the 2 n 64-bit keys the sort path would hold
+    return v;
+  }
+};
+
 struct hawk_hapset {
   hawk_ctx* ctx;
   uint32_t n_hap, S;
@@ -126,14 +187,11 @@ struct hawk_hapset {
   int64_t min_gen, max_gen;  // range of genomic positions the position maps reach (collapse sort key)
   uint64_t cols_cap = 0;      // rows the guide-table columns currently hold (0: never reserved)
   uint64_t cols_gen = 0;      // bumped by every hawk_search: a hawk_table of an older generation is stale
-  uint64_t collapse_gen = 0;  // generation of the table whose collapse results sit in the c* buffers
   std::vector<double> cfd_host;  // the CFD tables resident in `cfd`
   // workspace reused across searches
   DevBuf keepF, keepR, counts, offsets, totals, misc, cfd, partial, sites, hits, guides, lists;
-  DevBuf ckeys, cvals, cflags, cgidx, ctemp, cgoff, cgc, ccnt, cfull;  // hawk_table_collapse
-  DevBuf ctable, cocc, cdense, cgkey, cgslot;                          // ... its hash-table path
-  uint64_t last_groups = 0;   // groups of the last collapse on this set (sizes the table of the next one)
-  std::shared_ptr<uint64_t> plan_groups;  // ... shared with the expansion plan the set came from: the next run of the plan starts from it
+  CollapseWs cws;             // hawk_table_collapse*
+  std::shared_ptr<uint64_t> plan_groups;  // cws.last_groups shared with the expansion plan the set came from: the next run of the plan starts from it
   DevBuf otoff, otcode, otid, othit;  // hawk_offtarget_scan: bucketed guides, gathered hit sites
   DevBuf otsum;                       // hawk_offtarget_summary: counters, per-guide sums, CFD tables - sized by the guides, not the hits
   DevBuf big;                 // tiles whose rows exceed the hand-over list (k_search_emit's work list)
@@ -147,11 +205,9 @@ struct hawk_hapset {
   DevBuf refhp;               // REF's PAM hits + prefix counts per strand (k_ref_hits), keyed like refbits
   uint64_t cs_tcap = 0;       // template rows a search of this view may need (raised to the plan's bound after an overflow)
   DevBuf cs_res, cs_tbase, cs_trows, cs_inst;  // per distinct cluster 32 B {rows per strand, hits, candidates} {first template row, REF hits before / behind}, first template row; template rows; per instance 16 B {rows, first template row, haplotype row shifted, position} (k_cs_count -> k_cs_emit_rows)
-  DevBuf cmini[8], cm_gid;   // hawk_table_collapse of such a table: REF's rows + the template rows as a table of their own, their groups
   DevBuf colsA[8];
   DevBuf rowsA;               // packed rows of a cluster-searched table (colsA then stages REF's rows only)
   uint64_t rows_cap = 0;
-  DevBuf crep[8];  // hawk_table_collapse_export: one representative row per group
 };
 
 // An expansion plan keeps everything an expansion needs in HBM - the variant table, the carried-variant lists, the
@@ -226,6 +282,8 @@ struct hawk_table {
 };
 // HAWK_E_INVALID when a later hawk_search on the same set has overwritten the table's columns
 inline bool hawk_table_stale(const hawk_table* t) { return t->hs && t->gen != t->hs->cols_gen; }
+// the collapse results live in the set's workspace: valid for the table that was collapsed last, until the next search
+inline bool collapse_valid(const hawk_table* t) { return t && t->collapsed && t->hs && !hawk_table_stale(t) && t->hs->cws.gen == t->gen; }
 
 // hawk_table_resolve_unphased's handle (hawk_api_resolve.hip); hawk_resolve_groups (hawk_api_ugroups.hip) reads it as well
 struct hawk_resolve {

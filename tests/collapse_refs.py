@@ -1,6 +1,6 @@
 """Reference and case builders for tests/test_gpu_collapse.py, all on the CPU: a dictionary grouping of a guide table's own rows
 (the report's groupby, reports.py:958-1008, with the model scorers' flanks in the key where asked), the key-width arithmetic of
-collapse_rows (hawk_api_collapse.hip) restated, and hand-built haplotype sets - short sequences with a free position map -
+the collapse driver (hawk_api_collapse.hip) restated, and hand-built haplotype sets - short sequences with a free position map -
 placed on the seams of the collapse: one key field at a time, a flank base in and just outside the compared slice, position-map
 spans one below and exactly at the steps of the sort key, thousands of different rows under one (start, strand).  Every builder
 PROVES its seam from the oracle's search of the same set; a case that has drifted off its seam fails in its builder, and
@@ -62,7 +62,7 @@ def reference_arrays(groups, gc, perm, off):
     return (want_perm, want_off, np.array([gc[k][0] for k in keys], dtype=np.uint8), np.array([gc[k][1] for k in keys], dtype=np.uint8))
 
 
-# ---- the sort key's widths (collapse_rows in hawk_api_collapse.hip, restated) ----------------------------------------------
+# ---- the sort key's widths (the collapse driver in hawk_api_collapse.hip, restated) ----------------------------------------
 SPAN_MAX = 0xffffffff
 
 
@@ -331,6 +331,20 @@ def case_counts(n_groups, copies):
     return c
 
 
+def case_isolated_pams(k):
+    """exactly k groups of one row: a REF-only A/T background with k isolated AGG, 30 nt apart - k forward rows, no reverse hit.
+    (1, 255, 256 and 257 groups, of one row and of two, are case_counts' above; this adds the count between 1 and 255 at which the
+    bits of the (group number, row) sort step from 1 to 2.)"""
+    c = Direct(f"isolated-{k}", "NGG", 20, False)
+    rng = np.random.default_rng(67)
+    c.add(_filler(rng, 40, c.pam) + "".join("AGG" + _filler(rng, 27, c.pam) for _ in range(k)) + _filler(rng, 40, c.pam), is_ref=True)
+    g, _ = c.rows()
+    groups, _ = c.reference()
+    c.prove(f"{k} forward rows of REF", len(g) == k and (g["strand"] == 0).all())
+    c.prove(f"{k} groups of one row", len(groups) == k and all(len(v) == 1 for v in groups.values()))
+    return c
+
+
 GC_SHAPES = [(1, "NGG", False), (1, "TTTV", True), (20, "NGG", False), (20, "TTTV", True), (41, "NGG", False), (40, "TTTV", True),
              (43, "G", False), (43, "G", True)]
 
@@ -505,7 +519,7 @@ def case_table_memory():
 
 CASES_A = ([lambda s=s: case_stop_only(s) for s in (0, 1)] + [case_origin, lambda: case_case_only("spacer0"), lambda: case_case_only("pam-last"),
            case_iupac, case_many_identical] + [lambda n=n, m=m: case_counts(n, m) for m in (1, 2) for n in (255, 256, 257)] +
-           [lambda: case_counts(1, 1)] + [lambda a=a: case_gc(*a) for a in GC_SHAPES])
+           [lambda: case_counts(1, 1)] + [lambda a=a: case_gc(*a) for a in GC_SHAPES] + [lambda: case_isolated_pams(2)])
 
 
 # ---- E: panels for the template path (built on test_gpu_clusters.Panel: sites are 0-based indices into the region string) ------
