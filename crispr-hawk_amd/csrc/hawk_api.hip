@@ -150,7 +150,7 @@ int hawk_init(int device, hawk_ctx** out) {
   HIPCHK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
   for (int i = 0; i < (int)(sizeof(ctx->ev) / sizeof(ctx->ev[0])); ++i)
     HIPCHK(i < HAWK_EV_TIMED ? hipEventCreate(&ctx->ev[i]) : hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
-  HIPCHK(hipHostMalloc(&ctx->pinned, 256, hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(&ctx->pinned, sizeof(PinnedBlock), hipHostMallocDefault));
   g_ctx_of[device] = ctx; g_ctx_refs[device] = 1;
   *out = ctx;
   return HAWK_OK;

@@ -254,9 +254,7 @@ static int collapse_by_templates(hawk_table* t, uint32_t flank_up, uint32_t flan
   // every mini row's group number, then every table row's; the table's rows sorted by (group, row)
   HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));
   hawk_launch_cc_gidm(ctx->stream, ws.perm(nm), ws.group_off(), nm, G, ws.m_gid.as<uint32_t>());
-  ClDict cd;
-  memset(&cd, 0, sizeof(cd));
-  cd.n_inst = vx->cl.n_inst; cd.n_uniq = vx->cl.n_uniq; cd.inst_uid = vx->cl.inst_uid.as<uint32_t>();
+  const ClDict cd = vx->cl.view();
   const CollapseKey key = {t->cols, hs->d_is_ref, n, (int)t->guidelen, (int)t->pamlen, (int)t->right, (int)flank_up, (int)flank_down, hs->min_gen};
   const CollapseHashView v = ws.hash_view(tb, n, 0);  // no table: the rows' group numbers come from their template rows
   hawk_launch_cs_gid(ctx->stream, cd, hs->cs_res.p, d_moff, hs->offsets.as<uint64_t>() + t->plane_tiles, r0, n, ws.m_gid.as<uint32_t>(), v.gid, v.vals);

@@ -102,7 +102,7 @@ static int search_reserve(SearchRun* r, const hawk_search_params* p) {
     return rc;
   r->shards = &hs->misc.as<SearchMisc>()->shards[0][0];
   r->blk = &hs->misc.as<SearchMisc>()->blk;
-  r->h = static_cast<SearchStatusBlock*>(r->ctx->pinned);
+  r->h = &static_cast<PinnedBlock*>(r->ctx->pinned)->search;
   GuideParams& gp = r->gp;
   gp.pamlen = sp.pamlen; gp.guidelen = sp.guidelen; gp.right = sp.right; gp.L = sp.L;
   gp.score_cfdon = (int32_t)p->score_cfdon;  // 1: a non-ACGT base under a lookup is HAWK_E_CFD; 2: it scores NaN ("NA")
@@ -172,12 +172,8 @@ static int search_view_args(SearchRun* r) {
   va.ref_S = hs->S; va.hp = hs->refhp.as<uint4>();
   va.recs_ = vx->recs.p; va.alt_codes = vx->codes.as<uint8_t>(); va.hv_off = vx->off.as<uint64_t>(); va.tiles_ = vx->tiles.p;
   if (!r->by_cluster) return HAWK_OK;
-  const auto& cl = vx->cl;
-  cd.n_inst = cl.n_inst; cd.n_uniq = cl.n_uniq;
-  cd.inst_uid = cl.inst_uid.as<uint32_t>(); cd.inst_o = cl.inst_o.as<int32_t>(); cd.inst_row = cl.inst_row.as<uint32_t>();
-  cd.inst_pa = cl.inst_pa.as<int32_t>(); cd.inst_rb = cl.inst_rb.as<int32_t>();
-  cd.u_rec = cl.u_rec.as<uint32_t>(); cd.u_n = cl.u_n.as<uint32_t>(); cd.u_row = cl.u_row.as<uint32_t>(); cd.u_o = cl.u_o.as<int32_t>();
-  cd.u_seg = cl.u_seg.as<uint32_t>();
+  const ClusterDictionary& cl = vx->cl;
+  cd = cl.view();
   // template rows: packed as the search produces them.  Their number is bounded by the window starts of the distinct clusters
   // (cl.slots: 2 strands x every start), but a PAM keeps a few per cent of those: reserve 16 rows per distinct cluster, and
   // if a search needs more it produces no table (k_cs_count sees the counter), says so and is rerun with the bound reserved

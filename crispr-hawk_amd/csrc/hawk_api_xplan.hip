@@ -1,10 +1,9 @@
-// hawk_api_xplan.hip - C ABI: expansion plans, plan views and the cluster dictionary (f1)
+// hawk_api_xplan.hip - C ABI: expansion plans, plan views, the rows' text and metadata (f1; the cluster dictionary: hawk_api_cldict.hip)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -14,8 +13,8 @@
 
 #include "hawk_host.h"
 
-// The slots of hawk_ctx::ev this file records: the kernels a call times for its caller (kernel_ms), and the dictionary build (build_ms).
-enum XplanEvent { EV_KERNELS_BEGIN = 0, EV_KERNELS_END = 1, EV_BUILD_BEGIN = 8, EV_BUILD_END = 9 };
+// The slots of hawk_ctx::ev this file records: the kernels a call times for its caller (kernel_ms).
+enum XplanEvent { EV_KERNELS_BEGIN = 0, EV_KERNELS_END = 1 };
 
 extern "C" {
 
@@ -30,10 +29,9 @@ void hawk_xplan_destroy(hawk_xplan* x) {
   for (auto& p : x->ref_plane) hawk_pool_free(p);
   for (auto& b : x->ref5) b.release();
   DevBuf* bufs[] = {&x->recs, &x->heads, &x->tiles, &x->codes, &x->off, &x->hlen, &x->hash,
-                    &x->m_is_ref, &x->m_ss, &x->m_se, &x->m_seg_off, &x->m_seg_rel, &x->m_seg_gen, &x->m_tile,
-                    &x->cl.inst_uid, &x->cl.inst_o, &x->cl.inst_row, &x->cl.inst_pa, &x->cl.inst_rb, &x->cl.u_rec, &x->cl.u_n, &x->cl.u_row,
-                    &x->cl.u_o, &x->cl.u_seg};
+                    &x->m_is_ref, &x->m_ss, &x->m_se, &x->m_seg_off, &x->m_seg_rel, &x->m_seg_gen, &x->m_tile};
   for (auto* b : bufs) b->release();
+  x->cl.release();
   delete x;
 }
 
@@ -185,164 +183,6 @@ int hawk_xplan_run(hawk_xplan* x, hawk_hapset** out, uint64_t* hash_out, float* 
   if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, ctx->ev[EV_KERNELS_BEGIN], ctx->ev[EV_KERNELS_END]);
   *out = hs;
   return HAWK_OK;
-}
-
-// The cluster dictionary of a plan (hawk_csearch.hip): which rows carry which distinct variant cluster.  Built once per plan,
-// from the records and the rows' scan bounds; a search of a view then does the per-window work once per distinct cluster.
-// Not usable (the per-word search of hawk_vsearch.hip takes the plan instead) when a chain of variants is longer than the
-// builder accepts, when two different clusters share a hash, or when sharing is too thin to pay for the template rows.
-static int xplan_build_dict(hawk_xplan* x) {
-  auto& cl = x->cl;
-  if (cl.built) return HAWK_OK;
-  cl.built = true; cl.usable = false; cl.status = 0; cl.n_inst = cl.n_uniq = cl.n_real = 0; cl.slots = 0; cl.build_ms = 0.f;
-  hawk_ctx* ctx = x->ctx;
-  hipStream_t st = ctx->stream;
-  const uint32_t n = x->n_hap;
-  if (x->ncar == 0 || x->ncar >= (1ull << 32) - 2 || n < 2) { cl.status = 4; return HAWK_OK; }
-  PoolScope tmp;
-  // Sizes first - nothing below waits for a count from the device.  An instance starts at a record or closes a row, so records + rows
-  // bounds their number: the instance arrays, the list and the grids of the passes are sized by the bound, the passes read the true
-  // counts on the device, and the host learns them together with the number of distinct clusters, once, at the end.
-  const uint32_t n_var = x->n_var;
-  const uint32_t ch_bound = hawk_cl_chunk_bound(x->ncar, n);  // the rows' records in chunks (hawk_csearch.hip)
-  const uint32_t inst_bound = (uint32_t)x->ncar + n;
-  const uint32_t bm_words = n_var / 32 + 1;
-  // The table of the clusters that are more than their variant: at least two slots per listed instance would always do, but the
-  // distinct clusters are a small fraction of the instances and clearing 32 bytes x 2^25 slots costs more than every kernel of this
-  // build - so the first attempt takes two slots per distinct cluster EXPECTED (the last build's count, else an eighth of the
-  // instances), gives up after 64 probes (status bit 8), and the pass is repeated with the full size
-  uint32_t tsize = 1024;
-  while (tsize < 2u * inst_bound && tsize < (1u << 30)) tsize <<= 1;
-  uint32_t tsmall = std::min<uint32_t>(1u << 16, tsize);
-  { const uint64_t expect = cl.last_uniq ? (uint64_t)cl.last_uniq * 2 : (uint64_t)inst_bound / 8; while (tsmall < expect && tsmall < tsize) tsmall <<= 1; }
-  const uint32_t u_bound0 = n_var + std::min<uint32_t>(tsmall, inst_bound);  // cluster numbers of the first attempt: the variants, then what its table can hold
-  // everything that starts from zero, in ONE block cleared by ONE memset: status, counters, the chunks' counts, the variants' bitmap
-  // and describers, the clusters' template-row bounds, the first attempt's table
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t z_status = 0, z_counters = 256, z_results = 512, z_cnt = 768,
-               z_claim = z_cnt + up(((size_t)ch_bound + 4) * 8), z_vdesc = z_claim + up((size_t)bm_words * 4),
-               z_span2 = z_vdesc + up((size_t)std::max<uint32_t>(n_var, 1) * 8), z_tab = z_span2 + up((size_t)u_bound0 * 4),
-               z_end = z_tab + (size_t)tsmall * hawk_cl_slot_bytes();
-  char* d_zero;
-  TEMPCHK(tmp, &d_zero, z_end);
-  uint32_t* const d_status = reinterpret_cast<uint32_t*>(d_zero + z_status);
-  uint32_t* const d_counters = reinterpret_cast<uint32_t*>(d_zero + z_counters);
-  unsigned long long* const d_results = reinterpret_cast<unsigned long long*>(d_zero + z_results);
-  uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(d_zero + z_cnt);
-  uint32_t* const d_lcnt = d_cnt + ((ch_bound + 3) & ~3u);  // (16-byte aligned: k_scan2_u32 loads four counts at a time)
-  uint32_t* const d_claim = reinterpret_cast<uint32_t*>(d_zero + z_claim);
-  void* const d_vdesc = d_zero + z_vdesc;
-  uint32_t *d_ch_off, *d_ch_row, *d_base, *d_lbase, *d_state;
-  void* d_list;
-  TEMPCHK(tmp, &d_ch_off, (size_t)(n + 1) * 4);
-  TEMPCHK(tmp, &d_ch_row, (size_t)ch_bound * 4);
-  TEMPCHK(tmp, &d_base, (size_t)(ch_bound + 1) * 4);
-  TEMPCHK(tmp, &d_lbase, (size_t)(ch_bound + 1) * 4);
-  TEMPCHK(tmp, &d_list, (size_t)inst_bound * hawk_cl_listed_bytes());
-  TEMPCHK(tmp, &d_state, (size_t)inst_bound * 4);
-  int rc;
-  if ((rc = cl.inst_uid.reserve((size_t)inst_bound * 4)) || (rc = cl.inst_o.reserve((size_t)inst_bound * 4)) ||
-      (rc = cl.inst_row.reserve((size_t)inst_bound * 4)) || (rc = cl.inst_pa.reserve((size_t)inst_bound * 4)) ||
-      (rc = cl.inst_rb.reserve((size_t)inst_bound * 4)))
-    return rc;
-  uint32_t* const t_uid = cl.inst_uid.as<uint32_t>();   // the instances stay in the order they are built in: (row, position)
-  uint32_t* const t_row = cl.inst_row.as<uint32_t>();
-  int32_t* const t_o = cl.inst_o.as<int32_t>();
-  int32_t* const t_pa = cl.inst_pa.as<int32_t>();
-  int32_t* const t_rb = cl.inst_rb.as<int32_t>();
-  HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_BEGIN], st));
-  HIPCHK(hipMemsetAsync(d_zero, 0, z_end, st));
-  // chunks per row -> their offsets and rows, then the instances every chunk opens and how many of them go on the list of the
-  // clusters that are more than their variant - and, from a large job's first chunks, the variants they describe (the number of
-  // chunks is only known on the device - rows that scan nothing have
-  // none: the count pass and its scan run over the bound; chunks beyond the last one open nothing)
-  hawk_launch_cl_chunks(st, x->off.as<uint64_t>(), x->m_is_ref.as<uint8_t>(), x->m_ss.as<int32_t>(), x->m_se.as<int32_t>(), n, d_ch_off, d_ch_row);
-  hawk_launch_cl_count(st, x->heads.p, x->off.as<uint64_t>(), x->hlen.as<uint32_t>(), x->m_ss.as<int32_t>(), x->m_se.as<int32_t>(), d_ch_off, d_ch_row, n,
-                       n_var, ch_bound, d_cnt, d_lcnt, d_vdesc);
-  if (hawk_cl_head_chunks(ch_bound))  // (beside the scan, in its launch: the bitmap of the variants the first chunks described)
-    hawk_launch_scan2_u32(st, d_cnt, d_lcnt, ch_bound, d_base, d_lbase, d_vdesc, d_claim, n_var);
-  else
-    hawk_launch_scan2_u32(st, d_cnt, d_lcnt, ch_bound, d_base, d_lbase);
-  const uint32_t* const d_n_inst = d_base + ch_bound;
-  const uint32_t* const d_n_list = d_lbase + ch_bound;
-  // One pass = cut the rows (a one-record shareable instance is its variant; the rest goes on the list), the listed instances through
-  // the table, the distinct clusters' descriptions, the listed instances that share a cluster - queued without a read-back in
-  // between.  The host reads the counts once, at the end, and repeats the pass if the small table gave up.
-  // (read back into the context's page-locked block, behind the 64 bytes a search's status block takes: a copy into pageable memory is staged)
-  unsigned long long* const res = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->pinned) + 128);
-  for (int k = 0; k < 8; ++k) res[k] = 0;
-  uint32_t status = 0, n_inst = 0, n_uniq = 0, n_real = 0;
-  auto pass = [&](uint32_t tsz, uint32_t max_probe, uint32_t fail_bit, bool first) -> int {
-    const uint32_t u_bound = n_var + std::min<uint32_t>(tsz, inst_bound);  // the variants, then what the table can hold
-    uint32_t* d_span2 = reinterpret_cast<uint32_t*>(d_zero + z_span2);
-    void* d_tab = d_zero + z_tab;
-    if (!first) {  // the repeat: its own, larger table and bounds, the counters cleared again.  The variants' bitmap and describers stay:
-      // the counting pass and the scan, which are not repeated, left the first rows' there, and who describes a variant does not depend on the table
-      TEMPCHK(tmp, &d_span2, (size_t)u_bound * 4);
-      TEMPCHK(tmp, &d_tab, (size_t)tsz * hawk_cl_slot_bytes());
-      HIPCHK(hipMemsetAsync(d_tab, 0, (size_t)tsz * hawk_cl_slot_bytes(), st));
-      HIPCHK(hipMemsetAsync(d_span2, 0, (size_t)u_bound * 4, st));
-      HIPCHK(hipMemsetAsync(d_zero + z_counters, 0, z_cnt - z_counters, st));               // counters, results
-    }
-    int rc2;
-    if ((rc2 = cl.u_rec.reserve((size_t)u_bound * 4)) || (rc2 = cl.u_n.reserve((size_t)u_bound * 4)) || (rc2 = cl.u_row.reserve((size_t)u_bound * 4)) ||
-        (rc2 = cl.u_o.reserve((size_t)u_bound * 4)) || (rc2 = cl.u_seg.reserve((size_t)u_bound * 4)))
-      return rc2;
-    hawk_launch_cl_fill(st, x->heads.p, x->off.as<uint64_t>(), x->hlen.as<uint32_t>(), x->m_ss.as<int32_t>(), x->m_se.as<int32_t>(), n, d_ch_off, d_ch_row,
-                        ch_bound, d_base, d_lbase, t_o, t_row, t_pa, t_rb, t_uid, d_vdesc, d_claim, n_var, d_list, d_status);
-    hawk_launch_cl_finish(st, inst_bound, d_n_inst, d_n_list, d_counters, d_results, n_var, u_bound, d_tab, tsz - 1, max_probe, fail_bit, d_list, d_state, d_vdesc, x->heads.p,
-                          t_uid, t_row, x->m_seg_off.as<uint32_t>(), x->m_seg_rel.as<uint32_t>(), cl.u_rec.as<uint32_t>(), cl.u_n.as<uint32_t>(),
-                          cl.u_row.as<uint32_t>(), cl.u_o.as<int32_t>(), cl.u_seg.as<uint32_t>(), d_span2, d_status);
-    HIPCHK(hipMemcpyAsync(res, d_results, 64, hipMemcpyDeviceToHost, st));  // {instances, the table's clusters, the variants that are clusters, template rows, status}
-    HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_END], st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    n_inst = (uint32_t)res[0]; status = (uint32_t)res[4];
-    n_uniq = std::min<uint32_t>(n_var + (uint32_t)res[1], u_bound);  // the range of the numbers
-    n_real = (uint32_t)(res[1] + res[2]);
-    return HAWK_OK;
-  };
-  if ((rc = pass(tsmall, tsmall < tsize ? 64u : 0xffffffffu, tsmall < tsize ? 8u : 2u, true))) return rc;
-  if (status & 8u) {  // the small table filled up: once more with two slots per instance
-    status &= ~8u;
-    HIPCHK(hipMemcpyAsync(d_status, &status, 4, hipMemcpyHostToDevice, st));
-    if ((rc = pass(tsize, 0xffffffffu, 2u, false))) return rc;
-  }
-  if (n_inst == 0) { cl.status = 4; return HAWK_OK; }
-  if (n_inst > inst_bound) { snprintf(hawk_hip_err_buf(), 256, "hawk_xplan_view: instance count beyond its bound"); return HAWK_E_HIP; }
-  cl.n_inst = n_inst; cl.n_uniq = n_uniq; cl.n_real = n_real; cl.last_uniq = (uint32_t)res[1];
-  (void)hipEventElapsedTime(&cl.build_ms, ctx->ev[EV_BUILD_BEGIN], ctx->ev[EV_BUILD_END]);
-  cl.slots = n_uniq ? res[3] : 0;
-  cl.status = status;
-  // worth it when clusters are shared (the template rows are extra traffic otherwise) and the templates fit a sane budget
-  // (HAWK_CLUSTER_MAX_SLOTS template rows, default 2^27 = 10 GB; HAWK_CLUSTER_MIN_SHARE instances per distinct cluster, default 3:
-  // read per call so that tests can send small panels down this path)
-  const char* e1 = getenv("HAWK_CLUSTER_MAX_SLOTS");
-  const char* e2 = getenv("HAWK_CLUSTER_MIN_SHARE");
-  const uint64_t max_slots = e1 ? strtoull(e1, nullptr, 10) : (1ull << 27);
-  const double min_share = e2 ? atof(e2) : 3.0;
-  if (!status && (cl.slots > max_slots || (double)n_inst < min_share * (double)std::max<uint32_t>(n_real, 1))) cl.status = 4;
-  cl.usable = cl.status == 0;
-  return HAWK_OK;
-}
-
-int hawk_xplan_cluster_stats(const hawk_xplan* x, uint32_t* usable, uint32_t* n_instances, uint32_t* n_distinct, uint64_t* template_slots,
-                             float* build_ms, uint32_t* status) {
-  if (!x) return HAWK_E_INVALID;
-  if (usable) *usable = x->cl.built && x->cl.usable ? 1u : 0u;
-  if (n_instances) *n_instances = x->cl.n_inst;
-  if (n_distinct) *n_distinct = x->cl.n_real;
-  if (template_slots) *template_slots = x->cl.slots;
-  if (build_ms) *build_ms = x->cl.build_ms;
-  if (status) *status = x->cl.built ? x->cl.status : 0xffffffffu;
-  return HAWK_OK;
-}
-
-int hawk_xplan_cluster_rebuild(hawk_xplan* x) {
-  if (!x || !x->has_meta || x->ref_index != 0) return HAWK_E_INVALID;
-  HIPCHK(hipSetDevice(x->ctx->device));
-  x->cl.built = false;
-  return xplan_build_dict(x);
 }
 
 int hawk_xplan_view(hawk_xplan* x, hawk_hapset** out) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hawk_cl.h"
+
 #define HAWK_PLANES 5   // A, C, G, T (the IUPAC nibble's bits, encoder.py:18-34) and V (lower case)
 #define HAWK_PAD 10     // GUIDESEQPAD, guide.py:21
 #define HAWK_BLOCK 256  // threads per workgroup = 4 wavefronts
@@ -138,7 +140,7 @@ void hawk_launch_vsearch(hipStream_t st, int pass, const HapSetDev& hs, const Vc
                          const struct RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, uint32_t* counts0, unsigned long long* shards,
                          const uint64_t* offsets, struct GuideCols out, int* status, uint32_t tile0, uint32_t n_tiles);
 void hawk_launch_ref_hits(hipStream_t st, const HapSetDev& hs, const ScanParams& p, int32_t ref_index, void* hp);
-// The cluster dictionary of an expansion plan (hawk_csearch.hip): every row's records cut into clusters (variants whose
+// The cluster dictionary of an expansion plan (hawk_cldict.hip): every row's records cut into clusters (variants whose
 // alleles lie within 64 positions of each other), identical clusters of different rows numbered once.
 struct ClDict {
   uint32_t n_inst, n_uniq;
@@ -157,29 +159,14 @@ size_t hawk_cs_row_bytes();
 void hawk_launch_scan2_u32(hipStream_t st, const uint32_t* cnt_a, const uint32_t* cnt_b, uint32_t n, uint32_t* off_a, uint32_t* off_b,
                            const void* desc = nullptr, uint32_t* desc_bits = nullptr, uint32_t n_desc = 0);  // two arrays, one launch; beside it, if asked for:
                            // which of n_desc 64-bit words are not 0, as a bitmap of n_desc / 32 + 1 words
+// hawk_cldict.hip: a build of the dictionary, pass by pass, over the views of hawk_cl.h
 void hawk_launch_hx_heads(hipStream_t st, const void* recs, const uint32_t* hv_idx, uint64_t n, void* heads);  // {o, rs, alt_len, variant} per record
-// (the hawk_launch_cl_* passes take the HEADS as `recs`)
-uint32_t hawk_cl_chunk_bound(uint64_t n_records, uint32_t n_rows);  // room for ch_row / the chunks' counts
-void hawk_launch_cl_chunks(hipStream_t st, const uint64_t* hv_off, const uint8_t* is_ref, const int32_t* ss, const int32_t* se, uint32_t n_rows,
-                           uint32_t* ch_off, uint32_t* ch_row);
+void hawk_launch_cl_chunks(hipStream_t st, const ClBuild& b);  // rows -> chunks: ch_off, ch_row
 uint32_t hawk_cl_head_chunks(uint32_t ch_bound);  // the first chunks, whose variants the counting pass describes (0: a small job, none)
-void hawk_launch_cl_count(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
-                          const uint32_t* ch_off, const uint32_t* ch_row, uint32_t n_rows, uint32_t n_var, uint32_t ch_bound, uint32_t* cnt /* zeroed */,
-                          uint32_t* lcnt /* zeroed */, void* var_desc /* 8 B per variant, zeroed */);  // per chunk: the instances it opens, and how
-                          // many of them go on the list; the first hawk_cl_head_chunks() chunks also describe the variants they carry
-void hawk_launch_cl_fill(hipStream_t st, const void* recs, const uint64_t* hv_off, const uint32_t* hap_len, const int32_t* ss, const int32_t* se,
-                         uint32_t n_rows, const uint32_t* ch_off, const uint32_t* ch_row, uint32_t ch_bound, const uint32_t* inst_base,
-                         const uint32_t* list_base, int32_t* o, uint32_t* row, int32_t* pa, int32_t* rb, uint32_t* inst_uid,
-                         void* var_desc /* as hawk_launch_cl_count left it */, const uint32_t* claim_bits /* n_var bits: who is described */, uint32_t n_var,
-                         void* cx_list /* hawk_cl_listed_bytes() per listed instance */, uint32_t* status);
-size_t hawk_cl_slot_bytes();    // a slot of the table of the listed instances' clusters
-size_t hawk_cl_listed_bytes();  // a list entry
-void hawk_launch_cl_finish(hipStream_t st, uint32_t list_bound, const uint32_t* n_inst_dev, const uint32_t* n_list_dev, uint32_t* counters /* 8, zeroed */,
-                           unsigned long long* results /* 8: instances, table clusters, variant clusters, template rows, status */, uint32_t n_var, uint32_t u_cap,
-                           void* tab /* zeroed */, uint32_t mask, uint32_t max_probe, uint32_t fail_bit, const void* cx_list, uint32_t* cx_state,
-                           const void* var_desc, const void* recs, uint32_t* inst_uid, const uint32_t* inst_row, const uint32_t* seg_off,
-                           const uint32_t* seg_rel, uint32_t* u_rec, uint32_t* u_n, uint32_t* u_row, int32_t* u_o, uint32_t* u_seg, uint32_t* u_span2,
-                           uint32_t* status);
+void hawk_launch_cl_count(hipStream_t st, const ClBuild& b);  // per chunk: the instances it opens (cnt), and how many of them go on the list
+                          // (lcnt); the first hawk_cl_head_chunks() chunks also describe the variants they carry
+void hawk_launch_cl_fill(hipStream_t st, const ClBuild& b);   // behind the scan of the counts: the instances, the list, the variants' describers
+void hawk_launch_cl_finish(hipStream_t st, const ClBuild& b, const ClTable& t, const ClUniq& cu);  // the list through the table, the clusters' descriptions, the result block
 void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const struct GuideParams& gp,
                               const struct RefInfo& ri, void* res /* 32 B per distinct cluster */, uint32_t* tbase, void* trows,
                               unsigned long long* t_count, uint64_t t_cap, int* status);

@@ -35,8 +35,7 @@ struct hawk_ctx {
   // Scratch of the call that is running: every C-ABI call records the events it times with and reads them before it returns.
   // No call may read an event another call recorded (two calls use the same slots for different intervals).
   hipEvent_t ev[12];
-  void* pinned = nullptr;  // 256 B of page-locked host memory: hawk_search reads the device's SearchStatusBlock back into it ([0, 64)),
-                           // the cluster dictionary's build its result block ([128, 192))
+  void* pinned = nullptr;  // page-locked host memory: a PinnedBlock (below)
 };
 
 // What hs->misc holds while hawk_search runs.  The host and the kernels' launchers share the status block; the host reads it back
@@ -57,6 +56,14 @@ static_assert(sizeof(SearchStatusBlock) == 64 && sizeof(SearchMisc) == 4096 + 64
 static_assert(offsetof(SearchMisc, shards) == 0 && offsetof(SearchMisc, blk) == 4096, "status block layout");
 static_assert(offsetof(SearchStatusBlock, status) == 0 && offsetof(SearchStatusBlock, template_rows) == 8 &&
               offsetof(SearchStatusBlock, big_count) == 16 && offsetof(SearchStatusBlock, totals) == 32, "status block layout");
+// hawk_ctx::pinned: what the two read-backs that go through page-locked memory land in (a copy into pageable memory is staged)
+struct PinnedBlock {
+  SearchStatusBlock search;  // [0, 64) hawk_search
+  char gap0[64];
+  ClResults dict;            // [128, 192) the build of the cluster dictionary
+  char gap1[64];
+};
+static_assert(offsetof(PinnedBlock, search) == 0 && offsetof(PinnedBlock, dict) == 128 && sizeof(PinnedBlock) == 256, "page-locked block layout");
 
 // Caching device allocator, one per device: a freed block goes to a free list and is handed to the next request of a
 // similar size, so a per-tile loop (expand -> search -> collapse, tile after tile) allocates its planes, columns and
@@ -210,6 +217,30 @@ struct hawk_hapset {
   uint64_t rows_cap = 0;
 };
 
+// The cluster dictionary of an expansion plan, as the host keeps it (kernels: hawk_cldict.hip; build: hawk_api_cldict.hip).
+struct ClusterDictionary {
+  bool built = false, usable = false;
+  uint32_t n_inst = 0, n_uniq = 0;  // n_uniq: the RANGE of the distinct clusters' numbers (variants first - with holes - then the table's)
+  uint32_t n_real = 0;              // how many distinct clusters there are
+  uint32_t last_uniq = 0;  // distinct clusters of the previous build (sizes the first hash table of the next)
+  uint64_t slots = 0;     // bound on the template rows of a search: window starts x 2 strands over all distinct clusters
+  uint32_t status = 0;    // why it is not usable: ClStatus bits (hawk_cl.h)
+  float build_ms = 0.f;
+  DevBuf inst_uid, inst_o, inst_row, inst_pa, inst_rb, u_rec, u_n, u_row, u_o, u_seg;
+  void release() {
+    for (DevBuf* b : {&inst_uid, &inst_o, &inst_row, &inst_pa, &inst_rb, &u_rec, &u_n, &u_row, &u_o, &u_seg}) b->release();
+  }
+  ClDict view() const {  // what the kernels of a search read (hawk_device.h)
+    ClDict cd;
+    cd.n_inst = n_inst; cd.n_uniq = n_uniq;
+    cd.inst_uid = inst_uid.as<uint32_t>(); cd.inst_o = inst_o.as<int32_t>(); cd.inst_row = inst_row.as<uint32_t>();
+    cd.inst_pa = inst_pa.as<int32_t>(); cd.inst_rb = inst_rb.as<int32_t>();
+    cd.u_rec = u_rec.as<uint32_t>(); cd.u_n = u_n.as<uint32_t>(); cd.u_row = u_row.as<uint32_t>(); cd.u_o = u_o.as<int32_t>();
+    cd.u_seg = u_seg.as<uint32_t>();
+    return cd;
+  }
+};
+
 // An expansion plan keeps everything an expansion needs in HBM - the variant table, the carried-variant lists, the
 // per-workgroup variant ranges and (after hawk_xplan_finish_meta) the metadata of the rows it produces - so that running
 // it is device work only: the per-tile loop of a whole-contig search re-expands its tiles without touching the host.
@@ -235,18 +266,9 @@ struct hawk_xplan {
   uint32_t n_ref_rows = 0;
   std::vector<int64_t> rev0, rev1;  // hawk_xplan_create_gt: posmap_rev of every row at the two positions asked for
   std::shared_ptr<uint64_t> groups = std::make_shared<uint64_t>(0);  // groups the last collapse of a set of this plan found
-  // the cluster dictionary (hawk_csearch.hip), built by the first hawk_xplan_view after the metadata is set
-  struct {
-    bool built = false, usable = false;
-    uint32_t n_inst = 0, n_uniq = 0;  // n_uniq: the RANGE of the distinct clusters' numbers (variants first - with holes - then the table's)
-    uint32_t n_real = 0;              // how many distinct clusters there are
-    uint32_t last_uniq = 0;  // distinct clusters of the previous build (sizes the first hash table of the next)
-    uint64_t slots = 0;     // bound on the template rows of a search: window starts x 2 strands over all distinct clusters
-    uint32_t status = 0;    // why it is not usable: 1 a chain of > 4096 records, 2 hash collision, 4 too large / too little sharing
-    float build_ms = 0.f;
-    DevBuf inst_uid, inst_o, inst_row, inst_pa, inst_rb, u_rec, u_n, u_row, u_o, u_seg;
-  } cl;
+  ClusterDictionary cl;  // built by the first hawk_xplan_view after the metadata is set (hawk_api_cldict.hip)
 };
+int xplan_build_dict(hawk_xplan* x);  // hawk_api_cldict.hip: builds x->cl unless it stands; HAWK_OK also when the result is not usable
 
 // genotypes of a VCF block in HBM and, after hawk_gt_lists, the carried-variant lists of every chromosome copy
 struct hawk_gt {

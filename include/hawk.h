@@ -163,7 +163,7 @@ int hawk_xplan_text(hawk_xplan* x, uint32_t n_rows, const uint32_t* rows, const 
  * planes (hawk_pam_scan, hawk_hapset_download_plane, hawk_offtarget_scan ...) returns HAWK_E_INVALID on a view; tables,
  * collapse, export and gather work as on any set.  The plan must outlive the view. */
 int hawk_xplan_view(hawk_xplan* x, hawk_hapset** out);
-/* The cluster dictionary hawk_xplan_view builds for a plan (crispr-hawk_amd/csrc/hawk_csearch.hip): a row's carried variants
+/* The cluster dictionary hawk_xplan_view builds for a plan (crispr-hawk_amd/csrc/hawk_cldict.hip): a row's carried variants
  * fall into clusters (alleles within 64 positions of each other - the reach of one padded guide window); a cluster carried by
  * many chromosome copies is searched ONCE per hawk_search and its rows copied to every carrier.  usable = 0: the plan is
  * searched per row instead (status 1: a chain of more than 4096 variants, 2: two different clusters with one hash, 4: too

@@ -21,7 +21,7 @@ from oracle import oracle as ora  # noqa: E402
 from test_gpu_clusters import Panel, _same_rows  # noqa: E402
 
 N_SAMPLES = 800
-HEAD_LISTED = 16384  # CL_HEAD_LISTED (hawk_csearch.hip)
+HEAD_LISTED = 16384  # CL_HEAD_LISTED (hawk_cldict.hip)
 
 
 def entry_panel(seed, kind):

@@ -1,4 +1,4 @@
-"""The per-cluster search of a plan view (hawk_csearch.hip, xplan_build_dict in hawk_api_xplan.hip) at the limits it hard-codes:
+"""The per-cluster search of a plan view (hawk_csearch.hip; its dictionary: hawk_cldict.hip, xplan_build_dict in hawk_api_cldict.hip) at the limits it hard-codes:
 the 44-base core and one-base / sixteen-base PAMs, the 64-position link between records, the 4096-record chain cap, the row-bound
 classes of an instance, the seams of the cutting passes (wave, slice, chunk), the head launch and the bitmap read from HBM,
 the default sharing and template-slot thresholds.  Every case compares the view's table with the ORACLE's rows (carrier
@@ -245,7 +245,7 @@ def test_chain_cap(monkeypatch, chain):
 
 
 # ---- D: row bounds ---------------------------------------------------------------------------------------------------------
-# cl_cut (hawk_csearch.hip) classes an instance by where its windows (starts [o_first - 43, o_end), L <= 44) can fall against the
+# cl_cut (hawk_cldict.hip) classes an instance by where its windows (starts [o_first - 43, o_end), L <= 44) can fall against the
 # row's scan range [ss, se) and the string [PAD, hl - 44 - PAD]: outside (any of its comparisons holds: no cluster), interior (all
 # of them hold: shareable) or neither (a cluster of its own row); run_inside (all hold) lets the search count the clean run in front
 # without the row.  Each comparison: (name, predicate, holds when its value is <= 0 ('le') or >= 0 ('ge')).

@@ -1,4 +1,4 @@
-"""The cutting passes of the cluster dictionary (k_cl_count / k_cl_fill, cl_cut in hawk_csearch.hip) beyond the seams
+"""The cutting passes of the cluster dictionary (k_cl_count / k_cl_fill, cl_cut in hawk_cldict.hip) beyond the seams
 tests/test_gpu_clusters.py pins, and the table passes at the size where the head of the list is a launch of its own:
   1. clusters of 5, 8, 9 and 70 records (the walk takes a cluster's second and third record from the lanes above and every further
      one from memory) that end at a wave's last lane, one before it and one past it, or run through the end of a slice or a chunk;
@@ -135,7 +135,7 @@ def test_record_in_front_from_another_wave():
 
 
 # ---- 3: claims from the counting pass --------------------------------------------------------------------------------------
-HEAD_CHUNKS = 96  # CL_HEAD_CHUNKS (hawk_csearch.hip)
+HEAD_CHUNKS = 96  # CL_HEAD_CHUNKS (hawk_cldict.hip)
 
 
 def _claims_panel(seed, n_var=2000, step=40, af=0.05, n_samples=800):
