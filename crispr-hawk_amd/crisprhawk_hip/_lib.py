@@ -40,7 +40,7 @@ EXPORTS = [
     "hawk_offtarget_bulge_summary", "hawk_host_offtarget_bulge_summary",
     "hawk_gnomad_scan", "hawk_gnomad_records", "hawk_gnomad_text", "hawk_gnomad_text_download", "hawk_gnomad_destroy",
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
-    "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
+    "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_create_ugroups", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",
     "hawk_host_effects", "hawk_host_round4",
     "hawk_table_resolve_unphased", "hawk_resolve_download", "hawk_resolve_free", "hawk_host_resolve_unphased",
     "hawk_resolve_groups", "hawk_ugroups_download", "hawk_ugroups_free", "hawk_host_unphased_groups",

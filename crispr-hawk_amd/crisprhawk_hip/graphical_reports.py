@@ -106,7 +106,10 @@ class GroupEffects:
 
     `groups`: a hapset.GuideTable that is collapsed and still on the device (engine "device": hawk_effects_create, nothing is
     downloaded), or group columns - a hapset.GroupTable, reports.ReportGroups, tiling's merged groups - which go through
-    hawk_effects_create_columns ("device") or hawk_host_effects ("host").  `order` is the row order reports.group_columns returned,
+    hawk_effects_create_columns ("device") or hawk_host_effects ("host").  A hapset.UnphasedGroups that still holds its device
+    result (resolve_unphased_groups(..., keep_resident=True)) is ranked where it lies on engine "device"
+    (hawk_effects_create_ugroups: no group column is uploaded); without the handle, or on "host", it is group columns like any
+    other.  `order` is the row order reports.group_columns returned,
     `hap_samples[h]` the samples label of haplotype row h, `is_ref_hap[h]` whether it is REF."""
 
     def __init__(self, groups, hap_samples: Sequence[str], is_ref_hap, order, engine: str = "device"):
@@ -136,6 +139,14 @@ class GroupEffects:
             fx, tm = C.c_void_p(), _lib.EffectsTiming()
             _lib.check(self._L.hawk_effects_create(groups._t, _p(rank), _p(self._hap_off), _p(self._sid), C.c_uint32(len(hap_samples)),
                                                    C.c_uint32(self._n_ids), C.byref(fx), C.byref(tm)), "hawk_effects_create")
+            self._fx = fx
+            self.timing = {k: getattr(tm, k) for k, _ in tm._fields_ if k != "reserved"}
+            return
+        if engine == "device" and getattr(groups, "_ug", None) is not None:  # resident groups: already in (start, strand, ...) order
+            self._rank = rank
+            fx, tm = C.c_void_p(), _lib.EffectsTiming()
+            _lib.check(self._L.hawk_effects_create_ugroups(groups._ug, _p(rank), _p(self._hap_off), _p(self._sid), C.c_uint32(len(hap_samples)),
+                                                           C.c_uint32(self._n_ids), C.byref(fx), C.byref(tm)), "hawk_effects_create_ugroups")
             self._fx = fx
             self.timing = {k: getattr(tm, k) for k, _ in tm._fields_ if k != "reserved"}
             return

@@ -106,7 +106,8 @@ class Haplotype(Region):
         variants = _sort_variants(variants)
         start = self.coordinates.start
         cur: Dict[int, str] = {}        # SNV letter written so far, by genomic position
-        sites = []
+        snv_sites: Dict[int, Tuple[int, bytes, bytes]] = {}   # insertion-ordered: a later record at a position replaces the earlier one
+        indel_sites = []                                      # and moves to the end; the indels follow the SNVs (_sort_variants)
         va: Dict[int, List[Tuple[str, str, int]]] = {}
         off = 0                          # length change of the indels already applied (they come last, by position)
         deleted: List[Tuple[int, int]] = []
@@ -139,16 +140,17 @@ class Haplotype(Region):
                     exception_handler(CrisprHawkIupacTableError, f"An error occurred while encoding {refnt}>{alt} at position {pos} as IUPAC character",
                                       os.EX_DATAERR, self._debug, e)
                 cur[pos] = letter.lower()
-                sites = [x for x in sites if x[0] != pos] + [(pos, ref.encode(), letter.encode())]
+                snv_sites.pop(pos, None)
+                snv_sites[pos] = (pos, ref.encode(), letter.encode())
             else:
                 va = {p_: a_ for p_, a_ in va.items() if p_ <= posrel or p_ >= stop}
                 va = {(p_ + chain if p_ > posrel else p_): a_ for p_, a_ in va.items()}
-                sites.append((pos, ref.encode(), alt.encode()))
+                indel_sites.append((pos, ref.encode(), alt.encode()))
                 if chain < 0:
                     deleted.append((pos, pos - chain))
                 off += chain
         try:
-            arr, seg = expand_haplotype(self._arr, start, sites)
+            arr, seg = expand_haplotype(self._arr, start, list(snv_sites.values()) + indel_sites)
         except HaplotypeBuildError as e:
             raise ValueError(str(e)) from e
         self._arr, self._seg = arr, seg

@@ -427,7 +427,8 @@ class UnphasedGroups:
     group as columns + CSR member haplotypes (each haplotype once, ascending; the first is the representative's) - the fields
     reports.ReportGroups has, plus `rep_src_row` (the table row of the representative), `hap`, `is_ref` (the group's origin),
     `timing` (hawk_ugroups_timing; empty on the host engine) and `resolve_timing`.  Groups ascend by (start, strand, origin, stop,
-    core planes): csrc/hawk_ugroups.h."""
+    core planes): csrc/hawk_ugroups.h.  Made with `keep_resident=True` the object also keeps the device result (`_ug`, a
+    hawk_ugroups handle) for graphical_reports.GroupEffects until close()."""
 
     def __init__(self, guidelen: int, pamlen: int, right: bool, n_groups: int, n_members: int, device: Optional[int] = None):
         self.guidelen, self.pamlen, self.right, self.n_groups, self.n_members = guidelen, pamlen, bool(right), n_groups, n_members
@@ -442,6 +443,19 @@ class UnphasedGroups:
         self.member_off = pe(ng + 1, np.uint64); self.member_hap = pe(n_members, np.uint32)
         self.member_off[-1:] = 0
         self.timing, self.resolve_timing, self.engine, self.n_kept = {}, {}, "device", 0
+        self._ug, self._L, self.n_hap = None, None, 0
+
+    def close(self) -> None:
+        """Give the device result back (the downloaded columns stay)."""
+        if self._ug is not None:
+            self._L.hawk_ugroups_free(self._ug)
+            self._ug = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     @property
     def window_len(self) -> int:
@@ -627,14 +641,17 @@ class GuideTable:
             out.timing = {}
         return out
 
-    def resolve_unphased_groups(self, haplotypes, pam, cfd_tables=None, flank: Tuple[int, int] = (0, 0), engine: str = "device") -> "UnphasedGroups":
+    def resolve_unphased_groups(self, haplotypes, pam, cfd_tables=None, flank: Tuple[int, int] = (0, 0), engine: str = "device",
+                                keep_resident: bool = False) -> "UnphasedGroups":
         """The report groups of the rows' resolved IUPAC windows (resolve_unphased, then what reports.report_from_guides and
         scoring.cfdon_score do with the guides) without a Guide object: the kept guides stay in HBM, are keyed as the report
         merges them - `flank` = (4, 3) keeps guides apart that differ in the bases the model scorers read - scored with CFDon
         against the REF guide at the same (start, strand) when `cfd_tables = (mm, pam)` is given (NaN otherwise and without a
         partner), and come back as one representative per group + CSR member haplotypes (`engine="device"`:
         hawk_table_resolve_unphased + hawk_resolve_groups; `"host"`: the twins on the downloaded columns).  Call it before
-        download().  Raises _lib.HawkResolveDeclined where the resolution declines, _lib.HawkStatusError on any other status."""
+        download().  `keep_resident=True` (pass it by keyword; device engine only): the groups also stay in HBM behind the
+        returned object, where graphical_reports.GroupEffects ranks them (hawk_effects_create_ugroups), until its close().
+        Raises _lib.HawkResolveDeclined where the resolution declines, _lib.HawkStatusError on any other status."""
         if self._t is None:
             raise RuntimeError("resolve_unphased_groups() needs the device-resident table: call it before download()")
         if engine not in ("device", "host"):
@@ -647,6 +664,8 @@ class GuideTable:
         key = np.ascontiguousarray(key, np.uint64); off = np.ascontiguousarray(off, np.uint32); ref = np.ascontiguousarray(ref, np.uint8)
         bits, bitsrc = pam if isinstance(pam, tuple) else (pam.bits, pam.bitsrc)
         L, n = self._hs._L, self.n_rows
+        if keep_resident and engine != "device":
+            raise ValueError("keep_resident: the groups stay in HBM on engine='device' only")
         if engine == "host":
             hap = np.empty(n, np.uint32); pos = np.empty(n, np.uint32); strand = np.empty(n, np.uint8); start = np.empty(n, np.int64)
             stop = np.empty(n, np.int64); flags = np.empty(n, np.uint8); win = np.empty((5, n), np.uint64)
@@ -674,8 +693,11 @@ class GuideTable:
         try:
             g = UnphasedGroups(self.guidelen, self.pamlen, self.right, ng.value, nm.value, getattr(self._hs, "device", None))
             _lib.check(L.hawk_ugroups_download(gh, *g._args()), "hawk_ugroups_download")
+            if keep_resident:
+                g._ug, g._L, g.n_hap, gh = gh, L, len(self._hs.hap_len), None
         finally:
-            L.hawk_ugroups_free(gh)
+            if gh is not None:
+                L.hawk_ugroups_free(gh)
         g.n_kept = nk.value
         g.timing = {k: getattr(tm, k) for k, _ in tm._fields_ if k != "reserved"}
         g.resolve_timing = {k: getattr(rtm, k) for k, _ in rtm._fields_ if k != "reserved"}

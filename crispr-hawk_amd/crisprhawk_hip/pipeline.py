@@ -124,7 +124,7 @@ UNPHASED_REPORTS = (None, "groups", "objects")
 
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
                        ot=None, ann=None, lap=None, tables=None, unphased_engine=None, unphased_report=None, azimuth_model=None,
-                       deepcpf1_weights=None, plm_on=False) -> str:
+                       deepcpf1_weights=None, plm_on=False, fx=None) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows; their
     windows resolved on the device table, search_guides.search's `unphased_engine`) and the fallback for phased records the device expansion
@@ -142,10 +142,20 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
                  HAWK_UNPHASED_ENGINE) asks for the host.
       "objects"  the reference's order of business on Guide objects: annotate -> reverse_guides -> CFDon -> report
                  (reports.report_from_guides; the model-score columns say NA).  The phased fallback always takes it.
-    Either way there is no collapsed table in HBM for the variant-effect stage: `graphical_reports` / `candidate_guides` on such
-    an interval stay a ValueError (_search_intervals)."""
+    `fx` (search_files' `unphased_effects=True` with `graphical_reports` / `candidate_guides`; unphased intervals with records
+    only): the "groups" route keeps its groups in HBM and runs the variant-effect stage on them (_interval_effects, as
+    _finish_interval does on a collapsed table).  Nothing else can serve the stage: "objects", the host engine, a resolution
+    that declines or refuses are then a ValueError naming `graphical_reports`, raised before any file of the interval is written.
+    The phased fallback never receives `fx`: there the stage stays a ValueError (_search_intervals)."""
     if unphased_report not in UNPHASED_REPORTS:
         raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
+    mode = unphased_report or os.environ.get("HAWK_UNPHASED_REPORT") or "groups"
+    engine = unphased_engine or os.environ.get("HAWK_UNPHASED_ENGINE") or "device"
+    if fx is not None and mode not in ("groups", "objects"):
+        raise ValueError(f"HAWK_UNPHASED_REPORT={mode!r}: 'groups' or 'objects'")
+    if fx is not None and (mode != "groups" or engine == "host"):
+        why = f"unphased_report={mode!r} builds Guide objects" if mode != "groups" else "the host engine was asked for (unphased_engine / HAWK_UNPHASED_ENGINE)"
+        raise ValueError(f"graphical_reports / candidate_guides on an unphased interval rank the report groups in device memory: {why}")
     from . import haplotypes as hap_mod
     from .annotation import reverse_guides
     from .haplotype import Haplotype
@@ -160,22 +170,26 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         haps = build(haps, region, vcf.samples, records, phased, debug)
     for i, h in enumerate(haps):
         h.id = f"hap_{i:08d}"
-    if tables is not None:  # the strings are on the host already: the same writer, no kernel
-        tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, [h.id for h in haps],
-                                                      [h.variants for h in haps], [h.samples for h in haps],
-                                                      sequences=[h.sequence.sequence for h in haps])
+    def write_table():
+        if tables is not None:  # the strings are on the host already: the same writer, no kernel
+            tables[str(coord)] = hap_mod.haplotypes_table(coord.contig, coord.start, coord.stop, outdir, [h.id for h in haps],
+                                                          [h.variants for h in haps], [h.samples for h in haps],
+                                                          sequences=[h.sequence.sequence for h in haps])
+    if fx is None:  # (with the stage on, the table waits until the resolution has not refused: no file before a ValueError)
+        write_table()
     if records and not phased:
-        mode = unphased_report or os.environ.get("HAWK_UNPHASED_REPORT") or "groups"
         if mode not in ("groups", "objects"):
             raise ValueError(f"HAWK_UNPHASED_REPORT={mode!r}: 'groups' or 'objects'")
-        engine = unphased_engine or os.environ.get("HAWK_UNPHASED_ENGINE") or "device"
         if mode == "groups" and engine == "host":
             print_verbosity("Unphased report from Guide objects: the host engine was asked for", 0, VERBOSITYLVL[3])
         elif mode == "groups":
             path = _unphased_groups_report(coord, region, haps, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, azimuth_model,
-                                           deepcpf1_weights, plm_on)
+                                           deepcpf1_weights, plm_on, fx, write_table)
             if path is not None:
                 return path
+    if fx is not None:
+        raise ValueError("graphical_reports / candidate_guides: this interval's report comes from Guide objects, which leave no report groups "
+                         "in device memory for the variant-effect stage")
     guides = search(pam, region, haps, None, guidelen, right, bool(records), phased, 0, debug, unphased_engine=unphased_engine)
     cfd = None
     if mm is not None:
@@ -204,9 +218,10 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 
 
 def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool, ot, ann, lap,
-                            azimuth_model, deepcpf1_weights, plm_on) -> Optional[str]:
+                            azimuth_model, deepcpf1_weights, plm_on, fx=None, before_files=None) -> Optional[str]:
     """_search_host_built's "groups" route from the built haplotypes to the report file; None: the device declined or refused
-    and the caller takes the object route."""
+    and the caller takes the object route.  With `fx` the groups stay in HBM for the variant-effect stage, a decline or refusal
+    is a ValueError, and `before_files()` runs once the groups are made, ahead of the interval's first file."""
     from ._lib import HawkStatusError
     from .search_guides import _device_set
     lap = lap or (lambda stage: None)
@@ -216,10 +231,14 @@ def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right:
         tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right, download=False)
         azimuth_on = pam.cas_system in (SPCAS9, XCAS9) and azimuth_model is not None
         deepcpf1_on = pam.cas_system == CPF1 and deepcpf1_weights is not None
+        resident = dict(keep_resident=True) if fx is not None and fx["on"] else {}  # candidates alone need only the columns
         try:
             groups = tab.resolve_unphased_groups(haps, pam, (mm, pt) if mm is not None else None,
-                                                 (4, 3) if (azimuth_on or deepcpf1_on) else (0, 0), "device")
+                                                 (4, 3) if (azimuth_on or deepcpf1_on) else (0, 0), "device", **resident)
         except HawkStatusError as e:  # a decline (HawkResolveDeclined) or a refusal; a HIP failure is a HawkDeviceError and is raised
+            if fx is not None:
+                raise ValueError(f"graphical_reports / candidate_guides: the device made no report groups of this unphased interval ({e}), and "
+                                 "the route over Guide objects leaves none in device memory for the variant-effect stage") from e
             print_verbosity(f"Unphased report from Guide objects: {e}", 0, VERBOSITYLVL[3])
             return None
         finally:
@@ -227,10 +246,19 @@ def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right:
         is_ref_hap = np.asarray(ds.is_ref, dtype=bool)
     finally:
         ds.close()
-    lap("host-built route: planes, search, resolution and report groups on the device")
-    bed_start, bed_stop = coord.start + PADDING, coord.stop - PADDING
-    cols, order, plain, _ = _group_report_columns(coord, groups, reports.HapLabels.from_objects(haps), is_ref_hap, pam, guidelen, right, outdir,
-                                                  mm is not None, debug, ot, ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
+    try:  # (the resident groups own their memory: they outlive the table and the set)
+        lap("host-built route: planes, search, resolution and report groups on the device")
+        if before_files is not None:
+            before_files()
+        bed_start, bed_stop = coord.start + PADDING, coord.stop - PADDING
+        labels = reports.HapLabels.from_objects(haps)
+        cols, order, plain, scores = _group_report_columns(coord, groups, labels, is_ref_hap, pam, guidelen, right, outdir, mm is not None, debug, ot,
+                                                           ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
+        if fx is not None:
+            _interval_effects(coord, groups if fx["on"] else None, labels, is_ref_hap, cols, order, plain, scores, pam, guidelen, outdir, debug,
+                              bed_start, bed_stop, fx, lap)
+    finally:
+        groups.close()
     return _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_start, bed_stop, lap)
 
 
@@ -270,14 +298,15 @@ def _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_st
 
 
 # Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
-# candidate_guides, figures, unphased_report and unphased_engine sit before `annotations`), and only the order of the last three parameters is held fixed.
+# candidate_guides, figures, unphased_report, unphased_engine and unphased_effects sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
                  device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
                  timings: Optional[Dict[str, float]] = None, offtargets_table: bool = True, offtargets_summary: bool = False,
                  graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
-                 unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, annotations: Optional[List[str]] = None,
+                 unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, unphased_effects: bool = False,
+                 annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
                  tables: Optional[Dict[str, str]] = None) -> Dict[str, str]:
@@ -314,7 +343,14 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     --candidate-guides) are forced into the delta tables and each gets its sub-report
     crisprhawk_candidate_guides__{contig}_{position}_{pam}_{guidelen}.tsv (candidate_guides.subset_reports).  Pass a dict as
     `figures` and it is filled with {str(coordinate): [paths]}.  Intervals whose haplotypes are built on the host (unphased
-    VCFs, records the device expansion declines) have no device table: asking for the stage there is a ValueError.
+    VCFs, records the device expansion declines) have no device table: asking for the stage there is a ValueError - unless
+    `unphased_effects=True`, which runs the stage of an unphased interval on its report groups while they are still in HBM
+    (the "groups" route below with the groups kept resident; hawk_effects_create_ugroups) and writes the same files as for a
+    phased interval, model-score delta tables included.  The stage then needs that route: `unphased_report="objects"`, the host
+    engine, or a resolution the device declines or refuses (the message carries the status) is a ValueError naming
+    `graphical_reports`, raised before any file of that interval is written.  An unphased VCF without a record in the interval
+    takes the variant-free device route: report and figures of a run without a VCF.  Records of a phased VCF that the device
+    expansion declines keep the ValueError.
     `unphased_report` (unphased VCFs; None reads HAWK_UNPHASED_REPORT, else "groups"): "groups" turns the resolved guides into
     report groups on the device and writes the report through the phased route's column writer - no Guide object, and the
     model-score columns (`azimuth_model`, `deepcpf1_weights`, `plmcrispr_model`) are filled as in a phased report; "objects" is
@@ -389,27 +425,35 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                   figures=figures if figures is not None else {})
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
-                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on, unphased_report, unphased_engine)
+                                 ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on, unphased_report, unphased_engine,
+                                 bool(unphased_effects))
     finally:
         if ann is not None:
             ann.close()
 
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
-                      deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False, unphased_report=None, unphased_engine=None) -> Dict[str, str]:
+                      deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False, unphased_report=None, unphased_engine=None,
+                      unphased_effects=False) -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
-    def no_table():
-        if fx is not None and (fx["on"] or fx["cgs"]):
+    stage_on = fx is not None and (fx["on"] or bool(fx["cgs"]))
+
+    def no_table(unphased=False):
+        if stage_on:
             raise ValueError("graphical_reports / candidate_guides: this interval's haplotypes are built on the host, so there is no collapsed "
-                             "table on the device for the variant-effect stage")
+                             "table on the device for the variant-effect stage" +
+                             (" (unphased_effects=True runs it on the unphased report groups in device memory)" if unphased else ""))
     for coord in bed:
         seq = fastas[coord.contig].fetch(coord).sequence
         v = vcf_by_contig.get(coord.contig)
+        if v is not None and not v.phased and stage_on and unphased_effects and not v.fetch(coord):
+            v = None  # no record in the interval: REF alone, the variant-free device route and its collapsed table
         if v is not None and not v.phased:
-            no_table()
+            if not unphased_effects:
+                no_table(True)
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
                                                    pt if score else None, debug, ot, ann, lap, tables, unphased_engine, unphased_report,
-                                                   azimuth_model, deepcpf1_weights, plm_on)
+                                                   azimuth_model, deepcpf1_weights, plm_on, fx if stage_on else None)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])
@@ -451,6 +495,24 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
     return paths
 
 
+def _interval_effects(coord, resident, labels, is_ref_hap, cols, order, plain, scores, pam, guidelen, outdir, debug, bed_start, bed_stop, fx,
+                      lap) -> None:
+    """The variant-effect stage of one interval, by the report's row order: delta and type tables from `resident` - the collapsed
+    table of a phased interval or the resident report groups of an unphased one, still in HBM; None when only candidates were
+    asked for - and the candidates' sub-reports from the report's columns.  Fills fx["figures"]."""
+    from . import candidate_guides as cg_mod, graphical_reports as gr_mod
+    made = []
+    if resident is not None:
+        made += gr_mod.compute_graphical_reports(resident, labels, (cols, order, plain), coord, outdir, fx["cgs"], scores, is_ref_hap=is_ref_hap,
+                                                 debug=debug)
+    if fx["cgs"]:
+        from .coordinate import Coordinate
+        made += list(cg_mod.subset_reports(fx["cgs"], {Coordinate(coord.contig, bed_start, bed_stop, 0): (cols, order, plain)}, pam, guidelen,
+                                           outdir, debug).values())
+    fx["figures"][str(coord)] = made
+    lap("variant effects: delta, type and candidate tables")
+
+
 def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, pam, guidelen, right, outdir, score, debug, ot, ann, azimuth_on, deepcpf1_on,
                      bed_start, bed_stop, paths, lap, tables, fx, plm_on=False) -> None:
     """One interval from its exported groups to its files: scorers, annotation join, report, the optional tables.  `tab`: the
@@ -459,17 +521,8 @@ def _finish_interval(coord, tab, groups, ds, plan, labels, info, vt, kept, seq, 
         cols, order, plain, scores = _group_report_columns(coord, groups, labels, np.asarray(ds.is_ref, dtype=bool), pam, guidelen, right, outdir, score,
                                                            debug, ot, ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
         if fx is not None:  # the table is still collapsed in HBM: the effects stage ranks its groups there, by the report's row order
-            from . import candidate_guides as cg_mod, graphical_reports as gr_mod
-            made = []
-            if tab is not None:
-                made += gr_mod.compute_graphical_reports(tab, labels, (cols, order, plain), coord, outdir, fx["cgs"], scores,
-                                                         is_ref_hap=np.asarray(ds.is_ref, dtype=bool), debug=debug)
-            if fx["cgs"]:
-                from .coordinate import Coordinate
-                made += list(cg_mod.subset_reports(fx["cgs"], {Coordinate(coord.contig, bed_start, bed_stop, 0): (cols, order, plain)}, pam, guidelen,
-                                                   outdir, debug).values())
-            fx["figures"][str(coord)] = made
-            lap("variant effects: delta, type and candidate tables")
+            _interval_effects(coord, tab, labels, np.asarray(ds.is_ref, dtype=bool), cols, order, plain, scores, pam, guidelen, outdir, debug,
+                              bed_start, bed_stop, fx, lap)
         if tables is not None:  # the plan's metadata is finished; its rows as text, batch by batch, straight into the file
             from . import haplotypes as hap_mod
             hap_ids, hap_samples = [labels.ids[r] for r in kept], [labels.samples[r] for r in kept]

@@ -46,7 +46,8 @@ static FxDev fx_dev(const hawk_effects* f) {
 }
 
 // The score-independent passes.  `src` holds DEVICE pointers of everything create reads and the handle does not keep: stop, win,
-// the member lists, the haplotype rows' origin and sample lists.  f->start / strand / rank are filled already.
+// the member lists, the haplotype rows' origin and sample lists.  f->start / strand / rank are filled already.  d_hap_is_ref NULL:
+// f->is_ref is filled already as well (hawk_effects_create_ugroups: the groups carry their origin).
 static int fx_build(hawk_effects* f, const FxCols& src, const uint8_t* d_hap_is_ref, hawk_effects_timing* timing, hipEvent_t ev_begin) {
   hawk_ctx* ctx = f->ctx;
   hipStream_t st = ctx->stream;
@@ -59,7 +60,7 @@ static int fx_build(hawk_effects* f, const FxCols& src, const uint8_t* d_hap_is_
   uint32_t* d_long;
   TEMPCHK(tmp, &d_long, G * 4 + 4);
   HIPCHK(hipMemsetAsync(f->counts.p, 0, 64, st));
-  hawk_launch_fx_isref_gather(st, d_hap_is_ref, src.member_hap, src.member_off, G, f->is_ref.as<uint8_t>());
+  if (d_hap_is_ref) hawk_launch_fx_isref_gather(st, d_hap_is_ref, src.member_hap, src.member_off, G, f->is_ref.as<uint8_t>());
   FxDev F = fx_dev(f);
   F.c = src;
   F.c.n_groups = G;
@@ -184,6 +185,58 @@ int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap
   d.n_groups = G; d.win_stride = rep.cap; d.stop = rep.stop; d.win = rep.win; d.member_off = hs->cws.group_off(); d.member_hap = d_mem;
   d.hap_off = d_hoff; d.sample_id = d_sid; d.n_hap = n_hap; d.n_sample_ids = n_sample_ids; d.guidelen = t->guidelen; d.pamlen = t->pamlen; d.right = t->right;
   if ((rc = fx_build(f, d, hs->d_is_ref, timing, ctx->ev[0]))) return fail(rc);
+  *out = f;
+  return HAWK_OK;
+}
+
+int hawk_effects_create_ugroups(hawk_ugroups* g, const uint32_t* rank, const uint64_t* hap_off, const uint32_t* sample_id, uint32_t n_hap,
+                                uint32_t n_sample_ids, hawk_effects** out, hawk_effects_timing* timing) {
+  if (out) *out = nullptr;
+  if (!out || !g) return HAWK_E_INVALID;
+  hawk_ctx* ctx = g->ctx;
+  const uint64_t G = g->n_groups;
+  if (n_hap != g->n_hap) return HAWK_E_INVALID;
+  int bad = fx_check_sizes(G, n_sample_ids, g->guidelen, g->pamlen);
+  if (!bad) bad = fx_check_samples(hap_off, sample_id, n_hap, n_sample_ids);
+  if (!bad) bad = fx_check_rank(rank, G);
+  if (bad) return bad == 2 ? HAWK_E_UNSUPPORTED : HAWK_E_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hawk_effects* f = new (std::nothrow) hawk_effects();
+  if (!f) return HAWK_E_INVALID;
+  f->ctx = ctx; f->G = G; f->guidelen = g->guidelen; f->pamlen = g->pamlen; f->right = g->right; f->n_sample_ids = n_sample_ids;
+  f->has_cfdon = g->has_cfd;
+  hipStream_t st = ctx->stream;
+  auto fail = [&](int code) { fx_release(f); return code; };
+  const uint64_t NS = hap_off[n_hap];
+  PoolScope tmp;
+  uint64_t* d_hoff; uint32_t* d_sid;
+  int rc;
+  if ((rc = f->start.reserve(G * 8 + 8)) || (rc = f->strand.reserve(G + 1)) || (rc = f->rank.reserve(G * 4 + 4)) || (rc = f->cfdon.reserve(G * 8 + 8)) ||
+      (rc = f->is_ref.reserve(G + 1)) || (rc = tmp.alloc((void**)&d_hoff, ((uint64_t)n_hap + 1) * 8)) || (rc = tmp.alloc((void**)&d_sid, NS * 4 + 4)))
+    return fail(rc);
+  hipError_t e = hipEventRecord(ctx->ev[0], st);
+  auto cp = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, kind, st);
+  };
+  // the handle's own copies (it outlives `g`); stop, the window planes and the member lists are read in place, by create alone
+  cp(f->start.p, g->b[UG_B_START].p, G * 8, hipMemcpyDeviceToDevice); cp(f->strand.p, g->b[UG_B_STRAND].p, G, hipMemcpyDeviceToDevice);
+  cp(f->cfdon.p, g->b[UG_B_CFDON].p, G * 8, hipMemcpyDeviceToDevice); cp(f->is_ref.p, g->b[UG_B_ISREF].p, G, hipMemcpyDeviceToDevice);
+  cp(f->rank.p, rank, G * 4, hipMemcpyHostToDevice);
+  cp(d_hoff, hap_off, ((uint64_t)n_hap + 1) * 8, hipMemcpyHostToDevice); cp(d_sid, sample_id, NS * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    snprintf(hawk_hip_err_buf(), 256, "hawk_effects_create_ugroups: %s", hipGetErrorString(e));
+    (void)hipStreamSynchronize(st);
+    return fail(HAWK_E_HIP);
+  }
+  FxCols d;
+  memset(&d, 0, sizeof(d));
+  d.n_groups = G; d.win_stride = G; d.stop = g->b[UG_B_STOP].as<int64_t>(); d.win = g->b[UG_B_WIN].as<uint64_t>();
+  d.member_off = g->b[UG_B_MOFF].as<uint64_t>(); d.member_hap = g->b[UG_B_MHAP].as<uint32_t>();
+  d.hap_off = d_hoff; d.sample_id = d_sid; d.n_hap = n_hap; d.n_sample_ids = n_sample_ids; d.guidelen = g->guidelen; d.pamlen = g->pamlen; d.right = g->right;
+  if ((rc = fx_build(f, d, nullptr, timing, ctx->ev[0]))) {
+    (void)hipStreamSynchronize(st);
+    return fail(rc);
+  }
   *out = f;
   return HAWK_OK;
 }

@@ -9,14 +9,7 @@
 
 #include "hawk_host.h"
 
-#define UG_NBUF 13
-struct hawk_ugroups {
-  hawk_ctx* ctx;
-  uint64_t n_groups = 0, n_members = 0;
-  DevBuf b[UG_NBUF];  // rep_src_row, hap, pos, strand, start, stop, is_ref, cfdon, win, gc_num, gc_den, member_off, member_hap
-  hawk_ugroups_timing tm;
-};
-
+// (struct hawk_ugroups, UG_NBUF: hawk_host.h - hawk_effects_create_ugroups in hawk_api_effects.hip reads the result too)
 static void ug_release(hawk_ugroups* g) {
   for (DevBuf& b : g->b) b.release();
   delete g;
@@ -45,6 +38,7 @@ int hawk_resolve_groups(hawk_resolve* r, const double* cfd_mm, const double* cfd
   hawk_ugroups* G = new (std::nothrow) hawk_ugroups();
   if (!G) return HAWK_E_OOM;
   G->ctx = ctx;
+  G->n_hap = r->hs->n_hap; G->guidelen = g.guidelen; G->pamlen = g.pamlen; G->right = g.right; G->has_cfd = cfd_mm != nullptr;
   memset(&G->tm, 0, sizeof(G->tm));
   G->tm.n_kept = n;
   if (!n) {  // a valid, empty result

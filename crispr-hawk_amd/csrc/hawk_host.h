@@ -329,6 +329,18 @@ inline UrDev ur_dev(const hawk_resolve* r) {
   return d;
 }
 
+// hawk_resolve_groups' result (hawk_api_ugroups.hip); hawk_effects_create_ugroups (hawk_api_effects.hip) reads it where it lies
+#define UG_NBUF 13
+enum { UG_B_STRAND = 3, UG_B_START = 4, UG_B_STOP = 5, UG_B_ISREF = 6, UG_B_CFDON = 7, UG_B_WIN = 8, UG_B_MOFF = 11, UG_B_MHAP = 12 };
+struct hawk_ugroups {
+  hawk_ctx* ctx;
+  uint64_t n_groups = 0, n_members = 0;
+  uint32_t n_hap = 0, guidelen = 0, pamlen = 0, right = 0;  // of the set and the table the groups were made from
+  bool has_cfd = false;                                      // CFD tables were given: cfdon holds scores, not NaN alone
+  DevBuf b[UG_NBUF];  // rep_src_row, hap, pos, strand, start, stop, is_ref, cfdon, win, gc_num, gc_den, member_off, member_hap
+  hawk_ugroups_timing tm;
+};
+
 int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c);
 
 // shared by the C-ABI translation units (hawk_api_*.hip)

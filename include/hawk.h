@@ -736,6 +736,16 @@ int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_
  * (k_fx_groups: position heads, guide type, the duplicate rule, the four type counts; k_fx_samples_*: distinct samples per group);
  * nothing of the table is downloaded, and the handle keeps its own copies, so it outlives the table and later searches.
  * hawk_effects_create_columns does the same from host arrays (tests; callers whose groups were merged on the host).
+ * hawk_effects_create_ugroups keeps hawk_effects_create's contract with the report groups of an unphased resolution (a
+ * hawk_ugroups result, declared below with hawk_resolve_groups) in place of a collapsed table's: rank, hap_off and sample_id come
+ * from the host, every group column is read where it lies in HBM - the groups ascend by (start, strand, ...), so a position's
+ * groups are contiguous - and the origin of a group is the result's is_ref (what k_fx_isref_gather makes of the set's flags and
+ * the first members).  n_hap must be the set's the groups were made from (HAWK_E_INVALID otherwise).  A valid empty result gives
+ * a valid handle of zero groups.  Groups made without CFD tables hold NaN alone in cfdon: hawk_effects_rank(score = NULL) on such
+ * a handle is HAWK_E_INVALID, as after _create_columns without cfdon.  The handle keeps its own copies of start, strand, origin,
+ * rank and CFDon: it outlives the hawk_ugroups result, the hawk_resolve handle, the table and the set.
+ * All three: on every status but HAWK_OK *out stays NULL (create_ugroups writes it so; the other two leave it untouched) and
+ * nothing stays allocated; timing->upload_ms covers the host arrays and the device-to-device copies.
  * hawk_effects_rank, once per score on the same handle: `family` HAWK_FX_SIGNED (score_cfdon) or HAWK_FX_ABSOLUTE (azimuth, rs3,
  * deepcpf1); `score` = double[n_groups], or NULL for the table's CFDon; candidates are positions (start, strand), they come
  * first in the order given, then the best K - n_cand other positions that have a REF group.  1 <= K <= HAWK_FX_MAX_K and
@@ -757,6 +767,7 @@ int hawk_host_f32_repr(const uint8_t* text, const uint64_t* start, const uint32_
 #define HAWK_FX_NONE 0xffffffffu       /* "no group" / "no position" in pos_ref, chosen, pos_first_rank */
 #define HAWK_FX_TYPE_UNKNOWN 255        /* an alternative without a lower-case base in spacer or PAM */
 typedef struct hawk_effects hawk_effects;
+struct hawk_ugroups; /* hawk_resolve_groups' result: typedef'd below */
 typedef struct {
   uint64_t n_groups, win_stride;
   const int64_t* start;
@@ -797,6 +808,8 @@ typedef struct {
 int hawk_effects_create(hawk_table* t, const uint32_t* rank, const uint64_t* hap_off, const uint32_t* sample_id, uint32_t n_hap,
                         uint32_t n_sample_ids, hawk_effects** out, hawk_effects_timing* timing);
 int hawk_effects_create_columns(hawk_ctx* ctx, const hawk_effects_columns* cols, hawk_effects** out, hawk_effects_timing* timing);
+int hawk_effects_create_ugroups(struct hawk_ugroups* g, const uint32_t* rank, const uint64_t* hap_off, const uint32_t* sample_id,
+                                uint32_t n_hap, uint32_t n_sample_ids, hawk_effects** out, hawk_effects_timing* timing);
 int hawk_effects_rank(hawk_effects* fx, int family, const double* score, const int64_t* cand_start, const uint8_t* cand_strand,
                       uint32_t n_cand, uint32_t K, uint32_t* n_chosen, uint64_t* n_alts, hawk_effects_timing* timing);
 int hawk_effects_download(hawk_effects* fx, const hawk_effects_out* out);
