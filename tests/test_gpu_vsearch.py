@@ -1,9 +1,13 @@
 """hawk_xplan_view: the search straight from an expansion plan - per dirty word of every row (hawk_vsearch.hip) and per
 distinct variant cluster (hawk_csearch.hip) - against the search on the planes the
 same plan materialises (hawk_xplan_run + hawk_search, itself held to the reference's fixtures and the oracle by
-test_gpu_parity.py): every column, row for row, and the job totals, on inputs that reach each path of the kernel -
-tiles with no variant, the usual few, more records than LDS stages, more dirty words than one pass holds, long
-insertions and deletions across word / tile edges, rows that end in a tile, PAMs of every shape."""
+test_gpu_parity.py): every column, row for row, and the job totals, on seeded random panels AIMED at the paths of the
+kernels - tiles with no variant, the usual few, more records than LDS stages, more dirty words than one pass holds, long
+insertions and deletions across word / tile edges, rows that end in a tile, PAMs of every shape.  This is a campaign: nothing
+here checks that a panel lands on the path it was drawn for, the per-word search is compared with the plane search and
+only the cluster table with the oracle, and HAWK_CLUSTER_MIN_SHARE=0 keeps the dictionary usable throughout.  The seams of
+the per-word search, each proved on the CPU, its table against the oracle directly, and the route a small panel takes by
+default are in tests/test_gpu_vsearch_seams.py (cases: tests/vsearch_refs.py)."""
 import os
 
 import numpy as np
