@@ -151,6 +151,9 @@ int hawk_init(int device, hawk_ctx** out) {
   for (int i = 0; i < (int)(sizeof(ctx->ev) / sizeof(ctx->ev[0])); ++i)
     HIPCHK(i < HAWK_EV_TIMED ? hipEventCreate(&ctx->ev[i]) : hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
   HIPCHK(hipHostMalloc(&ctx->pinned, sizeof(PinnedBlock), hipHostMallocDefault));
+  int khz = 0;
+  HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
+  ctx->wall_clock_khz = khz > 0 ? khz : 100000;  // (a device that reports none: gfx9's constant 100 MHz)
   g_ctx_of[device] = ctx; g_ctx_refs[device] = 1;
   *out = ctx;
   return HAWK_OK;

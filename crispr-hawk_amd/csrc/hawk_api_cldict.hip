@@ -10,9 +10,6 @@
 
 static_assert(CL_MAX_ROWS == HAWK_ROW_MAX_HAP, "cl_build_sizes declines the rows the packed layout cannot hold");
 
-// The slots of hawk_ctx::ev a build records (build_ms).
-enum ClBuildEvent { EV_BUILD_BEGIN = 8, EV_BUILD_END = 9 };
-
 // The zero block of a build - one allocation, one memset - seen through the layout of cl_build_sizes.
 struct ClZero {
   char* base;
@@ -89,7 +86,6 @@ static int dict_attempt(hawk_xplan* x, const ClBuild& b, const ClTable& t, uint3
   hawk_launch_cl_fill(st, b);
   hawk_launch_cl_finish(st, b, t, cu);
   HIPCHK(hipMemcpyAsync(res, b.tally.results, sizeof(ClResults), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_END], st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   return HAWK_OK;
@@ -131,7 +127,6 @@ int xplan_build_dict(hawk_xplan* x) {
   ClBuild b = {};
   int rc;
   if ((rc = dict_reserve(x, sz, tmp, &zero, &b))) return rc;
-  HIPCHK(hipEventRecord(ctx->ev[EV_BUILD_BEGIN], st));
   HIPCHK(hipMemsetAsync(zero.base, 0, sz.z_end, st));
   dict_cut(st, b);
   ClResults* const res = &static_cast<PinnedBlock*>(ctx->pinned)->dict;
@@ -139,6 +134,10 @@ int xplan_build_dict(hawk_xplan* x) {
   ClTable t;
   t.tab = zero.tab(); t.mask = sz.tsmall - 1; t.max_probe = sz.max_probe; t.fail_bit = sz.fail_bit; t.u_cap = sz.u_bound;
   if ((rc = dict_attempt(x, b, t, zero.span2(), res))) return rc;
+  // build_ms: from where k_cl_chunks began to where k_cl_results ended, by the device's wall clock (the result block carries both
+  // stamps) - the build's kernels, without the memset in front of them and the copy behind.  No event is recorded.  A repeated
+  // attempt clears the block on the device and does not cut the rows again: the first attempt's begin is kept here.
+  const unsigned long long build_begin = res->begin;
   if (res->status & CL_ST_FIRST_TABLE) {  // the small table filled up: once more with two slots per instance
     // The repeat: its own, larger table and bounds, the counters cleared again.  The variants' bitmap and describers stay: the counting
     // pass and the scan, which are not repeated, left the first rows' there, and who describes a variant does not depend on the table
@@ -155,7 +154,7 @@ int xplan_build_dict(hawk_xplan* x) {
   }
   if (res->instances == 0) { cl.status = CL_ST_DECLINED; return HAWK_OK; }
   if ((uint32_t)res->instances > sz.inst_bound) { snprintf(hawk_hip_err_buf(), 256, "hawk_xplan_view: instance count beyond its bound"); return HAWK_E_HIP; }
-  (void)hipEventElapsedTime(&cl.build_ms, ctx->ev[EV_BUILD_BEGIN], ctx->ev[EV_BUILD_END]);
+  cl.build_ms = hawk_stamp_ms(ctx, build_begin, res->end);
   dict_decide(cl, *res, x->n_var, t.u_cap);
   return HAWK_OK;
 }

@@ -28,19 +28,30 @@ int hawk_reserve_cols(DevBuf (&b)[8], uint64_t cap, GuideCols* c) {
 
 #define HAWK_RETRY_TEMPLATES (-100)  // private to this file: the template rows of a cluster search outgrew their reservation
 
-// The slots of hawk_ctx::ev a search records, each named for the interval it opens or closes.  A recorded event is a packet of its
-// own between two kernels of its stream (5-6 us on the main stream of a C3 search, profiles/ref_overlap.md): an interval that begins
-// where another one ends shares that event instead of recording a second one behind it.
-enum SearchEvent {
-  EV_BEGIN, EV_COUNT_DONE, EV_OFFSETS_DONE, EV_EMIT_BEGIN, EV_EMIT_END, EV_LIST_EMIT_END,  // every search
-  EV_VIEW_COUNT_BEGIN, EV_VIEW_EMIT_BEGIN,                                                 // a view of an expansion plan
-  EV_TEMPLATES_DONE,                                                                       // ... searched per cluster
-  // ordering only: REF's passes on the side stream are done (the forks wait on the event that opens the stage on the main stream)
-  EV_COUNT_JOIN = HAWK_EV_TIMED, EV_EMIT_JOIN,
-  EV_SLOTS
-};
+// A search records no timed event.  A recorded event is a packet of its own between two kernels of its stream (5-6 us on the main
+// stream of a C3 search, profiles/ref_overlap.md), and two kernels with nothing between them follow each other in 0.2 us: the
+// stage boundaries are STAMPS instead - the kernel that opens the next interval stores the device's wall clock into its slot of
+// SearchMisc::stamps (hawk_stamp, hawk_device.h), the memset of the search clears the slots and the status copy brings them back.
+// Where an interval ends and no kernel of ours follows on that stream (the end of the emit; the offsets when no emit is queued
+// behind them) a one-thread launch stamps it (hawk_launch_stamp).  An interval that begins where another one ends shares its stamp.
+// The events left are the four that order the two streams of a cluster search (created without timing): the main stream records a
+// fork where the side stream may begin, the side stream a join where its work is done.
+enum SearchEvent { EV_COUNT_FORK = HAWK_EV_TIMED, EV_COUNT_JOIN, EV_EMIT_FORK, EV_EMIT_JOIN, EV_SLOTS };
 static_assert(EV_SLOTS == sizeof(hawk_ctx::ev) / sizeof(hipEvent_t), "hawk_ctx::ev ends with the search's ordering events");
-static_assert(EV_TEMPLATES_DONE < HAWK_EV_TIMED, "the slots in front of the joins carry timestamps");
+enum SearchStamp {
+  ST_COUNT_BEGIN,       // the main stream's first count-side kernel: k_search_count, or k_cs_templates of a cluster search
+  ST_VIEW_COUNT_BEGIN,  // pass 0 of the per-word search (a cluster search: ST_COUNT_BEGIN)
+  ST_CS_COUNT,          // k_cs_count: the templates are done
+  ST_SCAN_BEGIN,        // the first scan kernel: the count side is done
+  ST_OFFSETS_DONE,      // the offsets are done: the first kernel of a speculative emit (which it opens as well), else a stamp launch
+  ST_EMIT_BEGIN,        // the first kernel of an emit that is not queued straight behind the scan
+  ST_LIST_BEGIN,        // k_emit_list where it is not the emit's first kernel (a cluster search: on the side stream)
+  ST_LIST_END,          // k_search_emit
+  ST_VIEW_EMIT_BEGIN,   // pass 1 of the per-word search; k_rows_pack of a cluster search
+  ST_EMIT_END,          // a stamp launch in front of the status copy
+  ST_SLOTS
+};
+static_assert(ST_SLOTS <= HAWK_SEARCH_STAMPS, "SearchMisc::stamps holds every slot");
 
 // One attempt of hawk_search: what its stages share.  search_classify .. search_view_args fill it, the stages behind them read it.
 struct SearchRun {
@@ -56,8 +67,10 @@ struct SearchRun {
   unsigned long long* shards;     // hs->misc on the device (SearchMisc): the shard sums ...
   SearchStatusBlock* blk;         // ... and the status block every launcher is handed its fields of
   SearchStatusBlock* h;           // the status block as last read back (hawk_ctx::pinned)
+  unsigned long long* stamps;     // SearchMisc::stamps on the device, [ST_SLOTS]
+  const unsigned long long* h_stamps;  // ... and as last read back
   uint64_t* table_cap;            // rows the set's table holds: hs->rows_cap for a cluster search, else hs->cols_cap
-  SearchEvent emit_begin;         // what opened the last emit: EV_OFFSETS_DONE straight behind the scan (a speculative emit), else EV_EMIT_BEGIN
+  SearchStamp emit_begin;         // what opened the last emit: ST_OFFSETS_DONE straight behind the scan (a speculative emit), else ST_EMIT_BEGIN
 };
 
 // Parameter checks, and which path runs.  A view of an expansion plan (hawk_xplan_view) holds no planes: its REF row runs through the
@@ -86,7 +99,7 @@ static int search_classify(hawk_hapset* hs, const hawk_search_params* p, SearchR
   r->stage_cap = r->by_cluster ? 2ull * hs->hap_len[hs->ref_index] + 64 : 0;
   r->table_cap = r->by_cluster ? &hs->rows_cap : &hs->cols_cap;
   r->tcap = r->t_rows_used = 0;
-  r->emit_begin = EV_EMIT_BEGIN;
+  r->emit_begin = ST_EMIT_BEGIN;
   return HAWK_OK;
 }
 // The workspaces every path needs, and what points into them.  Hand-over lists (2 KB per tile): the count pass leaves each small
@@ -103,6 +116,8 @@ static int search_reserve(SearchRun* r, const hawk_search_params* p) {
   r->shards = &hs->misc.as<SearchMisc>()->shards[0][0];
   r->blk = &hs->misc.as<SearchMisc>()->blk;
   r->h = &static_cast<PinnedBlock*>(r->ctx->pinned)->search;
+  r->stamps = hs->misc.as<SearchMisc>()->stamps;
+  r->h_stamps = static_cast<PinnedBlock*>(r->ctx->pinned)->stamps;
   GuideParams& gp = r->gp;
   gp.pamlen = sp.pamlen; gp.guidelen = sp.guidelen; gp.right = sp.right; gp.L = sp.L;
   gp.score_cfdon = (int32_t)p->score_cfdon;  // 1: a non-ACGT base under a lookup is HAWK_E_CFD; 2: it scores NaN ("NA")
@@ -190,48 +205,49 @@ static int search_view_args(SearchRun* r) {
 }
 // The side stream's work behind a fork is done -> the main stream goes on.  Nothing between a fork and its join returns: if the join
 // cannot be queued the host waits for the side stream instead, so no caller ever meets REF's kernels still in flight.
+// (The wait costs the main stream about 6 us although REF's passes ended long before.  Joining on the HOST instead - it waits for
+// the side stream, then queues what follows - removes both wait packets from a C3 trace and 0.005-0.012 ms of device time, but the step's
+// wall time did not follow beyond its run-to-run spread at C3, an eighth of it, or C4: profiles/search_stamps.md.  Not built in.)
 static hipError_t search_join(SearchRun* r, SearchEvent done) {
   hipError_t e = hipEventRecord(r->ctx->ev[done], r->side);
   if (e == hipSuccess) e = hipStreamWaitEvent(r->st, r->ctx->ev[done], 0);
   if (e != hipSuccess) (void)hipStreamSynchronize(r->side);
   return e;
 }
+
 // The count side: the plane kernels' tiles, then the view's share - templates + a count per cluster instance, or pass 0 of the
 // per-word search - then the offset scan, which leaves the totals in the status block.  A cluster search forks: REF's tiles are
 // counted on the side stream (counts[0, plane_tiles), the hand-over lists, the work list) while the main stream makes the templates
 // and counts the instances (counts[plane_tiles, ..)); the shard sums and the status take atomics from both.  The scan reads both
-// halves: the join stands right in front of it, behind EV_COUNT_DONE, so the cluster passes' brackets hold nothing but their kernels
-// (and begin at EV_BEGIN: the main stream has nothing in front of them).
-static int search_count(SearchRun* r) {
+// halves: the join stands right in front of it.  The stamps: every kernel named below stamps its own begin, so the cluster passes'
+// brackets hold nothing but their kernels; `emit_follows`: a speculative emit is queued straight behind the scan and its first
+// kernel stamps the offsets done, else a stamp launch does.
+static int search_count(SearchRun* r, bool emit_follows) {
   hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
   SearchStatusBlock* blk = r->blk; uint32_t* counts = hs->counts.as<uint32_t>();
+  unsigned long long* stamps = r->stamps;
   const bool fork = r->by_cluster;
-  HIPCHK(hipEventRecord(ev[EV_BEGIN], st));
-  if (!fork) {
-    hawk_launch_search(st, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
-                       &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
-    if (r->vx) HIPCHK(hipEventRecord(ev[EV_VIEW_COUNT_BEGIN], st));
-  }
-  if (r->by_cluster) {
-    hawk_launch_cs_templates(st, r->d, r->va, r->cd, r->sp, r->gp, r->ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, &blk->template_rows,
-                             r->tcap, &blk->status);
-    (void)hipEventRecord(ev[EV_TEMPLATES_DONE], st);
-    hawk_launch_cs_count(st, r->d, r->va, r->cd, r->sp, hs->cs_res.p, &blk->template_rows, r->tcap, counts + r->plane_tiles, hs->cs_inst.p,
-                         r->shards);
-  } else if (r->vx) {
-    hawk_launch_vsearch(st, 0, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, hs->vcnt0.as<uint32_t>(), r->shards, nullptr, GuideCols{}, &blk->status,
-                        r->plane_tiles, r->v_tiles);
-  }
-  HIPCHK(hipEventRecord(ev[EV_COUNT_DONE], st));
   if (fork) {
-    // the main stream's kernels are queued first: at the head of a search the device is waiting for the host
-    HIPCHK(hipStreamWaitEvent(r->side, ev[EV_BEGIN], 0));  // (nothing is queued on the side stream yet)
+    // the fork stands at the head, where the device is waiting for the host anyway: behind the memset, in front of the templates
+    HIPCHK(hipEventRecord(ev[EV_COUNT_FORK], st));
+    hawk_launch_cs_templates(st, r->d, r->va, r->cd, r->sp, r->gp, r->ri, hs->cs_res.p, hs->cs_tbase.as<uint32_t>(), hs->cs_trows.p, &blk->template_rows,
+                             r->tcap, &blk->status, stamps + ST_COUNT_BEGIN);
+    hawk_launch_cs_count(st, r->d, r->va, r->cd, r->sp, hs->cs_res.p, &blk->template_rows, r->tcap, counts + r->plane_tiles, hs->cs_inst.p,
+                         r->shards, stamps + ST_CS_COUNT);
+    // the main stream's kernels are queued first
+    HIPCHK(hipStreamWaitEvent(r->side, ev[EV_COUNT_FORK], 0));  // (nothing is queued on the side stream yet)
     hawk_launch_search(r->side, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
-                       &blk->big_count, hs->big.as<unsigned long long>(), nullptr, r->plane_tiles);
+                       &blk->big_count, hs->big.as<unsigned long long>(), r->plane_tiles);
     HIPCHK(search_join(r, EV_COUNT_JOIN));
+  } else {
+    hawk_launch_search(st, 0, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, r->shards, nullptr, GuideCols{}, &blk->status, hs->lists.as<uint32_t>(),
+                       &blk->big_count, hs->big.as<unsigned long long>(), r->plane_tiles, stamps + ST_COUNT_BEGIN);
+    if (r->vx)
+      hawk_launch_vsearch(st, 0, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, counts, hs->vcnt0.as<uint32_t>(), r->shards, nullptr, GuideCols{}, &blk->status,
+                          r->plane_tiles, r->v_tiles, stamps + ST_VIEW_COUNT_BEGIN);
   }
-  hawk_launch_mscan(st, counts, r->nscan, hs->partial.as<unsigned long long>(), r->shards, hs->offsets.as<uint64_t>(), &blk->totals);
-  HIPCHK(hipEventRecord(ev[EV_OFFSETS_DONE], st));
+  hawk_launch_mscan(st, counts, r->nscan, hs->partial.as<unsigned long long>(), r->shards, hs->offsets.as<uint64_t>(), &blk->totals, stamps + ST_SCAN_BEGIN);
+  if (!emit_follows) hawk_launch_stamp(st, stamps + ST_OFFSETS_DONE);
   HIPCHK(hipGetLastError());
   return HAWK_OK;
 }
@@ -247,44 +263,50 @@ static int search_reserve_table(SearchRun* r, uint64_t cap, GuideCols* cols, Gui
   table->rows = hs->rowsA.as<uint4>(); table->cap = cap; table->startp = r->ri.startp;
   return HAWK_OK;
 }
-// The emit side, between its two events (`launch` false: a table of no rows); `behind_scan`: nothing has been queued since the offset
-// scan, whose event then opens the emit as well.  Plane kernels (all rows of a set with planes; REF's
+// The emit side, between its two stamps (`launch` false: a table of no rows - two stamp launches); `behind_scan`: nothing has been
+// queued since the offset scan, and the stamp that opens the emit closes the offsets as well.  Plane kernels (all rows of a set with planes; REF's
 // rows of a view) and the per-word search of a view write columns; the cluster search writes packed rows (k_cs_emit_rows), and REF's
 // rows - staged as columns - are packed in front of them.  The kernels take their offsets from HBM and refuse to write past the capacity.
 // A cluster search forks here too: REF's emit chain and its packing run on the side stream and write the table's rows
 // [0, offsets[plane_tiles]) (through the staging columns, which nothing else touches); k_cs_emit_rows, the only kernel on the main stream,
-// writes every row behind them.  The join stands in front of EV_EMIT_END, and so in front of whatever reads the status block or the table.
+// writes every row behind them.  The join stands in front of the end stamp, and so in front of whatever reads the status block or the
+// table.  The fork is the one event left between two kernels of the main stream: REF's chain needs the offsets.
 static int search_emit(SearchRun* r, const GuideCols& cols, const GuideCols& packed, bool launch, bool behind_scan) {
   hawk_hapset* hs = r->hs; hipStream_t st = r->st; hipEvent_t* ev = r->ctx->ev;
   SearchStatusBlock* blk = r->blk; const uint64_t* offsets = hs->offsets.as<uint64_t>();
-  r->emit_begin = behind_scan ? EV_OFFSETS_DONE : EV_EMIT_BEGIN;
-  if (!behind_scan) HIPCHK(hipEventRecord(ev[EV_EMIT_BEGIN], st));
+  unsigned long long* stamps = r->stamps;
+  r->emit_begin = behind_scan ? ST_OFFSETS_DONE : ST_EMIT_BEGIN;
+  unsigned long long* begin = stamps + r->emit_begin;
   if (launch) {
     const hipStream_t ref_st = r->by_cluster ? r->side : st;
     if (r->by_cluster) {  // the main stream's kernel first, then the fork (nothing is queued on the side stream yet)
+      HIPCHK(hipEventRecord(ev[EV_EMIT_FORK], st));
       hawk_launch_cs_emit_rows(st, r->cd.n_inst, hs->cs_inst.p, hs->cs_trows.p, offsets + r->plane_tiles, &blk->template_rows,
-                               r->tcap, packed.rows, packed.cap, &blk->status);
-      HIPCHK(hipStreamWaitEvent(r->side, ev[r->emit_begin], 0));
+                               r->tcap, packed.rows, packed.cap, &blk->status, begin);
+      HIPCHK(hipStreamWaitEvent(r->side, ev[EV_EMIT_FORK], 0));
     }
+    // k_emit_list opens the emit where it is the first kernel; k_search_emit begins where it ends
     hawk_launch_search(ref_st, 1, r->d, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), r->shards, offsets, cols, &blk->status, hs->lists.as<uint32_t>(),
-                       &blk->big_count, hs->big.as<unsigned long long>(), ev[EV_LIST_EMIT_END], r->plane_tiles);
-    if (r->vx) (void)hipEventRecord(ev[EV_VIEW_EMIT_BEGIN], ref_st);
+                       &blk->big_count, hs->big.as<unsigned long long>(), r->plane_tiles, r->by_cluster ? stamps + ST_LIST_BEGIN : begin, stamps + ST_LIST_END);
     if (r->by_cluster) {
-      hawk_launch_rows_pack(ref_st, cols, offsets + r->plane_tiles, 0, std::min<uint64_t>(r->stage_cap, packed.cap), packed.rows, packed.startp, &blk->status);
+      hawk_launch_rows_pack(ref_st, cols, offsets + r->plane_tiles, 0, std::min<uint64_t>(r->stage_cap, packed.cap), packed.rows, packed.startp, &blk->status,
+                            stamps + ST_VIEW_EMIT_BEGIN);
       HIPCHK(search_join(r, EV_EMIT_JOIN));
     } else if (r->vx) {
       hawk_launch_vsearch(st, 1, r->d, r->va, r->sp, r->gp, r->ri, hs->d_tile_meta, hs->counts.as<uint32_t>(), hs->vcnt0.as<uint32_t>(), r->shards, offsets, cols,
-                          &blk->status, r->plane_tiles, r->v_tiles);
+                          &blk->status, r->plane_tiles, r->v_tiles, stamps + ST_VIEW_EMIT_BEGIN);
     }
+  } else {
+    hawk_launch_stamp(st, begin);
   }
-  HIPCHK(hipEventRecord(ev[EV_EMIT_END], st));
+  hawk_launch_stamp(st, stamps + ST_EMIT_END);
   HIPCHK(hipGetLastError());
   return HAWK_OK;
 }
 // The status block after the count side (and a speculative emit): totals, status, and the template rows a cluster search used.
 // If those outgrew their reservation the rerun reserves what this search asked for (+ 1/8), at most the plan's bound.
 static int search_read_block(SearchRun* r) {
-  HIPCHK(hipMemcpyAsync(r->h, r->blk, sizeof(SearchStatusBlock), hipMemcpyDeviceToHost, r->st));
+  HIPCHK(hipMemcpyAsync(r->h, r->blk, sizeof(SearchStatusBlock) + sizeof(SearchMisc::stamps), hipMemcpyDeviceToHost, r->st));
   HIPCHK(hipStreamSynchronize(r->st));
   if (!r->by_cluster) return HAWK_OK;
   const uint64_t tcu = r->h->template_rows;
@@ -293,23 +315,26 @@ static int search_read_block(SearchRun* r) {
   return HAWK_OK;
 }
 
+// The intervals, from the stamps as last read back.  The device's clock begins an interval with the kernel that opens it: the time the
+// device stood idle in front of a stage's first kernel belongs to no interval.
 static void search_timing(const SearchRun* r, uint64_t nrows, hawk_timing* timing) {
-  const hawk_hapset* hs = r->hs; hipEvent_t* ev = r->ctx->ev;
-  const hipEvent_t emit_begin = ev[r->emit_begin];
+  const hawk_hapset* hs = r->hs; const unsigned long long* t = r->h_stamps;
+  const auto ms = [&](int a, int b) { return hawk_stamp_ms(r->ctx, t[a], t[b]); };
+  const SearchStamp emit_begin = r->emit_begin;
   memset(timing, 0, sizeof(*timing));
-  (void)hipEventElapsedTime(&timing->count_ms, ev[EV_BEGIN], ev[EV_COUNT_DONE]);
-  (void)hipEventElapsedTime(&timing->offsets_ms, ev[EV_COUNT_DONE], ev[EV_OFFSETS_DONE]);
-  (void)hipEventElapsedTime(&timing->emit_ms, emit_begin, ev[EV_EMIT_END]);
-  if (nrows) (void)hipEventElapsedTime(&timing->emit_list_ms, emit_begin, ev[EV_LIST_EMIT_END]);
-  (void)hipEventElapsedTime(&timing->total_ms, ev[EV_BEGIN], ev[EV_EMIT_END]);
+  timing->count_ms = ms(ST_COUNT_BEGIN, ST_SCAN_BEGIN);
+  timing->offsets_ms = ms(ST_SCAN_BEGIN, ST_OFFSETS_DONE);
+  timing->emit_ms = ms(emit_begin, ST_EMIT_END);
+  if (nrows) timing->emit_list_ms = ms(r->by_cluster ? ST_LIST_BEGIN : emit_begin, ST_LIST_END);
+  timing->total_ms = ms(ST_COUNT_BEGIN, ST_EMIT_END);
   if (r->vx) {
     // a cluster search: the main stream holds the cluster passes alone, their brackets open with the stage's
-    const hipEvent_t v_count_begin = ev[r->by_cluster ? EV_BEGIN : EV_VIEW_COUNT_BEGIN];
-    (void)hipEventElapsedTime(&timing->v_count_ms, v_count_begin, ev[EV_COUNT_DONE]);
-    if (nrows) (void)hipEventElapsedTime(&timing->v_emit_ms, ev[EV_VIEW_EMIT_BEGIN], ev[EV_EMIT_END]);
+    const SearchStamp v_count_begin = r->by_cluster ? ST_COUNT_BEGIN : ST_VIEW_COUNT_BEGIN;
+    timing->v_count_ms = ms(v_count_begin, ST_SCAN_BEGIN);
+    if (nrows) timing->v_emit_ms = ms(ST_VIEW_EMIT_BEGIN, ST_EMIT_END);
     timing->v_path = r->by_cluster ? 2u : 1u;
-    if (r->by_cluster) (void)hipEventElapsedTime(&timing->v_templates_ms, v_count_begin, ev[EV_TEMPLATES_DONE]);
-    if (r->by_cluster && nrows) (void)hipEventElapsedTime(&timing->v_emit_rows_ms, emit_begin, ev[EV_EMIT_END]);
+    if (r->by_cluster) timing->v_templates_ms = ms(v_count_begin, ST_CS_COUNT);
+    if (r->by_cluster && nrows) timing->v_emit_rows_ms = ms(emit_begin, ST_EMIT_END);
   }
   uint64_t pos = 0;
   for (uint32_t h = 0; h < hs->n_hap; ++h) pos += (uint64_t)std::max(0, hs->scan_stop[h] - hs->scan_start[h]);
@@ -343,9 +368,10 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
   int rc;
   if ((rc = search_classify(hs, p, &r)) || (rc = search_reserve(&r, p)) || (rc = search_upload_cfd(&r, p))) return rc;
   HIPCHK(hipMemsetAsync(r.hs->misc.p, 0, sizeof(SearchMisc), r.st));
-  if ((rc = search_ref(&r, p)) || (rc = search_view_args(&r)) || (rc = search_count(&r))) return rc;
+  if ((rc = search_ref(&r, p)) || (rc = search_view_args(&r))) return rc;
   uint64_t& table_cap = *r.table_cap;
   const bool speculative = table_cap != 0;
+  if ((rc = search_count(&r, speculative))) return rc;
   GuideCols cols, table;
   if (speculative && ((rc = search_reserve_table(&r, table_cap, &cols, &table)) || (rc = search_emit(&r, cols, table, true, true)))) return rc;
   if ((rc = search_read_block(&r))) return rc;
@@ -357,7 +383,8 @@ static int hawk_search_once(hawk_hapset* hs, const hawk_search_params* p, hawk_t
     if ((rc = search_reserve_table(&r, std::max<uint64_t>(std::max<uint64_t>(nrows, 1), table_cap), &cols, &table))) return rc;
     table_cap = table.cap;
     if ((rc = search_emit(&r, cols, table, nrows != 0, false))) return rc;
-    HIPCHK(hipMemcpyAsync(&r.h->status, &r.blk->status, sizeof(int), hipMemcpyDeviceToHost, r.st));
+    // (the status, and the stamps of this emit; nothing else in the block has changed)
+    HIPCHK(hipMemcpyAsync(r.h, r.blk, sizeof(SearchStatusBlock) + sizeof(SearchMisc::stamps), hipMemcpyDeviceToHost, r.st));
     HIPCHK(hipStreamSynchronize(r.st));
   }
   if (timing) search_timing(&r, nrows, timing);

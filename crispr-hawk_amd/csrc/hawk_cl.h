@@ -39,11 +39,13 @@ struct __attribute__((aligned(32))) ClListed {  // a listed instance: all the ta
 };
 static_assert(sizeof(ClListed) == 32, "list entry layout");
 
-// What k_cl_results writes and the host reads of a finished attempt, in one copy.
+// What k_cl_results writes and the host reads of a finished attempt, in one copy - and the device's wall clock (hawk_stamp) where
+// the build's first kernel began (k_cl_chunks; a repeated attempt clears the block, the host keeps the first attempt's) and where
+// k_cl_results ended.
 struct ClResults {
-  unsigned long long instances, table_clusters, variant_clusters, template_rows, status, pad[3];
+  unsigned long long instances, table_clusters, variant_clusters, template_rows, status, begin, end, pad;
 };
-static_assert(sizeof(ClResults) == 64, "result block layout");
+static_assert(sizeof(ClResults) == 64 && offsetof(ClResults, begin) == 40 && offsetof(ClResults, end) == 48, "result block layout");
 
 // ---- what the launchers of a build take (hawk_device.h) ----------------------------------------------
 struct ClPlan {  // what every pass reads of the plan

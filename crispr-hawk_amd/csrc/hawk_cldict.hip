@@ -41,8 +41,9 @@ __device__ __forceinline__ bool cl_starts(const HxHead* __restrict__ recs, uint6
 // rows -> chunks, one workgroup: chunks per row, their offsets (ch_off[n_rows + 1]) and every chunk's row
 __global__ __launch_bounds__(1024) void k_cl_chunks(const uint64_t* __restrict__ hv_off, const uint8_t* __restrict__ is_ref, const int32_t* __restrict__ ss,
                                                     const int32_t* __restrict__ se, uint32_t n_rows, uint32_t* __restrict__ ch_off,
-                                                    uint32_t* __restrict__ ch_row) {
+                                                    uint32_t* __restrict__ ch_row, unsigned long long* stamp) {
   __shared__ uint32_t s_w[1024 / WAVE];
+  hawk_stamp(stamp);  // a build begins here (ClResults::begin)
   uint32_t carry = 0;
   for (uint32_t r0 = 0; r0 < n_rows; r0 += 1024) {
     const uint32_t row = r0 + threadIdx.x;
@@ -440,6 +441,7 @@ __global__ __launch_bounds__(256) void k_cl_describe(const uint32_t* __restrict_
 __global__ void k_cl_results(const uint32_t* __restrict__ n_inst, const uint32_t* __restrict__ counters, const unsigned long long* __restrict__ slots_total,
                              const uint32_t* __restrict__ status, unsigned long long* __restrict__ out) {
   out[0] = *n_inst; out[1] = counters[0]; out[2] = counters[1]; out[3] = *slots_total; out[4] = *status;
+  out[6] = wall_clock64();  // ClResults::end: the attempt's kernels are done
 }
 // The listed instances that found their hash in the table: number from the slot, identity compared record by record with the instance
 // that opened the cluster (exactness: same hash is not same cluster until then).  Loads level by level.
@@ -498,7 +500,8 @@ __global__ __launch_bounds__(256) void k_cl_uid(const ClListed* __restrict__ cx_
 // ---- launchers: the views of hawk_cl.h unpacked into the kernels' parameter lists ----------------------
 // rows -> chunks: ch_off[n_rows + 1] (chunks in front of every row) and the chunks' rows (room: hawk_cl_chunk_bound)
 void hawk_launch_cl_chunks(hipStream_t st, const ClBuild& b) {
-  hipLaunchKernelGGL(k_cl_chunks, dim3(1), dim3(1024), 0, st, b.plan.hv_off, b.plan.is_ref, b.plan.ss, b.plan.se, b.plan.n_rows, b.ch.ch_off, b.ch.ch_row);
+  hipLaunchKernelGGL(k_cl_chunks, dim3(1), dim3(1024), 0, st, b.plan.hv_off, b.plan.is_ref, b.plan.ss, b.plan.se, b.plan.n_rows, b.ch.ch_off, b.ch.ch_row,
+                     &b.tally.results->begin);
 }
 // The first CL_HEAD_CHUNKS chunks (a few dozen rows) describe the variants they carry in the COUNTING pass, which cuts them anyway;
 // the launch of the scan turns the describers into the bitmap, and the cutting pass - one launch - describes what they left.  A

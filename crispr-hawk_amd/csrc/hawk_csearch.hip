@@ -67,7 +67,8 @@ __device__ __forceinline__ int64_t posmap_hint(const HapSetDev& hs, uint32_t k0,
 // at tbase[u] (strand 0 in position order, then strand 1), packed: a workgroup adds up its clusters' rows and takes its
 // stretch of the template array with one atomic.
 __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, ClDict cd, ScanParams p, GuideParams gp, RefInfo ri,
-                                                      uint4* __restrict__ res, uint32_t* __restrict__ tbase, CsRow* __restrict__ trows, unsigned long long* __restrict__ t_count, uint64_t t_cap, int* status) {
+                                                      uint4* __restrict__ res, uint32_t* __restrict__ tbase, CsRow* __restrict__ trows, unsigned long long* __restrict__ t_count, uint64_t t_cap, int* status,
+                                                      unsigned long long* stamp) {
   __shared__ double s_cfd[336];
   __shared__ uint32_t s_w[256 / WAVE];
   __shared__ unsigned long long s_base;
@@ -75,6 +76,7 @@ __global__ __launch_bounds__(256) void k_cs_templates(HapSetDev hs, VcArgs va, C
   __shared__ uint32_t s_k[2][256];   // ... the window starts its filters keep, per strand
   __shared__ uint32_t s_e[256];      // ... and how many the group's lanes before it keep (strand 0 | strand 1 << 16)
   const uint32_t tid = threadIdx.x;
+  hawk_stamp(stamp);
   if (gp.score_cfdon) for (uint32_t i = tid; i < 336; i += 256) s_cfd[i] = gp.cfd_mm[i];
   __syncthreads();
   const uint32_t gl = tid & (CS_G - 1);
@@ -330,8 +332,10 @@ __device__ __forceinline__ uint4 cs_inst_load(const uint4* q) {
 #define CS_CNT_U 4
 __global__ __launch_bounds__(256) void k_cs_count(HapSetDev hs, VcArgs va, ClDict cd, ScanParams p, const uint4* __restrict__ res,
                                                   const unsigned long long* __restrict__ t_count, uint64_t t_cap,
-                                                  uint32_t* __restrict__ group_counts, uint4* __restrict__ inst, unsigned long long* __restrict__ shards) {
+                                                  uint32_t* __restrict__ group_counts, uint4* __restrict__ inst, unsigned long long* __restrict__ shards,
+                                                  unsigned long long* stamp) {
   __shared__ uint32_t s_red[256 / WAVE][2];
+  hawk_stamp(stamp);
   const uint32_t i0 = blockIdx.x * (256 * CS_CNT_U) + threadIdx.x;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const bool ovf = *t_count > t_cap;  // the template rows outgrew their reservation: no table (the host reruns the search)
@@ -416,7 +420,7 @@ template <int NI, int CE_CH>
 __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uint4* __restrict__ inst,
                                                       const CsRow* __restrict__ trows, const uint64_t* __restrict__ offsets,
                                                       const unsigned long long* __restrict__ t_count, uint64_t t_cap, uint4* __restrict__ rows,
-                                                      uint64_t cap, int* status) {
+                                                      uint64_t cap, int* status, unsigned long long* stamp) {
   // everything below is private to a wave (its own LDS slices, no workgroup barrier): the four waves of a workgroup drift apart freely
   constexpr int NE = NI * WAVE;
   constexpr int CE_SUB = CE_CH / 16;  // 16-byte loads per lane and chunk
@@ -425,6 +429,7 @@ __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uin
   __shared__ int32_t s_dq[4][NE];
   __shared__ uint32_t s_src[4][2][CE_CH], s_rh[4][2][CE_CH];
   __shared__ int32_t s_rdq[4][2][CE_CH];
+  hawk_stamp(stamp);
   if (*t_count > t_cap) return;  // the template rows outgrew their reservation (k_cs_count left no counts): the host reruns the search
   const uint32_t wv = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
   const uint32_t i0 = (blockIdx.x * 4 + wv) * NE;  // the wave's first instance
@@ -510,8 +515,9 @@ __global__ __launch_bounds__(256) void k_cs_emit_rows(uint32_t n_inst, const uin
 constexpr int CS_EMIT_NI = 4, CS_EMIT_CH = 256;
 void hawk_cs_emit_geometry(uint32_t* inst_per_wave, uint32_t* rows_per_chunk) { *inst_per_wave = CS_EMIT_NI * WAVE; *rows_per_chunk = CS_EMIT_CH; }
 void hawk_launch_cs_emit_rows(hipStream_t st, uint32_t n_inst, const void* inst, const void* trows, const uint64_t* offsets,
-                              const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status) {
-  if (!n_inst) return;
+                              const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status,
+                              unsigned long long* stamp) {
+  if (!n_inst) { if (stamp) hawk_launch_stamp(st, stamp); return; }
   // 256 instances per wave, 256 rows in flight per wave (184 VGPRs: two waves per SIMD).  Measured on C3 (profiles/r04_emit_rows.md):
   // 64 / 128 / 256 rows in flight at 8 / 4 / 2 waves per SIMD: 0.53 / 0.47 / 0.45 ms before the offset scan went to one entry per
   // 64 instances, 0.39 (128 rows, 128 instances) / 0.38 after - few waves with long contiguous bursts write best.
@@ -524,21 +530,23 @@ void hawk_launch_cs_emit_rows(hipStream_t st, uint32_t n_inst, const void* inst,
   // behind the build (0.434 for 0.467) and the records made that gain moot.
   constexpr int NI = CS_EMIT_NI, CH = CS_EMIT_CH;
   hipLaunchKernelGGL((k_cs_emit_rows<NI, CH>), dim3((n_inst + 256 * NI - 1) / (256 * NI)), dim3(256), 0, st, n_inst, static_cast<const uint4*>(inst),
-                     static_cast<const CsRow*>(trows), offsets, t_count, t_cap, static_cast<uint4*>(rows), cap, status);
+                     static_cast<const CsRow*>(trows), offsets, t_count, t_cap, static_cast<uint4*>(rows), cap, status, stamp);
 }
 
 void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const GuideParams& gp,
-                              const RefInfo& ri, void* res, uint32_t* tbase, void* trows, unsigned long long* t_count, uint64_t t_cap, int* status) {
-  if (!cd.n_uniq) return;
+                              const RefInfo& ri, void* res, uint32_t* tbase, void* trows, unsigned long long* t_count, uint64_t t_cap, int* status,
+                              unsigned long long* stamp) {
+  if (!cd.n_uniq) { if (stamp) hawk_launch_stamp(st, stamp); return; }
   const uint32_t nb = (uint32_t)(((uint64_t)cd.n_uniq * CS_G + 255) / 256);
   hipLaunchKernelGGL(k_cs_templates, dim3(nb), dim3(256), 0, st, hs, va, cd, p, gp, ri, static_cast<uint4*>(res), tbase, static_cast<CsRow*>(trows),
-                     t_count, t_cap, status);
+                     t_count, t_cap, status, stamp);
 }
 void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const void* res,
-                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, void* inst, unsigned long long* shards) {
-  if (!cd.n_inst) return;
+                          const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, void* inst, unsigned long long* shards,
+                          unsigned long long* stamp) {
+  if (!cd.n_inst) { if (stamp) hawk_launch_stamp(st, stamp); return; }
   hipLaunchKernelGGL(k_cs_count, dim3((cd.n_inst + 256 * CS_CNT_U - 1) / (256 * CS_CNT_U)), dim3(256), 0, st, hs, va, cd, p, static_cast<const uint4*>(res), t_count, t_cap,
-                     group_counts, static_cast<uint4*>(inst), shards);
+                     group_counts, static_cast<uint4*>(inst), shards, stamp);
 }
 
 // columns -> packed rows (REF's rows, which the plane kernels write as columns; a columnar table before an exchange) and back:
@@ -547,7 +555,8 @@ void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va,
 // panel of few variants).  Like every other writer of a table the kernel then refuses instead of writing past the end - the launch is
 // rounded up to 256 threads, and those between max_rows and the next multiple used to write up to 255 rows behind the allocation.
 __global__ __launch_bounds__(256) void k_rows_pack(GuideCols c, const uint64_t* __restrict__ n_dev, uint64_t n_host, uint64_t max_rows, uint4* __restrict__ rows,
-                                                   int64_t startp, int* status) {
+                                                   int64_t startp, int* status, unsigned long long* stamp) {
+  hawk_stamp(stamp);
   const uint64_t n = n_dev ? *n_dev : n_host;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (n > max_rows) { if (i == 0) atomicCAS(status, 0, -3 /* HAWK_E_CAPACITY */); return; }
@@ -587,9 +596,9 @@ __global__ __launch_bounds__(256) void k_rows_unpack(const uint4* __restrict__ r
   }
 }
 void hawk_launch_rows_pack(hipStream_t st, const GuideCols& src, const uint64_t* n_dev, uint64_t n_host, uint64_t max_rows, uint4* rows, int64_t startp,
-                           int* status) {
-  if (!max_rows) return;
-  hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((max_rows + 255) / 256)), dim3(256), 0, st, src, n_dev, n_host, max_rows, rows, startp, status);
+                           int* status, unsigned long long* stamp) {
+  if (!max_rows) { if (stamp) hawk_launch_stamp(st, stamp); return; }
+  hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((max_rows + 255) / 256)), dim3(256), 0, st, src, n_dev, n_host, max_rows, rows, startp, status, stamp);
 }
 void hawk_launch_rows_unpack(hipStream_t st, const uint4* rows, uint64_t n, int64_t startp, const GuideCols& dst) {
   if (!n) return;

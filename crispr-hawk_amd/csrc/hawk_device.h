@@ -79,7 +79,14 @@ struct GuideCols {
 };
 #define HAWK_ROW_HAP_SHIFT 9
 #define HAWK_ROW_MAX_HAP (1u << 23)
+// A stage boundary is timed by the kernel that opens the next interval: thread 0 of workgroup 0 stores the device's wall clock
+// (a constant-rate counter, hipDeviceAttributeWallClockRate) into its slot of a stamp block the host reads back with the results.
+// A null slot stamps nothing.  Where no kernel follows on the stream, hawk_launch_stamp queues a one-thread kernel that does it.
+void hawk_launch_stamp(hipStream_t st, unsigned long long* slot);
 #ifdef __HIPCC__
+__device__ __forceinline__ void hawk_stamp(unsigned long long* slot) {
+  if (slot && blockIdx.x == 0 && threadIdx.x == 0) *slot = wall_clock64();
+}
 // field access for either layout (the branch is uniform over a launch)
 __device__ __forceinline__ const uint32_t* gc_roww(const GuideCols& c, uint64_t i) { return reinterpret_cast<const uint32_t*>(c.rows) + i * 16; }
 __device__ __forceinline__ uint32_t gc_hap(const GuideCols& c, uint64_t i) { return c.rows ? gc_roww(c, i)[1] >> HAWK_ROW_HAP_SHIFT : c.hap[i]; }
@@ -106,7 +113,7 @@ __device__ __forceinline__ uint64_t gc_win(const GuideCols& c, int pl, uint64_t 
 // columns [0, n) -> packed rows [0, n) (n read on the device: *n_dev, or n_host when n_dev is null) and back (null destination
 // columns are skipped).  Packing reports HAWK_E_UNSUPPORTED through *status for a row the layout cannot hold.
 void hawk_launch_rows_pack(hipStream_t st, const GuideCols& src, const uint64_t* n_dev, uint64_t n_host, uint64_t max_rows, uint4* rows, int64_t startp,
-                           int* status);
+                           int* status, unsigned long long* stamp = nullptr);
 void hawk_launch_rows_unpack(hipStream_t st, const uint4* rows, uint64_t n, int64_t startp, const GuideCols& dst);
 
 struct GuideParams {
@@ -138,7 +145,8 @@ struct VcArgs {
 };
 void hawk_launch_vsearch(hipStream_t st, int pass, const HapSetDev& hs, const VcArgs& va, const ScanParams& p, const struct GuideParams& gp,
                          const struct RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, uint32_t* counts0, unsigned long long* shards,
-                         const uint64_t* offsets, struct GuideCols out, int* status, uint32_t tile0, uint32_t n_tiles);
+                         const uint64_t* offsets, struct GuideCols out, int* status, uint32_t tile0, uint32_t n_tiles,
+                         unsigned long long* stamp = nullptr);
 void hawk_launch_ref_hits(hipStream_t st, const HapSetDev& hs, const ScanParams& p, int32_t ref_index, void* hp);
 // The cluster dictionary of an expansion plan (hawk_cldict.hip): every row's records cut into clusters (variants whose
 // alleles lie within 64 positions of each other), identical clusters of different rows numbered once.
@@ -169,12 +177,13 @@ void hawk_launch_cl_fill(hipStream_t st, const ClBuild& b);   // behind the scan
 void hawk_launch_cl_finish(hipStream_t st, const ClBuild& b, const ClTable& t, const ClUniq& cu);  // the list through the table, the clusters' descriptions, the result block
 void hawk_launch_cs_templates(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const struct GuideParams& gp,
                               const struct RefInfo& ri, void* res /* 32 B per distinct cluster */, uint32_t* tbase, void* trows,
-                              unsigned long long* t_count, uint64_t t_cap, int* status);
+                              unsigned long long* t_count, uint64_t t_cap, int* status, unsigned long long* stamp = nullptr);
 void hawk_launch_cs_count(hipStream_t st, const HapSetDev& hs, const VcArgs& va, const ClDict& cd, const ScanParams& p, const void* res,
                           const unsigned long long* t_count, uint64_t t_cap, uint32_t* group_counts, void* inst /* 16 B per instance */,
-                          unsigned long long* shards);
+                          unsigned long long* shards, unsigned long long* stamp = nullptr);
 void hawk_launch_cs_emit_rows(hipStream_t st, uint32_t n_inst, const void* inst, const void* trows, const uint64_t* offsets,
-                              const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status);
+                              const unsigned long long* t_count, uint64_t t_cap, void* rows, uint64_t cap, int* status,
+                              unsigned long long* stamp = nullptr);
 void hawk_cs_emit_geometry(uint32_t* inst_per_wave, uint32_t* rows_per_chunk);  // of the instantiation hawk_launch_cs_emit_rows launches
 // hawk_meta.hip: the rows' metadata of an expansion plan, built on the device
 void hawk_launch_list_check(hipStream_t st, const uint64_t* row_off, uint32_t n_rows, const uint32_t* hv_idx, const int32_t* hv_o,
@@ -285,7 +294,8 @@ void hawk_launch_emit_hits(hipStream_t st, const HapSetDev& hs, uint32_t bph, co
 void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const ScanParams& p, const GuideParams& gp,
                         const RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, unsigned long long* shards,
                         const uint64_t* offsets, GuideCols out, int* status, uint32_t* lists, uint32_t* big_count,
-                        unsigned long long* big_list, hipEvent_t mid = nullptr, uint32_t n_tiles = 0xffffffffu);
+                        unsigned long long* big_list, uint32_t n_tiles = 0xffffffffu, unsigned long long* stamp = nullptr,
+                        unsigned long long* stamp_mid = nullptr);  // stamp: the pass's first kernel; stamp_mid: k_search_emit (pass 1)
 // ---- the collapse (hawk_collapse.hip).  These structs are host-side: the kernels keep their plain parameter lists.
 struct CollapseKey {  // the rows of one table and what two of them are compared on
   GuideCols c; const uint8_t* is_ref; uint64_t n;
@@ -350,7 +360,7 @@ void hawk_launch_gt_fill(hipStream_t st, uint32_t n_cols, const int32_t* var_r0,
 enum { HAWK_MSCAN_ONE = 0, HAWK_MSCAN_M1_M23 = 1, HAWK_MSCAN_WIDE = 2, HAWK_MSCAN_M1_M2_M3 = 3 };  // k_mscan_one / k_mscan1 + k_mscan23 / k_mscan1w + k_mscan23w / k_mscan1, 2, 3
 int hawk_mscan_route(uint64_t n, bool shards, bool aligned);
 void hawk_launch_mscan(hipStream_t st, const uint32_t* counts, uint64_t n, unsigned long long* partial,
-                       const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals);
+                       const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals, unsigned long long* stamp = nullptr);
 void hawk_launch_cfd(hipStream_t st, const char* wt, const char* sg, uint32_t len, const char* pam2, uint64_t n,
                      const double* mm, const double* pamtab, double* out, int* status);
 void hawk_launch_deepcpf1(hipStream_t st, const char* seqs, uint64_t n, const float* w, float* out, int* status);

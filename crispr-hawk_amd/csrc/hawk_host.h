@@ -26,6 +26,7 @@ char* hawk_hip_err_buf();  // thread-local text of the last HIP failure (hawk_la
   } while (0)
 
 #define HAWK_EV_TIMED 10  // slots [0, HAWK_EV_TIMED) of hawk_ctx::ev carry timestamps; the slots behind them only order two streams
+                          // (hawk_search, which times itself by stamps: hawk_stamp_ms below)
 struct hawk_ctx {
   int device;
   hipStream_t stream;
@@ -34,12 +35,20 @@ struct hawk_ctx {
   hipStream_t side = nullptr;
   // Scratch of the call that is running: every C-ABI call records the events it times with and reads them before it returns.
   // No call may read an event another call recorded (two calls use the same slots for different intervals).
-  hipEvent_t ev[12];
+  hipEvent_t ev[14];
   void* pinned = nullptr;  // page-locked host memory: a PinnedBlock (below)
+  int wall_clock_khz = 0;  // rate of the device's wall clock (hipDeviceAttributeWallClockRate): what a stamp counts in
 };
+// Milliseconds between two stamps (hawk_stamp, hawk_device.h).  A stamp nobody wrote is still the 0 its block was cleared to, and
+// an interval with such an end - or with its ends out of order - is 0, never a huge or a negative number.
+inline float hawk_stamp_ms(const hawk_ctx* ctx, unsigned long long begin, unsigned long long end) {
+  if (!begin || !end || end < begin || ctx->wall_clock_khz <= 0) return 0.f;
+  return (float)((double)(end - begin) / (double)ctx->wall_clock_khz);
+}
 
 // What hs->misc holds while hawk_search runs.  The host and the kernels' launchers share the status block; the host reads it back
-// whole (64 bytes, one copy into hawk_ctx::pinned).  The offsets are what the device side has always been handed.
+// whole, with the stamp block behind it (192 bytes, one copy into hawk_ctx::pinned).  The offsets are what the device side has always
+// been handed.
 struct SearchStatusBlock {
   int status;                        // the FIRST status a kernel raised (0: none)
   int pad0;
@@ -48,22 +57,28 @@ struct SearchStatusBlock {
   uint32_t pad1[3];
   ScanTotals totals;
 };
+#define HAWK_SEARCH_STAMPS 16  // slots of the stamp block (SearchStamp, hawk_api_search.hip): the wall clock at the stage boundaries
 struct SearchMisc {
   unsigned long long shards[256][2];  // candidate / hit partial sums
   SearchStatusBlock blk;
+  unsigned long long stamps[HAWK_SEARCH_STAMPS];  // cleared with the rest, written by hawk_stamp, read back behind the status block
 };
-static_assert(sizeof(SearchStatusBlock) == 64 && sizeof(SearchMisc) == 4096 + 64, "status block layout");
-static_assert(offsetof(SearchMisc, shards) == 0 && offsetof(SearchMisc, blk) == 4096, "status block layout");
+static_assert(sizeof(SearchStatusBlock) == 64 && sizeof(SearchMisc) == 4096 + 64 + 8 * HAWK_SEARCH_STAMPS, "status block layout");
+static_assert(offsetof(SearchMisc, shards) == 0 && offsetof(SearchMisc, blk) == 4096 && offsetof(SearchMisc, stamps) == 4096 + 64, "status block layout");
 static_assert(offsetof(SearchStatusBlock, status) == 0 && offsetof(SearchStatusBlock, template_rows) == 8 &&
               offsetof(SearchStatusBlock, big_count) == 16 && offsetof(SearchStatusBlock, totals) == 32, "status block layout");
 // hawk_ctx::pinned: what the two read-backs that go through page-locked memory land in (a copy into pageable memory is staged)
 struct PinnedBlock {
-  SearchStatusBlock search;  // [0, 64) hawk_search
+  SearchStatusBlock search;                       // [0, 64) hawk_search ...
+  unsigned long long stamps[HAWK_SEARCH_STAMPS];  // [64, 192) ... and its stamps: the same copy (SearchMisc::blk, ::stamps)
   char gap0[64];
-  ClResults dict;            // [128, 192) the build of the cluster dictionary
+  ClResults dict;                                 // [256, 320) the build of the cluster dictionary
   char gap1[64];
 };
-static_assert(offsetof(PinnedBlock, search) == 0 && offsetof(PinnedBlock, dict) == 128 && sizeof(PinnedBlock) == 256, "page-locked block layout");
+static_assert(offsetof(PinnedBlock, search) == 0 && offsetof(PinnedBlock, stamps) == sizeof(SearchStatusBlock) && offsetof(PinnedBlock, dict) == 256 &&
+              sizeof(PinnedBlock) == 384, "page-locked block layout");
+static_assert(offsetof(PinnedBlock, stamps) - offsetof(PinnedBlock, search) == offsetof(SearchMisc, stamps) - offsetof(SearchMisc, blk),
+              "the status block and the stamps cross in one copy");
 
 // Caching device allocator, one per device: a freed block goes to a free list and is handed to the next request of a
 // similar size, so a per-tile loop (expand -> search -> collapse, tile after tile) allocates its planes, columns and

@@ -426,13 +426,17 @@ __device__ __forceinline__ void search_tile(const HapSetDev& hs, const ScanParam
 __global__ __launch_bounds__(HAWK_BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT_WAVES, 8)))
 void k_search_count(HapSetDev hs, ScanParams p, GuideParams gp, RefInfo ri, const TileMeta* __restrict__ tmeta,
                     uint32_t* __restrict__ counts, unsigned long long* __restrict__ shards, int* status,
-                    uint32_t* __restrict__ lists, uint32_t* __restrict__ big_count, unsigned long long* __restrict__ big_list) {
+                    uint32_t* __restrict__ lists, uint32_t* __restrict__ big_count, unsigned long long* __restrict__ big_list,
+                    unsigned long long* stamp) {
+  hawk_stamp(stamp);
   search_tile<0>(hs, p, gp, ri, tmeta, counts, shards, nullptr, GuideCols{}, status, lists, blockIdx.x, big_count, big_list, -1);
 }
 __global__ __launch_bounds__(HAWK_BLOCK)
 void k_search_emit(HapSetDev hs, ScanParams p, GuideParams gp, RefInfo ri, const TileMeta* __restrict__ tmeta,
                    uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets, GuideCols out, int* status,
-                   uint32_t* __restrict__ lists, const uint32_t* __restrict__ big_count, const unsigned long long* __restrict__ big_list) {
+                   uint32_t* __restrict__ lists, const uint32_t* __restrict__ big_count, const unsigned long long* __restrict__ big_list,
+                   unsigned long long* stamp) {
+  hawk_stamp(stamp);
   const uint32_t n_big = *big_count;
 #pragma unroll 1
   for (uint32_t i = blockIdx.x; i < n_big; i += gridDim.x) {  // workgroup-uniform
@@ -456,12 +460,14 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_emit_list(HapSetDev hs, ScanPara
                                                           const TileMeta* __restrict__ tmeta,
                                                           const uint32_t* __restrict__ counts,
                                                           const uint64_t* __restrict__ offsets,
-                                                          const uint32_t* __restrict__ lists, GuideCols out, int* status) {
+                                                          const uint32_t* __restrict__ lists, GuideCols out, int* status,
+                                                          unsigned long long* stamp) {
   __shared__ __attribute__((aligned(16))) uint32_t s_pl[HAWK_PLANES][LDS_ROW];
   __shared__ uint32_t s_segrel[NSEG];
   __shared__ int64_t s_seggen[NSEG];
   __shared__ double s_cfd[336];
   __shared__ uint32_t s_nloc;
+  hawk_stamp(stamp);
   const uint32_t tid = threadIdx.x;
   // Workgroups are dealt to the 8 XCDs round-robin, each XCD with its own L2: give every XCD a contiguous
   // run of tiles, so that the rows of neighbouring tiles (which share cache lines at their seams) meet in one L2.
@@ -591,22 +597,26 @@ void hawk_launch_ref_bits(hipStream_t st, const HapSetDev& hs, const ScanParams&
   hipLaunchKernelGGL(k_ref_bits, dim3(nb), dim3(HAWK_BLOCK), 0, st, hs, p, ri, bitsF, bitsR);
 }
 
+// the end of an interval no kernel of ours follows on its stream (hawk_stamp, hawk_device.h)
+__global__ void k_stamp(unsigned long long* slot) { hawk_stamp(slot); }
+void hawk_launch_stamp(hipStream_t st, unsigned long long* slot) { hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, st, slot); }
+
 void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const ScanParams& p, const GuideParams& gp,
                         const RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, unsigned long long* shards,
                         const uint64_t* offsets, GuideCols out, int* status, uint32_t* lists, uint32_t* big_count,
-                        unsigned long long* big_list, hipEvent_t mid, uint32_t n_tiles) {
+                        unsigned long long* big_list, uint32_t n_tiles, unsigned long long* stamp, unsigned long long* stamp_mid) {
   const uint32_t ntile = n_tiles == 0xffffffffu ? hs.n_hap * p.bph : n_tiles;  // a plan view: the REF row's tiles only
-  if (!ntile) { if (pass == 1 && mid) (void)hipEventRecord(mid, st); return; }
+  if (!ntile) return;
   const dim3 grid(ntile), block(HAWK_BLOCK);
   if (pass == 0) {
-    hipLaunchKernelGGL(k_search_count, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, shards, status, lists, big_count, big_list);
+    hipLaunchKernelGGL(k_search_count, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, shards, status, lists, big_count, big_list, stamp);
   } else {
     // small tiles are assembled from their hand-over lists, the named big ones recompute
-    hipLaunchKernelGGL(k_emit_list, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, lists, out, status);
-    if (mid) (void)hipEventRecord(mid, st);  // timing: k_emit_list ends here
+    hipLaunchKernelGGL(k_emit_list, grid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, lists, out, status, stamp);
     // a walk over the work list (<= 128 entries per REF tile, usually ~8; one per other big tile)
     const dim3 egrid(ntile * 8u < 2048u ? ntile * 8u : 2048u);
-    hipLaunchKernelGGL(k_search_emit, egrid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, out, status, lists, big_count, big_list);
+    hipLaunchKernelGGL(k_search_emit, egrid, block, 0, st, hs, p, gp, ri, tmeta, counts, offsets, out, status, lists, big_count, big_list,
+                       stamp_mid);  // timing: k_emit_list ends where this kernel begins
   }
 }
 
@@ -619,8 +629,9 @@ void hawk_launch_search(hipStream_t st, int pass, const HapSetDev& hs, const Sca
 #define MS_TILE 1024  // entries per workgroup (4 per thread)
 
 __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1(const uint32_t* __restrict__ counts, uint64_t n,
-                                                        unsigned long long* __restrict__ partial) {
+                                                        unsigned long long* __restrict__ partial, unsigned long long* stamp) {
   __shared__ unsigned long long s_sum;
+  hawk_stamp(stamp);
   if (threadIdx.x == 0) s_sum = 0;
   __syncthreads();
   const uint64_t i0 = (uint64_t)blockIdx.x * MS_TILE + threadIdx.x * 4;
@@ -729,9 +740,10 @@ __global__ __launch_bounds__(HAWK_BLOCK) void k_mscan23(const uint32_t* __restri
 // workgroup - were tried: 25 us of dependent loads against 14 us for the two-launch scan.)
 __global__ __launch_bounds__(1024) void k_mscan_one(const uint32_t* __restrict__ counts, uint32_t n, uint32_t ipt,
                                                      const unsigned long long* __restrict__ shards, uint64_t* __restrict__ offsets,
-                                                     ScanTotals* __restrict__ totals) {
+                                                     ScanTotals* __restrict__ totals, unsigned long long* stamp) {
   __shared__ uint32_t s_w[1024 / WAVE];
   __shared__ unsigned long long s_aux[2];
+  hawk_stamp(stamp);
   const uint32_t t = threadIdx.x;
   if (t < 2) s_aux[t] = 0;
   const uint32_t i0 = t * ipt, i1 = i0 + ipt < n ? i0 + ipt : n;
@@ -758,8 +770,10 @@ __global__ __launch_bounds__(1024) void k_mscan_one(const uint32_t* __restrict__
 // instances of a plan view (hawk_csearch.hip): the single-workgroup scan of k_mscan2 in between would cost more than both.
 #define MSW_IPT 16
 #define MSW_TILE (HAWK_BLOCK * MSW_IPT)
-__global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1w(const uint32_t* __restrict__ counts, uint64_t n, unsigned long long* __restrict__ partial) {
+__global__ __launch_bounds__(HAWK_BLOCK) void k_mscan1w(const uint32_t* __restrict__ counts, uint64_t n, unsigned long long* __restrict__ partial,
+                                                         unsigned long long* stamp) {
   __shared__ unsigned long long s_sum;
+  hawk_stamp(stamp);
   if (threadIdx.x == 0) s_sum = 0;
   __syncthreads();
   const uint64_t i0 = (uint64_t)blockIdx.x * MSW_TILE + threadIdx.x * MSW_IPT;
@@ -842,26 +856,26 @@ int hawk_mscan_route(uint64_t n, bool shards, bool aligned) {
 // groups to those, and the collapse by templates calls only when there are distinct clusters.  With n == 0 and no shard sums the
 // grids below would have 0 workgroups, which is not a launch.
 void hawk_launch_mscan(hipStream_t st, const uint32_t* counts, uint64_t n, unsigned long long* partial,
-                       const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals) {
+                       const unsigned long long* shards, uint64_t* offsets, ScanTotals* totals, unsigned long long* stamp) {
   const bool aligned = (reinterpret_cast<uintptr_t>(counts) & 15) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 15) == 0;
   const uint32_t nb = (uint32_t)((n + MS_TILE - 1) / MS_TILE);
   const uint32_t nbw = (uint32_t)((n + MSW_TILE - 1) / MSW_TILE);
   switch (hawk_mscan_route(n, shards != nullptr, aligned)) {
     case HAWK_MSCAN_ONE: {
       const uint32_t ipt = (uint32_t)((n + 1023) / 1024);
-      hipLaunchKernelGGL(k_mscan_one, dim3(1), dim3(1024), 0, st, counts, (uint32_t)n, ipt ? ipt : 1u, shards, offsets, totals);
+      hipLaunchKernelGGL(k_mscan_one, dim3(1), dim3(1024), 0, st, counts, (uint32_t)n, ipt ? ipt : 1u, shards, offsets, totals, stamp);
       return;
     }
     case HAWK_MSCAN_WIDE:
-      hipLaunchKernelGGL(k_mscan1w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan1w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial, stamp);
       hipLaunchKernelGGL(k_mscan23w, dim3(nbw), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nbw, shards, offsets, totals);
       return;
     case HAWK_MSCAN_M1_M23:
-      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, stamp);
       hipLaunchKernelGGL(k_mscan23, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, nb, shards, offsets, totals);
       return;
     default:  // HAWK_MSCAN_M1_M2_M3
-      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial);
+      hipLaunchKernelGGL(k_mscan1, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, stamp);
       hipLaunchKernelGGL(k_mscan2, dim3(1), dim3(1024), 0, st, partial, (uint64_t)nb, shards, totals);
       hipLaunchKernelGGL(k_mscan3, dim3(nb), dim3(HAWK_BLOCK), 0, st, counts, n, partial, offsets);
   }

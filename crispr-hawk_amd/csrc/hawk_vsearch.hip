@@ -29,7 +29,8 @@ template <int PASS>
 __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, ScanParams p, GuideParams gp, RefInfo ri,
                                                        const TileMeta* __restrict__ tmeta, uint32_t* __restrict__ counts,
                                                        uint32_t* __restrict__ counts0, unsigned long long* __restrict__ shards,
-                                                       const uint64_t* __restrict__ offsets, GuideCols out, int* status, uint32_t tile0) {
+                                                       const uint64_t* __restrict__ offsets, GuideCols out, int* status, uint32_t tile0,
+                                                       unsigned long long* stamp) {
   __shared__ HxVar s_v[VC_MAXV];
   __shared__ uint32_t s_str[5][3][VC_SLOTS];  // the slots' 96-bit strings: position 32 w - PAD + i at bit i
   __shared__ uint32_t s_kw[2][VC_SLOTS];      // kept window starts of the slot's word, per strand
@@ -44,6 +45,7 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
   __shared__ uint32_t s_red[VC_BLOCK / WAVE][4];
   __shared__ uint32_t s_n;
   const uint32_t tid = threadIdx.x;
+  hawk_stamp(stamp);
   const HxVar* __restrict__ vrecs = static_cast<const HxVar*>(va.recs_);
   const HxTile* __restrict__ vtiles = static_cast<const HxTile*>(va.tiles_);
   uint32_t tile = tile0 + blockIdx.x;
@@ -353,12 +355,13 @@ __global__ __launch_bounds__(VC_BLOCK) void k_vsearch(HapSetDev hs, VcArgs va, S
 
 void hawk_launch_vsearch(hipStream_t st, int pass, const HapSetDev& hs, const VcArgs& va, const ScanParams& p, const GuideParams& gp,
                          const RefInfo& ri, const TileMeta* tmeta, uint32_t* counts, uint32_t* counts0, unsigned long long* shards,
-                         const uint64_t* offsets, GuideCols out, int* status, uint32_t tile0, uint32_t n_tiles) {
-  if (!n_tiles) return;
+                         const uint64_t* offsets, GuideCols out, int* status, uint32_t tile0, uint32_t n_tiles,
+                         unsigned long long* stamp) {
+  if (!n_tiles) { if (stamp) hawk_launch_stamp(st, stamp); return; }
   if (pass == 0)
-    hipLaunchKernelGGL(k_vsearch<0>, dim3(n_tiles), dim3(VC_BLOCK), 0, st, hs, va, p, gp, ri, tmeta, counts, counts0, shards, offsets, out, status, tile0);
+    hipLaunchKernelGGL(k_vsearch<0>, dim3(n_tiles), dim3(VC_BLOCK), 0, st, hs, va, p, gp, ri, tmeta, counts, counts0, shards, offsets, out, status, tile0, stamp);
   else
-    hipLaunchKernelGGL(k_vsearch<1>, dim3(n_tiles), dim3(VC_BLOCK), 0, st, hs, va, p, gp, ri, tmeta, counts, counts0, shards, offsets, out, status, tile0);
+    hipLaunchKernelGGL(k_vsearch<1>, dim3(n_tiles), dim3(VC_BLOCK), 0, st, hs, va, p, gp, ri, tmeta, counts, counts0, shards, offsets, out, status, tile0, stamp);
 }
 
 
