@@ -44,6 +44,8 @@ EXPORTS = [
     "hawk_host_effects", "hawk_host_round4",
     "hawk_table_resolve_unphased", "hawk_resolve_download", "hawk_resolve_free", "hawk_host_resolve_unphased",
     "hawk_resolve_groups", "hawk_ugroups_download", "hawk_ugroups_free", "hawk_host_unphased_groups",
+    "hawk_gt_parse_unphased", "hawk_ubuild_lists", "hawk_ubuild_lists_download", "hawk_ubuild_signatures", "hawk_ubuild_fill", "hawk_ubuild_free",
+    "hawk_hapset_pack_ascii_rows", "hawk_host_unphased_rows",
     "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
 ]
 
@@ -154,6 +156,38 @@ class UgroupsTiming(C.Structure):
                 ("n_members", C.c_uint64)]
 
 
+class UbuildInput(C.Structure):
+    _fields_ = [("codes", C.c_void_p), ("n_lines", C.c_uint64), ("n_samples", C.c_uint32), ("n_var", C.c_uint32), ("var_line", C.c_void_p),
+                ("var_allele", C.c_void_p), ("var_off", C.c_void_p), ("var_mask", C.c_void_p), ("var_ref", C.c_void_p), ("ref", C.c_void_p),
+                ("ref_len", C.c_uint32), ("row_base", C.c_uint32)]
+
+
+class UbuildRows(C.Structure):
+    _fields_ = [("row_cap", C.c_uint64), ("entry_cap", C.c_uint64), ("seqs", C.c_void_p), ("member_off", C.c_void_p), ("member_sample", C.c_void_p),
+                ("sample_off", C.c_void_p), ("list_idx", C.c_void_p), ("sig", C.c_void_p), ("al_key", C.c_void_p), ("al_off", C.c_void_p),
+                ("al_ref", C.c_void_p), ("n_rows", C.c_uint64), ("n_members", C.c_uint64), ("n_entries", C.c_uint64), ("n_keys", C.c_uint64)]
+
+
+class UbuildDecline(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("reserved", C.c_int32), ("var", C.c_int64)]
+
+
+UBUILD_REASONS = {1: "a genotype column that is not two '/'-separated allele numbers, or a record without one column per sample",
+                  2: "an equal-length allele longer than one base", 3: "an alt or ref base outside A/C/G/T",
+                  4: "the reference sequence does not hold the record's ref base", 5: "an SNV outside the region",
+                  6: "more than 2^32 - 1 carried-variant entries",
+                  7: "a sample carries an alt twice at one position (the host builder's IUPAC encoding fails there)"}
+
+
+class UnphasedBuildDeclined(Exception):
+    """workload.expand_unphased_from_vcf declined (include/hawk.h: HAWK_UBUILD_*): the caller builds the interval's haplotypes on
+    the host, which raises what the reference raises, or succeeds."""
+
+    def __init__(self, reason: int, detail: str = ""):
+        self.reason = reason
+        super().__init__(f"{UBUILD_REASONS.get(reason, 'the fixed columns of a record')}{' (' + detail + ')' if detail else ''}")
+
+
 RESOLVE_REASONS = {1: "an ambiguous position without allele entries", 2: "more than one haplotype flagged REF",
                    3: "a REF row with more than one combination", 4: "a row of more than 2^32 - 1 combinations",
                    5: "a row whose kept guides do not fit the batch budget"}
@@ -204,6 +238,7 @@ def lib() -> C.CDLL:
         L.hawk_effects_free.restype = None
         L.hawk_resolve_free.restype = None
         L.hawk_ugroups_free.restype = None
+        L.hawk_ubuild_free.restype = None
         L.hawk_plm_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:

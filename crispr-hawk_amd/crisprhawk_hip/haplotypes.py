@@ -148,9 +148,23 @@ def add_variants_unphased(haplotypes: List[Haplotype], region: Region, samples: 
     snvs = [v for v in alleles if v.vtype[0] == VTYPES[0]]
     if snvs:
         haplotypes.extend(_unphased_set(_Stretch.whole(region), _deal(snvs, samples, (0,)), phased, debug))
+    haplotypes.extend(unphased_indel_windows(region, [v for v in alleles if v.vtype[0] != VTYPES[0]], snvs, phased, debug))
+    return haplotypes
+
+
+def indel_in_region(region: Region, indel: VariantRecord) -> bool:
     c = region.coordinates
-    for indel in (v for v in alleles if v.vtype[0] != VTYPES[0]):
-        if not c.startp <= indel.position < c.stopp:
+    return c.startp <= indel.position < c.stopp
+
+
+def unphased_indel_windows(region: Region, indels: Seq[VariantRecord], snvs: Seq[VariantRecord], phased: bool, debug: bool) -> List[Haplotype]:
+    """The short haplotypes of add_variants_unphased: per indel allele inside the region (in the order given) the region cut to
+    100 nt around it, built for the indel's carriers from the indel and those of `snvs` (biallelic SNV records, in file order)
+    that lie inside the window.  SNVs outside every window change nothing: the device builder of the whole-region rows
+    (workload.expand_unphased_from_vcf) hands over the ones inside alone."""
+    haplotypes: List[Haplotype] = []
+    for indel in indels:
+        if not indel_in_region(region, indel):
             continue
         carriers = set(indel.samples[0][0]) if len(indel.samples) else set()
         if not carriers:

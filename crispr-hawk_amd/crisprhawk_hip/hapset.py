@@ -107,6 +107,33 @@ class DeviceHapSet:
         self.stride = s.value
         return self
 
+    @classmethod
+    def allocate(cls, hap_len: np.ndarray, device: Optional[int] = None) -> "DeviceHapSet":
+        """A set of rows of the given lengths with zeroed planes and no metadata yet: the caller fills the rows (pack_rows, the
+        unphased row builder of workload.expand_unphased_from_vcf) and calls set_meta."""
+        hap_len = np.ascontiguousarray(hap_len, dtype=np.uint32)
+        if len(hap_len) == 0:
+            raise ValueError("empty haplotype set")
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().hawk_hapset_create(_lib.context(device), len(hap_len), _p(hap_len), C.byref(handle)), "hawk_hapset_create")
+        return cls.from_handle(handle, hap_len, device)
+
+    def pack_rows(self, first_row: int, seqs: Sequence) -> None:
+        """hawk_hapset_pack_ascii_rows: cased ASCII into rows first_row .. first_row + len(seqs) - 1, the other rows untouched"""
+        if not len(seqs):
+            return
+        arrs = [_as_u8(s) for s in seqs]
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+        blob = np.ascontiguousarray(np.concatenate(arrs)) if len(arrs) > 1 else np.ascontiguousarray(arrs[0])
+        bad = C.c_uint64(0)
+        rc = self._L.hawk_hapset_pack_ascii_rows(self._h, int(first_row), len(arrs), _p(blob), _p(off), C.byref(bad))
+        if rc == _lib.HAWK_E_IUPAC:
+            hidx = int(np.searchsorted(off, bad.value, side="right") - 1)
+            raise _lib.HawkStatusError(rc, "hawk_hapset_pack_ascii_rows", f"haplotype {first_row + hidx} position {bad.value - int(off[hidx])} "
+                                                                          f"({bytes(blob[bad.value:bad.value + 1])!r})")
+        _lib.check(rc, "hawk_hapset_pack_ascii_rows")
+
     def __init__(self, haps: Sequence[HostHaplotype], device: Optional[int] = None):
         L = _lib.lib()
         self._ctx = _lib.context(device)

@@ -124,7 +124,7 @@ UNPHASED_REPORTS = (None, "groups", "objects")
 
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
                        ot=None, ann=None, lap=None, tables=None, unphased_engine=None, unphased_report=None, azimuth_model=None,
-                       deepcpf1_weights=None, plm_on=False, fx=None) -> str:
+                       deepcpf1_weights=None, plm_on=False, fx=None, unphased_haplotypes="host", device=None) -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows; their
     windows resolved on the device table, search_guides.search's `unphased_engine`) and the fallback for phased records the device expansion
@@ -146,7 +146,9 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
     only): the "groups" route keeps its groups in HBM and runs the variant-effect stage on them (_interval_effects, as
     _finish_interval does on a collapsed table).  Nothing else can serve the stage: "objects", the host engine, a resolution
     that declines or refuses are then a ValueError naming `graphical_reports`, raised before any file of the interval is written.
-    The phased fallback never receives `fx`: there the stage stays a ValueError (_search_intervals)."""
+    The phased fallback never receives `fx`: there the stage stays a ValueError (_search_intervals).
+    `unphased_haplotypes="device"` (unphased intervals): the whole-region rows are built on the device first (_unphased_device_built);
+    where that route does not apply or declines, the interval is built here as if it had not been asked for."""
     if unphased_report not in UNPHASED_REPORTS:
         raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
     mode = unphased_report or os.environ.get("HAWK_UNPHASED_REPORT") or "groups"
@@ -156,6 +158,11 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
     if fx is not None and (mode != "groups" or engine == "host"):
         why = f"unphased_report={mode!r} builds Guide objects" if mode != "groups" else "the host engine was asked for (unphased_engine / HAWK_UNPHASED_ENGINE)"
         raise ValueError(f"graphical_reports / candidate_guides on an unphased interval rank the report groups in device memory: {why}")
+    if unphased_haplotypes == "device" and not phased:
+        path = _unphased_device_built(coord, seq, vcf, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, tables, mode, engine,
+                                      azimuth_model, deepcpf1_weights, plm_on, fx, device)
+        if path is not None:
+            return path
     from . import haplotypes as hap_mod
     from .annotation import reverse_guides
     from .haplotype import Haplotype
@@ -217,16 +224,58 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
     return path
 
 
+UNPHASED_HAPLOTYPES = (None, "host", "device")
+HOST_BUILT_LAP = "host-built route: unphased haplotypes built on the host"
+DEVICE_BUILT_LAP = "host-built route: unphased haplotypes built on the device"
+
+
+def _unphased_device_built(coord, seq: str, vcf, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool, ot, ann, lap, tables,
+                           mode: str, engine: str, azimuth_model, deepcpf1_weights, plm_on, fx, device) -> Optional[str]:
+    """An unphased interval with its whole-region rows built on the device (workload.expand_unphased_from_vcf) and the "groups"
+    report made from that set, its labels and its allele table: no VariantRecord per line, no string per carrier.  None - with a
+    line at verbosity level 3 that says why - where the route does not apply ("objects", the host engine, haplotype_table=True
+    whose writer wants the strings), where the builder declines, and where the resolution declines or refuses: the caller then
+    builds the interval on the host, which raises or succeeds as it always has.  An interval without records is the caller's too."""
+    from ._lib import UnphasedBuildDeclined
+    from .workload import expand_unphased_from_vcf
+    why = None
+    if mode != "groups":
+        why = f"unphased_report={mode!r} builds Guide objects from Haplotype objects"
+    elif engine == "host":
+        why = "the host engine was asked for (unphased_engine / HAWK_UNPHASED_ENGINE)"
+    elif tables is not None:
+        why = "haplotype_table=True writes the table from the host-built strings"
+    if why is not None:
+        print_verbosity(f"Unphased haplotypes built on the host: {why}", 0, VERBOSITYLVL[3])
+        return None
+    blk = vcf.fetch_block(coord)
+    if len(blk) == 0:
+        return None
+    try:
+        built = expand_unphased_from_vcf(seq, coord.start, coord.stop, blk, vcf.samples, len(pam), device, coord=coord, debug=debug)
+    except UnphasedBuildDeclined as e:
+        print_verbosity(f"Unphased haplotypes built on the host: the device builder declined: {e}", 0, VERBOSITYLVL[3])
+        return None
+    return _unphased_groups_report(coord, None, None, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, azimuth_model, deepcpf1_weights,
+                                   plm_on, fx, None, built=built)
+
+
 def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool, ot, ann, lap,
-                            azimuth_model, deepcpf1_weights, plm_on, fx=None, before_files=None) -> Optional[str]:
+                            azimuth_model, deepcpf1_weights, plm_on, fx=None, before_files=None, built=None) -> Optional[str]:
     """_search_host_built's "groups" route from the built haplotypes to the report file; None: the device declined or refused
     and the caller takes the object route.  With `fx` the groups stay in HBM for the variant-effect stage, a decline or refusal
-    is a ValueError, and `before_files()` runs once the groups are made, ahead of the interval's first file."""
+    is a ValueError, and `before_files()` runs once the groups are made, ahead of the interval's first file.
+    `built` (in place of `region` and `haps`): what workload.expand_unphased_from_vcf returned - the set is searched as it lies,
+    the resolution reads its allele table and the report its row labels."""
     from ._lib import HawkStatusError
     from .search_guides import _device_set
     lap = lap or (lambda stage: None)
-    lap("host-built route: unphased haplotypes built on the host")
-    ds = _device_set(region, haps, len(pam))
+    if built is not None:
+        lap(DEVICE_BUILT_LAP)
+        ds, row_labels, haps = built[0], built[1], built[2]  # (`haps`: what resolve_unphased_groups reads, here the allele table)
+    else:
+        lap(HOST_BUILT_LAP)
+        ds, row_labels = _device_set(region, haps, len(pam)), haps
     try:
         tab = ds.search(pam.bits, pam.bitsrc, len(pam), guidelen, right, download=False)
         azimuth_on = pam.cas_system in (SPCAS9, XCAS9) and azimuth_model is not None
@@ -251,7 +300,7 @@ def _unphased_groups_report(coord, region, haps, pam: PAM, guidelen: int, right:
         if before_files is not None:
             before_files()
         bed_start, bed_stop = coord.start + PADDING, coord.stop - PADDING
-        labels = reports.HapLabels.from_objects(haps)
+        labels = reports.HapLabels.from_objects(row_labels)
         cols, order, plain, scores = _group_report_columns(coord, groups, labels, is_ref_hap, pam, guidelen, right, outdir, mm is not None, debug, ot,
                                                            ann, azimuth_on, deepcpf1_on, plm_on, bed_start, bed_stop, lap)
         if fx is not None:
@@ -306,6 +355,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                  graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
                  unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, unphased_effects: bool = False,
+                 unphased_haplotypes: Optional[str] = None,
                  annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
@@ -355,10 +405,23 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     report groups on the device and writes the report through the phased route's column writer - no Guide object, and the
     model-score columns (`azimuth_model`, `deepcpf1_weights`, `plmcrispr_model`) are filled as in a phased report; "objects" is
     the route over Guide objects and pandas, whose model-score columns say NA (_search_host_built).  `unphased_engine` as
-    search_guides.search takes it; "host" implies the object route.  (Everything from `timings` on is meant to be passed by
-    keyword.)"""
+    search_guides.search takes it; "host" implies the object route.
+    `unphased_haplotypes` (unphased VCFs; None reads HAWK_UNPHASED_HAPLOTYPES, else "host"): "host" builds every haplotype of an
+    interval in Python (haplotypes.add_variants_unphased); "device" builds the whole-region SNV rows from the genotype text on
+    the device (workload.expand_unphased_from_vcf; the indel windows stay on the host builder) for an interval with records on
+    the "groups" route with the device engine - `unphased_effects=True` works on top of it - and writes the same files.
+    "objects", the host engine and `haplotype_table=True` (whose writer wants the strings) build that interval on the host, as
+    does an interval the device builder declines (a malformed or haploid genotype, a multi-base substitution, a base outside
+    A/C/G/T, a ref base the sequence does not hold, an SNV outside the region, an alt one sample carries twice at a position):
+    the host builder then raises or succeeds exactly as under "host".  A line at verbosity level 3 says why.  (Everything from
+    `timings` on is meant to be passed by keyword.)"""
     if unphased_report not in UNPHASED_REPORTS:
         raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
+    if unphased_haplotypes not in UNPHASED_HAPLOTYPES:
+        raise ValueError(f"unphased_haplotypes {unphased_haplotypes!r}: None, 'host' or 'device'")
+    builder = unphased_haplotypes or os.environ.get("HAWK_UNPHASED_HAPLOTYPES") or "host"
+    if builder not in ("host", "device"):
+        raise ValueError(f"HAWK_UNPHASED_HAPLOTYPES={builder!r}: 'host' or 'device'")
     import time as _time
     check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
@@ -426,7 +489,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
                                  ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on, unphased_report, unphased_engine,
-                                 bool(unphased_effects))
+                                 bool(unphased_effects), builder)
     finally:
         if ann is not None:
             ann.close()
@@ -434,7 +497,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
                       deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False, unphased_report=None, unphased_engine=None,
-                      unphased_effects=False) -> Dict[str, str]:
+                      unphased_effects=False, unphased_haplotypes="host") -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
     stage_on = fx is not None and (fx["on"] or bool(fx["cgs"]))
 
@@ -453,7 +516,7 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
                 no_table(True)
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
                                                    pt if score else None, debug, ot, ann, lap, tables, unphased_engine, unphased_report,
-                                                   azimuth_model, deepcpf1_weights, plm_on, fx if stage_on else None)
+                                                   azimuth_model, deepcpf1_weights, plm_on, fx if stage_on else None, unphased_haplotypes, device)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])

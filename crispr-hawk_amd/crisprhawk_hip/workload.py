@@ -634,7 +634,8 @@ def expand_from_vcf(region_seq: str, startp: int, stopp: int, block, samples: Li
     from . import _lib
     from .hapset import _p
     if not phased:
-        raise ValueError("expand_from_vcf builds phased haplotypes; unphased VCFs go through haplotypes.py")
+        raise ValueError("expand_from_vcf builds phased haplotypes; the rows of an unphased VCF are built by expand_unphased_from_vcf "
+                         "(or on the host, haplotypes.add_variants_unphased)")
     ref_set = _ref_only_set(region_seq, startp, stopp, pamlen, device)
     vt = VcfVariants(block)
     if len(vt) == 0:
@@ -683,6 +684,296 @@ class RowLabel:
 
     def __init__(self, samples: str, variants: str, afs, hid: str, segments):
         self.samples, self.variants, self.afs, self.id, self.segments = samples, variants, afs, hid, segments
+
+
+_BASE_IDX = np.full(256, 255, dtype=np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    _BASE_IDX[_c] = _i
+
+
+def unphased_snv_table(block, vt: "VcfVariants", region_len: int, startp: int):
+    """The SNV alleles of a block, in `vt`'s order, as the arrays hawk_ubuild_lists takes: (indices into vt, var_line, var_allele,
+    var_off, var_mask, var_ref).  Raises _lib.UnphasedBuildDeclined for what the device builder does not take: an equal-length
+    allele longer than one base (the host builder reads its first base), a base outside A/C/G/T, an SNV outside the region."""
+    from ._lib import UnphasedBuildDeclined
+    n = len(vt)
+    snv = np.zeros(n, dtype=bool)
+    for j in range(n):
+        f = block.fixed[int(vt.line[j])]
+        raw_alt = f[4] if vt.allele[j] == 1 and "," not in f[4] else f[4].split(",")[int(vt.allele[j]) - 1]
+        if len(f[3]) == len(raw_alt):
+            if len(raw_alt) != 1:
+                raise UnphasedBuildDeclined(2, vt.id[j])
+            snv[j] = True
+    sel = np.flatnonzero(snv)
+    refb = _BASE_IDX[np.frombuffer("".join(vt.ref[int(j)] for j in sel).encode("latin-1", "replace"), dtype=np.uint8)] if len(sel) else np.zeros(0, np.uint8)
+    altb = _BASE_IDX[np.frombuffer("".join(vt.alt[int(j)] for j in sel).encode("latin-1", "replace"), dtype=np.uint8)] if len(sel) else np.zeros(0, np.uint8)
+    bad = np.flatnonzero((refb > 3) | (altb > 3))
+    if len(bad):
+        raise UnphasedBuildDeclined(3, vt.id[int(sel[bad[0]])])
+    off = vt.pos[sel] - int(startp)
+    out = np.flatnonzero((off < 0) | (off >= region_len))
+    if len(out):
+        raise UnphasedBuildDeclined(5, vt.id[int(sel[out[0]])])
+    return (sel, np.ascontiguousarray(vt.line[sel], dtype=np.uint32), np.ascontiguousarray(vt.allele[sel], dtype=np.uint8),
+            np.ascontiguousarray(off, dtype=np.uint32), (np.uint8(1) << altb).astype(np.uint8), np.ascontiguousarray(refb, dtype=np.uint8))
+
+
+def _merged_sites(pos: np.ndarray, bits: np.ndarray):
+    """an ascending entry list -> its sites: distinct positions, the entries' bits OR-ed"""
+    first = np.flatnonzero(np.concatenate(([True], pos[1:] != pos[:-1])))
+    return pos[first], np.bitwise_or.reduceat(bits, first)
+
+
+def group_unphased_rows(sample_off: np.ndarray, idx: np.ndarray, sig: np.ndarray, var_off: np.ndarray, var_mask: np.ndarray, var_ref: np.ndarray):
+    """Carriers grouped into distinct rows (_merge_equal on the rows they would give): samples sharing a 128-bit signature are
+    compared site for site - the signature only proposes - and a sample that differs from every row with its signature opens a
+    row of its own.  -> [[sample, ...]] in first-carrier order, members ascending."""
+    e_pos = var_off[idx]
+    e_bits = var_mask[idx] | (np.uint8(1) << var_ref[idx])
+    so = sample_off.astype(np.int64)
+    sites = lambda s: _merged_sites(e_pos[so[s]:so[s + 1]], e_bits[so[s]:so[s + 1]])
+    rows: List[List[int]] = []
+    by_sig: Dict[Tuple[int, int], List[int]] = {}
+    head_sites = {}
+    for s in np.flatnonzero(np.diff(so) > 0).tolist():
+        mine = None
+        found = None
+        for k in by_sig.get((int(sig[s, 0]), int(sig[s, 1])), ()):
+            h = rows[k][0]
+            if np.array_equal(idx[so[h]:so[h + 1]], idx[so[s]:so[s + 1]]):
+                found = k
+                break
+            mine = sites(s) if mine is None else mine
+            if k not in head_sites:
+                head_sites[k] = sites(h)
+            if np.array_equal(mine[0], head_sites[k][0]) and np.array_equal(mine[1], head_sites[k][1]):
+                found = k
+                break
+        if found is None:
+            by_sig.setdefault((int(sig[s, 0]), int(sig[s, 1])), []).append(len(rows))
+            rows.append([s])
+        else:
+            rows[found].append(s)
+    return rows
+
+
+def unphased_snv_labels(groups, sample_off: np.ndarray, idx: np.ndarray, sel: np.ndarray, vt: "VcfVariants", samples: List[str], segments,
+                        row_base: int) -> List["RowLabel"]:
+    """The labels _merge_equal gives the distinct whole-region rows: samples and variants as sorted unions over the members (a
+    member's `variants` is the id list of what it carries, in list order), afs of the first member, `hap_%08d` by row index."""
+    so = sample_off.astype(np.int64)
+    out = []
+    for k, members in enumerate(groups):
+        head = idx[so[members[0]]:so[members[0] + 1]]
+        strings = {",".join(vt.id[int(sel[j])] for j in head.tolist())}
+        for s in members[1:]:
+            mine = idx[so[s]:so[s + 1]]
+            if not np.array_equal(mine, head):
+                strings.add(",".join(vt.id[int(sel[j])] for j in mine.tolist()))
+        afs = {vt.id[int(sel[j])]: vt.af[int(sel[j])] for j in head.tolist()}
+        out.append(RowLabel(",".join(sorted({samples[s] for s in members})), ",".join(sorted(strings)), afs, f"hap_{row_base + k:08d}", segments))
+    return out
+
+
+def unphased_snv_alleles(groups, sample_off: np.ndarray, idx: np.ndarray, v_off: np.ndarray, v_ref: np.ndarray, row_base: int):
+    """The allele table of the distinct whole-region rows in search_guides.flatten_variant_alleles' format: one key per carried
+    position of a row's first member (row << 32 | offset), one entry per carried allele there, its ref's index in "ACGT"."""
+    if not groups:
+        return np.zeros(0, np.uint64), np.zeros(1, np.uint32), np.zeros(0, np.uint8)
+    so = sample_off.astype(np.int64)
+    heads = [idx[so[m[0]]:so[m[0] + 1]] for m in groups]
+    j = np.concatenate(heads).astype(np.int64)
+    rows = np.repeat(np.arange(row_base, row_base + len(groups), dtype=np.uint64), [len(h) for h in heads])
+    e_key = (rows << np.uint64(32)) | v_off[j].astype(np.uint64)
+    first = np.flatnonzero(np.concatenate(([True], e_key[1:] != e_key[:-1])))
+    return e_key[first], np.concatenate((first, [len(e_key)])).astype(np.uint32), v_ref[j].astype(np.uint8)
+
+
+def unphased_rows_host(region_seq: str, startp: int, block, samples: List[str], codes: np.ndarray):
+    """The distinct whole-region rows of an unphased block by the host twin (hawk_host_unphased_rows; no device): `codes` =
+    the block's allele codes [n_lines][2 * n_samples] as hawk_gt_parse_unphased gives them.  -> (row strings, [RowLabel] with
+    ids from hap_00000001, the rows' allele table, the twin's per-sample lists (sample_off, idx), signatures, member lists).
+    Raises _lib.UnphasedBuildDeclined as expand_unphased_from_vcf does."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import UnphasedBuildDeclined
+    from .hapset import _p
+    vt = VcfVariants(block)
+    ref = np.frombuffer(region_seq.upper().encode("ascii"), dtype=np.uint8)
+    sel, v_line, v_allele, v_off, v_mask, v_ref = unphased_snv_table(block, vt, len(ref), startp)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ns = len(samples)
+    inp = _lib.UbuildInput(codes.ctypes.data, len(block), ns, len(sel), v_line.ctypes.data, v_allele.ctypes.data, v_off.ctypes.data,
+                           v_mask.ctypes.data, v_ref.ctypes.data, ref.ctypes.data, len(ref), 1)
+    out, dec = _lib.UbuildRows(), _lib.UbuildDecline()
+    L = _lib.lib()
+
+    def call():
+        rc = L.hawk_host_unphased_rows(C.byref(inp), C.byref(out), C.byref(dec))
+        if rc != _lib.HAWK_OK and dec.reason:
+            raise UnphasedBuildDeclined(dec.reason, vt.id[int(sel[dec.var])] if dec.var >= 0 else "")
+        _lib.check(rc, "hawk_host_unphased_rows")
+    call()  # the counts; then buffers of exactly their size
+    nr, ne = int(out.n_rows), int(out.n_entries)
+    seqs = np.zeros(nr * len(ref), np.uint8); member_off = np.zeros(nr + 1, np.uint32); member = np.zeros(int(out.n_members), np.uint32)
+    sample_off = np.zeros(ns + 1, np.uint64); idx = np.zeros(ne, np.uint32); sig = np.zeros((ns, 2), np.uint64)
+    out.row_cap, out.entry_cap = nr, ne
+    out.seqs, out.member_off, out.member_sample = seqs.ctypes.data, member_off.ctypes.data, member.ctypes.data
+    out.sample_off, out.list_idx, out.sig = sample_off.ctypes.data, idx.ctypes.data, sig.ctypes.data
+    call()
+    groups = [member[int(member_off[k]):int(member_off[k + 1])].tolist() for k in range(nr)]
+    so = sample_off.astype(np.int64)
+    n_al = int(sum(so[m[0] + 1] - so[m[0]] for m in groups))
+    al_key = np.zeros(int(out.n_keys), np.uint64); al_off = np.zeros(int(out.n_keys) + 1, np.uint32); al_ref = np.zeros(n_al, np.uint8)
+    out.seqs = out.member_off = out.member_sample = out.sample_off = out.list_idx = out.sig = None
+    out.entry_cap = n_al
+    out.al_key, out.al_off, out.al_ref = al_key.ctypes.data, al_off.ctypes.data, al_ref.ctypes.data
+    call()
+    rows = [seqs[k * len(ref):(k + 1) * len(ref)].tobytes().decode("ascii") for k in range(nr)]
+    labels = unphased_snv_labels(groups, sample_off, idx, sel, vt, samples, PosSegments.identity(int(startp), len(ref)), 1)
+    return rows, labels, (al_key, al_off, al_ref), (sample_off, idx), sig, groups
+
+
+def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, samples: List[str], pamlen: int, device: Optional[int] = None,
+                             coord=None, debug: bool = True):
+    """The haplotype set of an unphased interval with its whole-region rows built on the device: what
+    search_guides._device_set(region, haplotypes.add_variants_unphased(...), pamlen) holds, row for row - REF, then one IUPAC row
+    per distinct carrier of SNVs (hawk_gt_parse_unphased -> hawk_ubuild_lists -> hawk_ubuild_signatures -> hawk_ubuild_fill: no
+    row ever exists as text), then the indel-window rows, which stay on the host builder (haplotypes.unphased_indel_windows on the
+    records of the indels and of the SNVs inside their windows alone) and are packed into the same set.
+    `coord`: the interval's Coordinate (default: Coordinate(contig of the block, startp, stopp, 0)).
+    Returns (DeviceHapSet with is_ref / ref_index set, [RowLabel] per row, the rows' allele table (key, off, ref) in
+    search_guides.flatten_variant_alleles' format, the indel-window Haplotype objects, kernel ms {parse, lists, signatures, fill}).
+    Raises _lib.UnphasedBuildDeclined where the builder declines (include/hawk.h: HAWK_UBUILD_*); nothing is left allocated."""
+    import ctypes as C
+    from . import _lib
+    from . import haplotypes as hap_mod
+    from ._lib import UnphasedBuildDeclined
+    from .coordinate import Coordinate
+    from .haplotype import Haplotype
+    from .hapset import DeviceHapSet, _p
+    from .region import Region
+    from .search_guides import compute_scan_start_stop, flatten_variant_alleles
+    from .sequence import Sequence as Seq_
+    from .variant import VTYPES, VariantRecord
+    if len(block) == 0:
+        raise ValueError("expand_unphased_from_vcf needs the records of the interval")
+    try:
+        vt = VcfVariants(block)
+    except ValueError as e:
+        raise UnphasedBuildDeclined(0, str(e)) from e
+    L = _lib.lib()
+    ctx = _lib.context(device)
+    n_ref = len(region_seq)
+    sel, v_line, v_allele, v_off, v_mask, v_ref = unphased_snv_table(block, vt, n_ref, startp)
+    ms = {"parse": 0.0, "lists": 0.0, "signatures": 0.0, "fill": 0.0}
+    if coord is None:
+        coord = Coordinate(block.fixed[0][0], int(startp), int(stopp), 0)
+    seq_obj = Seq_(region_seq, debug)
+    region = Region(seq_obj, coord)                         # the Region and the REF haplotype the host route builds
+    ref_hap = Haplotype(seq_obj, coord, False, 0, debug)
+    g, u, ds = C.c_void_p(), C.c_void_p(), None
+    t = C.c_float(0)
+    text = np.ascontiguousarray(block.text)
+    _lib.check(L.hawk_gt_parse_unphased(ctx, _p(text), C.c_uint64(len(text)), _p(block.line_off), _p(block.gt_off), C.c_uint64(len(block)),
+                                        len(samples), C.byref(g), C.byref(t)), "hawk_gt_parse_unphased")
+    ms["parse"] = float(t.value)
+    try:
+        flags = np.zeros(len(block), dtype=np.uint8)
+        _lib.check(L.hawk_gt_codes(g, None, _p(flags)), "hawk_gt_codes")
+        if np.any(flags):
+            i = int(np.flatnonzero(flags)[0])
+            raise UnphasedBuildDeclined(1, f"record {i}, flags {int(flags[i])}")
+        # ---- the distinct whole-region rows, from the lists
+        groups: List[List[int]] = []
+        sample_off = np.zeros(len(samples) + 1, dtype=np.uint64)
+        idx = np.zeros(0, dtype=np.uint32)
+        if len(sel):
+            rc = L.hawk_ubuild_lists(g, _p(v_line), _p(v_allele), _p(v_off), _p(v_mask), _p(v_ref), len(sel), _p(sample_off), C.byref(u), C.byref(t))
+            if rc == _lib.HAWK_E_CAPACITY:
+                raise UnphasedBuildDeclined(6)
+            _lib.check(rc, "hawk_ubuild_lists")
+            ms["lists"] = float(t.value)
+            if int(sample_off[-1]):
+                sig = np.zeros((len(samples), 2), dtype=np.uint64)
+                dec = C.c_int64(-1)
+                rc = L.hawk_ubuild_signatures(u, _p(sig), C.byref(dec), C.byref(t))
+                if rc == _lib.HAWK_E_UNSUPPORTED and dec.value >= 0:
+                    raise UnphasedBuildDeclined(7, vt.id[int(sel[dec.value])])
+                _lib.check(rc, "hawk_ubuild_signatures")
+                ms["signatures"] = float(t.value)
+                idx = np.zeros(int(sample_off[-1]), dtype=np.uint32)
+                _lib.check(L.hawk_ubuild_lists_download(u, _p(idx)), "hawk_ubuild_lists_download")
+                # REF holds the ref base of every variant somebody carries (the fill kernel checks the sites of the rows it writes,
+                # which are each group's first member's: a later member's record is checked here)
+                carried = np.unique(idx)
+                wrong = np.flatnonzero(_BASE_IDX[ref_hap.array[v_off[carried]]] != v_ref[carried])
+                if len(wrong):
+                    raise UnphasedBuildDeclined(4, vt.id[int(sel[carried[wrong[0]]])])
+                groups = group_unphased_rows(sample_off, idx, sig, v_off, v_mask, v_ref)
+        n_snv_rows = len(groups)
+        # ---- the indel windows, on the host: the records of the indels and of the SNVs inside their windows
+        windows = []
+        is_snv = np.zeros(len(vt), dtype=bool)
+        is_snv[sel] = True
+        indel_lines = sorted(set(vt.line[~is_snv].tolist()))
+        if indel_lines:
+            recs: Dict[int, VariantRecord] = {}
+
+            def record(i: int) -> VariantRecord:
+                if i not in recs:
+                    v = VariantRecord(debug)
+                    a, b = int(block.line_off[i]), int(block.line_off[i + 1])
+                    v.read_vcf_line(bytes(text[a:b]).decode().strip().split(), samples, False)
+                    recs[i] = v
+                return recs[i]
+            indels = [a for i in indel_lines for a in record(i).split() if a.vtype[0] != VTYPES[0]]
+            near = np.zeros(len(sel), dtype=bool)
+            snv_pos = vt.pos[sel]
+            for a in indels:
+                if hap_mod.indel_in_region(region, a) and len(a.samples) and a.samples[0][0]:
+                    _, lo, hi = hap_mod._Stretch.around(region, a)
+                    near |= (snv_pos >= lo) & (snv_pos <= hi)
+            snvs = [a for i in sorted(set(v_line[near].tolist())) for a in record(i).split() if a.vtype[0] == VTYPES[0]]
+            windows = hap_mod.unphased_indel_windows(region, indels, snvs, False, debug)
+        # ---- the set: REF, the SNV rows, the window rows
+        hap_len = np.array([n_ref] * (1 + n_snv_rows) + [len(w.sequence) for w in windows], dtype=np.uint32)
+        ds = DeviceHapSet.allocate(hap_len, device)
+        ds.pack_rows(0, [ref_hap.array])
+        ds.pack_rows(1 + n_snv_rows, [w.array for w in windows])
+        if n_snv_rows:
+            row_sample = np.array([m[0] for m in groups], dtype=np.uint32)
+            dec = C.c_int64(-1)
+            rc = L.hawk_ubuild_fill(u, ds._h, 0, 1, n_snv_rows, _p(row_sample), C.byref(dec), C.byref(t))
+            if rc == _lib.HAWK_E_UNSUPPORTED and dec.value >= 0:
+                raise UnphasedBuildDeclined(4, vt.id[int(sel[dec.value])])
+            _lib.check(rc, "hawk_ubuild_fill")
+            ms["fill"] = float(t.value)
+        ref_scan = compute_scan_start_stop(ref_hap, region.start, region.stop, pamlen)
+        meta = [HostHaplotype(b"", ref_hap.segments, True, ref_scan)] + [HostHaplotype(b"", ref_hap.segments, False, ref_scan)] * n_snv_rows
+        meta += [HostHaplotype(b"", w.segments, w.samples == "REF", compute_scan_start_stop(w, region.start, region.stop, pamlen)) for w in windows]
+        ds.set_meta(meta)
+        # ---- labels and the allele table
+        labels = [RowLabel("REF", "NA", {}, "hap_00000000", ref_hap.segments)]
+        labels += unphased_snv_labels(groups, sample_off, idx, sel, vt, samples, ref_hap.segments, 1)
+        for k, w in enumerate(windows):
+            w.id = f"hap_{1 + n_snv_rows + k:08d}"
+            labels.append(RowLabel(w.samples, w.variants, w.afs, w.id, w.segments))
+        key, off, ref = unphased_snv_alleles(groups, sample_off, idx, v_off, v_ref, 1)
+        if windows:
+            k2, o2, r2 = flatten_variant_alleles(windows)
+            key = np.concatenate((key, k2 + (np.uint64(1 + n_snv_rows) << np.uint64(32))))
+            off = np.concatenate((off, o2[1:] + np.uint32(len(ref)))).astype(np.uint32)
+            ref = np.concatenate((ref, r2)).astype(np.uint8)
+        out, ds = ds, None
+        return out, labels, (key, off, ref), windows, ms
+    finally:
+        if ds is not None:
+            ds.close()
+        if u:
+            L.hawk_ubuild_free(u)
+        L.hawk_gt_destroy(g)
 
 
 def row_labels(reg: SynthRegion, ds, info: List[HapInfo], kept: List[int]) -> List[Optional[RowLabel]]:

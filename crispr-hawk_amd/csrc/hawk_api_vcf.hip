@@ -14,10 +14,10 @@
 
 #include "hawk_host.h"
 
-extern "C" {
-
-int hawk_gt_parse(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, const uint64_t* gt_off,
-                  uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms) {
+typedef void (*GtParseLauncher)(hipStream_t, const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint8_t*, uint8_t*);
+// hawk_gt_parse and hawk_gt_parse_unphased: the same upload and the same object, the kernel that reads a genotype differs
+static int gt_parse_with(GtParseLauncher launch, hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off,
+                         const uint64_t* gt_off, uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms) {
   if (!ctx || !out || !n_samples || (n_lines && (!text || !line_off || !gt_off))) return HAWK_E_INVALID;
   // every offset the kernel dereferences is checked here
   for (uint64_t i = 0; i < n_lines; ++i)
@@ -41,7 +41,7 @@ int hawk_gt_parse(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const u
     HIPCHK(hipMemcpyAsync(d_go, gt_off, n_lines * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(g->d_codes, 0xff, ncode, st));  // samples a short record does not reach read as missing
     HIPCHK(hipEventRecord(ctx->ev[0], st));
-    hawk_launch_gt_parse(st, d_text, d_lo, d_go, n_lines, n_samples, g->d_codes, g->d_flags);
+    launch(st, d_text, d_lo, d_go, n_lines, n_samples, g->d_codes, g->d_flags);
     HIPCHK(hipEventRecord(ctx->ev[1], st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
@@ -49,6 +49,18 @@ int hawk_gt_parse(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const u
   }
   *out = g;
   return HAWK_OK;
+}
+
+extern "C" {
+
+int hawk_gt_parse(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, const uint64_t* gt_off,
+                  uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms) {
+  return gt_parse_with(hawk_launch_gt_parse, ctx, text, text_len, line_off, gt_off, n_lines, n_samples, out, kernel_ms);
+}
+
+int hawk_gt_parse_unphased(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, const uint64_t* gt_off,
+                           uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms) {
+  return gt_parse_with(hawk_launch_gt_parse_unphased, ctx, text, text_len, line_off, gt_off, n_lines, n_samples, out, kernel_ms);
 }
 
 int hawk_gt_from_codes(hawk_ctx* ctx, const uint8_t* codes, uint64_t n_lines, uint32_t n_samples, hawk_gt** out) {

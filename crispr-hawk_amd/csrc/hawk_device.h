@@ -541,6 +541,25 @@ void hawk_launch_ug_heads(hipStream_t st, const UgWork& w, uint64_t n, const uin
 void hawk_launch_ug_emit(hipStream_t st, const UgDev& u, const UgWork& w, const uint32_t* order, const uint32_t* gflag, const uint32_t* mflag,
                          const uint64_t* gidx /* [n + 1] */, const uint64_t* midx /* [n + 1] */, const UgOut& o);
 
+// ---- the whole-region rows of an unphased VCF (hawk_ubuild.hip; the rules themselves: hawk_ubuild.h)
+#include "hawk_ubuild.h"
+struct UbLists {             // device pointers
+  uint32_t n_samples, n_var;
+  const uint64_t* off;       // [n_samples + 1] CSR of the per-sample carried lists
+  const uint32_t* idx;       // ascending variant indices
+  const uint32_t* var_off;   // [n_var] offset in the region, ascending
+  const uint8_t* var_mask;   // [n_var] the alt's 4-bit mask
+  const uint8_t* var_ref;    // [n_var] the ref base 0-3
+};
+void hawk_launch_gt_parse_unphased(hipStream_t st, const uint8_t* text, const uint64_t* line_off, const uint64_t* gt_off, uint64_t n_lines,
+                                   uint32_t n_samples, uint8_t* codes, uint8_t* flags);
+void hawk_launch_ub_count(hipStream_t st, const uint8_t* codes, uint32_t n_samples, const uint32_t* var_line, const uint8_t* var_allele,
+                          uint32_t n_var, unsigned long long* ballots, uint32_t* count /* [n_samples] */);
+void hawk_launch_ub_fill(hipStream_t st, uint32_t n_samples, uint32_t n_var, const unsigned long long* ballots, const uint64_t* off, uint32_t* idx);
+void hawk_launch_ub_sig(hipStream_t st, const UbLists& l, unsigned long long* sig /* [n_samples][2] */, unsigned long long* decline /* ~0 */);
+void hawk_launch_ub_rows(hipStream_t st, uint32_t* const* plane, uint32_t S, uint32_t ref_row, uint32_t first_row, uint32_t n_rows,
+                         const uint32_t* row_sample, const UbLists& l, unsigned long long* decline /* ~0 */);
+
 #define FX_TOPK_MAX_BLOCKS 1024u
 void hawk_launch_fx_isref_gather(hipStream_t st, const uint8_t* hap_is_ref, const uint32_t* member_hap, const uint64_t* member_off, uint64_t n_groups, uint8_t* out);
 void hawk_launch_fx_groups(hipStream_t st, const FxDev& F);

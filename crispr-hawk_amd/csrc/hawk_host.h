@@ -301,6 +301,22 @@ struct hawk_gt {
   std::vector<int64_t> h_delta;         // per column: sum of the length changes of its carried variants
 };
 
+// the per-sample carried SNV lists of an unphased block and the variant table they index, in HBM (hawk_api_ubuild.hip)
+struct hawk_ubuild {
+  hawk_ctx* ctx;
+  uint32_t n_samples = 0, n_var = 0;
+  uint64_t n_entries = 0;
+  uint32_t max_off = 0;                 // the largest var_off: a row the lists are expanded into is longer than that
+  DevBuf off, idx, var_off, var_mask, var_ref;
+  std::vector<uint64_t> h_off;          // [n_samples + 1]
+  UbLists view() const {
+    UbLists l;
+    l.n_samples = n_samples; l.n_var = n_var; l.off = off.as<uint64_t>(); l.idx = idx.as<uint32_t>();
+    l.var_off = var_off.as<uint32_t>(); l.var_mask = var_mask.as<uint8_t>(); l.var_ref = var_ref.as<uint8_t>();
+    return l;
+  }
+};
+
 struct hawk_table {
   hawk_hapset* hs;  // nullptr for a merged table (hawk_table_gather): it owns its columns
   hawk_ctx* ctx;

@@ -18,6 +18,7 @@
 #include "hawk_effects.h"
 #include "hawk_resolve.h"
 #include "hawk_ugroups.h"
+#include "hawk_ubuild.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -1300,6 +1301,105 @@ int hawk_host_unphased_groups(const hawk_resolve_columns* cols, const int64_t* s
     }
   }
   if (member_off) member_off[ng] = nm;
+  return HAWK_OK;
+}
+
+// ---- the whole-region rows of an unphased VCF (hawk_ubuild.h): the host twin of hawk_ubuild_lists / _signatures / _fill
+int hawk_host_unphased_rows(const hawk_ubuild_input* in, hawk_ubuild_rows* out, hawk_ubuild_decline* decline) {
+  if (decline) { decline->reason = 0; decline->reserved = 0; decline->var = -1; }
+  if (!in || !out) return HAWK_E_INVALID;
+  out->n_rows = out->n_members = out->n_entries = out->n_keys = 0;
+  const uint32_t ns = in->n_samples, nv = in->n_var;
+  if (!ns || (in->n_lines && !in->codes) || (in->ref_len && !in->ref) ||
+      (nv && (!in->var_line || !in->var_allele || !in->var_off || !in->var_mask || !in->var_ref)))
+    return HAWK_E_INVALID;
+  auto declined = [&](int reason, int64_t var) {
+    if (decline) { decline->reason = reason; decline->var = var; }
+    return reason == UB_DECL_ENTRIES ? HAWK_E_CAPACITY : HAWK_E_UNSUPPORTED;
+  };
+  for (uint32_t j = 0; j < nv; ++j) {
+    if (in->var_line[j] >= in->n_lines || in->var_allele[j] == 0 || in->var_allele[j] == 255 || in->var_ref[j] > 3 || in->var_mask[j] > 15 ||
+        (j && in->var_off[j] < in->var_off[j - 1]))
+      return HAWK_E_INVALID;
+  }
+  for (uint32_t j = 0; j < nv; ++j)
+    if (in->var_off[j] >= in->ref_len) return declined(UB_DECL_OUTSIDE, j);
+  // the lists: per sample, ascending variant indices; REF is checked where a variant is carried, as the fill kernel does
+  std::vector<uint64_t> off((size_t)ns + 1, 0);
+  std::vector<uint32_t> idx;
+  int64_t bad_ref = -1;
+  for (uint32_t s = 0; s < ns; ++s) {
+    for (uint32_t j = 0; j < nv; ++j) {
+      const uint8_t* c = in->codes + ((size_t)in->var_line[j] * ns + s) * 2u;
+      if (!ub_carried(c[0], c[1], in->var_allele[j])) continue;
+      idx.push_back(j);
+      if (ub_base_index((uint8_t)in->ref[in->var_off[j]]) != in->var_ref[j] && (bad_ref < 0 || (int64_t)j < bad_ref)) bad_ref = j;
+    }
+    off[s + 1] = idx.size();
+    if (off[s + 1] > UB_MAX_ENTRIES) return declined(UB_DECL_ENTRIES, -1);
+  }
+  if (bad_ref >= 0) return declined(UB_DECL_REF, bad_ref);
+  // merged sites and signatures; rows merge on the exact site sequence, first carrier first
+  typedef std::vector<std::pair<uint32_t, uint32_t>> Sites;
+  std::vector<Sites> sites(ns);
+  std::vector<uint64_t> sig((size_t)ns * 2, 0);
+  int64_t repeat = -1;
+  for (uint32_t s = 0; s < ns; ++s) {
+    for (uint64_t e = off[s]; e < off[s + 1]; ++e) {
+      const uint32_t j = idx[e], refbit = 1u << in->var_ref[j];
+      if (sites[s].empty() || sites[s].back().first != in->var_off[j]) sites[s].emplace_back(in->var_off[j], refbit);
+      if (!ub_site_add(refbit, &sites[s].back().second, in->var_mask[j]) && (repeat < 0 || (int64_t)j < repeat)) repeat = j;
+      sites[s].back().second |= (uint32_t)in->var_mask[j] | refbit;  // the expression k_ub_sig uses: every entry's ref bit and alt
+    }
+    for (const auto& st : sites[s]) ub_sig_add(st.first, st.second, &sig[2 * (size_t)s], &sig[2 * (size_t)s + 1]);
+  }
+  if (repeat >= 0) return declined(UB_DECL_REPEAT, repeat);
+  std::vector<uint32_t> head;                 // first carrier of every distinct row
+  std::vector<std::vector<uint32_t>> members;
+  for (uint32_t s = 0; s < ns; ++s) {
+    if (sites[s].empty()) continue;
+    size_t k = 0;
+    for (; k < head.size(); ++k)
+      if (sig[2 * (size_t)head[k]] == sig[2 * (size_t)s] && sig[2 * (size_t)head[k] + 1] == sig[2 * (size_t)s + 1] && sites[head[k]] == sites[s]) break;
+    if (k == head.size()) { head.push_back(s); members.emplace_back(); }
+    members[k].push_back(s);
+  }
+  const uint64_t nr = head.size();
+  uint64_t nm = 0, nk = 0, ne = 0;
+  for (uint64_t k = 0; k < nr; ++k) { nm += members[k].size(); nk += sites[head[k]].size(); ne += off[head[k] + 1] - off[head[k]]; }
+  out->n_rows = nr; out->n_members = nm; out->n_entries = idx.size(); out->n_keys = nk;
+  if ((out->seqs || out->member_off) && out->row_cap < nr) return HAWK_E_CAPACITY;
+  if (out->list_idx && out->entry_cap < idx.size()) return HAWK_E_CAPACITY;
+  if ((out->al_key || out->al_off || out->al_ref) && out->entry_cap < ne) return HAWK_E_CAPACITY;
+  if (out->sample_off) std::copy(off.begin(), off.end(), out->sample_off);
+  if (out->list_idx) std::copy(idx.begin(), idx.end(), out->list_idx);
+  if (out->sig) std::copy(sig.begin(), sig.end(), out->sig);
+  static const char kCode[] = "?acmgrsvtwyhkdbn";  // a carried site is lower case
+  uint64_t mi = 0, ki = 0, ei = 0;
+  for (uint64_t k = 0; k < nr; ++k) {
+    const uint32_t h = head[k];
+    if (out->seqs) {
+      char* row = out->seqs + k * (uint64_t)in->ref_len;
+      memcpy(row, in->ref, in->ref_len);
+      for (const auto& st : sites[h]) row[st.first] = kCode[st.second & 15u];
+    }
+    if (out->member_off) out->member_off[k] = (uint32_t)mi;
+    for (uint32_t s : members[k]) {
+      if (out->member_sample) out->member_sample[mi] = s;
+      ++mi;
+    }
+    // the allele table of the first member: one key per carried position, one entry per carried allele there
+    uint64_t e = off[h];
+    for (const auto& st : sites[h]) {
+      if (out->al_key) out->al_key[ki] = ((uint64_t)(in->row_base + k) << 32) | st.first;
+      if (out->al_off) out->al_off[ki] = (uint32_t)ei;
+      for (; e < off[h + 1] && in->var_off[idx[e]] == st.first; ++e, ++ei)
+        if (out->al_ref) out->al_ref[ei] = in->var_ref[idx[e]];
+      ++ki;
+    }
+  }
+  if (out->member_off) out->member_off[nr] = (uint32_t)mi;
+  if (out->al_off) out->al_off[nk] = (uint32_t)ei;
   return HAWK_OK;
 }
 

@@ -946,6 +946,95 @@ int hawk_host_unphased_groups(const hawk_resolve_columns* cols, const int64_t* s
                               uint64_t* out_win, uint8_t* gc_num, uint8_t* gc_den, uint64_t* member_off, uint32_t* member_hap,
                               uint64_t* n_groups, uint64_t* n_members);
 
+/* ---- the whole-region IUPAC rows of an unphased VCF, built on the device from the genotype text: what
+ * add_variants_unphased (haplotypes.py:370-712) does for the SNV alleles - one region-long row per carrier, equal rows merged -
+ * without a string on the host.  The rules are stated once, in csrc/hawk_ubuild.h, for the kernels (k_gt_parse_unphased, k_ub_sig,
+ * k_ub_rows) and for hawk_host_unphased_rows.
+ *
+ * hawk_gt_parse_unphased: hawk_gt_parse's arguments and object (codes[n_lines][2*n_samples], hawk_gt_codes downloads them) under the
+ *   unphased genotype rule.  With g = a column up to its first ':': part 0 of g split at '/' -> column 2s, part 1 -> column 2s + 1
+ *   (0 REF, k = k-th ALT, 255 for '.', clamp at 254).  Flags per record, OR-ed over its first n_samples columns:
+ *     1 = g is not exactly two '/'-separated parts, or holds a '|' (haploid, three or more parts, empty, phased);
+ *     2 = the record does not have n_samples columns;
+ *     4 = one of the first two '/'-parts is neither '.' nor all ASCII digits; its code stays 255 ("0|1" is one part that is no
+ *         number: 1 and 4).
+ * hawk_ubuild_lists: variants j = (record var_line[j], allele var_allele[j] in 1..254, offset var_off[j] in the region, the alt's
+ *   4-bit mask var_mask[j] (A 1, C 2, G 4, T 8), ref base var_ref[j] 0-3), var_off ascending (HAWK_E_INVALID otherwise): the SNV
+ *   alleles of the block in the caller's order.  Sample s carries j iff codes[var_line[j]][2s] or [2s + 1] equals var_allele[j]
+ *   (_genotypes_to_samples(phased=False), slot 0).  One ascending list per SAMPLE is built on the device and stays there with the
+ *   variant table; sample_off[n_samples + 1] (host) receives the CSR offsets, hawk_ubuild_lists_download the indices.  More than
+ *   2^32 - 1 entries: HAWK_E_CAPACITY; more than 65535 x 1024 variants (the count kernel's grid): HAWK_E_UNSUPPORTED; nothing left
+ *   allocated either way.
+ * hawk_ubuild_signatures: sig[n_samples][2], 128 bits over each sample's merged sites (offset, REF's bit | the carried alts' bits),
+ *   computed from the lists before any plane is written; a sample without entries gives (0, 0).  Equal rows have equal signatures;
+ *   the caller compares the lists of samples that share one before it merges them.  A sample that carries an alt twice at one
+ *   position (a duplicated record, or alt == ref behind another allele): HAWK_E_UNSUPPORTED with the first such variant in
+ *   *decline_var - the host builder's sequential IUPAC encoding fails there, so the caller hands the interval to it.
+ * hawk_ubuild_fill: rows [first_row, first_row + n_rows) of an ordinary set - each as long as row ref_row, which is packed already
+ *   and not among them - become REF with the sites of sample row_sample[r]: at a carried position the A/C/G/T bits are REF's OR-ed
+ *   with every carried alt's and the V bit is set; everything else, padding included, is REF's.  One pass, each word written
+ *   once.  A site where REF does not hold exactly the variant's ref base in upper case: HAWK_E_UNSUPPORTED with the first such
+ *   variant in *decline_var - nothing faults, the caller discards the set.  HAWK_E_INVALID, with nothing written: rows outside the
+ *   set or of another length, a sample or a var_off the lists / REF do not have, a plan view, another context's set.
+ * hawk_hapset_pack_ascii_rows: hawk_hapset_pack_ascii for rows [first_row, first_row + n_rows) alone (seq_off[n_rows + 1] into
+ *   `seqs`): REF and the host-built window rows of such a set.  The other rows are not touched.
+ * hawk_host_unphased_rows: the same rows from host arrays by the same header, single-threaded, no device: codes + variant table +
+ *   REF bytes -> the distinct rows as cased ASCII (seqs[row_cap][ref_len]), their members (first carrier first, samples ascending),
+ *   the per-sample lists and signatures, and the allele table of the rows (hawk_resolve_alleles' layout: key = (row_base + row)
+ *   << 32 | offset, one entry per carried allele of the FIRST member, ref byte 0-3).  Counts are always written; an output that is
+ *   not NULL needs its capacity (row_cap rows; entry_cap list entries / allele entries), else HAWK_E_CAPACITY.  Declines
+ *   (HAWK_E_UNSUPPORTED, reason and variant in *decline): HAWK_UBUILD_OUTSIDE, HAWK_UBUILD_REF (checked for every CARRIED
+ *   variant, whichever sample carries it), HAWK_UBUILD_REPEAT; HAWK_UBUILD_ENTRIES is HAWK_E_CAPACITY.  The remaining reasons are the caller's: it reads the flags and the fixed columns. */
+#define HAWK_UBUILD_GENOTYPE 1 /* a record flag of the unphased parse */
+#define HAWK_UBUILD_MNV 2      /* an equal-length allele longer than one base */
+#define HAWK_UBUILD_BASE 3     /* an alt or ref base outside A/C/G/T */
+#define HAWK_UBUILD_REF 4      /* REF does not hold exactly the record's ref base at a site */
+#define HAWK_UBUILD_OUTSIDE 5  /* an SNV outside the region */
+#define HAWK_UBUILD_ENTRIES 6  /* more than 2^32 - 1 list entries */
+#define HAWK_UBUILD_REPEAT 7   /* a sample carries an alt twice at one position */
+typedef struct hawk_ubuild hawk_ubuild;
+typedef struct {
+  const uint8_t* codes; /* [n_lines][2 * n_samples] */
+  uint64_t n_lines;
+  uint32_t n_samples, n_var;
+  const uint32_t* var_line;
+  const uint8_t* var_allele;
+  const uint32_t* var_off;
+  const uint8_t* var_mask;
+  const uint8_t* var_ref;
+  const char* ref; /* REF's bytes */
+  uint32_t ref_len, row_base;
+} hawk_ubuild_input;
+typedef struct {
+  uint64_t row_cap, entry_cap;
+  char* seqs;              /* [row_cap][ref_len] */
+  uint32_t* member_off;    /* [row_cap + 1] */
+  uint32_t* member_sample; /* [n_samples] */
+  uint64_t* sample_off;    /* [n_samples + 1] */
+  uint32_t* list_idx;      /* [entry_cap] */
+  uint64_t* sig;           /* [n_samples][2] */
+  uint64_t* al_key;        /* [entry_cap] */
+  uint32_t* al_off;        /* [entry_cap + 1] */
+  uint8_t* al_ref;         /* [entry_cap] */
+  uint64_t n_rows, n_members, n_entries, n_keys;
+} hawk_ubuild_rows;
+typedef struct {
+  int32_t reason, reserved; /* HAWK_UBUILD_*, 0: none */
+  int64_t var;              /* the first offending variant, or -1 */
+} hawk_ubuild_decline;
+int hawk_gt_parse_unphased(hawk_ctx* ctx, const uint8_t* text, uint64_t text_len, const uint64_t* line_off, const uint64_t* gt_off,
+                           uint64_t n_lines, uint32_t n_samples, hawk_gt** out, float* kernel_ms);
+int hawk_ubuild_lists(hawk_gt* g, const uint32_t* var_line, const uint8_t* var_allele, const uint32_t* var_off, const uint8_t* var_mask,
+                      const uint8_t* var_ref, uint32_t n_var, uint64_t* sample_off, hawk_ubuild** out, float* kernel_ms);
+int hawk_ubuild_lists_download(hawk_ubuild* u, uint32_t* idx);
+int hawk_ubuild_signatures(hawk_ubuild* u, uint64_t* sig, int64_t* decline_var, float* kernel_ms);
+int hawk_ubuild_fill(hawk_ubuild* u, hawk_hapset* hs, uint32_t ref_row, uint32_t first_row, uint32_t n_rows, const uint32_t* row_sample,
+                     int64_t* decline_var, float* kernel_ms);
+void hawk_ubuild_free(hawk_ubuild* u);
+int hawk_hapset_pack_ascii_rows(hawk_hapset* hs, uint32_t first_row, uint32_t n_rows, const char* seqs, const uint64_t* seq_off,
+                                uint64_t* bad_index);
+int hawk_host_unphased_rows(const hawk_ubuild_input* in, hawk_ubuild_rows* out, hawk_ubuild_decline* decline);
+
 /* ---- PLM-CRISPR (scores/plm_crispr/train_general.py, class sgrna_net, forward with train=False; wrapper
  * scores/plm_crispr/plm_crispr.py:136-258): n guide+PAM 23-mers -> n fp32 scores, all arithmetic in fp32 (lin1 and lin3 on the
  * f32-input MFMA).  The 83 MB of parameters and the protein branch's result live in HBM behind a handle.
