@@ -46,6 +46,8 @@ EXPORTS = [
     "hawk_resolve_groups", "hawk_ugroups_download", "hawk_ugroups_free", "hawk_host_unphased_groups",
     "hawk_gt_parse_unphased", "hawk_ubuild_lists", "hawk_ubuild_lists_download", "hawk_ubuild_signatures", "hawk_ubuild_fill", "hawk_ubuild_free",
     "hawk_hapset_pack_ascii_rows", "hawk_host_unphased_rows",
+    "hawk_uwin_instances", "hawk_uwin_download", "hawk_uwin_signatures", "hawk_uwin_group", "hawk_uwin_fill", "hawk_uwin_free",
+    "hawk_host_unphased_windows",
     "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
 ]
 
@@ -172,11 +174,30 @@ class UbuildDecline(C.Structure):
     _fields_ = [("reason", C.c_int32), ("reserved", C.c_int32), ("var", C.c_int64)]
 
 
+class UwinInput(C.Structure):
+    _fields_ = [("n_indel", C.c_uint32), ("region_len", C.c_uint32), ("line", C.c_void_p), ("allele", C.c_void_p), ("off", C.c_void_p),
+                ("ref_len", C.c_void_p), ("alt_len", C.c_void_p), ("pool_off", C.c_void_p), ("pool", C.c_void_p), ("pool_len", C.c_uint64),
+                ("rank_sample", C.c_void_p), ("ref", C.c_void_p)]
+
+
+class UwinLists(C.Structure):
+    _fields_ = [("codes", C.c_void_p), ("n_lines", C.c_uint64), ("n_samples", C.c_uint32), ("n_var", C.c_uint32), ("sample_off", C.c_void_p),
+                ("list_idx", C.c_void_p), ("var_off", C.c_void_p), ("var_mask", C.c_void_p), ("var_ref", C.c_void_p)]
+
+
+class UwinRows(C.Structure):
+    _fields_ = [("inst_cap", C.c_uint64), ("row_cap", C.c_uint64), ("seq_cap", C.c_uint64), ("inst_off", C.c_void_p), ("inst_sample", C.c_void_p),
+                ("inst_lo", C.c_void_p), ("inst_hi", C.c_void_p), ("sig", C.c_void_p), ("head", C.c_void_p), ("forged_sig", C.c_void_p),
+                ("seqs", C.c_void_p), ("seq_off", C.c_void_p), ("n_inst", C.c_uint64), ("n_rows", C.c_uint64), ("n_seq", C.c_uint64)]
+
+
 UBUILD_REASONS = {1: "a genotype column that is not two '/'-separated allele numbers, or a record without one column per sample",
                   2: "an equal-length allele longer than one base", 3: "an alt or ref base outside A/C/G/T",
                   4: "the reference sequence does not hold the record's ref base", 5: "an SNV outside the region",
                   6: "more than 2^32 - 1 carried-variant entries",
-                  7: "a sample carries an alt twice at one position (the host builder's IUPAC encoding fails there)"}
+                  7: "a sample carries an alt twice at one position (the host builder's IUPAC encoding fails there)",
+                  8: "an indel that does not fit the window the host builder cuts around it",
+                  9: "a base of an indel's ref or alt outside A/C/G/T"}
 
 
 class UnphasedBuildDeclined(Exception):
@@ -239,6 +260,7 @@ def lib() -> C.CDLL:
         L.hawk_resolve_free.restype = None
         L.hawk_ugroups_free.restype = None
         L.hawk_ubuild_free.restype = None
+        L.hawk_uwin_free.restype = None
         L.hawk_plm_free.restype = None
         L.hawk_comm_last_error.restype = C.c_char_p
         for name in EXPORTS:

@@ -124,7 +124,8 @@ UNPHASED_REPORTS = (None, "groups", "objects")
 
 def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool,
                        ot=None, ann=None, lap=None, tables=None, unphased_engine=None, unphased_report=None, azimuth_model=None,
-                       deepcpf1_weights=None, plm_on=False, fx=None, unphased_haplotypes="host", device=None) -> str:
+                       deepcpf1_weights=None, plm_on=False, fx=None, unphased_haplotypes="host", device=None,
+                       unphased_indel_windows="host") -> str:
     """One BED interval with the haplotypes built on the host by the mirror of the reference's own construction
     (haplotypes.py:106-368 phased, 370-712 unphased) - the route of unphased VCFs (IUPAC haplotypes + indel windows; their
     windows resolved on the device table, search_guides.search's `unphased_engine`) and the fallback for phased records the device expansion
@@ -160,7 +161,7 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
         raise ValueError(f"graphical_reports / candidate_guides on an unphased interval rank the report groups in device memory: {why}")
     if unphased_haplotypes == "device" and not phased:
         path = _unphased_device_built(coord, seq, vcf, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, tables, mode, engine,
-                                      azimuth_model, deepcpf1_weights, plm_on, fx, device)
+                                      azimuth_model, deepcpf1_weights, plm_on, fx, device, unphased_indel_windows)
         if path is not None:
             return path
     from . import haplotypes as hap_mod
@@ -225,17 +226,20 @@ def _search_host_built(coord, seq: str, vcf, phased: bool, pam: PAM, guidelen: i
 
 
 UNPHASED_HAPLOTYPES = (None, "host", "device")
+UNPHASED_INDEL_WINDOWS = (None, "host", "device")
 HOST_BUILT_LAP = "host-built route: unphased haplotypes built on the host"
 DEVICE_BUILT_LAP = "host-built route: unphased haplotypes built on the device"
 
 
 def _unphased_device_built(coord, seq: str, vcf, pam: PAM, guidelen: int, right: bool, outdir: str, mm, pt, debug: bool, ot, ann, lap, tables,
-                           mode: str, engine: str, azimuth_model, deepcpf1_weights, plm_on, fx, device) -> Optional[str]:
+                           mode: str, engine: str, azimuth_model, deepcpf1_weights, plm_on, fx, device, indel_windows: str = "host") -> Optional[str]:
     """An unphased interval with its whole-region rows built on the device (workload.expand_unphased_from_vcf) and the "groups"
     report made from that set, its labels and its allele table: no VariantRecord per line, no string per carrier.  None - with a
     line at verbosity level 3 that says why - where the route does not apply ("objects", the host engine, haplotype_table=True
     whose writer wants the strings), where the builder declines, and where the resolution declines or refuses: the caller then
-    builds the interval on the host, which raises or succeeds as it always has.  An interval without records is the caller's too."""
+    builds the interval on the host, which raises or succeeds as it always has.  An interval without records is the caller's too.
+    `indel_windows="device"` builds the indel windows on the device too; where only that builder declines (HAWK_UBUILD_WINDOW,
+    HAWK_UBUILD_INDEL_BASE, an indel's HAWK_UBUILD_REF) the interval is built once more with the windows on the host."""
     from ._lib import UnphasedBuildDeclined
     from .workload import expand_unphased_from_vcf
     why = None
@@ -247,15 +251,25 @@ def _unphased_device_built(coord, seq: str, vcf, pam: PAM, guidelen: int, right:
         why = "haplotype_table=True writes the table from the host-built strings"
     if why is not None:
         print_verbosity(f"Unphased haplotypes built on the host: {why}", 0, VERBOSITYLVL[3])
+        if indel_windows == "device":
+            print_verbosity("unphased_indel_windows='device' not used: the interval is built on the host", 0, VERBOSITYLVL[3])
         return None
     blk = vcf.fetch_block(coord)
     if len(blk) == 0:
         return None
-    try:
-        built = expand_unphased_from_vcf(seq, coord.start, coord.stop, blk, vcf.samples, len(pam), device, coord=coord, debug=debug)
-    except UnphasedBuildDeclined as e:
-        print_verbosity(f"Unphased haplotypes built on the host: the device builder declined: {e}", 0, VERBOSITYLVL[3])
-        return None
+    built = None
+    if indel_windows == "device":
+        try:
+            built = expand_unphased_from_vcf(seq, coord.start, coord.stop, blk, vcf.samples, len(pam), device, coord=coord, debug=debug,
+                                             indel_windows="device")
+        except UnphasedBuildDeclined as e:  # one step down: the SNV rows on the device, the windows on the host
+            print_verbosity(f"Unphased indel windows built on the host: the device builder declined: {e}", 0, VERBOSITYLVL[3])
+    if built is None:
+        try:
+            built = expand_unphased_from_vcf(seq, coord.start, coord.stop, blk, vcf.samples, len(pam), device, coord=coord, debug=debug)
+        except UnphasedBuildDeclined as e:
+            print_verbosity(f"Unphased haplotypes built on the host: the device builder declined: {e}", 0, VERBOSITYLVL[3])
+            return None
     return _unphased_groups_report(coord, None, None, pam, guidelen, right, outdir, mm, pt, debug, ot, ann, lap, azimuth_model, deepcpf1_weights,
                                    plm_on, fx, None, built=built)
 
@@ -347,7 +361,7 @@ def _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_st
 
 
 # Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
-# candidate_guides, figures, unphased_report, unphased_engine and unphased_effects sit before `annotations`), and only the order of the last three parameters is held fixed.
+# candidate_guides, figures, unphased_report, unphased_engine, unphased_effects, unphased_haplotypes and unphased_indel_windows sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
                  device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
@@ -355,7 +369,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                  graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
                  unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, unphased_effects: bool = False,
-                 unphased_haplotypes: Optional[str] = None,
+                 unphased_haplotypes: Optional[str] = None, unphased_indel_windows: Optional[str] = None,
                  annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
@@ -413,8 +427,13 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     "objects", the host engine and `haplotype_table=True` (whose writer wants the strings) build that interval on the host, as
     does an interval the device builder declines (a malformed or haploid genotype, a multi-base substitution, a base outside
     A/C/G/T, a ref base the sequence does not hold, an SNV outside the region, an alt one sample carries twice at a position):
-    the host builder then raises or succeeds exactly as under "host".  A line at verbosity level 3 says why.  (Everything from
-    `timings` on is meant to be passed by keyword.)"""
+    the host builder then raises or succeeds exactly as under "host".  A line at verbosity level 3 says why.
+    `unphased_indel_windows` (None reads HAWK_UNPHASED_INDEL_WINDOWS, else "host"): under "device" the 201-nt indel
+    windows of such an interval are built on the device as well (hawk_uwin_*: no VariantRecord, no Haplotype, no row string).  It
+    takes effect only where `unphased_haplotypes="device"` does; elsewhere a line at verbosity level 3 says it was not used.  Where
+    the window builder declines (an indel that does not fit its window, an indel base outside A/C/G/T, an indel ref the row does not
+    hold) the interval is rebuilt one step down - device SNV rows, host windows - with a level-3 line naming reason and variant;
+    if that declines too, the host builder takes over as above.  (Everything from `timings` on is meant to be passed by keyword.)"""
     if unphased_report not in UNPHASED_REPORTS:
         raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
     if unphased_haplotypes not in UNPHASED_HAPLOTYPES:
@@ -422,6 +441,13 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     builder = unphased_haplotypes or os.environ.get("HAWK_UNPHASED_HAPLOTYPES") or "host"
     if builder not in ("host", "device"):
         raise ValueError(f"HAWK_UNPHASED_HAPLOTYPES={builder!r}: 'host' or 'device'")
+    if unphased_indel_windows not in UNPHASED_INDEL_WINDOWS:
+        raise ValueError(f"unphased_indel_windows {unphased_indel_windows!r}: None, 'host' or 'device'")
+    windows = unphased_indel_windows or os.environ.get("HAWK_UNPHASED_INDEL_WINDOWS") or "host"
+    if windows not in ("host", "device"):
+        raise ValueError(f"HAWK_UNPHASED_INDEL_WINDOWS={windows!r}: 'host' or 'device'")
+    if windows == "device" and builder != "device":
+        print_verbosity("unphased_indel_windows='device' not used: it builds behind unphased_haplotypes='device'", 0, VERBOSITYLVL[3])
     import time as _time
     check_annotation_args(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames)
     _t = [_time.perf_counter()]
@@ -489,7 +515,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     try:
         return _search_intervals(Bed(bedfile, PADDING, debug), fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot,
                                  ann, azimuth_model, deepcpf1_weights, paths, lap, tables, fx, plm_on, unphased_report, unphased_engine,
-                                 bool(unphased_effects), builder)
+                                 bool(unphased_effects), builder, windows)
     finally:
         if ann is not None:
             ann.close()
@@ -497,7 +523,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
 
 def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, score, mmt, pt, device, debug, ot, ann, azimuth_model,
                       deepcpf1_weights, paths, lap, tables=None, fx=None, plm_on=False, unphased_report=None, unphased_engine=None,
-                      unphased_effects=False, unphased_haplotypes="host") -> Dict[str, str]:
+                      unphased_effects=False, unphased_haplotypes="host", unphased_indel_windows="host") -> Dict[str, str]:
     """search_files' loop over the BED intervals."""
     stage_on = fx is not None and (fx["on"] or bool(fx["cgs"]))
 
@@ -516,7 +542,8 @@ def _search_intervals(bed, fastas, vcf_by_contig, pam, guidelen, right, outdir, 
                 no_table(True)
             paths[str(coord)] = _search_host_built(coord, seq, v, False, pam, guidelen, right, outdir, mmt if score else None,
                                                    pt if score else None, debug, ot, ann, lap, tables, unphased_engine, unphased_report,
-                                                   azimuth_model, deepcpf1_weights, plm_on, fx if stage_on else None, unphased_haplotypes, device)
+                                                   azimuth_model, deepcpf1_weights, plm_on, fx if stage_on else None, unphased_haplotypes, device,
+                                                   unphased_indel_windows)
             continue
         from .readers import VcfBlock
         blk = v.fetch_block(coord) if v is not None else VcfBlock(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint64), [])

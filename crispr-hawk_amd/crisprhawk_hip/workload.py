@@ -835,8 +835,222 @@ def unphased_rows_host(region_seq: str, startp: int, block, samples: List[str], 
     return rows, labels, (al_key, al_off, al_ref), (sample_off, idx), sig, groups
 
 
+# ---------------------------------------------------------------------------------------------- unphased indel windows
+INDEL_WINDOWS = ("host", "device")
+WINDOW_FLANK = 100  # haplotypes.INDEL_WINDOW, csrc/hawk_uwin.h: UW_FLANK
+
+
+class IndelTable:
+    """The indel alleles of a block inside the interval as given (haplotypes.indel_in_region), in (record, allele) order, as the
+    arrays hawk_uwin_instances takes, and their window geometry (csrc/hawk_uwin.h states it; here it only places labels)."""
+
+    def __init__(self, vt: "VcfVariants", is_snv: np.ndarray, region_len: int, startp: int, coord):
+        ind = np.flatnonzero(~is_snv)
+        ind = ind[np.lexsort((vt.allele[ind], vt.line[ind]))]
+        pos = vt.pos[ind]
+        ind = ind[(pos >= coord.startp) & (pos < coord.stopp)]
+        self.sel = ind
+        n = len(ind)
+        self.line = np.ascontiguousarray(vt.line[ind], dtype=np.uint32)
+        self.allele = np.ascontiguousarray(vt.allele[ind], dtype=np.uint8)
+        o = vt.pos[ind] - int(startp)
+        self.off = np.where((o < 0) | (o >= region_len), 0xffffffff, o).astype(np.uint32)  # (outside the sequence: the builder declines)
+        refs, alts = [vt.ref[int(j)] for j in ind], [vt.alt[int(j)] for j in ind]
+        self.ref_len = np.array([len(r) for r in refs], dtype=np.uint32)
+        self.alt_len = np.array([len(a) for a in alts], dtype=np.uint32)
+        self.pool_off = np.zeros(n, dtype=np.uint32)
+        if n:
+            self.pool_off[1:] = np.cumsum((self.ref_len + self.alt_len)[:-1], dtype=np.uint64).astype(np.uint32)
+        text = "".join(r + a for r, a in zip(refs, alts))
+        self.pool = _BASE_IDX[np.frombuffer(text.encode("latin-1", "replace"), dtype=np.uint8)] if text else np.zeros(0, np.uint8)
+        # single-base refs as the allele table wants them: the index in ACGT, 255 for anything else
+        first = self.pool[self.pool_off] if n else np.zeros(0, np.uint8)
+        self.ref_byte = np.where(self.ref_len == 1, first, 255).astype(np.uint8)
+        # geometry (valid for the indels the builder does not decline)
+        o = o.astype(np.int64)
+        self.o = o
+        self.grow = self.alt_len.astype(np.int64) - self.ref_len.astype(np.int64)
+        self.span = np.where(self.grow > 0, 1, 1 - self.grow)
+        self.a = np.maximum(0, o - WINDOW_FLANK)
+        self.b = np.minimum(region_len - 1, o - self.grow + WINDOW_FLANK)
+        self.rowlen = self.b - self.a + 1 + self.grow
+        self.i = o - self.a
+
+    def __len__(self) -> int:
+        return len(self.sel)
+
+    def c_input(self, rank_sample: np.ndarray, ref: np.ndarray):
+        """(hawk_uwin_input, the arrays it points into)"""
+        from . import _lib
+        keep = (self.line, self.allele, self.off, self.ref_len, self.alt_len, self.pool_off, self.pool, rank_sample, ref)
+        inp = _lib.UwinInput(len(self), len(ref), self.line.ctypes.data, self.allele.ctypes.data, self.off.ctypes.data, self.ref_len.ctypes.data,
+                             self.alt_len.ctypes.data, self.pool_off.ctypes.data, self.pool.ctypes.data, len(self.pool), rank_sample.ctypes.data,
+                             ref.ctypes.data)
+        return inp, keep
+
+    def segments(self, k: int, startp: int) -> PosSegments:
+        """expand_haplotype's position map of indel k's rows: identity from the window's start, a deletion's jump behind the anchor,
+        an insertion's bases on the anchor's position; a segment opening at the row's end is dropped"""
+        i, grow, g0 = int(self.i[k]), int(self.grow[k]), int(startp) + int(self.o[k])
+        if grow < 0:
+            rel, gen = [0, i + 1], [int(startp) + int(self.a[k]), g0 + 1 - grow]
+        else:
+            rel = [0] + list(range(i + 1, i + grow + 2))
+            gen = [int(startp) + int(self.a[k])] + [g0] * grow + [g0 + 1]
+        rel, gen = np.asarray(rel, dtype=np.uint32), np.asarray(gen, dtype=np.int64)
+        keep = rel < int(self.rowlen[k])
+        return PosSegments(rel[keep], gen[keep], int(self.rowlen[k]))
+
+
+def _window_scan(seg: PosSegments, lo: int, hi: int, region_start: int, region_stop: int, pamlen: int) -> Tuple[int, int]:
+    """search_guides.compute_scan_start_stop for a window haplotype that covers [lo, hi], from its segments (KeyError where the
+    reverse position map lacks the position, as there)"""
+    def rev(p):
+        r = seg.rev(p)
+        if r < 0:
+            raise KeyError(p)
+        return r
+    stop_p = min(region_stop - WINDOW_FLANK, hi)
+    if stop_p == region_stop - WINDOW_FLANK and seg.rev(stop_p) < 0:
+        for p in range(stop_p, seg.max_gen() + 1):
+            if seg.rev(p) >= 0:
+                stop_p = p
+                break
+    scan_stop = rev(stop_p) - pamlen + 1
+    return rev(max(region_start + WINDOW_FLANK, lo)), scan_stop
+
+
+def _flat_ranges(lo: np.ndarray, hi: np.ndarray):
+    """ranges [lo[k], hi[k]) laid end to end: (the flat indices, the range each one belongs to)"""
+    n = (hi - lo).astype(np.int64)
+    owner = np.repeat(np.arange(len(n), dtype=np.int64), n)
+    start = np.concatenate(([0], np.cumsum(n)[:-1])) if len(n) else np.zeros(0, np.int64)
+    return lo.astype(np.int64)[owner] + (np.arange(int(n.sum()), dtype=np.int64) - start[owner]), owner
+
+
+def unphased_window_rows(wt: IndelTable, inst_off: np.ndarray, inst_sample: np.ndarray, inst_lo: np.ndarray, inst_hi: np.ndarray, head: np.ndarray,
+                         idx: np.ndarray, sel: np.ndarray, v_off: np.ndarray, v_ref: np.ndarray, vt: "VcfVariants", samples: List[str], startp: int,
+                         region_start: int, region_stop: int, pamlen: int, row_base: int):
+    """The distinct window rows of (instances, heads) - hawk_uwin_* or hawk_host_unphased_windows - with everything
+    haplotypes.unphased_indel_windows attaches to them: -> (row_inst: the head instance of every row, in row order; hap_len;
+    [RowLabel] with ids from hap_{row_base}; [HostHaplotype] without sequences: segments and scan bounds; the rows' allele table
+    (key, off, ref) with off[0] == 0).  Labels: samples = the members' names (instances come in name order), variants = the sorted
+    union of the members' own id strings (a member's SNVs in list order, skipped ones included, then the indel), afs of the head."""
+    n_inst = len(head)
+    inst_indel = np.repeat(np.arange(len(wt), dtype=np.int64), np.diff(inst_off.astype(np.int64)))
+    head = head.astype(np.int64)
+    is_head = head == np.arange(n_inst)
+    row_inst = np.flatnonzero(is_head)
+    n_rows = len(row_inst)
+    row_of_inst = (np.cumsum(is_head) - 1)[head] if n_inst else np.zeros(0, np.int64)
+    row_indel = inst_indel[row_inst]
+    hap_len = wt.rowlen[row_indel].astype(np.uint32)
+    lo, hi = inst_lo.astype(np.int64), inst_hi.astype(np.int64)
+    # members whose entries are not their head's, one by one: the only ones that add a variants string of their own
+    same = (hi - lo) == (hi - lo)[head]
+    cand = np.flatnonzero(same & ~is_head & (hi > lo))
+    if len(cand):
+        mine, owner = _flat_ranges(lo[cand], hi[cand])
+        theirs = lo[head[cand]][owner] + (mine - lo[cand][owner])
+        differs = np.zeros(len(cand), dtype=bool)
+        np.logical_or.at(differs, owner, idx[mine] != idx[theirs])
+        same[cand[differs]] = False
+    ids = vt.id
+    text = lambda k: ",".join([ids[int(sel[j])] for j in idx[lo[k]:hi[k]].tolist()] + [ids[int(wt.sel[inst_indel[k]])]])
+    strings = [{text(int(k))} for k in row_inst]
+    for k in np.flatnonzero(~same).tolist():
+        strings[int(row_of_inst[k])].add(text(k))
+    order = np.argsort(row_of_inst, kind="stable")
+    names = np.asarray(samples, dtype=object)[inst_sample[order]]
+    cuts = np.concatenate(([0], np.cumsum(np.bincount(row_of_inst, minlength=n_rows)))) if n_inst else np.zeros(1, np.int64)
+    segs = {int(k): wt.segments(int(k), startp) for k in np.unique(row_indel)}
+    scans = {k: _window_scan(s, int(startp) + int(wt.a[k]), int(startp) + int(wt.b[k]), region_start, region_stop, pamlen) for k, s in segs.items()}
+    labels, meta = [], []
+    for r in range(n_rows):
+        k, w = int(row_inst[r]), int(row_indel[r])
+        members = names[cuts[r]:cuts[r + 1]].tolist()
+        var_ids = [ids[int(sel[j])] for j in idx[lo[k]:hi[k]].tolist()] + [ids[int(wt.sel[w])]]
+        afs = {}
+        for j in idx[lo[k]:hi[k]].tolist():
+            afs[ids[int(sel[j])]] = vt.af[int(sel[j])]
+        afs[var_ids[-1]] = vt.af[int(wt.sel[w])]
+        labels.append(RowLabel(",".join(sorted(set(members))), ",".join(sorted(strings[r])), afs, f"hap_{row_base + r:08d}", segs[w]))
+        meta.append(HostHaplotype(b"", segs[w], False, scans[w]))
+    # the allele table: the head's applied sites that are not strictly inside a deleted span, at their row positions, and the indel
+    # behind the anchor's own alleles
+    e, owner = _flat_ranges(lo[row_inst], hi[row_inst])
+    w = row_indel[owner]
+    off = v_off[idx[e]].astype(np.int64)
+    a, o, grow = wt.a[w], wt.o[w], wt.grow[w]
+    keep = (off - a < wt.rowlen[w]) & ~((off > o) & (off < o + wt.span[w]))
+    e, owner, off, a, o, grow = e[keep], owner[keep], off[keep], a[keep], o[keep], grow[keep]
+    pos = np.where(off <= o, off - a, off - a + grow)
+    rows = np.concatenate((owner, np.arange(n_rows, dtype=np.int64)))
+    pos = np.concatenate((pos, wt.i[row_indel]))
+    refb = np.concatenate((v_ref[idx[e]].astype(np.uint8), wt.ref_byte[row_indel]))
+    late = np.concatenate((np.zeros(len(e), np.int64), np.ones(n_rows, np.int64)))
+    order = np.lexsort((late, pos, rows))
+    e_key = ((rows[order] + row_base).astype(np.uint64) << np.uint64(32)) | pos[order].astype(np.uint64)
+    first = np.flatnonzero(np.concatenate(([True], e_key[1:] != e_key[:-1]))) if len(e_key) else np.zeros(0, np.int64)
+    alleles = (e_key[first], np.concatenate((first, [len(e_key)])).astype(np.uint32), refb[order])
+    return row_inst.astype(np.uint32), hap_len, labels, meta, alleles
+
+
+def _name_ranks(samples: List[str]) -> np.ndarray:
+    """the sample columns in the order of their sorted names (the order unphased_indel_windows walks an indel's carriers in)"""
+    return np.asarray(sorted(range(len(samples)), key=lambda s: samples[s]), dtype=np.uint32)
+
+
+def unphased_windows_host(region_seq: str, startp: int, block, samples: List[str], codes: np.ndarray, coord, pamlen: int, row_base: int = 1,
+                          forged_sig: Optional[np.ndarray] = None):
+    """The indel-window rows of an unphased block by the host twin (hawk_host_unphased_windows over the lists of
+    hawk_host_unphased_rows; no device).  -> dict(rows: the row strings, labels, meta, alleles, hap_len, row_inst, inst_off,
+    inst_sample, inst_lo, inst_hi, sig, head, table: the IndelTable).  `forged_sig` [n_inst][2] replaces the signatures the grouping
+    reads.  Raises _lib.UnphasedBuildDeclined as expand_unphased_from_vcf(indel_windows="device") does."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import UnphasedBuildDeclined
+    vt = VcfVariants(block)
+    ref = np.frombuffer(region_seq.encode("latin-1", "replace"), dtype=np.uint8)
+    sel, v_line, v_allele, v_off, v_mask, v_ref = unphased_snv_table(block, vt, len(ref), startp)
+    _, _, _, (sample_off, idx), _, _ = unphased_rows_host(region_seq, startp, block, samples, codes)
+    is_snv = np.zeros(len(vt), dtype=bool)
+    is_snv[sel] = True
+    wt = IndelTable(vt, is_snv, len(ref), startp, coord)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    inp, keep = wt.c_input(_name_ranks(samples), ref)
+    lists = _lib.UwinLists(codes.ctypes.data, len(block), len(samples), len(sel), sample_off.ctypes.data, idx.ctypes.data, v_off.ctypes.data,
+                           v_mask.ctypes.data, v_ref.ctypes.data)
+    out, dec = _lib.UwinRows(), _lib.UbuildDecline()
+    L = _lib.lib()
+
+    def call():
+        rc = L.hawk_host_unphased_windows(C.byref(inp), C.byref(lists), C.byref(out), C.byref(dec))
+        if rc != _lib.HAWK_OK and dec.reason:
+            raise UnphasedBuildDeclined(int(dec.reason), vt.id[int(wt.sel[dec.var])] if dec.var >= 0 else "")
+        _lib.check(rc, "hawk_host_unphased_windows")
+    if forged_sig is not None:
+        forged_sig = np.ascontiguousarray(forged_sig, dtype=np.uint64)
+        out.forged_sig = forged_sig.ctypes.data
+    call()  # the counts; then buffers of exactly their size
+    ni, nr, nq = int(out.n_inst), int(out.n_rows), int(out.n_seq)
+    inst_off = np.zeros(len(wt) + 1, np.uint64)
+    inst_sample, inst_lo, inst_hi = np.zeros(ni, np.uint32), np.zeros(ni, np.uint64), np.zeros(ni, np.uint64)
+    sig, head, seqs, seq_off = np.zeros((ni, 2), np.uint64), np.zeros(ni, np.uint32), np.zeros(nq, np.uint8), np.zeros(nr + 1, np.uint64)
+    out.inst_cap, out.row_cap, out.seq_cap = ni, nr, nq
+    out.inst_off, out.inst_sample, out.inst_lo, out.inst_hi = inst_off.ctypes.data, inst_sample.ctypes.data, inst_lo.ctypes.data, inst_hi.ctypes.data
+    out.sig, out.head, out.seqs, out.seq_off = sig.ctypes.data, head.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data
+    call()
+    del keep
+    row_inst, hap_len, labels, meta, alleles = unphased_window_rows(wt, inst_off, inst_sample, inst_lo, inst_hi, head, idx, sel, v_off, v_ref, vt, samples,
+                                                                    startp, coord.start, coord.stop, pamlen, row_base)
+    rows = [seqs[int(seq_off[k]):int(seq_off[k + 1])].tobytes().decode("ascii") for k in range(nr)]
+    return dict(rows=rows, labels=labels, meta=meta, alleles=alleles, hap_len=hap_len, row_inst=row_inst, inst_off=inst_off, inst_sample=inst_sample,
+                inst_lo=inst_lo, inst_hi=inst_hi, sig=sig, head=head, table=wt)
+
+
 def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, samples: List[str], pamlen: int, device: Optional[int] = None,
-                             coord=None, debug: bool = True):
+                             coord=None, debug: bool = True, indel_windows: str = "host"):
     """The haplotype set of an unphased interval with its whole-region rows built on the device: what
     search_guides._device_set(region, haplotypes.add_variants_unphased(...), pamlen) holds, row for row - REF, then one IUPAC row
     per distinct carrier of SNVs (hawk_gt_parse_unphased -> hawk_ubuild_lists -> hawk_ubuild_signatures -> hawk_ubuild_fill: no
@@ -845,6 +1059,12 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
     `coord`: the interval's Coordinate (default: Coordinate(contig of the block, startp, stopp, 0)).
     Returns (DeviceHapSet with is_ref / ref_index set, [RowLabel] per row, the rows' allele table (key, off, ref) in
     search_guides.flatten_variant_alleles' format, the indel-window Haplotype objects, kernel ms {parse, lists, signatures, fill}).
+    `indel_windows="device"`: the window rows are built on the device too, behind the SNV rows of the same set - the indel table
+    comes from VcfVariants and the block's fixed columns, the carriers of every indel from the codes in name order
+    (hawk_uwin_instances), their rows are grouped on a signature over the surviving sites with an exact comparison behind it
+    (hawk_uwin_signatures, hawk_uwin_group) and written by hawk_uwin_fill; labels, segments, scan bounds and the allele-table tail
+    come from the instance arrays (unphased_window_rows).  No VariantRecord, no Haplotype, no row string; the fourth return value
+    is then [], and the ms dict gains window_instances, window_signatures, window_groups and window_fill.
     Raises _lib.UnphasedBuildDeclined where the builder declines (include/hawk.h: HAWK_UBUILD_*); nothing is left allocated."""
     import ctypes as C
     from . import _lib
@@ -859,6 +1079,8 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
     from .variant import VTYPES, VariantRecord
     if len(block) == 0:
         raise ValueError("expand_unphased_from_vcf needs the records of the interval")
+    if indel_windows not in INDEL_WINDOWS:
+        raise ValueError(f"indel_windows {indel_windows!r}: 'host' or 'device'")
     try:
         vt = VcfVariants(block)
     except ValueError as e:
@@ -873,8 +1095,11 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
     seq_obj = Seq_(region_seq, debug)
     region = Region(seq_obj, coord)                         # the Region and the REF haplotype the host route builds
     ref_hap = Haplotype(seq_obj, coord, False, 0, debug)
-    g, u, ds = C.c_void_p(), C.c_void_p(), None
+    g, u, ds, uw = C.c_void_p(), C.c_void_p(), None, C.c_void_p()
     t = C.c_float(0)
+    is_snv = np.zeros(len(vt), dtype=bool)
+    is_snv[sel] = True
+    wt = IndelTable(vt, is_snv, n_ref, startp, coord) if indel_windows == "device" else None
     text = np.ascontiguousarray(block.text)
     _lib.check(L.hawk_gt_parse_unphased(ctx, _p(text), C.c_uint64(len(text)), _p(block.line_off), _p(block.gt_off), C.c_uint64(len(block)),
                                         len(samples), C.byref(g), C.byref(t)), "hawk_gt_parse_unphased")
@@ -889,7 +1114,7 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
         groups: List[List[int]] = []
         sample_off = np.zeros(len(samples) + 1, dtype=np.uint64)
         idx = np.zeros(0, dtype=np.uint32)
-        if len(sel):
+        if len(sel) or (wt is not None and len(wt)):
             rc = L.hawk_ubuild_lists(g, _p(v_line), _p(v_allele), _p(v_off), _p(v_mask), _p(v_ref), len(sel), _p(sample_off), C.byref(u), C.byref(t))
             if rc == _lib.HAWK_E_CAPACITY:
                 raise UnphasedBuildDeclined(6)
@@ -915,9 +1140,32 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
         n_snv_rows = len(groups)
         # ---- the indel windows, on the host: the records of the indels and of the SNVs inside their windows
         windows = []
-        is_snv = np.zeros(len(vt), dtype=bool)
-        is_snv[sel] = True
-        indel_lines = sorted(set(vt.line[~is_snv].tolist()))
+        indel_lines = sorted(set(vt.line[~is_snv].tolist())) if wt is None else []
+        win = None  # the device's window rows: (row_inst, hap_len, labels, meta, alleles)
+        if wt is not None and len(wt):
+            ms.update(window_instances=0.0, window_signatures=0.0, window_groups=0.0, window_fill=0.0)
+            ref_bytes = np.frombuffer(region_seq.encode("latin-1", "replace"), dtype=np.uint8)
+            inp, keep = wt.c_input(_name_ranks(samples), ref_bytes)
+            inst_off = np.zeros(len(wt) + 1, dtype=np.uint64)
+            wdec = _lib.UbuildDecline()
+
+            def declined(rc, where):
+                if rc == _lib.HAWK_E_UNSUPPORTED and wdec.reason:
+                    raise UnphasedBuildDeclined(int(wdec.reason), vt.id[int(wt.sel[wdec.var])] if wdec.var >= 0 else "")
+                _lib.check(rc, where)
+            declined(L.hawk_uwin_instances(g, u, C.byref(inp), _p(inst_off), C.byref(uw), C.byref(wdec), C.byref(t)), "hawk_uwin_instances")
+            del keep
+            ms["window_instances"] = float(t.value)
+            n_inst = int(inst_off[-1])
+            inst_sample, inst_lo, inst_hi = np.zeros(n_inst, np.uint32), np.zeros(n_inst, np.uint64), np.zeros(n_inst, np.uint64)
+            wsig, whead = np.zeros((n_inst, 2), np.uint64), np.zeros(n_inst, np.uint32)
+            _lib.check(L.hawk_uwin_download(uw, _p(inst_sample), _p(inst_lo), _p(inst_hi)), "hawk_uwin_download")
+            declined(L.hawk_uwin_signatures(uw, _p(wsig), C.byref(wdec), C.byref(t)), "hawk_uwin_signatures")
+            ms["window_signatures"] = float(t.value)
+            _lib.check(L.hawk_uwin_group(uw, _p(wsig), _p(whead), C.byref(t)), "hawk_uwin_group")
+            ms["window_groups"] = float(t.value)
+            win = unphased_window_rows(wt, inst_off, inst_sample, inst_lo, inst_hi, whead, idx, sel, v_off, v_ref, vt, samples, startp,
+                                       region.start, region.stop, pamlen, 1 + n_snv_rows)
         if indel_lines:
             recs: Dict[int, VariantRecord] = {}
 
@@ -939,9 +1187,14 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
             windows = hap_mod.unphased_indel_windows(region, indels, snvs, False, debug)
         # ---- the set: REF, the SNV rows, the window rows
         hap_len = np.array([n_ref] * (1 + n_snv_rows) + [len(w.sequence) for w in windows], dtype=np.uint32)
+        if win is not None:
+            hap_len = np.concatenate((hap_len, win[1]))
         ds = DeviceHapSet.allocate(hap_len, device)
         ds.pack_rows(0, [ref_hap.array])
         ds.pack_rows(1 + n_snv_rows, [w.array for w in windows])
+        if win is not None and len(win[0]):
+            _lib.check(L.hawk_uwin_fill(uw, ds._h, 0, 1 + n_snv_rows, len(win[0]), _p(win[0]), C.byref(t)), "hawk_uwin_fill")
+            ms["window_fill"] = float(t.value)
         if n_snv_rows:
             row_sample = np.array([m[0] for m in groups], dtype=np.uint32)
             dec = C.c_int64(-1)
@@ -953,6 +1206,8 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
         ref_scan = compute_scan_start_stop(ref_hap, region.start, region.stop, pamlen)
         meta = [HostHaplotype(b"", ref_hap.segments, True, ref_scan)] + [HostHaplotype(b"", ref_hap.segments, False, ref_scan)] * n_snv_rows
         meta += [HostHaplotype(b"", w.segments, w.samples == "REF", compute_scan_start_stop(w, region.start, region.stop, pamlen)) for w in windows]
+        if win is not None:
+            meta += win[3]
         ds.set_meta(meta)
         # ---- labels and the allele table
         labels = [RowLabel("REF", "NA", {}, "hap_00000000", ref_hap.segments)]
@@ -966,11 +1221,19 @@ def expand_unphased_from_vcf(region_seq: str, startp: int, stopp: int, block, sa
             key = np.concatenate((key, k2 + (np.uint64(1 + n_snv_rows) << np.uint64(32))))
             off = np.concatenate((off, o2[1:] + np.uint32(len(ref)))).astype(np.uint32)
             ref = np.concatenate((ref, r2)).astype(np.uint8)
+        if win is not None:
+            labels += win[2]
+            k2, o2, r2 = win[4]
+            key = np.concatenate((key, k2))
+            off = np.concatenate((off, o2[1:] + np.uint32(len(ref)))).astype(np.uint32)
+            ref = np.concatenate((ref, r2)).astype(np.uint8)
         out, ds = ds, None
         return out, labels, (key, off, ref), windows, ms
     finally:
         if ds is not None:
             ds.close()
+        if uw:
+            L.hawk_uwin_free(uw)
         if u:
             L.hawk_ubuild_free(u)
         L.hawk_gt_destroy(g)

@@ -560,6 +560,31 @@ void hawk_launch_ub_sig(hipStream_t st, const UbLists& l, unsigned long long* si
 void hawk_launch_ub_rows(hipStream_t st, uint32_t* const* plane, uint32_t S, uint32_t ref_row, uint32_t first_row, uint32_t n_rows,
                          const uint32_t* row_sample, const UbLists& l, unsigned long long* decline /* ~0 */);
 
+// ---- the indel-window rows of an unphased VCF (hawk_uwin.hip; the rules themselves: hawk_uwin.h)
+#include "hawk_uwin.h"
+struct UwDev {                  // device pointers
+  uint32_t n_indel, n_samples, L;
+  uint64_t n_inst;
+  const uint32_t* line;         // [n_indel] the record of each indel allele, in (record, allele) order
+  const uint8_t* allele;        // [n_indel] its allele number
+  const uint32_t* off;          // [n_indel] its normalised offset in the region
+  const uint32_t *ref_len, *alt_len;
+  const uint32_t* pool_off;     // [n_indel] where its ref bases, then its alt bases, start in `pool`
+  const uint8_t* pool;          // ub_base_index of every base
+  const uint32_t* rank_sample;  // [n_samples] the sample columns in the order of their sorted names
+  const uint8_t* ref;           // [L] REF's bytes
+  const uint64_t* inst_off;     // [n_indel + 1] CSR of the instances
+  uint32_t *inst_indel, *inst_sample;
+  uint64_t *inst_lo, *inst_hi;  // the carrier's list entries inside the window
+};
+void hawk_launch_uw_count(hipStream_t st, const uint8_t* codes, const UwDev& d, unsigned long long* ballots, uint32_t* count /* [n_indel] */,
+                          unsigned long long* decline /* ~0; indel << 8 | reason */);
+void hawk_launch_uw_instances(hipStream_t st, const UwDev& d, const UbLists& l, const unsigned long long* ballots);
+void hawk_launch_uw_sig(hipStream_t st, const UwDev& d, const UbLists& l, unsigned long long* sig /* [n_inst][2] */, unsigned long long* decline);
+void hawk_launch_uw_group(hipStream_t st, const UwDev& d, const UbLists& l, const unsigned long long* sig, uint32_t* head /* [n_inst] */);
+void hawk_launch_uw_fill(hipStream_t st, uint32_t* const* plane, uint32_t S, uint32_t ref_row, uint32_t first_row, uint32_t n_rows,
+                         uint32_t qpr /* threads per row */, const uint32_t* row_inst, const UwDev& d, const UbLists& l);
+
 #define FX_TOPK_MAX_BLOCKS 1024u
 void hawk_launch_fx_isref_gather(hipStream_t st, const uint8_t* hap_is_ref, const uint32_t* member_hap, const uint64_t* member_off, uint64_t n_groups, uint8_t* out);
 void hawk_launch_fx_groups(hipStream_t st, const FxDev& F);

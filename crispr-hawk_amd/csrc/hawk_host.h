@@ -317,6 +317,27 @@ struct hawk_ubuild {
   }
 };
 
+// the indel table of an unphased block and its (indel, carrier) instances, in HBM (hawk_api_uwin.hip)
+struct hawk_uwin {
+  hawk_ctx* ctx;
+  hawk_ubuild* u = nullptr;             // the SNV lists the instances index: the caller's, it outlives this object
+  uint32_t n_indel = 0, n_samples = 0, L = 0;
+  uint64_t n_inst = 0;
+  DevBuf line, allele, off, ref_len, alt_len, pool_off, pool, rank_sample, ref, inst_off, inst_indel, inst_sample, inst_lo, inst_hi;
+  std::vector<uint32_t> h_off, h_ref_len, h_alt_len;  // [n_indel]
+  std::vector<uint64_t> h_inst_off;                  // [n_indel + 1]
+  UwDev view() const {
+    UwDev d;
+    d.n_indel = n_indel; d.n_samples = n_samples; d.L = L; d.n_inst = n_inst;
+    d.line = line.as<uint32_t>(); d.allele = allele.as<uint8_t>(); d.off = off.as<uint32_t>(); d.ref_len = ref_len.as<uint32_t>();
+    d.alt_len = alt_len.as<uint32_t>(); d.pool_off = pool_off.as<uint32_t>(); d.pool = pool.as<uint8_t>();
+    d.rank_sample = rank_sample.as<uint32_t>(); d.ref = ref.as<uint8_t>(); d.inst_off = inst_off.as<uint64_t>();
+    d.inst_indel = inst_indel.as<uint32_t>(); d.inst_sample = inst_sample.as<uint32_t>(); d.inst_lo = inst_lo.as<uint64_t>();
+    d.inst_hi = inst_hi.as<uint64_t>();
+    return d;
+  }
+};
+
 struct hawk_table {
   hawk_hapset* hs;  // nullptr for a merged table (hawk_table_gather): it owns its columns
   hawk_ctx* ctx;

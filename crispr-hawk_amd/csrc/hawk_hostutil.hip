@@ -19,6 +19,7 @@
 #include "hawk_resolve.h"
 #include "hawk_ugroups.h"
 #include "hawk_ubuild.h"
+#include "hawk_uwin.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -1400,6 +1401,112 @@ int hawk_host_unphased_rows(const hawk_ubuild_input* in, hawk_ubuild_rows* out, 
   }
   if (out->member_off) out->member_off[nr] = (uint32_t)mi;
   if (out->al_off) out->al_off[nk] = (uint32_t)ei;
+  return HAWK_OK;
+}
+
+// ---- the indel-window rows of an unphased VCF (hawk_uwin.h): the host twin of hawk_uwin_instances / _signatures / _group / _fill
+int hawk_host_unphased_windows(const hawk_uwin_input* in, const hawk_uwin_lists* lists, hawk_uwin_rows* out, hawk_ubuild_decline* decline) {
+  if (decline) { decline->reason = 0; decline->reserved = 0; decline->var = -1; }
+  if (!in || !lists || !out) return HAWK_E_INVALID;
+  out->n_inst = out->n_rows = out->n_seq = 0;
+  const uint32_t ni = in->n_indel, ns = lists->n_samples, L = in->region_len;
+  if (!ns || !L || !in->ref || !in->rank_sample || !lists->sample_off || (lists->n_lines && !lists->codes)) return HAWK_E_INVALID;
+  if (ni && (!in->line || !in->allele || !in->off || !in->ref_len || !in->alt_len || !in->pool_off || !in->pool)) return HAWK_E_INVALID;
+  const uint64_t ne = lists->sample_off[ns];
+  if (ne && (!lists->list_idx || !lists->var_off || !lists->var_mask || !lists->var_ref)) return HAWK_E_INVALID;
+  for (uint32_t s = 0; s < ns; ++s)
+    if (lists->sample_off[s + 1] < lists->sample_off[s]) return HAWK_E_INVALID;
+  for (uint64_t e = 0; e < ne; ++e)
+    if (lists->list_idx[e] >= lists->n_var || lists->var_off[lists->list_idx[e]] >= L || lists->var_ref[lists->list_idx[e]] > 3 ||
+        lists->var_mask[lists->list_idx[e]] > 15)
+      return HAWK_E_INVALID;
+  for (uint32_t k = 0; k < ni; ++k)
+    if (in->line[k] >= lists->n_lines || in->allele[k] == 0 || in->allele[k] == 255 ||
+        (uint64_t)in->pool_off[k] + in->ref_len[k] + in->alt_len[k] > in->pool_len)
+      return HAWK_E_INVALID;
+  {
+    std::vector<uint8_t> seen(ns, 0);
+    for (uint32_t r = 0; r < ns; ++r) {
+      if (in->rank_sample[r] >= ns || seen[in->rank_sample[r]]) return HAWK_E_INVALID;
+      seen[in->rank_sample[r]] = 1;
+    }
+  }
+  auto declined = [&](int reason, int64_t indel) {
+    if (decline) { decline->reason = reason; decline->var = indel; }
+    return HAWK_E_UNSUPPORTED;
+  };
+  const UwLists l{lists->list_idx, lists->var_off, lists->var_mask, lists->var_ref};
+  // instances in (indel, name rank) order; an indel nobody carries is never looked at
+  std::vector<uint64_t> inst_off((size_t)ni + 1, 0), lo, hi;
+  std::vector<uint32_t> inst_indel, inst_sample;
+  std::vector<UwGeom> geom(ni);
+  for (uint32_t k = 0; k < ni; ++k) {
+    bool checked = false;
+    for (uint32_t r = 0; r < ns; ++r) {
+      const uint32_t s = in->rank_sample[r];
+      const uint8_t* c = lists->codes + ((size_t)in->line[k] * ns + s) * 2u;
+      if (!ub_carried(c[0], c[1], in->allele[k])) continue;
+      if (!checked) {
+        const int why = uw_geometry(in->off[k], in->ref_len[k], in->alt_len[k], L, &geom[k]);
+        if (why) return declined(why, k);
+        if (!uw_bases_ok(in->pool + in->pool_off[k], in->ref_len[k] + in->alt_len[k])) return declined(UB_DECL_INDEL_BASE, k);
+        checked = true;
+      }
+      const uint64_t a = uw_lower_bound(l, lists->sample_off[s], lists->sample_off[s + 1], geom[k].a);
+      inst_indel.push_back(k); inst_sample.push_back(s);
+      lo.push_back(a); hi.push_back(uw_lower_bound(l, a, lists->sample_off[s + 1], geom[k].b + 1u));
+    }
+    inst_off[k + 1] = inst_indel.size();
+  }
+  const uint64_t n = inst_indel.size();
+  if (n >= 0xffffffffull) return HAWK_E_CAPACITY;
+  std::vector<uint64_t> sig(2 * n, 0);
+  for (uint64_t k = 0; k < n; ++k) {
+    const UwGeom& g = geom[inst_indel[k]];
+    uw_signature(l, g, lo[k], hi[k], &sig[2 * k], &sig[2 * k + 1]);
+    if (uw_check_ref(l, g, lo[k], hi[k], (const uint8_t*)in->ref, in->pool + in->pool_off[inst_indel[k]])) return declined(UB_DECL_REF, inst_indel[k]);
+  }
+  const uint64_t* gs = out->forged_sig ? out->forged_sig : sig.data();
+  std::vector<uint32_t> head(n);
+  uint64_t nr = 0, nseq = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    const UwGeom& g = geom[inst_indel[k]];
+    uint64_t h = k;
+    for (uint64_t c = inst_off[inst_indel[k]]; c < k; ++c)
+      if (gs[2 * c] == gs[2 * k] && gs[2 * c + 1] == gs[2 * k + 1] && uw_same_row(l, g, lo[c], hi[c], lo[k], hi[k])) { h = c; break; }
+    head[k] = (uint32_t)h;
+    if (h == k) { ++nr; nseq += g.rowlen; }
+  }
+  out->n_inst = n; out->n_rows = nr; out->n_seq = nseq;
+  if ((out->inst_sample || out->inst_lo || out->inst_hi || out->sig || out->head) && out->inst_cap < n) return HAWK_E_CAPACITY;
+  if (out->seq_off && out->row_cap < nr) return HAWK_E_CAPACITY;
+  if (out->seqs && out->seq_cap < nseq) return HAWK_E_CAPACITY;
+  if (out->inst_off) std::copy(inst_off.begin(), inst_off.end(), out->inst_off);
+  if (out->inst_sample) std::copy(inst_sample.begin(), inst_sample.end(), out->inst_sample);
+  if (out->inst_lo) std::copy(lo.begin(), lo.end(), out->inst_lo);
+  if (out->inst_hi) std::copy(hi.begin(), hi.end(), out->inst_hi);
+  if (out->sig) std::copy(sig.begin(), sig.end(), out->sig);
+  if (out->head) std::copy(head.begin(), head.end(), out->head);
+  static const char kLower[] = "?acmgrsvtwyhkdbn";
+  uint64_t ri = 0, si = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (head[k] != k) continue;
+    const UwGeom& g = geom[inst_indel[k]];
+    if (out->seq_off) out->seq_off[ri] = si;
+    if (out->seqs) {
+      char* row = out->seqs + si;
+      const uint8_t* alt = in->pool + in->pool_off[inst_indel[k]] + in->ref_len[inst_indel[k]];
+      for (uint32_t p = 0; p < g.rowlen; ++p) {
+        const int64_t src = uw_source(g, p);
+        row[p] = src >= 0 ? in->ref[src] : "acgt"[alt[-src - 1]];
+      }
+      uint64_t e = lo[k];
+      uint32_t off, bits;
+      while (uw_next_surviving(l, g, &e, hi[k], &off, &bits)) row[uw_site_pos(g, off)] = kLower[bits & 15u];
+    }
+    ++ri; si += g.rowlen;
+  }
+  if (out->seq_off) out->seq_off[nr] = si;
   return HAWK_OK;
 }
 

@@ -1035,6 +1035,89 @@ int hawk_hapset_pack_ascii_rows(hawk_hapset* hs, uint32_t first_row, uint32_t n_
                                 uint64_t* bad_index);
 int hawk_host_unphased_rows(const hawk_ubuild_input* in, hawk_ubuild_rows* out, hawk_ubuild_decline* decline);
 
+/* ---- the indel-window rows of an unphased VCF on the device: what haplotypes.unphased_indel_windows builds per indel allele
+ * inside the region and per carrier - the region cut to 100 nt either side of the indel, the indel and the carrier's SNVs inside
+ * that window applied, equal rows of one indel merged - from the genotype codes (hawk_gt_parse_unphased) and the per-sample SNV
+ * lists (hawk_ubuild_lists), without a record object or a row string.  The rules are stated once, in csrc/hawk_uwin.h (geometry,
+ * which sites are applied and which survive, the ref check, the signature), for the kernels (hawk_uwin.hip) and for
+ * hawk_host_unphased_windows.
+ *
+ * hawk_uwin_input: the indel alleles in (record, allele) order - the caller leaves out those outside the interval as given
+ *   (indel_in_region) - each with its record line[k], allele number allele[k], NORMALISED offset off[k] in the region
+ *   (adjust_multiallelic), ref_len[k] / alt_len[k], and pool_off[k]: where ub_base_index of its ref bases, then of its alt bases,
+ *   starts in pool[pool_len] (255: outside A/C/G/T).  rank_sample[n_samples]: the sample columns in the order of their sorted
+ *   names (a permutation); ref[region_len]: REF's bytes.
+ * hawk_uwin_instances: an instance is one (indel, carrier).  Instances are ordered by (indel, rank of the carrier's name);
+ *   inst_off[n_indel + 1] (host) receives their CSR offsets, hawk_uwin_download the carrier (its column) and the [lo, hi) range
+ *   of the carrier's list entries (indices into the entries of hawk_ubuild_lists_download) with an offset inside the window.
+ *   `u` stays the caller's and must outlive *out.  An indel nobody carries is never looked at.  Declines (HAWK_E_UNSUPPORTED,
+ *   reason and indel in *decline; nothing left allocated): HAWK_UBUILD_WINDOW, HAWK_UBUILD_INDEL_BASE, and HAWK_UBUILD_REF for an
+ *   alt of a deletion or a ref of an insertion longer than one base.  HAWK_E_INVALID: a line, allele number, pool range or rank the
+ *   inputs do not have, `u` of another genotype block.
+ * hawk_uwin_signatures: sig[n_inst][2], ub_sig_add over each instance's SURVIVING sites (an instance without one gives (0, 0)),
+ *   and the ref check of every instance: HAWK_UBUILD_REF where the row does not hold the indel's ref (REF's base exactly, or a
+ *   letter of the carrier's site there).
+ * hawk_uwin_group: head[k] = the first instance of k's indel whose surviving sites equal k's one by one, k itself if there is
+ *   none: the instances with head[k] == k, in order, are the distinct rows in first-seen order.  `sig` (host, [n_inst][2]) only
+ *   proposes: whatever values the caller passes - all equal, say - the heads are the same.
+ * hawk_uwin_fill: rows [first_row, first_row + n_rows) of an ordinary set become the window rows of instances row_inst[r]: source
+ *   before the anchor | the alt with the V bit on every base | source behind the span, the surviving sites OR-ed in (ACGT bits
+ *   REF's | the carried alts', V set); words past a row's length are zero, as hawk_hapset_pack_ascii leaves them.  Row ref_row
+ *   holds REF, packed already.  HAWK_E_INVALID, nothing written: rows outside the set, REF among them, a row whose length is not
+ *   the instance's, a REF row shorter than the region.
+ * hawk_host_unphased_windows: the same instances, signatures, heads and rows from host arrays by the same header,
+ *   single-threaded, no device.  The SNV lists are passed as hawk_host_unphased_rows (or the device) gave them.  Counts are
+ *   always written; an output that is not NULL needs its capacity, else HAWK_E_CAPACITY.  out->forged_sig, if not NULL, replaces
+ *   the signatures the grouping step reads (out->sig still receives the true ones). */
+#define HAWK_UBUILD_WINDOW 8     /* an indel that does not fit the window the host builder cuts around it */
+#define HAWK_UBUILD_INDEL_BASE 9 /* a base of an indel's ref or alt outside A/C/G/T */
+typedef struct hawk_uwin hawk_uwin;
+typedef struct {
+  uint32_t n_indel, region_len;
+  const uint32_t* line;
+  const uint8_t* allele;
+  const uint32_t* off;
+  const uint32_t* ref_len;
+  const uint32_t* alt_len;
+  const uint32_t* pool_off;
+  const uint8_t* pool;
+  uint64_t pool_len;
+  const uint32_t* rank_sample; /* [n_samples] */
+  const char* ref;             /* [region_len] */
+} hawk_uwin_input;
+typedef struct {
+  const uint8_t* codes; /* [n_lines][2 * n_samples] */
+  uint64_t n_lines;
+  uint32_t n_samples, n_var;
+  const uint64_t* sample_off; /* [n_samples + 1] */
+  const uint32_t* list_idx;
+  const uint32_t* var_off;
+  const uint8_t* var_mask;
+  const uint8_t* var_ref;
+} hawk_uwin_lists;
+typedef struct {
+  uint64_t inst_cap, row_cap, seq_cap;
+  uint64_t* inst_off;    /* [n_indel + 1] */
+  uint32_t* inst_sample; /* [inst_cap] */
+  uint64_t* inst_lo;     /* [inst_cap] */
+  uint64_t* inst_hi;     /* [inst_cap] */
+  uint64_t* sig;         /* [inst_cap][2] */
+  uint32_t* head;        /* [inst_cap] */
+  const uint64_t* forged_sig; /* [n_inst][2] or NULL */
+  char* seqs;            /* [seq_cap]: the distinct rows as cased ASCII, back to back */
+  uint64_t* seq_off;     /* [row_cap + 1] */
+  uint64_t n_inst, n_rows, n_seq;
+} hawk_uwin_rows;
+int hawk_uwin_instances(hawk_gt* g, hawk_ubuild* u, const hawk_uwin_input* in, uint64_t* inst_off, hawk_uwin** out,
+                        hawk_ubuild_decline* decline, float* kernel_ms);
+int hawk_uwin_download(hawk_uwin* w, uint32_t* inst_sample, uint64_t* inst_lo, uint64_t* inst_hi);
+int hawk_uwin_signatures(hawk_uwin* w, uint64_t* sig, hawk_ubuild_decline* decline, float* kernel_ms);
+int hawk_uwin_group(hawk_uwin* w, const uint64_t* sig, uint32_t* head, float* kernel_ms);
+int hawk_uwin_fill(hawk_uwin* w, hawk_hapset* hs, uint32_t ref_row, uint32_t first_row, uint32_t n_rows, const uint32_t* row_inst,
+                   float* kernel_ms);
+void hawk_uwin_free(hawk_uwin* w);
+int hawk_host_unphased_windows(const hawk_uwin_input* in, const hawk_uwin_lists* lists, hawk_uwin_rows* out, hawk_ubuild_decline* decline);
+
 /* ---- PLM-CRISPR (scores/plm_crispr/train_general.py, class sgrna_net, forward with train=False; wrapper
  * scores/plm_crispr/plm_crispr.py:136-258): n guide+PAM 23-mers -> n fp32 scores, all arithmetic in fp32 (lin1 and lin3 on the
  * f32-input MFMA).  The 83 MB of parameters and the protein branch's result live in HBM behind a handle.
