@@ -49,6 +49,7 @@ EXPORTS = [
     "hawk_uwin_instances", "hawk_uwin_download", "hawk_uwin_signatures", "hawk_uwin_group", "hawk_uwin_fill", "hawk_uwin_free",
     "hawk_host_unphased_windows",
     "hawk_plm_create", "hawk_plm_protein", "hawk_plm_score", "hawk_plm_timing", "hawk_plm_free",
+    "hawk_bgzf_inflate", "hawk_host_bgzf_inflate",
 ]
 
 
@@ -111,6 +112,11 @@ class GnomadTiming(C.Structure):
     _fields_ = [("upload_ms", C.c_float), ("scan_ms", C.c_float), ("len_ms", C.c_float), ("prefix_ms", C.c_float),
                 ("fill_ms", C.c_float), ("total_ms", C.c_float), ("n_records", C.c_uint64), ("n_kept", C.c_uint64),
                 ("out_bytes", C.c_uint64)]
+
+
+class BgzfTiming(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("inflate_ms", C.c_float), ("download_ms", C.c_float), ("total_ms", C.c_float),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("n_members", C.c_uint32), ("n_failed", C.c_uint32)]
 
 
 class EffectsColumns(C.Structure):

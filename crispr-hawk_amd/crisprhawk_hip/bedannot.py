@@ -53,11 +53,11 @@ class BedAnnotation:
     `fetch_features(contig, start, stop)` has the reference's meaning (the overlapping lines in file order, None for a contig
     the file does not have) and is the host-side statement of the overlap rule."""
 
-    def __init__(self, fname: str, verbosity: int = 0, debug: bool = True) -> None:
+    def __init__(self, fname: str, verbosity: int = 0, debug: bool = True, inflate: Optional[str] = None) -> None:
         from .readers import _TextSource
         self._fname, self._verbosity, self._debug = fname, verbosity, debug
         try:
-            self._src = _TextSource(fname)
+            self._src = _TextSource(fname, inflate, verbosity)  # `inflate`: who inflates a BGZF file's members (readers.inflate_route)
         except OSError as e:
             exception_handler(CrisprHawkAnnotationError, f"Cannot read annotation BED {fname}", os.EX_DATAERR, debug, e)
         self._contigs: Dict[str, _Contig] = {}

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from .crisprhawk_error import CrisprHawkConverterError
 from .exception_handlers import exception_handler
-from .readers import BgzfWriter, _TextSource
+from .readers import BgzfWriter, _TextSource, inflate_route
 from .utils import VERBOSITYLVL, print_verbosity
 
 # gnomAD populations (9 superpopulations and 1 collecting minority samples), the reference's order (converter.py:19-30)
@@ -295,12 +295,16 @@ def make_header(header_lines: List[bytes], joint: bool, fname: str, debug: bool)
 
 
 def convert_vcf(vcf_fname: str, joint: bool, keep: bool, suffix: str, outdir: str, verbosity: int, debug: bool, engine: str = "device",
-                device: Optional[int] = None, threads: int = 1) -> dict:
+                device: Optional[int] = None, threads: int = 1, inflate: Optional[str] = None) -> dict:
     """One sites VCF (plain, gzip or BGZF) -> `<outdir>/<name>.<suffix>.vcf.gz` (BGZF, no index: the package's reader builds its
     own).  Returns {"path", "engine", "records", "kept", "timing"}; failures go through exception_handler as
-    CrisprHawkConverterError / os.EX_DATAERR, and no temporary file survives one."""
+    CrisprHawkConverterError / os.EX_DATAERR, and no temporary file survives one.  `inflate`: who inflates a BGZF input's members
+    (readers.inflate_route: None reads HAWK_BGZF_INFLATE, default "zlib"); timing["inflate_route"] names it, and on "device"
+    timing["inflate_ms"] is the sum of the kernel's laps."""
     if engine not in ("device", "host"):
         raise ValueError(f"engine must be 'device' or 'host', not {engine!r}")
+    route = inflate_route(inflate)
+    source = None
     print_verbosity(f"Converting VCF {os.path.basename(vcf_fname)}", verbosity, VERBOSITYLVL[2])
     t_start = time.perf_counter()
     if not os.path.isfile(vcf_fname):
@@ -317,7 +321,9 @@ def convert_vcf(vcf_fname: str, joint: bool, keep: bool, suffix: str, outdir: st
     limit = batch_bytes()
 
     def timed_chunks():
-        it = _TextSource(vcf_fname).chunks()
+        nonlocal source
+        source = _TextSource(vcf_fname, route, verbosity)
+        it = source.chunks()
         while True:
             t0 = time.perf_counter()
             try:
@@ -378,7 +384,9 @@ def convert_vcf(vcf_fname: str, joint: bool, keep: bool, suffix: str, outdir: st
             os.remove(tmp_path)
     if failure:
         exception_handler(CrisprHawkConverterError, f"{failure} ({vcf_fname})", os.EX_DATAERR, debug)
-    timing = dict(secs, **ms, total=time.perf_counter() - t_start, batches=n_batches, in_bytes=in_bytes)
+    timing = dict(secs, **ms, total=time.perf_counter() - t_start, batches=n_batches, in_bytes=in_bytes, inflate_route=route)
+    if route == "device":
+        timing["inflate_ms"] = source.inflate_ms
     print_verbosity(f"{os.path.basename(vcf_fname)} converted in {timing['total']:.2f}s", verbosity, VERBOSITYLVL[3])
     return {"path": out_path, "engine": engine, "records": records, "kept": kept, "timing": timing}
 

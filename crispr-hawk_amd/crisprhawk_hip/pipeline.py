@@ -65,11 +65,12 @@ class AnnotationSet:
     """The annotation files of one search_files call: opened once, one device table per (file, contig) made on first use and
     reused across BED intervals.  `columns(contig)` is what reports.group_columns / report_frame take as `annotations`."""
 
-    def __init__(self, annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug: bool):
+    def __init__(self, annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug: bool,
+                 inflate: Optional[str] = None):
         from .bedannot import FUNC, GENE, BedAnnotation
         self.device = device
-        self.func = [BedAnnotation(f, 0, debug) for f in (annotations or [])]
-        self.gene = [BedAnnotation(f, 0, debug) for f in (gene_annotations or [])]
+        self.func = [BedAnnotation(f, 0, debug, inflate) for f in (annotations or [])]
+        self.gene = [BedAnnotation(f, 0, debug, inflate) for f in (gene_annotations or [])]
         for b in self.func:
             b.require(FUNC)
         for b in self.gene:
@@ -369,7 +370,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                  graphical_reports: bool = False,
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
                  unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, unphased_effects: bool = False,
-                 unphased_haplotypes: Optional[str] = None, unphased_indel_windows: Optional[str] = None,
+                 unphased_haplotypes: Optional[str] = None, unphased_indel_windows: Optional[str] = None, bgzf_inflate: Optional[str] = None,
                  annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
@@ -433,7 +434,12 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     takes effect only where `unphased_haplotypes="device"` does; elsewhere a line at verbosity level 3 says it was not used.  Where
     the window builder declines (an indel that does not fit its window, an indel base outside A/C/G/T, an indel ref the row does not
     hold) the interval is rebuilt one step down - device SNV rows, host windows - with a level-3 line naming reason and variant;
-    if that declines too, the host builder takes over as above.  (Everything from `timings` on is meant to be passed by keyword.)"""
+    if that declines too, the host builder takes over as above.
+    `bgzf_inflate` (None reads HAWK_BGZF_INFLATE, else "zlib"): who inflates the members of bgzipped VCF and annotation files -
+    "zlib" on this thread, "native" the library's host decoder, "device" its kernel (readers._TextSource); the text, and so every
+    output, is the same on all three.  (Everything from `timings` on is meant to be passed by keyword.)"""
+    from .readers import inflate_route
+    bgzf_inflate = inflate_route(bgzf_inflate)
     if unphased_report not in UNPHASED_REPORTS:
         raise ValueError(f"unphased_report {unphased_report!r}: None, 'groups' or 'objects'")
     if unphased_haplotypes not in UNPHASED_HAPLOTYPES:
@@ -490,7 +496,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     fastas = {fa.contig: fa}
     vcf_by_contig = {}
     for f in vcfs or []:
-        v = VCF(f, 0, debug)
+        v = VCF(f, 0, debug, inflate=bgzf_inflate)
         vcf_by_contig[v.contig] = v
     score = cfd_tables is not None and pam.cas_system in (SPCAS9, XCAS9) and not right
     mmt, pt = cfd_tables if score else (None, None)
@@ -503,7 +509,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     lap("open inputs (FASTA index, VCF header + line index)")
     ann = None
     if annotations or gene_annotations:
-        ann = AnnotationSet(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug)
+        ann = AnnotationSet(annotations, annotation_colnames, gene_annotations, gene_annotation_colnames, device, debug, bgzf_inflate)
         if ot is not None:
             ot["ann"] = ann
         lap("open annotation BED files")

@@ -166,16 +166,72 @@ class VcfBlock:
         return len(self.gt_off)
 
 
+INFLATE_ROUTES = ("zlib", "native", "device")
+BZ_STATUS = ("ok", "no gzip member", "a gzip header bgzip does not write", "the member ends before its stream", "ISIZE and the stream disagree",
+             "an invalid block", "an invalid code set or code", "an invalid symbol", "a distance before the member's first byte")
+
+
+def inflate_route(inflate: Optional[str]) -> str:
+    """which code inflates BGZF members: the argument, else HAWK_BGZF_INFLATE, else "zlib" """
+    if inflate is not None:
+        if inflate not in INFLATE_ROUTES:
+            raise ValueError(f"inflate {inflate!r}: None, 'zlib', 'native' or 'device'")
+        return inflate
+    route = os.environ.get("HAWK_BGZF_INFLATE") or "zlib"
+    if route not in INFLATE_ROUTES:
+        raise ValueError(f"HAWK_BGZF_INFLATE={route!r}: 'zlib', 'native' or 'device'")
+    return route
+
+
+def host_inflate_threads() -> int:
+    """threads of the "native" route: OMP_NUM_THREADS, else 16 - never the machine's core count, which a shared host does not grant"""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", ""))
+    except ValueError:
+        n = 0
+    return n if n > 0 else 16
+
+
+def bgzf_inflate(route: str, raw: np.ndarray, c_off: np.ndarray, u_off: np.ndarray, out: np.ndarray, device: Optional[int] = None):
+    """Members raw[c_off[k], c_off[k + 1]) -> out[u_off[k], u_off[k + 1]) by the library (include/hawk.h: hawk_host_bgzf_inflate for
+    "native", hawk_bgzf_inflate for "device").  Returns (status uint8 per member, the device call's timing or None); a member whose
+    status is not 0 has failed and its bytes of `out` mean nothing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.lib()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    c_off, u_off = np.ascontiguousarray(c_off, dtype=np.uint64), np.ascontiguousarray(u_off, dtype=np.uint64)
+    n = len(c_off) - 1
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    if route == "native":
+        rc = L.hawk_host_bgzf_inflate(p(raw), C.c_uint64(raw.size), p(c_off), p(u_off), C.c_uint32(n), p(out), p(status), C.c_uint32(host_inflate_threads()))
+        tm = None
+    else:
+        tm = _lib.BgzfTiming()
+        rc = L.hawk_bgzf_inflate(_lib.context(device), p(raw), C.c_uint64(raw.size), p(c_off), p(u_off), C.c_uint32(n), p(out), p(status), C.byref(tm))
+    if rc not in (_lib.HAWK_OK, _lib.HAWK_E_INVALID) or (rc == _lib.HAWK_E_INVALID and not status[:n].any()):
+        _lib.check(rc, "hawk_bgzf_inflate" if route == "device" else "hawk_host_bgzf_inflate")
+    return status[:n], tm
+
+
 class _TextSource:
     """Random access to the (decompressed) bytes of a VCF without holding them: a plain text file is read by seek; a
     BGZF file (bgzip: independent <= 64 KB gzip members with their size in the header's BC field) by inflating only the
     blocks a byte range touches; a plain gzip stream has no random access and is held decompressed (the one case that
-    costs memory).  `chunks()` streams the whole text once for the index pass."""
+    costs memory).  `chunks()` streams the whole text once for the index pass.
+
+    `inflate` chooses who inflates BGZF members (`inflate_route`): "zlib" one member at a time on this thread, "native" the
+    library's host decoder on several threads, "device" its kernel - both a chunk's or a range's members in one call, with the same
+    chunk boundaries and bytes as "zlib".  A member they refuse sends its chunk or range to the zlib loop, which raises or succeeds as
+    it always did.  Plain text and plain gzip ignore the switch: one serial stream has no independent members."""
 
     CHUNK = 32 << 20
 
-    def __init__(self, fname: str):
+    def __init__(self, fname: str, inflate: Optional[str] = None, verbosity: int = 0):
         self.fname = fname
+        self.inflate = inflate_route(inflate)
+        self._verbosity = verbosity
+        self.inflate_ms = self.upload_ms = self.download_ms = 0.0  # the "device" route: the laps of its calls, summed
         with open(fname, "rb") as f:
             head = f.read(18)
         self.kind = "plain"
@@ -214,6 +270,32 @@ class _TextSource:
         xlen = int.from_bytes(raw[10:12], "little")
         return zlib.decompress(raw[12 + xlen:-8], -15)
 
+    def _inflate_members(self, f, k0: int, k1: int) -> Optional[np.ndarray]:
+        """the text of members [k0, k1) by the library, their compressed bytes in one read; None when a member was refused"""
+        from . import _lib
+        c0, u0 = int(self._c_off[k0]), int(self._u_off[k0])
+        nraw, ntext = int(self._c_off[k1]) - c0, int(self._u_off[k1]) - u0
+        pinned = self.inflate == "device"
+        raw = _lib.pinned_empty(nraw, np.uint8) if pinned else np.empty(nraw, np.uint8)
+        f.seek(c0)
+        if f.readinto(memoryview(raw)) != nraw:
+            return None
+        out = _lib.pinned_empty(ntext, np.uint8) if pinned else np.empty(ntext, np.uint8)
+        status, tm = bgzf_inflate(self.inflate, raw, self._c_off[k0:k1 + 1] - c0, self._u_off[k0:k1 + 1] - u0, out)
+        if tm is not None:
+            self.inflate_ms += tm.inflate_ms
+            self.upload_ms += tm.upload_ms
+            self.download_ms += tm.download_ms
+        bad = np.flatnonzero(status)
+        if len(bad):
+            from .utils import VERBOSITYLVL, print_verbosity
+            k = k0 + int(bad[0])
+            what = BZ_STATUS[status[bad[0]]] if status[bad[0]] < len(BZ_STATUS) else f"status {status[bad[0]]}"
+            print_verbosity(f"{self.fname}: BGZF member {k} at byte {int(self._c_off[k])} refused by the {self.inflate} inflate ({what}); "
+                            "its members go to zlib", self._verbosity, VERBOSITYLVL[3])
+            return None
+        return out
+
     def chunks(self):
         """(offset of the chunk in the text, uint8 array) over the whole text."""
         if self.kind == "gzip":
@@ -227,6 +309,18 @@ class _TextSource:
                         break
                     yield off, np.frombuffer(raw, dtype=np.uint8)
                     off += len(raw)
+        elif self.inflate != "zlib":
+            with open(self.fname, "rb") as f:
+                k, nb = 0, len(self._c_off) - 1
+                while k < nb:
+                    k0, off, size = k, int(self._u_off[k]), 0
+                    while k < nb and size < self.CHUNK:  # the boundaries of the zlib route: members until the text reaches CHUNK
+                        size += int(self._u_off[k + 1] - self._u_off[k])
+                        k += 1
+                    text = self._inflate_members(f, k0, k)
+                    if text is None:
+                        text = np.frombuffer(b"".join(self._inflate(f, j) for j in range(k0, k)), dtype=np.uint8)
+                    yield off, text
         else:
             with open(self.fname, "rb") as f:
                 k, nb = 0, len(self._c_off) - 1
@@ -250,9 +344,12 @@ class _TextSource:
                 return np.frombuffer(f.read(hi - lo), dtype=np.uint8)
         k0 = int(np.searchsorted(self._u_off, lo, side="right") - 1)
         k1 = int(np.searchsorted(self._u_off, hi, side="left"))
-        with open(self.fname, "rb") as f:
-            data = b"".join(self._inflate(f, k) for k in range(k0, k1))
         base = int(self._u_off[k0])
+        with open(self.fname, "rb") as f:
+            text = self._inflate_members(f, k0, k1) if self.inflate != "zlib" and k1 > k0 else None
+            if text is not None:
+                return text[lo - base:hi - base]
+            data = b"".join(self._inflate(f, k) for k in range(k0, k1))
         return np.frombuffer(data, dtype=np.uint8)[lo - base:hi - base]
 
 
@@ -262,12 +359,12 @@ class VCF:
     line end, POS) - so a 2504-sample chromosome VCF (tens of GB of text) is never resident; a fetch reads just the bytes
     of the records it returns."""
 
-    def __init__(self, fname: str, verbosity: int = 0, debug: bool = True, vcfidx: Optional[str] = "") -> None:
+    def __init__(self, fname: str, verbosity: int = 0, debug: bool = True, vcfidx: Optional[str] = "", inflate: Optional[str] = None) -> None:
         self._debug, self._verbosity = debug, verbosity
         if not os.path.isfile(fname):
             exception_handler(FileNotFoundError, f"Cannot find input VCF {fname}", os.EX_DATAERR, debug)
         self._fname = fname
-        self._src = _TextSource(fname)
+        self._src = _TextSource(fname, inflate, verbosity)  # `inflate`: who inflates a BGZF file's members (inflate_route)
         self._mm = self._gt_abs = None
         if self._src.kind == "plain" and self._index_mapped():
             return

@@ -453,6 +453,17 @@ void hawk_launch_gn_text_len(hipStream_t st, const GnDev& G, const uint64_t* kid
 void hawk_launch_gn_text_fill(hipStream_t st, const GnDev& G, const uint64_t* kidx, const uint8_t* pool, const uint64_t* pool_off, uint64_t n_kept,
                               const uint64_t* off, uint8_t* out);
 
+// ---- BGZF members -> text, one wavefront per member (hawk_inflate.hip; the rules themselves: hawk_inflate.h)
+struct BzDev {
+  const uint8_t* in;      // the members' bytes from c_off[0] on
+  const uint64_t* c_off;  // [n + 1] as the caller gave them: member k = in[c_off[k] - c_off[0], c_off[k + 1] - c_off[0])
+  const uint64_t* u_off;  // [n + 1] likewise: its text = out[u_off[k] - u_off[0], u_off[k + 1] - u_off[0])
+  uint32_t n;
+  uint8_t* out;
+  uint8_t* status;        // [n] HAWK_BZ_*
+};
+void hawk_launch_bz_inflate(hipStream_t st, const BzDev& B, unsigned long long* stamp);
+
 // ---- variant effects on the report groups (hawk_effects.hip; the rules themselves: hawk_effects.h)
 #include "hawk_effects.h"
 struct FxDev {

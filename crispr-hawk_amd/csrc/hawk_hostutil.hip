@@ -20,6 +20,7 @@
 #include "hawk_ugroups.h"
 #include "hawk_ubuild.h"
 #include "hawk_uwin.h"
+#include "hawk_inflate.h"
 
 namespace {
 template <class F> void par_groups(uint64_t n_groups, F f) {
@@ -1508,6 +1509,32 @@ int hawk_host_unphased_windows(const hawk_uwin_input* in, const hawk_uwin_lists*
   }
   if (out->seq_off) out->seq_off[nr] = si;
   return HAWK_OK;
+}
+
+// ---- BGZF members -> text on the host: the decoder of hawk_inflate.h as one lane, the members handed out to `threads` threads
+int hawk_host_bgzf_inflate(const uint8_t* in, uint64_t in_bytes, const uint64_t* c_off, const uint64_t* u_off, uint32_t n_members,
+                           uint8_t* out, uint8_t* status, uint32_t threads) {
+  if (!bz_args_ok(in, in_bytes, c_off, u_off, n_members, out, status)) return HAWK_E_INVALID;
+  if (!n_members) return HAWK_OK;
+  unsigned nt = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
+  nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min(nt, 32u), n_members));
+  std::atomic<uint32_t> next(0), failed(0);
+  auto work = [&]() {
+    BzTables tables;
+    for (;;) {
+      const uint32_t k = next.fetch_add(1);
+      if (k >= n_members) break;
+      status[k] = (uint8_t)bz_inflate_member<BzHost>(in + c_off[k], c_off[k + 1] - c_off[k], out + u_off[k], u_off[k + 1] - u_off[k], &tables);
+      if (status[k] != HAWK_BZ_OK) failed.fetch_add(1);
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+  }
+  return failed.load() ? HAWK_E_INVALID : HAWK_OK;
 }
 
 }  // extern "C"

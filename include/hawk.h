@@ -1153,6 +1153,42 @@ int hawk_plm_score(hawk_plm* p, const char* seqs, uint32_t len, uint64_t n, uint
 int hawk_plm_timing(hawk_plm* p, int enable, float ms4[4]);
 void hawk_plm_free(hawk_plm* p);
 
+/* ---- BGZF members -> text (what readers._TextSource does with zlib, one member at a time): every member of a bgzipped VCF or BED
+ * is an independent gzip member of at most 64 KiB of text, so a batch of them inflates in one call, one wavefront per member
+ * (k_bz_inflate).  The rules - which headers, blocks and code sets are accepted (zlib's inflate decides), and that no member, however
+ * malformed, is read or written outside its ranges - are stated once, in csrc/hawk_inflate.h, for the kernel and for
+ * hawk_host_bgzf_inflate.  The CRC32 of the trailer is not checked (the zlib route never read it).
+ *
+ * Member k is in[c_off[k], c_off[k + 1]) - the whole gzip member, header and trailer - and its text goes to
+ * out[u_off[k], u_off[k + 1]); both offset arrays have n_members + 1 entries and are relative to `in` / `out`, which are host
+ * buffers (page-locked ones from hawk_host_alloc copy at link speed).  The device call uploads in[c_off[0], c_off[n_members]),
+ * inflates into device memory of the caching allocator, downloads out[u_off[0], u_off[n_members]) and status[n_members] and
+ * returns its workspace, all on the context's stream.  HAWK_OK when every member is HAWK_BZ_OK; HAWK_E_INVALID when any member
+ * failed - status[] says which and why, the bytes of a failed member's range are unspecified, no byte outside it is touched.
+ * HAWK_E_INVALID also, with nothing launched or written, for offsets that do not ascend, a member range outside in_bytes, or a
+ * missing array.  n_members == 0 is HAWK_OK.  `timing` (may be NULL): the laps by the device's wall clock.
+ * hawk_host_bgzf_inflate: the same header over the members on `threads` host threads (0: one per core, at most 32), no device. */
+enum hawk_bz_status {
+  HAWK_BZ_OK = 0,
+  HAWK_BZ_HEADER = 1,      /* no gzip magic, or a compression method other than deflate */
+  HAWK_BZ_UNSUPPORTED = 2, /* FLG is not exactly FEXTRA: not a member bgzip writes */
+  HAWK_BZ_INPUT = 3,       /* the member ends before its stream does */
+  HAWK_BZ_SIZE = 4,        /* ISIZE is not the range given for the text or exceeds 65536; the stream gives more or fewer bytes */
+  HAWK_BZ_BLOCK = 5,       /* block type 3, or a stored block whose LEN and ~LEN disagree */
+  HAWK_BZ_CODE = 6,        /* a code set zlib refuses, or a code an incomplete set does not hold */
+  HAWK_BZ_SYMBOL = 7,      /* length symbol 286 / 287, distance symbol 30 / 31 */
+  HAWK_BZ_DISTANCE = 8     /* a distance that reaches back past the member's first byte */
+};
+typedef struct {
+  float upload_ms, inflate_ms, download_ms, total_ms;
+  uint64_t in_bytes, out_bytes;
+  uint32_t n_members, n_failed;
+} hawk_bgzf_timing;
+int hawk_bgzf_inflate(hawk_ctx* ctx, const uint8_t* in, uint64_t in_bytes, const uint64_t* c_off, const uint64_t* u_off,
+                      uint32_t n_members, uint8_t* out, uint8_t* status, hawk_bgzf_timing* timing);
+int hawk_host_bgzf_inflate(const uint8_t* in, uint64_t in_bytes, const uint64_t* c_off, const uint64_t* u_off, uint32_t n_members,
+                           uint8_t* out, uint8_t* status, uint32_t threads);
+
 #ifdef __cplusplus
 }
 #endif
