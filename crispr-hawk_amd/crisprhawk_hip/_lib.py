@@ -38,6 +38,7 @@ EXPORTS = [
     "hawk_annot_create", "hawk_annot_query", "hawk_annot_download", "hawk_annot_free", "hawk_xplan_text",
     "hawk_offtarget_text", "hawk_offtarget_text_download", "hawk_host_offtarget_text",
     "hawk_offtarget_bulge_summary", "hawk_host_offtarget_bulge_summary",
+    "hawk_genome_variants", "hawk_offtarget_variant_scan", "hawk_host_offtarget_variant_scan",
     "hawk_gnomad_scan", "hawk_gnomad_records", "hawk_gnomad_text", "hawk_gnomad_text_download", "hawk_gnomad_destroy",
     "hawk_host_gnomad_lines", "hawk_host_f32_repr",
     "hawk_effects_create", "hawk_effects_create_columns", "hawk_effects_create_ugroups", "hawk_effects_rank", "hawk_effects_download", "hawk_effects_free",

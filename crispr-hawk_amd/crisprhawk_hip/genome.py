@@ -153,16 +153,148 @@ def row_geometry(lengths: Dict[str, int], guidelen: int, pamlen: int, piece: int
     return out
 
 
+# ---- SNVs added to an index (hawk_genome_variants): the off-target scan over a variant-enriched genome ---------------------------
+_BASE_CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
+# why a record is dropped (counted in variant_stats, never raised): not a single-base substitution; its contig is not in the
+# index; its position is outside the contig; the index holds N or another non-ACGT base there; its REF base is not the index's;
+# its ALT is its REF; no row of the index holds the position (a contig shorter than the shortest window)
+VARIANT_DROPS = ("not_snv", "unknown_contig", "out_of_contig", "ref_n", "ref_mismatch", "alt_is_ref", "no_row")
+_STATUS_DROP = {1: "ref_n", 2: "ref_mismatch", 3: "alt_is_ref"}  # include/hawk.h: HAWK_OV_*
+
+
+def variant_records(src) -> List[Tuple[str, int, str, str]]:
+    """`src` - (contig, pos0, ref, alt) tuples, a readers.VCF, a VCF path, or a list mixing them - as a list of (contig, 0-based
+    position, REF, ALT), multi-allelic records split per ALT."""
+    from .readers import VCF
+    if src is None:
+        return []
+    if isinstance(src, (str, VCF)) or hasattr(src, "__fspath__"):
+        src = [src]
+    out = []
+    for item in src:
+        if isinstance(item, VCF):
+            recs = item.sites()
+        elif isinstance(item, str) or hasattr(item, "__fspath__"):
+            recs = VCF(str(item)).sites()
+        else:
+            recs = [(str(item[0]), int(item[1]), str(item[2]), str(item[3]))]
+        for contig, pos, ref, alt in recs:
+            for a in alt.split(","):
+                out.append((contig, pos, ref.upper(), a.upper()))
+    return out
+
+
+def variant_entries(lengths: Dict[str, int], geo, records, row_lo: int = 0, row_hi: Optional[int] = None):
+    """The (row, q, ref, alt) entries hawk_genome_variants takes, from records and the rows of row_geometry (`geo`): a variant
+    in the overlap of two rows is entered in both; rows outside [row_lo, row_hi) (another rank's shard) are left out and the
+    rows are numbered from row_lo.  Returns (row uint32[], q uint32[], ref uint8[], alt uint8[], var int64[] = the record each
+    entry came from, dropped = {reason: count} of the records no entry was made for, kept = [(contig, pos0, ref, alt)] of the
+    records with an entry, in `var` numbering)."""
+    row_hi = len(geo) if row_hi is None else row_hi
+    by_contig: Dict[str, list] = {}
+    for k, (name, off, end, _own) in enumerate(geo):
+        by_contig.setdefault(name, []).append((off, end, k))
+    starts = {name: [r[0] for r in rows] for name, rows in by_contig.items()}
+    dropped = {k: 0 for k in VARIANT_DROPS}
+    dropped["other_shard"] = 0
+    row, q, rb, ab, var, kept = [], [], [], [], [], []
+    from bisect import bisect_right
+    for contig, pos, ref, alt in records:
+        if len(ref) != 1 or len(alt) != 1 or ref not in _BASE_CODE or alt not in _BASE_CODE:
+            dropped["not_snv"] += 1
+            continue
+        name = contig if contig in lengths else (contig[3:] if contig.startswith("chr") and contig[3:] in lengths else
+                                                 "chr" + contig if "chr" + contig in lengths else None)
+        if name is None:
+            dropped["unknown_contig"] += 1
+            continue
+        if not 0 <= pos < lengths[name]:
+            dropped["out_of_contig"] += 1
+            continue
+        if alt == ref:
+            dropped["alt_is_ref"] += 1
+            continue
+        rows = by_contig.get(name, [])
+        k = bisect_right(starts.get(name, []), pos) - 1  # the last row that starts at or before pos; earlier ones may still reach it
+        hit, mine = 0, 0
+        while k >= 0 and rows[k][1] > pos:
+            hit += 1
+            if row_lo <= rows[k][2] < row_hi:
+                if not mine:
+                    kept.append((name, pos, ref, alt))
+                mine += 1
+                row.append(rows[k][2] - row_lo); q.append(pos - rows[k][0]); rb.append(_BASE_CODE[ref]); ab.append(_BASE_CODE[alt])
+                var.append(len(kept) - 1)
+            k -= 1
+        if not hit:
+            dropped["no_row"] += 1
+        elif not mine:
+            dropped["other_shard"] += 1
+    return (np.array(row, np.uint32), np.array(q, np.uint32), np.array(rb, np.uint8), np.array(ab, np.uint8), np.array(var, np.int64),
+            dropped, kept)
+
+
+def variant_outcome(status: np.ndarray, var: np.ndarray, dropped: Dict[str, int], kept) -> Tuple[dict, list]:
+    """variant_stats from the entries' statuses (every entry of a variant gets the same one: the rows that share a position
+    hold the same base): (dict(applied=..., dropped={reason: count}), the applied (contig, pos0, ref, alt))."""
+    first = np.unique(var, return_index=True)[1] if len(var) else np.zeros(0, np.int64)
+    st = status[first]
+    dropped = dict(dropped)
+    for code, reason in _STATUS_DROP.items():
+        dropped[reason] += int((st == code).sum())
+    applied = [kept[i] for i in np.flatnonzero(st == 0).tolist()]
+    return dict(applied=len(applied), dropped=dropped), applied
+
+
+def _host_rows(contigs: Dict[str, str], geo):
+    """(text, seq_off uint64[rows + 1], scan_start int32[rows], scan_stop int32[rows]) of the rows of row_geometry"""
+    parts = [contigs[name][off:end] for name, off, end, _own in geo]
+    seq_off = np.zeros(len(geo) + 1, np.uint64)
+    np.cumsum([len(p) for p in parts], out=seq_off[1:])
+    return ("".join(parts).encode("ascii"), seq_off, np.zeros(len(geo), np.int32), np.array([own for *_x, own in geo], np.int32))
+
+
+OTV_COLUMNS = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
+               ("nmask", np.uint32), ("alt", np.uint32))
+
+
+def host_variant_scan(contigs: Dict[str, str], guidelen: int, pamlen: int, piece: int, records, guides: Sequence[str], pam, right: bool,
+                      max_mm: int, cap: int = 1 << 16):
+    """The variant rows of GenomeIndex(contigs, guidelen, pamlen, piece, variants=records).variant_arrays(guides, pam, right,
+    max_mm) made on the host, no device (hawk_host_offtarget_variant_scan: the resolver the kernel runs, in plain loops):
+    ({guide, row, q, strand, mm, code, nmask, alt} arrays in (row, q, strand, guide) order, variant_stats).  For tests and for
+    machines without a GPU; the product scans on the device."""
+    lens = {name: len(seq) for name, seq in contigs.items()}
+    geo = row_geometry(lens, guidelen, pamlen, piece, 0, guidelen)
+    row, q, rb, ab, var, dropped, kept = variant_entries(lens, geo, variant_records(records))
+    text, seq_off, ss, se = _host_rows(contigs, geo)
+    status = np.zeros(len(row), np.uint8)
+    g2 = encode_guides([g.upper() for g in guides])
+    par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), guidelen, int(bool(right)), max_mm)
+    while True:
+        o = {k: np.empty(cap, t) for k, t in OTV_COLUMNS}
+        n = C.c_uint64(0)
+        rc = _lib.lib().hawk_host_offtarget_variant_scan(text, _p(seq_off), C.c_uint32(len(geo)), _p(ss), _p(se), _p(row), _p(q), _p(rb), _p(ab),
+                                                          C.c_uint64(len(row)), _p(status), C.byref(par), _p(g2), C.c_uint32(len(g2)),
+                                                          *[_p(o[k]) for k, _t in OTV_COLUMNS], C.c_uint64(cap), C.byref(n))
+        if rc != _lib.HAWK_E_CAPACITY:
+            break
+        cap = int(n.value)
+    _lib.check(rc, "hawk_host_offtarget_variant_scan")
+    stats, _applied = variant_outcome(status, var, dropped, kept)
+    return {k: o[k][:int(n.value)].copy() for k, _t in OTV_COLUMNS}, stats
+
+
 class GenomeIndex:
     """`shard = (rank, world)`: the genome's rows (pieces) are block-partitioned over the ranks of a multi-GPU job
     ("shard the genome by contig/offset across ranks, guides replicated, rows gathered"); every rank keeps the
     descriptors of ALL rows, so a hit's global row index names its contig and offset anywhere."""
 
     def __init__(self, contigs: Dict[str, object], guidelen: int, pamlen: int, piece: int = 1 << 22, device: Optional[int] = None,
-                 shard: Optional[Tuple[int, int]] = None, max_bulge: int = 0):
+                 shard: Optional[Tuple[int, int]] = None, max_bulge: int = 0, variants=None):
         """`max_bulge`: the largest DNA bulge the index will be asked about - neighbouring rows then overlap by that many bases
         more, so that the longer windows of bulged sites (guidelen + bulge + pamlen) still lie inside one row.  Rows and the
-        window starts they own: row_geometry."""
+        window starts they own: row_geometry.  `variants`: SNVs to add to the index (add_variants)."""
         self.L = guidelen + pamlen
         self.guidelen, self.pamlen, self.max_bulge = guidelen, pamlen, int(max_bulge)
         if self.max_bulge < 0 or self.L + self.max_bulge > 32:
@@ -191,6 +323,74 @@ class GenomeIndex:
             self.ds = DeviceHapSet(haps, device)
             _lib.check(self.ds._L.hawk_genome_finalize(self.ds._h), "hawk_genome_finalize")
         self.last_timing = None
+        self._geo = geo
+        self.variant_stats = dict(applied=0, dropped={k: 0 for k in VARIANT_DROPS + ("other_shard",)})
+        self._var_applied: Dict[Tuple[str, int], str] = {}  # (contig, pos0) -> REF base of the positions that hold an ALT allele
+        self.has_variants = False
+        if variants is not None:
+            self.add_variants(variants)
+
+    # ---- the variant-enriched genome (hawk_genome_variants / hawk_offtarget_variant_scan) ------------------------------------
+    def add_variants(self, records) -> dict:
+        """Adds SNVs to the index: `records` = (contig, pos0, ref, alt) tuples, a readers.VCF or a VCF path (only the first five
+        columns are read: sites, no genotypes), or a list of them; multi-allelic records are split per ALT.  Every allele at a
+        position is taken to exist in somebody and every combination of alleles inside a window on one chromosome - genotypes and
+        phasing are not consulted (the enriched-genome semantics of CRISPRitz add-variants): what variant_arrays lists is an
+        UPPER BOUND on the sites a population carries.  A record that is no single-base substitution, names an unknown contig or
+        a position outside it, meets N (or another non-ACGT base) in the index, states a REF base that is not the index's, or an
+        ALT equal to its REF is dropped and counted in variant_stats = dict(applied, dropped={reason: count}) - never raised.
+        A sharded index adds the variants of its own rows (the others count as dropped['other_shard']).  Calling it again adds to
+        the set.  The plain scans (scan_arrays, bulge_arrays, summary) do not see the variants.  Returns this call's stats."""
+        recs = variant_records(records)
+        row, q, rb, ab, var, dropped, kept = variant_entries(self._lens, self._geo, recs, self.row_lo, self.row_hi)
+        status = np.zeros(len(row), np.uint8)
+        if self.ds is not None:
+            na, nd = C.c_uint64(0), C.c_uint64(0)
+            _lib.check(self.ds._L.hawk_genome_variants(self.ds._h, _p(row), _p(q), _p(rb), _p(ab), C.c_uint64(len(row)), _p(status),
+                                                       C.byref(na), C.byref(nd)), "hawk_genome_variants")
+            self.has_variants = True
+        stats, applied = variant_outcome(status, var, dropped, kept)
+        for name, pos, ref, _alt in applied:
+            self._var_applied[(name, pos)] = ref
+        self.variant_stats["applied"] += stats["applied"]
+        for k, v in stats["dropped"].items():
+            self.variant_stats["dropped"][k] += v
+        return stats
+
+    def variant_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20):
+        """One hawk_offtarget_variant_scan over this rank's rows - the sites only an ALT allele makes: ({guide, row (global), q,
+        strand, mm, code, nmask, alt} arrays in no particular order, timing).  A window (either strand, guide orientation) is
+        resolved against a guide position by position: a PAM position is satisfied iff its allele set ({REF} + its ALTs) meets the
+        PAM's IUPAC set and reads REF's base if that is in the set, else the lowest allele that is; a spacer position reads the
+        guide's base if the allele set holds it, else REF's (a mismatch; N is a mismatch).  A row is listed when every PAM position
+        is satisfied, mm <= max_mm and alt - bit i: window position i reads an ALT base - is not 0; rows with alt == 0 are
+        scan_arrays' and are not listed again, so a window may have a REF row there and an ALT row here for one guide: two alleles
+        of one locus.  code / nmask are the RESOLVED window.  Mismatch-only."""
+        self._set_window(self.guidelen)
+        g2 = encode_guides([g.upper() for g in guides])
+        if len(g2) and len(guides[0]) != self.guidelen:
+            raise ValueError(f"guides of {len(guides[0])} bases on an index built for {self.guidelen}")
+        if self.ds is None:
+            return {k: np.zeros(0, t) for k, t in OTV_COLUMNS}, _no_timing()
+        par = _lib.OtParams(pam.bits, pam.bitsrc, len(pam), self.guidelen, int(bool(right)), max_mm)
+        return self._collect("hawk_offtarget_variant_scan", (self.ds._h, C.byref(par), _p(g2), len(g2)), 8, cap, OTV_COLUMNS)
+
+    def variant_ids(self, h) -> List[str]:
+        """Per row of variant_arrays' columns the variants its window reads, as the guide report spells them - contig-pos1-REF/ALT,
+        joined by commas in ascending position."""
+        out = []
+        comp = (3, 2, 1, 0)
+        for i in range(len(h["guide"])):
+            name, off, _ = self.rows[int(h["row"][i])]
+            q, minus, code, alt = off + int(h["q"][i]), bool(h["strand"][i]), int(h["code"][i]), int(h["alt"][i])
+            ids = []
+            for k in range(self.L):
+                if (alt >> k) & 1:
+                    pos = q + (self.L - 1 - k if minus else k)
+                    b = (code >> (2 * k)) & 3
+                    ids.append((pos, f"{name}-{pos + 1}-{self._var_applied[(name, pos)]}/{'ACGT'[comp[b] if minus else b]}"))
+            out.append(",".join(s for _pos, s in sorted(ids)))
+        return out
 
     def _set_window(self, guidelen: int) -> None:
         """Which window starts every row owns depends on the window length (a window must fit its row): scans with another
@@ -219,10 +419,10 @@ class GenomeIndex:
     OT_COLUMNS = (("guide", np.uint32), ("row", np.uint32), ("q", np.uint32), ("strand", np.uint8), ("mm", np.uint8), ("code", np.uint64),
                   ("nmask", np.uint32), ("gaps", np.uint64), ("kind", np.uint8), ("size", np.uint8))
 
-    def _collect(self, fn: str, head: tuple, n_cols: int, cap: int):
+    def _collect(self, fn: str, head: tuple, n_cols: int, cap: int, columns=None):
         """One listing call `fn`(*head, the first n_cols OT_COLUMNS as outputs of `cap` rows, cap, &n, &timing), again with room for
         n + 1024 rows for as long as it answers HAWK_E_CAPACITY: (the columns trimmed to the n rows, row made global; timing)."""
-        cols = self.OT_COLUMNS[:n_cols]
+        cols = (columns or self.OT_COLUMNS)[:n_cols]
         while True:
             o = {k: np.empty(cap, t) for k, t in cols}
             n, tm = C.c_uint64(0), _lib.OtTiming()
@@ -407,12 +607,23 @@ class GenomeIndex:
                 for i in range(len(h["guide"]))]
 
     # ---- the off-targets table without an object per site (hawk_offtarget_text) ------------------------------------------
-    def offtarget_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int = 0, brna: int = 0, cap: int = 1 << 20):
+    def _check_variants(self, bdna: int = 0, brna: int = 0) -> None:
+        if bdna or brna:
+            raise ValueError("the variant pass is mismatch-only: bulges over ALT alleles are not enumerated (bdna = brna = 0 with variants)")
+        if not self.has_variants and self.ds is not None:
+            raise ValueError("no variants were added to the index (GenomeIndex(variants=...) / add_variants)")
+
+    def offtarget_arrays(self, guides: Sequence[str], pam, right: bool, max_mm: int, bdna: int = 0, brna: int = 0, cap: int = 1 << 20,
+                         variants: bool = False):
         """Every hit of `guides` as columns - one scan_arrays, one bulge_arrays per (type, size), concatenated with `kind`
         (0 = X, 1 = DNA, 2 = RNA) and `size` columns (gaps = 0 for un-bulged hits) - in the order the product's file has: the
         un-bulged hits in scan()'s order, then the bulged ones in scan_bulges()' order (guide, type, size, contig, position,
-        strand), by one lexsort of integer keys.  No OffTargetHit / BulgeHit is built.  The index's own window is put back."""
+        strand), by one lexsort of integer keys.  No OffTargetHit / BulgeHit is built.  The index's own window is put back.
+        `variants`: the rows of variant_arrays are appended as un-bulged hits (kind = size = gaps = 0) and the columns gain `alt`
+        (uint32, 0 on every other row); a window's ALT row sorts behind its REF row.  Bulges with variants are a ValueError."""
         self._check_bulges(bdna, brna)
+        if variants:
+            self._check_variants(bdna, brna)
         guides = [g.upper() for g in guides]
         h, _tm = self.scan_arrays(guides, pam, right, max_mm, cap)
         n0 = len(h["guide"])
@@ -420,9 +631,16 @@ class GenomeIndex:
         for _k, dna, b, hb in self._each_bulge(bdna, brna, lambda b, dna: self.bulge_arrays(guides, pam, right, max_mm, b, dna, cap)):
             nb = len(hb["guide"])
             parts.append(dict(hb, kind=np.full(nb, 1 if dna else 2, np.uint8), size=np.full(nb, b, np.uint8)))
-        cols = {k: np.concatenate([pt[k] for pt in parts]).astype(t, copy=False) for k, t in self.OT_COLUMNS}
+        if variants:
+            hv, self.last_variant_timing = self.variant_arrays(guides, pam, right, max_mm, cap)
+            nv = len(hv["guide"])
+            parts[0]["alt"] = np.zeros(n0, np.uint32)
+            parts.append(dict(hv, gaps=np.zeros(nv, np.uint64), kind=np.zeros(nv, np.uint8), size=np.zeros(nv, np.uint8)))
+        names = self.OT_COLUMNS + ((("alt", np.uint32),) if variants else ())
+        cols = {k: np.concatenate([pt[k] for pt in parts]).astype(t, copy=False) for k, t in names}
         # rows of a contig ascend with their offsets and own disjoint starts: (row, q) orders as (contig, position) does
-        order = np.lexsort((cols["strand"], cols["q"], cols["row"], cols["size"], cols["kind"], cols["guide"], cols["kind"] != 0))
+        keys = (cols["strand"], cols["q"], cols["row"], cols["size"], cols["kind"], cols["guide"], cols["kind"] != 0)
+        order = np.lexsort(((cols["alt"] != 0,) if variants else ()) + keys)
         return {k: np.ascontiguousarray(v[order]) for k, v in cols.items()}
 
     def row_table(self):
@@ -562,11 +780,17 @@ class GenomeIndex:
             timing = {k: getattr(tm, k) for k, _ in tm._fields_}
         return dict(hist=hist, cfd_e4=cfd, n_hits=int(nh.value), n_unscorable=int(nu.value)), timing
 
-    def scan(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20, comm=None) -> List[OffTargetHit]:
+    def scan(self, guides: Sequence[str], pam, right: bool, max_mm: int, cap: int = 1 << 20, comm=None, variants: bool = False) -> List[OffTargetHit]:
         """All windows within ``max_mm`` mismatches of any guide, both strands, sorted by
         (guide, contig order, position, strand).  With a communicator (parallel.RcclComm / TcpComm) the hits of every
-        rank's genome shard are gathered to rank 0, which returns the whole list (other ranks return [])."""
+        rank's genome shard are gathered to rank 0, which returns the whole list (other ranks return []).
+        `variants`: the sites only an ALT allele of the added SNVs makes (variant_arrays) are listed too, with their resolved
+        windows; a window's ALT hit follows its REF hit."""
         hits, _tm = self.scan_arrays(guides, pam, right, max_mm, cap)
+        if variants:
+            self._check_variants()
+            hv, self.last_variant_timing = self.variant_arrays(guides, pam, right, max_mm, cap)
+            hits = {k: np.concatenate([v, hv[k]]) for k, v in hits.items()}
         if comm is not None and comm.world > 1:
             parts = {k: comm.gatherv_bytes(v, 0) for k, v in hits.items()}
             if comm.rank != 0:

@@ -284,7 +284,7 @@ def _annotation_columns_device(annotations, anncolnames, chrom_names, chrom_of_r
 
 
 def _estimate_device(uniq, pam: PAM, genome: GenomeIndex, region, mm: int, bdna: int, brna: int, right: bool, outdir: str, debug: bool,
-                     annotations, anncolnames, device):
+                     annotations, anncolnames, device, variants: bool = False):
     """estimate_offtargets_spacers on arrays: the hits stay columns from the scan to the file.  Returns None when a label or a
     column name would need csv quoting (the caller takes the `objects` engine, which writes through pandas)."""
     from .bedannot import plain_labels
@@ -298,7 +298,7 @@ def _estimate_device(uniq, pam: PAM, genome: GenomeIndex, region, mm: int, bdna:
         from .scoring import _tables
         tables = _tables(debug)
     try:
-        arr = genome.offtarget_arrays(uniq, pam, right, mm, bdna, brna)
+        arr = genome.offtarget_arrays(uniq, pam, right, mm, bdna, brna, **({"variants": True} if variants else {}))
     except ValueError as e:
         exception_handler(CrisprHawkOffTargetsError, f"Off-targets search failed: {e}", os.EX_DATAERR, debug, e)
     n = len(arr["guide"])
@@ -321,6 +321,14 @@ def _estimate_device(uniq, pam: PAM, genome: GenomeIndex, region, mm: int, bdna:
             if any(ch in x for x in anames for ch in '"\t\n\r') or not all(plain_labels(c) for c in acols):
                 return None
             cols.update(zip(anames, acols))
+        if variants:  # behind any annotation column; built on the host, for the alt rows alone
+            from .reports import Ragged
+            is_alt = arr["alt"][order] != 0
+            sel = order[is_alt]
+            ids = genome.variant_ids({k: v[sel] for k, v in arr.items()})
+            it = iter(ids)
+            cols["origin"] = Ragged.from_strings(["alt" if a else "ref" for a in is_alt.tolist()])
+            cols["variant_id"] = Ragged.from_strings([next(it) if a else "NA" for a in is_alt.tolist()])
         fname = os.path.join(outdir, f"offtargets_{region.contig}_{region.start + PADDING}_{region.stop - PADDING}.tsv")
         try:
             if n == 0:
@@ -348,21 +356,37 @@ def _estimate_device(uniq, pam: PAM, genome: GenomeIndex, region, mm: int, bdna:
 
 def estimate_offtargets_spacers(spacers, pam: PAM, crispritz_index, region, mm: int, bdna: int, brna: int, guidelen: int, right: bool,
                                 outdir: str, verbosity: int, debug: bool, annotations=None, anncolnames=None, device=None,
-                                engine: str = "device") -> Dict[str, tuple]:
+                                engine: str = "device", variants: bool = False) -> Dict[str, tuple]:
     """estimate_offtargets for the columnar report (pipeline.search_files): the same stage - unique spacers -> device scan
     -> CFD -> offtargets_*.tsv -> per-spacer aggregates - without Guide objects.
     `engine`: "device" keeps the hits as columns from the scan to the file - GenomeIndex.offtarget_arrays, the rows' text and
     CFD written by hawk_offtarget_text, the file by hawk_host_tsv_write, the aggregates from arrays; "objects" is the route
     over one Offtarget per site (search -> report_offtargets -> offtargets_by_spacer).  Same file, same result; a label or
-    column name csv quoting reacts to sends the device engine's call to "objects"."""
+    column name csv quoting reacts to sends the device engine's call to "objects".
+    `variants`: the index (a GenomeIndex with SNVs added: add_variants) is scanned for the sites only an ALT allele makes as well
+    (GenomeIndex.variant_arrays: every allele is taken to exist, an upper bound; mismatch-only).  Their rows go through the same
+    sort, text, CFD and annotation join - spacer / pam / mm / cfd are those of the RESOLVED window - and the file gains two columns
+    behind any annotation column: `origin` (ref / alt) and `variant_id` (contig-pos1-REF/ALT of the ALT bases the row reads,
+    comma-joined in ascending position; NA on ref rows).  Counts and global CFD include them.  With bulges, with the `objects`
+    engine or on an index without variants it is a ValueError before any device work or file."""
     if engine not in ("device", "objects"):
         raise ValueError(f"engine {engine!r}: 'device' or 'objects'")
+    if variants:
+        if engine != "device":
+            raise ValueError("variants=True needs the 'device' engine: the object route lists the plain scan alone")
+        if bdna or brna:
+            raise ValueError("variants=True is mismatch-only: bulges over ALT alleles (bdna / brna) are not enumerated")
+        if not isinstance(crispritz_index, GenomeIndex) or not (crispritz_index.has_variants or crispritz_index.ds is None):
+            raise ValueError("variants=True needs a GenomeIndex with variants added (GenomeIndex(variants=...) / add_variants)")
     uniq = sorted({sp.upper() for sp in spacers})
     if engine == "device" and uniq:
         crispritz_index = _genome_index(crispritz_index, guidelen, len(pam), bdna)
-        res = _estimate_device(uniq, pam, crispritz_index, region, mm, bdna, brna, right, outdir, debug, annotations or [], anncolnames or [], device)
+        res = _estimate_device(uniq, pam, crispritz_index, region, mm, bdna, brna, right, outdir, debug, annotations or [], anncolnames or [], device,
+                               **({"variants": True} if variants else {}))
         if res is not None:
             return res
+        if variants:
+            raise ValueError("variants=True: an annotation label or column name needs csv quoting, which only the 'objects' engine writes")
     lines = search(_genome_index(crispritz_index, guidelen, len(pam), bdna), uniq, pam, right, mm, verbosity, debug, bdna, brna) if uniq else []
     ots = report_offtargets(lines, region, pam, guidelen, annotations or [], anncolnames or [], False, right, outdir, verbosity, debug, device)
     return offtargets_by_spacer(ots, uniq)

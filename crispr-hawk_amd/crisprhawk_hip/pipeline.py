@@ -106,7 +106,7 @@ def _offtargets(spacers, pam: PAM, ot, coord, guidelen: int, right: bool, outdir
     ann = ot.get("ann")
     return estimate_offtargets_spacers(spacers, pam, ot["genome"], coord, ot["mm"], ot["bdna"], ot["brna"], guidelen, right, outdir, 0, debug,
                                        ann.func if ann else None, ann.func_names if ann else None, ann.device if ann else None,
-                                       engine=ot.get("engine", "device"))
+                                       engine=ot.get("engine", "device"), **({"variants": True} if ot.get("variants") else {}))
 
 
 def _plan_row_variants(info, vt) -> List[bytes]:
@@ -362,7 +362,7 @@ def _write_group_report(coord, cols, order, plain, pam, guidelen, outdir, bed_st
 
 
 # Everything behind `outdir` is to be passed by keyword: new options are inserted where they belong (graphical_reports,
-# candidate_guides, figures, unphased_report, unphased_engine, unphased_effects, unphased_haplotypes and unphased_indel_windows sit before `annotations`), and only the order of the last three parameters is held fixed.
+# candidate_guides, figures, unphased_report, unphased_engine, unphased_effects, unphased_haplotypes, unphased_indel_windows and offtargets_variants sit before `annotations`), and only the order of the last three parameters is held fixed.
 def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidelen: int, right: bool, outdir: str,
                  cfd_tables=None, azimuth_model=None, deepcpf1_weights=None, plmcrispr_model=None,
                  device: Optional[int] = None, debug: bool = True, estimate_offtargets=None, mm: int = 4, bdna: int = 0, brna: int = 0,
@@ -371,7 +371,7 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
                  candidate_guides: Optional[List[str]] = None, figures: Optional[Dict[str, List[str]]] = None,
                  unphased_report: Optional[str] = None, unphased_engine: Optional[str] = None, unphased_effects: bool = False,
                  unphased_haplotypes: Optional[str] = None, unphased_indel_windows: Optional[str] = None, bgzf_inflate: Optional[str] = None,
-                 annotations: Optional[List[str]] = None,
+                 offtargets_variants=None, annotations: Optional[List[str]] = None,
                  annotation_colnames: Optional[List[str]] = None, gene_annotations: Optional[List[str]] = None,
                  gene_annotation_colnames: Optional[List[str]] = None, haplotype_table: bool = False,
                  tables: Optional[Dict[str, str]] = None) -> Dict[str, str]:
@@ -392,6 +392,13 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     `offtargets_summary=True` takes the same summary route at the given `bdna` / `brna` - the bulged rows are counted and their
     CFD summed inside the bulge kernel (GenomeIndex.summary(bdna=, brna=)) - and writes no offtargets_*.tsv either;
     `offtargets_table` is then not consulted.
+    `offtargets_variants` makes the off-target stage variant-aware: True adds the SNVs of `vcfs` to the genome index, a list of
+    VCF paths or (contig, pos0, ref, alt) records adds those (GenomeIndex.add_variants: sites only, genotypes and phasing are
+    not consulted - every allele is taken to exist, an upper bound), and the sites only an ALT allele makes
+    (GenomeIndex.variant_arrays) join the rows of offtargets_*.tsv, which gains the columns `origin` (ref / alt) and
+    `variant_id`; the `offtargets` / `cfd` columns of the guide report include them.  The variant pass is mismatch-only and
+    listed: with `bdna` / `brna`, `offtargets_table=False`, `offtargets_summary=True` or without `estimate_offtargets` it is a
+    ValueError before any file is written.  None / False: nothing changes, no new column, no new call.
     `annotations` / `gene_annotations` (the reference's --annotation / --gene-annotation BED files, plain, gzip or BGZF, no .tbi
     needed) add one column per file to every guide report - the 4th BED column, or feature:gene_name, of the features a guide
     overlaps - named by `annotation_colnames` / `gene_annotation_colnames` or annotation_{i} / gene_annotation_{i}; the
@@ -466,6 +473,16 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
     if not offtargets_summary and not offtargets_table and (bdna or brna):
         raise ValueError("offtargets_table=False is the mismatch-only summary: bulged sites (bdna / brna) need the off-targets table, "
                          "or offtargets_summary=True for the two report columns alone")
+    ot_variants = offtargets_variants is not None and offtargets_variants is not False
+    if ot_variants:
+        if estimate_offtargets is None:
+            raise ValueError("offtargets_variants needs the off-target stage: estimate_offtargets is None")
+        if bdna or brna:
+            raise ValueError("offtargets_variants is mismatch-only: bulges over ALT alleles (bdna / brna) are not enumerated")
+        if offtargets_summary or not offtargets_table:
+            raise ValueError("offtargets_variants lists its rows: offtargets_table=False / offtargets_summary=True sum the plain scan alone")
+        if offtargets_variants is True and not vcfs:
+            raise ValueError("offtargets_variants=True takes the SNVs of `vcfs`, and none were given")
     ot = None
     if estimate_offtargets is not None:
         from .genome import GenomeIndex, read_fasta
@@ -475,6 +492,9 @@ def search_files(fasta: str, bedfile: str, vcfs: List[str], pam_seq: str, guidel
         if isinstance(genome, dict):
             genome = GenomeIndex(genome, guidelen, len(pam_seq), device=device, max_bulge=bdna)  # once for all regions
         ot = dict(genome=genome, mm=mm, bdna=bdna, brna=brna, table=bool(offtargets_table) and not offtargets_summary)
+        if ot_variants:
+            genome.add_variants(list(vcfs) if offtargets_variants is True else offtargets_variants)
+            ot["variants"] = True
         if cfd_tables is not None:
             scoring.set_cfd_tables(*cfd_tables)
     if azimuth_model is not None:

@@ -559,6 +559,21 @@ class VCF:
             fixed.append(bytes(text[lo:lo + int(tabs[8])]).decode().split("\t"))
         return VcfBlock(text, line_off, gt_off, fixed)
 
+    def sites(self) -> List[Tuple[str, int, str, str]]:
+        """(CHROM as written, 0-based position, REF, ALT field) of every record: the first five columns alone - no sample column is
+        split, no VariantRecord made (GenomeIndex.add_variants: the variants of an enriched genome are sites, not genotypes)."""
+        out = []
+        n = len(self._starts)
+        for a in range(0, n, 4096):
+            b = min(n, a + 4096)
+            s0 = int(self._starts[a])
+            text = self._read(s0, int(self._ends[b - 1])).tobytes()
+            for s, e in zip(self._starts[a:b].tolist(), self._ends[a:b].tolist()):
+                f = text[s - s0:e - s0].split(b"\t", 5)
+                if len(f) >= 5:
+                    out.append((f[0].decode(), int(f[1]) - 1, f[3].decode(), f[4].decode().strip()))
+        return out
+
     @property
     def contig(self) -> str:  # variant.py:762-764
         return self._contig if self._contig.startswith("chr") else f"chr{self._contig}"

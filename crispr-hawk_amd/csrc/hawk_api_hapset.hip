@@ -75,6 +75,8 @@ void hawk_hapset_destroy(hawk_hapset* hs) {
                     &hs->big, &hs->refhp, &hs->vcnt0, &hs->cs_res, &hs->cs_tbase, &hs->cs_trows, &hs->cs_inst, &hs->rowsA};
   hs->cws.release();
   for (auto* b : bufs) b->release();
+  for (auto& b : hs->ovplane) b.release();
+  for (DevBuf* b : {&hs->ovsites, &hs->ovhits, &hs->ovstamp}) b->release();
   for (auto& b : hs->colsA) b.release();
   delete hs;
 }

@@ -299,6 +299,7 @@ int hawk_genome_finalize(hawk_hapset* rows) {
   hawk_launch_ot_onehot(rows->ctx->stream, rows->plane, (uint64_t)rows->n_hap * rows->S);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(rows->ctx->stream));
+  rows->finalized = true;
   return HAWK_OK;
 }
 

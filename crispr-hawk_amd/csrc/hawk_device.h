@@ -284,6 +284,27 @@ void hawk_launch_ot_bulge(hipStream_t st, const OtSite* sites, uint64_t n_sites,
                           int sp0, int max_mm, int dna, int bsize, OtBulgeHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_ot_bulge_sum(hipStream_t st, const OtSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, int guidelen,
                               int sp0, int max_mm, int dna, int bsize, const OtBulgeSummary& sm);
+// ---- the scan over a variant-enriched genome (hawk_otvar.hip; the rule that resolves a window: hawk_otvar.h)
+#include "hawk_otvar.h"
+struct OvPlanes { uint32_t* p[4]; };  // the allele planes of an index: REF one-hot | ALT, the rows' geometry
+struct OvSite {      // one PAM-bearing window that holds an ALT allele, in guide orientation
+  uint64_t code;     // REF's bases, base i at bits 2i,2i+1 (A0 C1 G2 T3)
+  uint32_t nmask;    // bit i: REF's base i is ambiguous
+  uint32_t am[4];    // bit i of am[b]: base b is in the allele set of position i
+  uint32_t q;        // window start inside the row | strand << 31
+  uint32_t row;
+  uint32_t pad;
+};
+struct OvHit { uint64_t code; uint32_t nmask, alt, q, row, guide, mm; };  // a variant row: the RESOLVED window, nothing to look up
+static_assert(sizeof(OvSite) == 40 && sizeof(OvHit) == 32, "record layouts");
+void hawk_launch_ov_fill(hipStream_t st, const HapSetDev& hs, const OvPlanes& al, const uint32_t* row, const uint32_t* q, const uint8_t* ref,
+                         const uint8_t* alt, uint64_t n, uint8_t* status);
+void hawk_launch_ov_filter(hipStream_t st, const HapSetDev& hs, const OvPlanes& al, const ScanParams& p, uint32_t* keepF, uint32_t* keepR,
+                           uint32_t* counts);
+void hawk_launch_ov_sites(hipStream_t st, const HapSetDev& hs, const OvPlanes& al, const ScanParams& p, const uint32_t* keepF,
+                          const uint32_t* keepR, const uint64_t* offsets, OvSite* sites);
+void hawk_launch_ov_match(hipStream_t st, const OvSite* sites, uint64_t n_sites, const uint64_t* guides, uint32_t n_guides, const OvGeom& g,
+                          int max_mm, OvHit* hits, uint64_t cap, unsigned long long* n_hits);
 void hawk_launch_pack(hipStream_t st, const uint8_t* ascii, const uint64_t* seq_off, uint32_t hap0, uint32_t n_hap_batch,
                       uint64_t batch_base, const uint32_t* hap_len, uint32_t S, uint32_t* const* plane,
                       unsigned long long* bad_index);

@@ -216,6 +216,11 @@ struct hawk_hapset {
   std::shared_ptr<uint64_t> plan_groups;  // cws.last_groups shared with the expansion plan the set came from: the next run of the plan starts from it
   DevBuf otoff, otcode, otid, othit;  // hawk_offtarget_scan: bucketed guides, gathered hit sites
   DevBuf otsum;                       // hawk_offtarget_summary: counters, per-guide sums, CFD tables - sized by the guides, not the hits
+  // a variant-enriched genome (hawk_genome_variants, hawk_api_otvar.hip): the four allele planes (REF one-hot | ALT) in the rows'
+  // geometry, and the workspace of hawk_offtarget_variant_scan - its site records, its rows, its stamps
+  bool finalized = false;     // hawk_genome_finalize has made the planes one-hot
+  bool has_variants = false;
+  DevBuf ovplane[4], ovsites, ovhits, ovstamp;
   DevBuf big;                 // tiles whose rows exceed the hand-over list (k_search_emit's work list)
   DevBuf refbits;             // REF's candidate-window bitmaps, one per strand (k_ref_bits)
   bool refbits_valid = false;

@@ -14,6 +14,7 @@
 #include "../../include/hawk.h"
 #include "hawk_ottext.h"
 #include "hawk_otbulge.h"
+#include "hawk_otvar.h"
 #include "hawk_gnomad.h"
 #include "hawk_effects.h"
 #include "hawk_resolve.h"
@@ -765,6 +766,88 @@ int hawk_host_offtarget_bulge_summary(const uint64_t* code, const uint32_t* nmas
   *n_hits = hits;
   *n_unscorable = uns;
   return HAWK_OK;
+}
+
+// ---- the off-target scan over a variant-enriched genome on the host ------------------------------------------------------------
+// hawk_genome_variants + hawk_offtarget_variant_scan without a device: the rows' text, the variant entries and the guides go
+// through ov_resolve (hawk_otvar.h) - the function k_ov_match runs for its survivors - in plain loops, every (window, strand,
+// guide).  Rows come out in (row, q, strand, guide) order.
+int hawk_host_offtarget_variant_scan(const char* seqs, const uint64_t* seq_off, uint32_t n_rows, const int32_t* scan_start,
+                                     const int32_t* scan_stop, const uint32_t* v_row, const uint32_t* v_q, const uint8_t* v_ref,
+                                     const uint8_t* v_alt, uint64_t n_var, uint8_t* v_status, const hawk_ot_params* p, const uint64_t* guides2,
+                                     uint32_t n_guides, uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand,
+                                     uint8_t* out_mm, uint64_t* out_code, uint32_t* out_nmask, uint32_t* out_alt, uint64_t cap, uint64_t* n_out) {
+  if (!p || !n_out || (n_rows && (!seqs || !seq_off || !scan_start || !scan_stop)) || (n_var && (!v_row || !v_q || !v_ref || !v_alt)) ||
+      (n_guides && !guides2))
+    return HAWK_E_INVALID;
+  if (p->guidelen == 0 || p->guidelen + p->pamlen > 32 || p->pamlen == 0 || p->pamlen > 16) return HAWK_E_UNSUPPORTED;
+  const int G = (int)p->guidelen, P = (int)p->pamlen, L = G + P;
+  for (uint32_t k = 0; k < p->pamlen; ++k)
+    if (((p->pam_fwd >> (4 * k)) & 15u) == 0) return HAWK_E_INVALID;  // every PAM position is an IUPAC code
+  std::vector<uint64_t> len(n_rows);
+  for (uint32_t h = 0; h < n_rows; ++h) {
+    if (seq_off[h + 1] < seq_off[h]) return HAWK_E_INVALID;
+    len[h] = seq_off[h + 1] - seq_off[h];
+    if (scan_start[h] < 0 || scan_stop[h] > (int64_t)len[h]) return HAWK_E_INVALID;
+    if (scan_stop[h] > scan_start[h] && (uint64_t)scan_stop[h] - 1 + (uint64_t)L > len[h]) return HAWK_E_INVALID;
+  }
+  for (uint64_t i = 0; i < n_var; ++i)
+    if (v_row[i] >= n_rows || v_q[i] >= len[v_row[i]] || v_ref[i] > 3 || v_alt[i] > 3) return HAWK_E_INVALID;
+  // per base: REF's code (4: ambiguous) and the allele set as a nibble
+  const uint64_t total = n_rows ? seq_off[n_rows] - seq_off[0] : 0;
+  std::vector<uint8_t> rbase(total), aset(total);
+  for (uint64_t i = 0; i < total; ++i) {
+    uint8_t b = 4;
+    switch (seqs[seq_off[0] + i] & 0xDF) { case 'A': b = 0; break; case 'C': b = 1; break; case 'G': b = 2; break; case 'T': b = 3; break; default: break; }
+    rbase[i] = b;
+    aset[i] = b < 4 ? (uint8_t)(1u << b) : 0;
+  }
+  for (uint64_t i = 0; i < n_var; ++i) {
+    const uint64_t at = seq_off[v_row[i]] - seq_off[0] + v_q[i];
+    uint8_t st = HAWK_OV_APPLIED;
+    if (rbase[at] == 4) st = HAWK_OV_REF_N;
+    else if (rbase[at] != v_ref[i]) st = HAWK_OV_REF_MISMATCH;
+    else if (v_alt[i] == v_ref[i]) st = HAWK_OV_ALT_IS_REF;
+    else aset[at] |= (uint8_t)(1u << v_alt[i]);
+    if (v_status) v_status[i] = st;
+  }
+  OvGeom g;
+  g.pam_fwd = p->pam_fwd; g.G = G; g.P = P; g.right = p->right ? 1 : 0;
+  uint64_t n = 0;
+  for (uint32_t h = 0; h < n_rows; ++h) {
+    const uint64_t base = seq_off[h] - seq_off[0];
+    for (int64_t q = scan_start[h]; q < scan_stop[h]; ++q)
+      for (int s = 0; s < 2; ++s) {
+        uint64_t rcode = 0;
+        uint32_t nmask = 0, am[4] = {0, 0, 0, 0};
+        for (int i = 0; i < L; ++i) {  // guide orientation: strand 1 is the reverse complement of the + strand window
+          const uint64_t at = base + (uint64_t)q + (uint64_t)(s ? L - 1 - i : i);
+          const uint8_t b = rbase[at], a = aset[at];
+          if (b == 4) nmask |= 1u << i;
+          else rcode |= (uint64_t)(s ? 3 - b : b) << (2 * i);
+          for (int x = 0; x < 4; ++x)
+            if ((a >> x) & 1) am[s ? 3 - x : x] |= 1u << i;
+        }
+        if (!ov_alt_positions(rcode, nmask, am, L)) continue;  // no ALT allele in the window: the plain scan's
+        for (uint32_t gi = 0; gi < n_guides; ++gi) {
+          const OvResolved r = ov_resolve(rcode, nmask, am, guides2[gi], g);
+          if (!r.ok || r.mm > (int)p->max_mm || !r.alt) continue;
+          if (n < cap) {
+            if (out_guide) out_guide[n] = gi;
+            if (out_row) out_row[n] = h;
+            if (out_q) out_q[n] = (uint32_t)q;
+            if (out_strand) out_strand[n] = (uint8_t)s;
+            if (out_mm) out_mm[n] = (uint8_t)r.mm;
+            if (out_code) out_code[n] = r.code;
+            if (out_nmask) out_nmask[n] = nmask;
+            if (out_alt) out_alt[n] = r.alt;
+          }
+          ++n;
+        }
+      }
+  }
+  *n_out = n;
+  return n > cap ? HAWK_E_CAPACITY : HAWK_OK;
 }
 
 // ---- gnomAD sites records -> population-genotype lines on the host ------------------------------------------------------------

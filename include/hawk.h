@@ -523,6 +523,51 @@ int hawk_host_offtarget_bulge_summary(const uint64_t* code, const uint32_t* nmas
                                       const double* cfd_mm, const double* cfd_pam, uint32_t* out_hist, int64_t* out_cfd_e4,
                                       uint64_t* n_hits, uint64_t* n_unscorable);
 
+/* ---- K7 over a variant-enriched genome: the sites only an ALT allele makes.  (The reference defers this to CRISPRitz over an
+ * enriched index and to CRISPRme; the semantics are this project's own, PARITY UNPINNED.)
+ * hawk_genome_variants, after hawk_genome_finalize: n SNV entries (row, position q inside the row, REF base, ALT base; bases
+ *   A0 C1 G2 T3) are added to the index.  The first call allocates four ALLELE planes in the rows' geometry - REF's one-hot planes
+ *   with the ALT bases OR-ed in, 4/5 of the genome planes' bytes; ALT alone is allele & ~REF - and later calls add to the set.  A
+ *   variant in the overlap of two rows is entered in both by the caller.  An entry is dropped, never refused, when the index
+ *   holds a non-ACGT base at its position (HAWK_OV_REF_N = 1), when its REF base is not the index's (HAWK_OV_REF_MISMATCH = 2) or
+ *   when its ALT is its REF (HAWK_OV_ALT_IS_REF = 3): status[i] (may be NULL) says which, 0 = applied; *n_applied / *n_dropped
+ *   count the entries.  HAWK_E_INVALID, with nothing written: a row or position outside the index, a base above 3, a set that was
+ *   not finalized, a plan view.  hawk_hapset_destroy frees the planes.  The plain scans never read them.
+ * The allele set of a position = {REF base} + {its ALT bases}; an N position keeps the empty set and stays ambiguous.  Genotypes
+ *   and phasing are not consulted: each allele is taken to exist in somebody and every combination inside a window on one
+ *   chromosome (the enriched-genome semantics of CRISPRitz add-variants): an UPPER BOUND on what a population carries.
+ * A window of guidelen + pamlen bases, either strand, in guide orientation, is resolved against one guide position by position
+ *   (csrc/hawk_otvar.h: ov_resolve, the one statement kernel and host share):
+ *     PAM position     satisfied iff its allele set meets the PAM's IUPAC set (a PAM 'N': any position, an ambiguous one
+ *                      included, as in hawk_offtarget_scan); resolved base = REF's if REF is in the PAM's set, else the lowest
+ *                      allele (A < C < G < T in guide orientation) of the intersection
+ *     spacer position  resolved base = the guide's if it is in the allele set, else REF's, a mismatch; ambiguous = mismatch
+ *   mm = mismatches of the resolved spacer, alt = bit i set where the resolved base (window position i) differs from REF's.
+ * hawk_offtarget_variant_scan lists a row per (window, strand, guide) with every PAM position satisfied, mm <= max_mm and
+ *   alt != 0.  Rows with alt == 0 are exactly hawk_offtarget_scan's and are not listed; a window may so have a REF row there and
+ *   an ALT row here for one guide - two alleles of one locus.  Mismatch-only, all pairs.  Columns, cap / *n_out / HAWK_E_CAPACITY
+ *   as hawk_offtarget_scan; out_code / out_nmask are the RESOLVED window (it feeds hawk_offtarget_text as it is), out_alt the alt
+ *   mask.  Unordered.  The timing block is filled from the device's wall clock stamped at the stage boundaries (scan_ms: the PAM
+ *   scan over the allele planes, the ALT-window filter and the offset scan; n_sites: PAM-bearing windows that hold an ALT allele).
+ *   HAWK_E_INVALID: no hawk_genome_variants call on the set, scan ranges that let a window reach past its row, what
+ *   hawk_offtarget_scan refuses. */
+int hawk_genome_variants(hawk_hapset* rows, const uint32_t* row, const uint32_t* q, const uint8_t* ref, const uint8_t* alt, uint64_t n,
+                         uint8_t* status, uint64_t* n_applied, uint64_t* n_dropped);
+int hawk_offtarget_variant_scan(hawk_hapset* rows, const hawk_ot_params* p, const uint64_t* guides2, uint32_t n_guides,
+                                uint32_t* out_guide, uint32_t* out_row, uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm,
+                                uint64_t* out_code, uint32_t* out_nmask, uint32_t* out_alt, uint64_t cap, uint64_t* n_out,
+                                hawk_ot_timing* timing);
+/* The same rows on the host, no device: the rows' text (row h = seqs[seq_off[h], seq_off[h + 1]), any case, non-ACGT = ambiguous),
+ * the window starts each row owns [scan_start[h], scan_stop[h]), the variant entries as hawk_genome_variants takes them (v_status
+ * as its status, may be NULL) and the guides go through ov_resolve in plain loops.  Rows in (row, q, strand, guide) order; more
+ * than cap: HAWK_E_CAPACITY with *n_out = required.  p->pam_rev is not read. */
+int hawk_host_offtarget_variant_scan(const char* seqs, const uint64_t* seq_off, uint32_t n_rows, const int32_t* scan_start,
+                                     const int32_t* scan_stop, const uint32_t* v_row, const uint32_t* v_q, const uint8_t* v_ref,
+                                     const uint8_t* v_alt, uint64_t n_var, uint8_t* v_status, const hawk_ot_params* p,
+                                     const uint64_t* guides2, uint32_t n_guides, uint32_t* out_guide, uint32_t* out_row,
+                                     uint32_t* out_q, uint8_t* out_strand, uint8_t* out_mm, uint64_t* out_code, uint32_t* out_nmask,
+                                     uint32_t* out_alt, uint64_t cap, uint64_t* n_out);
+
 /* The hits of hawk_offtarget_scan / hawk_offtarget_bulges as the rows of offtargets_{contig}_{start}_{stop}.tsv (offtargets.py:
  * 41-53, 530-544), written on the device: per row the eleven fields chrom, position, strand, grna, spacer, pam, mm, bulge_size,
  * bulg_type, cfd, elevation joined by tabs, no newline - byte for byte what the package's host chain prints for the hit
