@@ -5,8 +5,9 @@
 // guide orientation letter by letter, and resolved against the guide's letters by the rules of include/hawk.h.
 //   placed   an ALT that creates the GG of NGG; an ALT under the N of NGG alone (no row); an ALT that removes the one mismatch
 //            too many; an ALT no guide carries; two ALTs at one position; variants on an N, with a wrong REF, with ALT = REF
-//   random   300 genomes of 150 .. 400 letters (N sprinkled in) in one to three rows, SNVs at one per ~12 bases, 6 guides planted
-//            near windows, NGG / 20 and TTTV / 23 in front, max_mm 0 .. 4, output buffers of exactly the rows' number
+//   random   400 genomes of 150 .. 400 letters (N sprinkled in) in one to three rows, SNVs at one per ~12 bases, 6 guides planted
+//            near windows, NGG / 20, TTTV / 23 in front, TTTV / 28 in front (32 bases: every bit of the masks and the code) and
+//            NG / 6 (8 bases), max_mm 0 .. 4, output buffers of exactly the rows' number
 #include <algorithm>
 #include <cinttypes>
 #include <cstdint>
@@ -217,10 +218,11 @@ int main() {
     bad += run(c, "variants on an N, with a wrong REF, with ALT = REF");
   }
   std::mt19937_64 rng(20240611);
-  for (int it = 0; it < 300; ++it) {
-    const bool cpf = it & 1;
-    const std::string pam = cpf ? "TTTV" : "NGG";
-    const int G = cpf ? 23 : 20, L = G + (int)pam.size();
+  static const struct { const char* pam; int G; bool right; } systems[4] = {{"NGG", 20, false}, {"TTTV", 23, true}, {"TTTV", 28, true}, {"NG", 6, false}};
+  for (int it = 0; it < 400; ++it) {
+    const bool cpf = systems[it & 3].right;
+    const std::string pam = systems[it & 3].pam;
+    const int G = systems[it & 3].G, L = G + (int)pam.size();
     Case c;
     c.pam = pam; c.right = cpf; c.max_mm = (int)(rng() % 5);
     const int n_rows = 1 + (int)(rng() % 3);
@@ -234,7 +236,7 @@ int main() {
     for (int g = 0; g < 6; ++g) {  // guides cut out of the rows (either strand) and spoiled in up to three places
       const std::string& s = c.rows[rng() % n_rows];
       const int q = (int)(rng() % (s.size() - L));
-      std::string w = s.substr(q + (cpf ? 4 : 0), G);
+      std::string w = s.substr(q + (cpf ? (int)pam.size() : 0), G);
       if (rng() & 1) { std::reverse(w.begin(), w.end()); for (char& ch : w) ch = comp(ch); }
       for (char& ch : w) if (base_of(ch) < 0) ch = 'A';
       for (int k = (int)(rng() % 4); k > 0; --k) w[rng() % G] = ACGT[rng() % 4];

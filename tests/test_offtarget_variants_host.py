@@ -119,6 +119,118 @@ def test_random_genomes():
             assert stats == V.allele_sets(text, sc.records)[1]
 
 
+# ---- the scenes of the device's seam tests (test_gpu_offtarget_variant_seams.py), held here to the brute force without a device: a
+# scene that does not hold what it says, or a reference that is wrong, fails on a machine without a GPU --------------------------
+def _hold(sc, max_mm, piece, guides=None):
+    """the twin's rows of a seam scene == the brute force's, after the brute force and sites() were held to the scene's claims"""
+    contigs = sc.text()
+    want = sc.brute(max_mm, guides)
+    V.check_claims(sc, want, max_mm, None if guides is None else len(guides))
+    st = sc.sites()
+    assert all((c, p, s) in st for _g, c, p, s, _mm, _w, _a in want)  # a row's window bears the PAM and holds an ALT
+    h, stats = host_variant_scan(contigs, sc.G, sc.P, piece, sc.records, sc.guides if guides is None else guides,
+                                 V.make_pam(sc.pam_text, sc.right), sc.right, max_mm)
+    geo = row_geometry({k: len(v) for k, v in contigs.items()}, sc.G, sc.P, piece, 0, sc.G)
+    assert V.rows_as_tuples(h, geo, sc.L) == want
+    assert len(V.owned(st, geo)) == len(st)  # every window start that lies in its contig is owned by exactly one row
+    return want, stats, geo
+
+
+@pytest.mark.parametrize("pam_text,G,right", V.WINDOW_SYSTEMS)
+@pytest.mark.parametrize("mm_hi", (False, True))
+def test_window_length_scenes(pam_text, G, right, mm_hi):
+    sc = V.window_scene(pam_text, G, right)
+    max_mm = 0 if not mm_hi else 1 if G == 6 else 2
+    want, stats, _geo = _hold(sc, max_mm, V.PIECE)
+    assert {s for _g, _c, _p, s, *_r in want} == {0, 1} and len(want) >= len(sc.want)
+    assert stats == V.allele_sets(sc.text(), sc.records)[1]
+    L = sc.L
+    if L == 32:
+        assert sc.want["w0_31+"][2] == sc.want["w0_31-"][2] == 0x80000001
+    assert {sc.want[f"w{i}+"][2] for i in (0, L - 1)} == {1, 1 << (L - 1)}
+
+
+@pytest.mark.parametrize("pam_text,G,right,alphabet", V.SEAM_SYSTEMS)
+def test_filter_seam_scene(pam_text, G, right, alphabet):
+    from collections import Counter
+    sc = V.seam_scene(pam_text, G, right, alphabet)
+    want, stats, geo = _hold(sc, 0, V.BIG_PIECE)
+    assert len(geo) == 8 and stats["applied"] == len(sc.records)
+    L = sc.L
+    for B in V.SEAMS:  # where the seam windows and their ALTs lie
+        for tag in "+-":
+            assert sc.placed[f"far{B}{tag}"][2] == B - 1 and sc.placed[f"across{B}{tag}"][2] + L - 1 == B
+            assert sc.placed[f"after{B}{tag}"][2] + L == B and sc.placed[f"before{B}{tag}"][2] == B + 1
+        assert sc.want[f"far{B}+"][2] == 1 << (L - 1) and sc.want[f"far{B}-"][2] == 1
+    assert len(sc.absent) == 16
+    cells = Counter((r, q // V.TILE, s) for r, q, s in V.owned(sc.sites(), geo))
+    assert len(cells) == 32 and len(set(cells.values())) == 32  # every (row, workgroup, strand) holds its own number of sites
+    assert Counter((r, q // V.TILE, s) for r, q, s in V.owned([(c, p, s) for _g, c, p, s, *_r in want], geo)).keys() == cells.keys()
+
+
+@pytest.mark.parametrize("pam_text,G,right", SYSTEMS)
+@pytest.mark.parametrize("n", (1285, 8197))
+def test_row_end_scenes(pam_text, G, right, n):
+    for strand in (0, 1):
+        sc = V.row_end_scene(pam_text, G, right, n, strand)
+        assert n % 128 == 5 and sc.placed["end"][2:] == (n - sc.L, strand)
+        (ref, alt), = [(r, a) for c, p, r, a in sc.records if p == n - 1]
+        assert ref != alt and sc.text()["chr1"][n - 1] == ref
+        _want, _stats, geo = _hold(sc, 1, V.BIG_PIECE)
+        assert len(geo) == 1
+
+
+def test_dense_scene():
+    sc = V.dense_scene()
+    n, run = V.DENSE_N, V.DENSE_RUN
+    sets, ref_stats = V.allele_sets(sc.text(), sc.records)
+    assert (n - run) % 32 == 20 and all(len(a) == 4 for a in sets["chr1"][n - run:]) and len(sc.records) - run > 256
+    want, stats, _geo = _hold(sc, 0, V.BIG_PIECE)
+    assert stats == ref_stats and stats["dropped"]["ref_mismatch"] > 10
+    V.dense_claims(sc, want)
+    assert len(want) >= 2 * (run - sc.L + 1) * len(sc.guides)
+    _hold(sc, 1, V.BIG_PIECE, guides=sc.guides[:40])
+
+
+@pytest.mark.parametrize("max_mm", (0, 1))
+def test_pam_detail_scenes(max_mm):
+    sc = V.pam_lowest_scene()
+    _hold(sc, max_mm, V.PIECE)
+    assert {w[3] for _mm, w, _a in sc.want.values()} == {"A", "C"}
+    for letters in ("AG", "CG"):  # the - strand records state the complements: their lowest + strand letter is the other one
+        (alts,) = [a for c, p, r, a in sc.records if p == sc.placed[letters + "-"][2] + sc.L - 1 - 3]
+        assert sorted(alts.split(",")) == sorted(V.COMP[x] for x in letters) and V.COMP[min(alts.split(","))] != min(letters)
+    sc = V.pam_n_scene()
+    want, _stats, _geo = _hold(sc, max_mm, V.PIECE)
+    have = {(g, c, p, s): w for g, c, p, s, _mm, w, _a in want}
+    for tag in "+-":
+        assert have[sc.placed["under_pam_n" + tag]][20] == "N"
+        assert (sc.placed["spacer_n" + tag] in have) == (max_mm >= 1)
+        assert sc.placed["spacer_n" + tag][1:] in sc.sites()  # a site at either max_mm: only the pair is out of reach
+
+
+def test_incremental_and_shard_scene():
+    """The records dealt into three calls are the records; of three shards over the six rows two hold the overlap's variant"""
+    sc = V.shard_scene()
+    want, _stats, geo = _hold(sc, 2, V.PIECE)
+    calls = V.split_calls(sc.records)
+    flat = [r for c in calls for r in c]
+    assert sorted(flat) == sorted(variant_records(sc.records)) and all(len(c) > 10 for c in calls)
+    for tag in "+-":  # the two ALTs of one position lie in different calls
+        _gi, contig, pos, strand = sc.placed["two_alts" + tag]
+        at = pos + (sc.L - 1 - 6 if strand else 6)
+        assert sorted(sum((contig, at) == r[:2] for r in c) for c in calls) == [0, 1, 1]
+    assert V.brute(sc.text(), flat, sc.guides, "NGG", False, 2) == want
+    lens = {k: len(v) for k, v in sc.text().items()}
+    assert len(geo) == 6
+    gi, contig, pos, strand = sc.placed["shard_overlap"]
+    rec = [r for r in variant_records(sc.records) if r[:2] == (contig, pos + 10)]
+    assert len(rec) == 1
+    for r, (lo, hi) in enumerate(((0, 2), (2, 4), (4, 6))):
+        row, q, _rb, _ab, _var, dropped, kept = variant_entries(lens, geo, rec, lo, hi)
+        assert (row.tolist(), q.tolist(), dropped["other_shard"]) == (([1], [pos + 10 - 1024], 0), ([0], [pos + 10 - 2048], 0), ([], [], 1))[r]
+
+
 def test_refusals():
     import ctypes as C
     L = _lib.lib()
